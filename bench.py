@@ -123,7 +123,42 @@ def parse():
                         help="initialise the torch.distributed process group also at N = 1 (with "
                              "--backend nccl: RCCL loads and a communicator is made on one GPU) and "
                              "run the step through the collection path of ShardedLines")
-    return parser.parse_args()
+    parser.add_argument("--dump-outputs", metavar="DIR",
+                        help="after the timed steps, write what the last one delivered to its "
+                             "caller (rank 0) as DIR/<name>.npy, float64, at most 64 MB in all "
+                             "(see dump_outputs), so that two builds can be compared")
+    args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT = 64*10**6       # bytes that --dump-outputs may write in all
+DUMP_SEED = 20240601        # of the sample taken when the outputs are larger than that
+
+
+def dump_outputs(directory, arrays):
+    """Writes {name: float64 array} as directory/<name>.npy, whole when all of them fit
+    DUMP_LIMIT together; otherwise every array is replaced by the same fixed, seeded sample of
+    its flattened values, sorted by position (numpy.random.default_rng(DUMP_SEED).choice(size,
+    count, replace=False)), the budget shared equally.  directory/outputs.json records each
+    array's full shape and whether (and how many points) it was sampled."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT - (1 << 16)             # .npy headers and outputs.json
+    sample = sum(a.size for a in arrays.values())*8 > budget
+    per_array = budget//8//max(len(arrays), 1)
+    record = {"limit_bytes": DUMP_LIMIT, "seed": DUMP_SEED, "arrays": {}}
+    for name, values in arrays.items():
+        entry = {"shape": list(values.shape), "dtype": "float64", "sampled_points": None}
+        if sample and values.size > per_array:
+            index = np.sort(np.random.default_rng(DUMP_SEED).choice(values.size, per_array,
+                                                                    replace=False))
+            values = values.reshape(-1)[index]
+            entry["sampled_points"] = int(per_array)
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(values, np.float64))
+        record["arrays"][name] = entry
+    with open(os.path.join(directory, "outputs.json"), "w") as out:
+        json.dump(record, out, indent=1)
 
 
 def main():
@@ -280,6 +315,7 @@ def run():
         else None
     pending = [None, None]
     counter = [0]
+    delivered = [None]          # what the latest step hands its caller (--dump-outputs)
 
     def count_evals():
         """Closed-form evals of this rank's units (the engine's own count, one blocking pass)."""
@@ -309,9 +345,11 @@ def run():
             for m, formula in enumerate(molecules):
                 engine.compute(handles[formula], atmos.t, atmos.p, vmr[formula], *grid_args,
                                remove_pedestal=args.pedestal, out=host_spectra[m])
+            delivered[0] = host_spectra
             return
         pending[which] = sharded.run(atmos.t, atmos.p, vmr, dst=0, output=args.output,
                                      async_op=True)
+        delivered[0] = pending[which]
 
     exchange = {"count": 0, "wait_s": 0., "in_flight_s": 0., "sent": 0, "received": 0}
 
@@ -360,6 +398,28 @@ def run():
     busy_ms = engine.timing_busy()
     kernel_ms, launches = engine.timing(reset=True)
     engine.set_option("timing", 0)
+
+    if args.dump_outputs and rank == 0:
+        # fence() has settled every exchange, so the last step's result is complete; it is dumped
+        # before any later call can write its buffers again.  Device memory is copied by the
+        # engine, not by torch (no torch kernel or copy on the GPU, see the note further down).
+        def host_copy(value):
+            if isinstance(value, np.ndarray):
+                return np.array(value)
+            if not value.is_cuda:
+                return value.numpy().copy()
+            assert value.is_contiguous() and value.dtype == torch.float64
+            out = np.empty(tuple(value.shape), dtype=np.float64)
+            engine._check(engine.lib.lbl_copy_to_host(engine.handle, out.ctypes.data,
+                                                      value.data_ptr(), out.nbytes))
+            return out
+        if args.host_output:
+            result = {f: delivered[0][m] for m, f in enumerate(molecules)}
+        elif args.output == "total":
+            result = {"total": delivered[0].wait()}
+        else:
+            result = delivered[0].wait()
+        dump_outputs(args.dump_outputs, {name: host_copy(value) for name, value in result.items()})
 
     per_rank = None
     if grouped and not args.host_output:
