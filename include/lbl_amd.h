@@ -181,6 +181,8 @@ int lbl_fill_zero(lbl_engine *engine, double *k, int32_t n_levels, int64_t n,
  *   "workspace_bytes"     per-lane workspace that bounds the levels of one pass (default 4 GiB)
  *   "farfield"            0/1: distant lines by their power series (farfield.h); default 0
  *   "aligned_tiles"       0/1: cell-aligned tiles also without the far-field series; default 0
+ *   "wing_batches"        1, 2, 4, 8: most batches of eight far-wing lines per reciprocal in the
+ *                         four-points-per-lane kernel (each level may get fewer); default 8
  *   "overlap_pedestal"    0/1: pedestal pre-pass on a side stream beside the accumulate launch; default 1
  *   "scan_chain"          0/1: the pedestal recurrence by relaxation where it applies, the serial
  *                         chain behind it; 0 = the serial chain alone; default 1
@@ -432,6 +434,13 @@ int lbl_compat_state(int32_t *device, int32_t *resident);
 
 /* Library version string. */
 const char *lbl_version(void);
+
+/* Batches of eight far-wing lines that share one reciprocal (1, 2, 4 or 8), as the accumulate
+ * kernel chooses them per level from four binary-exponent bounds of its far-wing terms:
+ * bounds = {t_low, -t_high, b_low, -b_high} with 2^t_low <= t < 2^t_high for t = d^2 + gamma^2
+ * and 2^b_low <= |b| < 2^b_high for the non-zero Lorentz amplitudes; 0x7f7f7f7f marks a bound
+ * no line contributed to.  Exposed for tests. */
+int lbl_wing_batches(const int32_t *bounds);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@
 // gives cut points lo <= a1 <= f1 <= c1 <= c2 <= f2 <= a2 <= hi into that order:
 //   [f1,c1) and [c2,f2): windows certainly cover the whole tile and the tile is certainly
 //                        in the Lorentz far wing of the line  -> branch-free fast loop,
-//                        eight lines per reciprocal;
+//                        eight lines per reciprocal (up to 64 in accumulate_kernel<4>);
 //   [a1,f1) and [f2,a2): the same, and far enough away for the optional power series of
 //                        farfield.h (empty, f1 = a1 and f2 = a2, when that is off);
 //   [c1,c2):             the tile may hold points of the line's core -> core_lines(): per line
@@ -116,6 +116,8 @@ struct AccumulateArgs
     const LevelScalars * levels;    // [levels]
     const WorkItem * items;         // [n_items]
     const double * far_series;      // [levels][n_tiles][kFarTerms] or nullptr (farfield.h)
+    const int * wing_bounds;        // [levels][kWingBounds] (line_prep.h): range of the far-wing terms
+    int wing_batches;               // cap on wing_batches() (engine option "wing_batches")
     double * partial;               // [levels][partial_slots][64*P] sums of split tiles
     long long partial_slots;
     double * k;                     // [levels][level_stride]
@@ -236,7 +238,15 @@ __device__ __forceinline__ void accumulate_tile(const AccumulateArgs & a)
     if (LBL_ABLATED(a, 16)) { g.count[1] = 0; }                   // ... no core lines
     if (!LBL_ABLATED(a, 2))
     {
-        fast_ranges<P>(wing, fa0, fa1, fb0, fb1, v, acc);
+        // Batches of eight far-wing lines per reciprocal, per level (wing_batches()).
+        int batches = 1;
+        if (P == 4)
+        {
+            const int * __restrict__ wb = a.wing_bounds + level*kWingBounds;
+            const int bound[kWingBounds] = {wb[0], wb[1], wb[2], wb[3]};
+            batches = __builtin_amdgcn_readfirstlane(min(wing_batches(bound), a.wing_batches));
+        }
+        fast_ranges<P>(wing, fa0, fa1, fb0, fb1, batches, v, acc);
     }
     bool slab_in_use = false;
     if (!LBL_ABLATED(a, 1))
@@ -356,7 +366,11 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const AccumulateArgs a)
 // rows (now formed as doubles from the first one) and (double)v0 (now a kernel argument, i.e. in
 // scalar registers).  <4> compiles to 71 VGPRs without a spill (seven wavefronts per SIMD), <8> to
 // 80 with two instead of four spilled; same speed within +-1 % (profiles/r04_ab_spill.txt), where
-// the hint (6, 6) -- also free of spills, 77 VGPRs -- lost 2 %.
+// the hint (6, 6) -- also free of spills, 77 VGPRs -- lost 2 %.  Round 7: the running merge of
+// the far-wing loop (fast_ranges) takes <4> to 73 (six wavefronts per SIMD).  Asked for 7 it makes
+// do with 72 without scratch, but spills SGPRs and is slower or no faster on every bench leg
+// (config 1 +2.5 %); under this hint the merge wins on all of them
+// (profiles/r07_ab_wing_batches.txt).
 template <>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
 void accumulate_kernel<8>(const AccumulateArgs a)

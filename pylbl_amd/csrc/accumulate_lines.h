@@ -13,21 +13,27 @@ namespace lbl {
 // only whole groups of four are taken here, the caller sends the 0-3 left-over lines of each
 // range down the general path.  The records arrive by scalar loads whose latency is covered
 // by the other resident wavefronts of the SIMD.
+//
+// P = 4 (the form that carries the default workload; its SIMDs are full of fp64 FMA-class work
+// here, so only fewer operations per evaluation make it faster): every batch of eight lines
+// becomes one fraction n/t per row (wing_eight), merged into a running N/T -- N = N t + n T,
+// T = T t, three operations -- and `batches` of them (wave-uniform, per level: wing_batches(),
+// which keeps the products in range) share one reciprocal and one FMA into acc.  At most 8 line
+// records are held at a time, as before; the running sums take 2 P VGPRs.  The order of the
+// operations is fixed: results are bitwise the same from run to run.  batches = 1 is the plain
+// eight-line group.
 template <int P>
 __device__ __forceinline__ void fast_ranges(const LineWing * __restrict__ wing,
-                                            int a0, int a1, int b0, int b1,
+                                            int a0, int a1, int b0, int b1, int batches,
                                             const double (&v)[P], double (&acc)[P])
 {
     const int qa = (a1 - a0) >> 2;
     const int quads = qa + ((b1 - b0) >> 2);
     int q = 0;
 #if LBL_WING_GROUP == 8
-    // Two groups of four per step: eight lines share one reciprocal.
-    for (; q + 2 <= quads; q += 2)
-    {
-        const int ja = q < qa ? a0 + 4*q : b0 + 4*(q - qa);
-        const int jb = (q + 1) < qa ? a0 + 4*(q + 1) : b0 + 4*(q + 1 - qa);
-        WingTerm l[8];
+    auto eight = [&](int at, WingTerm (&l)[8]) {
+        const int ja = at < qa ? a0 + 4*at : b0 + 4*(at - qa);
+        const int jb = (at + 1) < qa ? a0 + 4*(at + 1) : b0 + 4*(at + 1 - qa);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
         {
@@ -35,6 +41,49 @@ __device__ __forceinline__ void fast_ranges(const LineWing * __restrict__ wing,
             l[i] = WingTerm{wa.centre, wa.g2, wa.bl};
             l[4 + i] = WingTerm{wb.centre, wb.g2, wb.bl};
         }
+    };
+    if (P == 4 && batches > 1)
+    {
+        const int eights = quads >> 1;
+        for (int o = 0; o < eights; )
+        {
+            const int stop = min(o + batches, eights);
+            double num[P], den[P];
+            {
+                WingTerm l[8];
+                eight(2*o, l);
+#pragma unroll
+                for (int p = 0; p < P; ++p)
+                {
+                    wing_eight(v[p], l, num[p], den[p]);
+                }
+            }
+            for (++o; o < stop; ++o)
+            {
+                WingTerm l[8];
+                eight(2*o, l);
+#pragma unroll
+                for (int p = 0; p < P; ++p)
+                {
+                    double n, t;
+                    wing_eight(v[p], l, n, t);
+                    num[p] = __builtin_fma(num[p], t, n*den[p]);
+                    den[p] = den[p]*t;
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < P; ++p)
+            {
+                acc[p] = __builtin_fma(num[p], rcp_newton(den[p]), acc[p]);
+            }
+        }
+        q = 2*eights;
+    }
+    // Two groups of four per step: eight lines share one reciprocal.
+    for (; q + 2 <= quads; q += 2)
+    {
+        WingTerm l[8];
+        eight(q, l);
 #pragma unroll
         for (int p = 0; p < P; ++p)
         {

@@ -136,6 +136,9 @@ int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_fo
                 prepare_blocks = (int)((n_lines + 255)/256);
                 const int schedule_blocks = want_k ? (int)((8ll*n_tiles + 255)/256) : 0;
                 prologue_blocks = (unsigned)std::max(prepare_blocks + schedule_blocks, 1);
+                // (every bound starts at kWingBoundsFill: byte 0x7f)
+                HIP_TRY(hipMemsetAsync(lane.wing_bounds.data, 0x7f,
+                                       (size_t)count*kWingBounds*sizeof(int), stream));
                 engine->timed(kTimePrepare, stream, [&] {
                     dim3 grid((unsigned)std::max(prepare_blocks + schedule_blocks, 1),
                               (unsigned)count);
@@ -144,7 +147,8 @@ int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_fo
                                        tiling, farfield, prepare_blocks, lane.wing.data,
                                        lane.core.data, lane.schedule.data,
                                        rq.derived != nullptr ? lane.derived.data : nullptr,
-                                       rq.evals != nullptr ? lane.evals.data : nullptr);
+                                       rq.evals != nullptr ? lane.evals.data : nullptr,
+                                       lane.wing_bounds.data);
                     HIP_TRY(hipGetLastError());
                 });
             }
@@ -191,6 +195,8 @@ int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_fo
             args.levels = lane.levels.data;
             args.items = plan.items.data;
             args.far_series = farfield ? lane.far_series.data : nullptr;
+            args.wing_bounds = lane.wing_bounds.data;
+            args.wing_batches = engine->wing_batches;
             args.partial = lane.partial.data;
             args.partial_slots = plan.partial_slots;
             args.level_stride = sums_stride;

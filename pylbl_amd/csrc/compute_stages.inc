@@ -198,6 +198,7 @@ void reserve_for_call(Lane & lane, const ComputeRequest & rq, const CallShape & 
     {
         lane.partial.reserve((size_t)std::max(1ll, chunk*plan.partial_slots*64*s.points));
     }
+    lane.wing_bounds.reserve((size_t)(chunk*kWingBounds));
     if (rq.evals != nullptr)
     {
         lane.evals.reserve(1);
@@ -277,6 +278,7 @@ struct HostPrep
     std::vector<LineWing> wing;
     std::vector<LineCore> core;
     std::vector<double> derived;
+    std::vector<int> wing_bounds;
 };
 
 void prepare_on_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq,
@@ -289,6 +291,7 @@ void prepare_on_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
         hp.wing.resize((size_t)(count*n_lines));
         hp.core.resize((size_t)(count*n_lines));
         if (rq.derived != nullptr) hp.derived.assign((size_t)(n_lines*8), 0.);
+        hp.wing_bounds.assign((size_t)(count*kWingBounds), kWingBoundsFill);
         unsigned long long total = 0;
         for (int l = 0; l < count; ++l)
         {
@@ -304,6 +307,14 @@ void prepare_on_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
                     m.column[3][j], m.column[4][j], m.column[5][j], m.column[6][j],
                     std::max(m.iso_slot[j], 0), ok, w, hp.core[(size_t)(l*n_lines + j)], d);
                 if (status == 1 && w.last >= w.first) total += w.last - w.first + 1;
+                int bound[kWingBounds];
+                wing_line_bounds(s.g, m.column[0][j], status, w,
+                                 hp.core[(size_t)(l*n_lines + j)], bound);
+                for (int b = 0; b < kWingBounds; ++b)
+                {
+                    int & least = hp.wing_bounds[(size_t)(l*kWingBounds + b)];
+                    least = std::min(least, bound[b]);
+                }
             }
         }
         engine->timed(kTimePrepare, stream, [&] {
@@ -312,6 +323,9 @@ void prepare_on_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
                                    stream));
             HIP_TRY(hipMemcpyAsync(lane.core.data, hp.core.data(),
                                    hp.core.size()*sizeof(LineCore), hipMemcpyHostToDevice,
+                                   stream));
+            HIP_TRY(hipMemcpyAsync(lane.wing_bounds.data, hp.wing_bounds.data(),
+                                   hp.wing_bounds.size()*sizeof(int), hipMemcpyHostToDevice,
                                    stream));
         });
         HIP_TRY(hipStreamSynchronize(stream));

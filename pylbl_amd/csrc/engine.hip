@@ -47,6 +47,13 @@ const char * lbl_version(void)
     return "pylbl_amd 0.1 (gfx950)";
 }
 
+int lbl_wing_batches(const int32_t * bounds)
+{
+    if (bounds == nullptr) return 1;
+    const int bound[kWingBounds] = {bounds[0], bounds[1], bounds[2], bounds[3]};
+    return wing_batches(bound);
+}
+
 int lbl_engine_create(int device, lbl_engine ** engine)
 {
     if (engine == nullptr) return fail(nullptr, LBL_BAD_ARGUMENT, "engine is NULL.");
@@ -451,6 +458,10 @@ int lbl_set_option(lbl_engine * engine, const char * name, int64_t value)
     else if (key == "aligned_tiles" && (value == 0 || value == 1))
     {
         engine->aligned_tiles = (int)value;
+    }
+    else if (key == "wing_batches" && (value == 1 || value == 2 || value == 4 || value == 8))
+    {
+        engine->wing_batches = std::min((int)value, kWingBatchesMax);
     }
 #ifdef LBL_ABLATE
     else if (key == "ablate" && value >= 0 && value <= 127)

@@ -181,6 +181,7 @@ struct Lane
     DeviceBuffer<double> far_series; // [levels][tiles][kFarTerms]
     DeviceBuffer<double> derived;
     DeviceBuffer<unsigned long long> evals;
+    DeviceBuffer<int> wing_bounds;  // [levels][kWingBounds] of the pass (line_prep.h)
     PedestalWorkspace pedestal;
     LevelScalars * pinned_levels = nullptr;
     size_t pinned_capacity = 0;
@@ -405,6 +406,7 @@ struct lbl_engine
     long long workspace_bytes = 4ll << 30;
     int ablate = 0;
     int aligned_tiles = 0;          // measured: no gain at 0.001 cm-1
+    int wing_batches = kWingBatchesMax; // cap on the far-wing batches per reciprocal (line_prep.h)
     int overlap_pedestal = 1;       // run the pedestal pre-pass beside the accumulate kernel
     int farfield = 0;               // sum distant lines by their power series (farfield.h)
     int scan_chain = 1;             // pedestal chain by relaxation (pedestal.h), serial chain behind it

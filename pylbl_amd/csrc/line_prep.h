@@ -103,6 +103,105 @@ __host__ __device__ inline void inner_index_range(double centre, double repwid, 
     last = (int)hi;
 }
 
+// Range of the far-wing terms of one level, as binary exponents (ilogb): what decides how many
+// batches of eight lines the far-wing loop may merge before one reciprocal (accumulate_lines.h,
+// fast_ranges).  Reduced over the lines by atomicMin from the fill value kWingBoundsFill (the
+// maxima are kept negated, so one operation and one fill value serve all four).
+enum WingBound
+{
+    kWingTLow,          // t = d^2 + g2 >= 2^kWingTLow for every far-wing (line, point) pair
+    kWingTHighNeg,      // -(e) with t < 2^e
+    kWingBLow,          // |bl| >= 2^kWingBLow for every line with bl != 0
+    kWingBHighNeg,      // -(e) with |bl| < 2^e
+    kWingBounds
+};
+constexpr int kWingBoundsFill = 0x7f7f7f7f;     // hipMemset byte 0x7f
+#ifndef LBL_WING_BATCHES
+#define LBL_WING_BATCHES 8      // most batches of eight far-wing lines per reciprocal: 1, 2, 4 or 8
+#endif
+constexpr int kWingBatchesMax = LBL_WING_BATCHES;
+
+// floor(log2 x) and floor(log2 x) + 1 for x > 0 and finite; anything else is made to look as
+// far out of range as an exponent can be (wing_batches() then answers 1).
+__host__ __device__ inline int wing_exponent_low(double x)
+{
+    return (x > 0. && x < 1.e300) ? ilogb(x) : -4096;
+}
+
+__host__ __device__ inline int wing_exponent_high(double x)
+{
+    return (x > 0. && x < 1.e300) ? ilogb(x) + 1 : 4096;
+}
+
+// The contribution of one line record to the four bounds (`bound` holds the line's values, to be
+// min-reduced).  Lines in a tile's far-wing ranges cover the whole tile (|d| <= cut_off + 1) and
+// lie beyond their own far-wing limit, |d| >= xlim0/repwid (schedule_tile: the core range of a
+// tile reaches core_reach*nu, core_reach bounds (xlim0/repwid)/nu over the table).  Accepted lines
+// there always have a real record; a line the range rule refused carries mark_empty's (centre 0,
+// g2 1, bl 0), so t = v^2 + 1 up to the end of the grid when its nu lies where the ranges look
+// (schedule_tile: a line that covers a tile has nu in [v0 - cut_off - 1, vn + cut_off)).
+__host__ __device__ inline void wing_line_bounds(const GridSpec & g, double nu, int status,
+                                                 const LineWing & w, const LineCore & c,
+                                                 int (&bound)[kWingBounds])
+{
+    bound[kWingTLow] = bound[kWingTHighNeg] = kWingBoundsFill;
+    bound[kWingBLow] = bound[kWingBHighNeg] = kWingBoundsFill;
+    if (status == 1 && w.last >= w.first)
+    {
+        const double reach = c.xlim0 > 0. ? (c.xlim0/c.repwid)*(1. - 1.e-6) : 0.;
+        const double far = (double)g.cut_off + 1.;
+        bound[kWingTLow] = wing_exponent_low(reach*reach + w.g2);
+        bound[kWingTHighNeg] = -wing_exponent_high(far*far + w.g2);
+        const double b = fabs(w.bl);
+        if (b != 0.)
+        {
+            bound[kWingBLow] = wing_exponent_low(b);
+            bound[kWingBHighNeg] = -wing_exponent_high(b);
+        }
+    }
+    else if (status == -1 && nu >= (double)(g.v0 - g.cut_off - 1) &&
+             nu < (double)(g.vn + g.cut_off))
+    {
+        const double v = fmax(fabs((double)g.v0), fabs((double)g.vn));
+        bound[kWingTHighNeg] = -wing_exponent_high(v*v + 1.);
+    }
+}
+
+// Batches of eight far-wing lines per reciprocal, from the reduced bounds: the largest
+// K in {1, 2, 4, 8} for which the running products of fast_ranges stay normal --
+// T = prod of 8K values of t and N = sum b_i prod_{j != i} t_j (at most 8K terms) within
+// 2^-1000 .. 2^1000.  K = 1 is the eight-line group that needs no bound (today's range).
+__host__ __device__ inline int wing_batches(const int (&bound)[kWingBounds])
+{
+    const long long t_lo = bound[kWingTLow], t_hi = -(long long)bound[kWingTHighNeg];
+    long long b_lo = bound[kWingBLow], b_hi = -(long long)bound[kWingBHighNeg];
+    if (t_lo == kWingBoundsFill || -t_hi == kWingBoundsFill)
+    {
+        return 1;           // no far-wing line at this level
+    }
+    if (b_lo == kWingBoundsFill)
+    {
+        b_lo = b_hi = 0;    // every bl is 0: N is 0
+    }
+    if (t_lo < -2000 || t_hi > 2000 || b_lo < -2000 || b_hi > 2000)
+    {
+        return 1;
+    }
+    for (int k = kWingBatchesMax; k > 1; k >>= 1)
+    {
+        const long long n = 8*k;
+        // (T >= 2^(n t_lo), N >= 2^((n-1) t_lo + b_lo) with the exponents floored; T < 2^(n t_hi),
+        // N < n 2^((n-1) t_hi + b_hi), n <= 2^6.)
+        const long long lowest = (t_lo < 0 ? n*t_lo : (n - 1)*t_lo) + (b_lo < 0 ? b_lo : 0);
+        const long long highest = (t_hi > 0 ? n*t_hi : (n - 1)*t_hi) + (b_hi > 0 ? b_hi : 0) + 6;
+        if (lowest >= -1000 && highest <= 1000 && n*t_lo >= -1000 && n*t_hi <= 1000)
+        {
+            return k;
+        }
+    }
+    return 1;
+}
+
 // status: 1 evaluated, 0 window right of the grid / empty, -1 not accepted by the range rule.
 // derived (optional, 8 doubles): centre, alpha, gamma, strength, first, last, status, 0.
 __host__ __device__ inline int prepare_line(const LevelScalars & lv, const GridSpec & g,

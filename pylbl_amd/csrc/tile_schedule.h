@@ -203,10 +203,12 @@ __device__ __forceinline__ void prepare_block(const LineTableView & t, const Lev
                                               LineWing * __restrict__ wing,
                                               LineCore * __restrict__ core,
                                               double * __restrict__ derived,
-                                              unsigned long long * __restrict__ evals)
+                                              unsigned long long * __restrict__ evals,
+                                              int * __restrict__ wing_bounds)
 {
     const long long j = (long long)block*blockDim.x + threadIdx.x;
     unsigned long long count = 0;
+    int bound[kWingBounds] = {kWingBoundsFill, kWingBoundsFill, kWingBoundsFill, kWingBoundsFill};
     if (j < t.n_lines)
     {
         LineWing w;
@@ -223,6 +225,37 @@ __device__ __forceinline__ void prepare_block(const LineTableView & t, const Lev
         if (status == 1 && w.last >= w.first)
         {
             count = (unsigned long long)(w.last - w.first + 1);
+        }
+        wing_line_bounds(g, nu, status, w, c, bound);
+    }
+    {
+        // The level's far-wing bounds (wing_batches()): minimum over the block, then one atomic
+        // per bound and block.
+        __shared__ int block_bound[4][kWingBounds];
+#pragma unroll
+        for (int b = 0; b < kWingBounds; ++b)
+        {
+            for (int offset = 32; offset > 0; offset >>= 1)
+            {
+                bound[b] = min(bound[b], __shfl_down(bound[b], offset, 64));
+            }
+        }
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0)
+        {
+#pragma unroll
+            for (int b = 0; b < kWingBounds; ++b) block_bound[wave][b] = bound[b];
+        }
+        __syncthreads();
+        if (threadIdx.x < kWingBounds)
+        {
+            const int b = threadIdx.x;
+            const int least = min(min(block_bound[0][b], block_bound[1][b]),
+                                  min(block_bound[2][b], block_bound[3][b]));
+            if (least != kWingBoundsFill)
+            {
+                atomicMin(wing_bounds + (long long)level*kWingBounds + b, least);
+            }
         }
     }
     if (evals != nullptr)
@@ -250,7 +283,8 @@ __global__ __launch_bounds__(256) void prologue_kernel(const LineTableView t,
                                                        LineCore * __restrict__ core,
                                                        TileSchedule * __restrict__ schedule,
                                                        double * __restrict__ derived,
-                                                       unsigned long long * __restrict__ evals)
+                                                       unsigned long long * __restrict__ evals,
+                                                       int * __restrict__ wing_bounds)
 {
     const int level = blockIdx.y;
     const LevelScalars & lv = use_inline ? inline_levels.level[level] : levels[level];
@@ -263,7 +297,8 @@ __global__ __launch_bounds__(256) void prologue_kernel(const LineTableView t,
     }
     if ((int)blockIdx.x < prepare_blocks)
     {
-        prepare_block(t, lv, g, rule, blockIdx.x, level, wing, core, derived, evals);
+        prepare_block(t, lv, g, rule, blockIdx.x, level, wing, core, derived, evals,
+                      wing_bounds);
         return;
     }
     const int thread = (blockIdx.x - prepare_blocks)*blockDim.x + threadIdx.x;

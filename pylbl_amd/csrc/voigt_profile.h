@@ -38,8 +38,11 @@ __device__ __forceinline__ double lorentz_one(double v, double centre, double g2
 }
 
 // Four far-wing lines at one point with a single reciprocal, added to `sum`:
-//   sum b_i/t_i = N/(t1 t2 t3 t4).  Products stay far from over/underflow because
-//   t = d^2 + gamma^2 lies in [~1e-12, ~1e3] for every window the reference allows.
+//   sum b_i/t_i = N/(t1 t2 t3 t4),  t = d^2 + gamma^2.  Of the far-wing (line, point) pairs
+//   t lies between (xlim0/repwid)^2 + gamma^2 (the line's far-wing limit: the schedule keeps
+//   the tile beyond it) and (cut_off + 1)^2 + gamma^2 (the tile lies in the window): products
+//   of four or eight of them stay in range for every window the reference allows; longer
+//   products (fast_ranges) only as far as the level's bounds permit (line_prep.h, wing_batches).
 __device__ __forceinline__ double lorentz_four(double v,
                                                double c1, double g1, double b1,
                                                double c2, double g2, double b2,
@@ -58,8 +61,9 @@ __device__ __forceinline__ double lorentz_four(double v,
     return __builtin_fma(num, rcp_newton(t12*t34), sum);
 }
 
-// Eight far-wing lines at one point with a single reciprocal (two levels more of the same
-// pairing): 40 FMA-class operations + 1 v_rcp_f64 per 8 evaluations.
+// Eight far-wing lines at one point as one fraction sum b_i/t_i = num/den (two levels more of
+// the same pairing): 8 subtractions, 8 FMAs for the t_i and 7 merges of two fractions at three
+// operations each -- 37 FMA-class operations.
 struct WingTerm
 {
     double centre, g2, bl;
@@ -75,7 +79,8 @@ __device__ __forceinline__ void wing_pair(double v, const WingTerm & p, const Wi
     den = t1*t2;
 }
 
-__device__ __forceinline__ double lorentz_eight(double v, const WingTerm (&l)[8], double sum)
+__device__ __forceinline__ void wing_eight(double v, const WingTerm (&l)[8],
+                                           double & num, double & den)
 {
     double n12, t12, n34, t34, n56, t56, n78, t78;
     wing_pair(v, l[0], l[1], n12, t12);
@@ -84,8 +89,19 @@ __device__ __forceinline__ double lorentz_eight(double v, const WingTerm (&l)[8]
     wing_pair(v, l[6], l[7], n78, t78);
     const double na = __builtin_fma(n12, t34, n34*t12), ta = t12*t34;
     const double nb = __builtin_fma(n56, t78, n78*t56), tb = t56*t78;
-    const double num = __builtin_fma(na, tb, nb*ta);
-    return __builtin_fma(num, rcp_newton(ta*tb), sum);
+    num = __builtin_fma(na, tb, nb*ta);
+    den = ta*tb;
+}
+
+// Eight far-wing lines at one point with a single reciprocal, added to `sum`: 40 FMA-class
+// operations + 1 v_rcp_f64 per 8 evaluations.  (fast_ranges<4> merges up to eight such
+// fractions before the reciprocal: 3 more operations per batch, the reciprocal block --
+// v_rcp_f64, Newton step, final FMA, ~6 FMA slots -- once per up to 64 lines.)
+__device__ __forceinline__ double lorentz_eight(double v, const WingTerm (&l)[8], double sum)
+{
+    double num, den;
+    wing_eight(v, l, num, den);
+    return __builtin_fma(num, rcp_newton(den), sum);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "lbl_continuum_load", "lbl_continuum_free", "lbl_grid_load", "lbl_grid_free",
     "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
+    "lbl_wing_batches",
 )
 
 VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
@@ -165,6 +166,7 @@ def library():
     lib.lbl_xsec_compute.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                      c_void_p, c_int32, c_void_p, c_int64]
     lib.lbl_xsec_bands.argtypes = [c_void_p, c_int32, c_double, c_double, c_void_p]
+    lib.lbl_wing_batches.argtypes = [c_void_p]
     for name in EXPORTED_SYMBOLS:
         if name not in ("lbl_last_error", "lbl_stream", "lbl_version"):
             getattr(lib, name).restype = c_int32
