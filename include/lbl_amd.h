@@ -173,6 +173,48 @@ int lbl_synchronize(lbl_engine *engine);
 int lbl_fill_zero(lbl_engine *engine, double *k, int32_t n_levels, int64_t n,
                   int64_t level_stride, int32_t flags);
 
+/* Optical depth and transmittance along paths (Spectroscopy.compute_path).  beta is a device
+ * block of absorption coefficients [m-1] whose row r (stride row_stride values) is flat level
+ * level_begin + r; the levels are n_paths paths of levels_per_path consecutive levels each, and
+ * this call covers the run [level_begin, level_begin + level_count) of them.  path_length (host,
+ * level_count values [m], finite and >= 0) is each level's length along its path.
+ *   tau_p = sum_l s_{p,l} beta_{p,l}, added level by level as tau = tau + s*beta from tau = 0:
+ *   upward from the path's first level, or with LBL_PATH_FROM_LAST downward from its last.
+ * A path's running tau lives in its row of carry (device, [n_paths][row_stride]) between runs:
+ * a run that starts inside a path in sweep order must carry LBL_PATH_CONTINUE, one that starts a
+ * path must not.  (The run alone decides this; the flag is there so that a caller who loses
+ * track of its runs gets LBL_BAD_ARGUMENT instead of a sum that silently restarts or goes on.)
+ * Runs of one sweep are queued in sweep order.  Only the first `columns` values of
+ * a row count.
+ * Outputs (device; LBL_PATH_OPTICAL_DEPTH -> optical_depth, LBL_PATH_TRANSMITTANCE ->
+ * transmittance = exp(-tau), not clamped):
+ *   n_bands == 0, per path:         row p of [n_paths][row_stride], written by the run that
+ *                                   finishes path p;
+ *   n_bands == 0, LBL_PATH_CUMULATIVE: row r of [level_count][row_stride]: tau after level
+ *                                   level_begin + r;
+ *   n_bands > 0: band b is columns [band_start[b], band_start[b+1]) (host, n_bands + 1
+ *                non-decreasing values in [0, columns]); the output is the arithmetic mean over
+ *                the band of tau or of exp(-tau), NaN for an empty band, in row p of
+ *                [n_paths][n_bands] (per path) or row r of [level_count][n_bands] (cumulative).
+ *                With LBL_PATH_CUMULATIVE the run's rows of beta are overwritten by the
+ *                cumulative tau, which the means then read.
+ * The means are reduced in a fixed order without atomics: repeated calls give the same bits.
+ * Ordered like lbl_fill_zero: behind everything queued on the engine; LBL_ASYNC returns after
+ * queueing.  LBL_BAD_ARGUMENT (message in lbl_last_error) for NULL pointers, columns > row_stride,
+ * bad band starts, negative or non-finite lengths, a run outside the levels or one whose
+ * LBL_PATH_CONTINUE does not match it, LBL_PATH_FROM_LAST without LBL_PATH_CUMULATIVE, or no
+ * quantity requested; the engine stays usable. */
+#define LBL_PATH_OPTICAL_DEPTH  0x100
+#define LBL_PATH_TRANSMITTANCE  0x200
+#define LBL_PATH_CUMULATIVE     0x400   /* one result per level instead of per path          */
+#define LBL_PATH_FROM_LAST      0x800   /* tau over levels l .. L-1, summed from L-1 down     */
+#define LBL_PATH_CONTINUE      0x1000   /* the run's first path goes on from its carry row    */
+int lbl_path_compute(lbl_engine *engine, double *beta, int64_t row_stride, int64_t columns,
+                     int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                     int32_t level_count, const double *path_length, int32_t n_bands,
+                     const int64_t *band_start, double *carry, double *optical_depth,
+                     double *transmittance, int32_t flags);
+
 /* Options (thirteen; anything else is LBL_BAD_ARGUMENT):
  *   "prep"                LBL_PREP_DEVICE (default) / LBL_PREP_HOST: where the per-line scalars are formed
  *   "points_per_lane"     0 = by the grid (default), 1/2/4/8 grid points per lane of the accumulate kernel

@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <numeric>
@@ -29,6 +30,7 @@
 #include "xsec.h"
 #include "farfield.h"
 #include "line_prep.h"
+#include "path.h"
 #include "pedestal.h"
 #include "tile_schedule.h"
 
@@ -39,6 +41,7 @@
 
 // (calibrate_delivery_lanes, used by lbl_engine_create)
 #include "delivery.inc"
+#include "path_entry.inc"
 
 extern "C" {
 

@@ -364,6 +364,54 @@ struct ContinuumGroup : LevelFeed<ContinuumLevel>
     DeviceBuffer<double> coarse, slopes;    // [levels][level_points]
 };
 
+// Tables of lbl_path_compute (path.h): the path lengths of a run, the band starts, each band's
+// first segment and the segments, staged in one page-locked block and uploaded in one copy; and
+// the band partial sums.  Every kernel that reads them runs on the engine's first stream, behind
+// the upload of the next call's tables.
+struct PathWorkspace
+{
+    DeviceBuffer<double> tables;
+    DeviceBuffer<double> partial;       // [rows][segments]
+    double * pinned = nullptr;
+    size_t pinned_capacity = 0;
+    hipEvent_t copied = nullptr;        // behind the last upload out of `pinned`
+    bool in_flight = false;
+
+    // The host may refill the pinned block once the copy that read it has run.
+    double * stage(size_t count)
+    {
+        if (in_flight) HIP_TRY(hipEventSynchronize(copied));
+        in_flight = false;
+        if (count > pinned_capacity)
+        {
+            if (pinned != nullptr) (void)hipHostFree(pinned);
+            pinned = nullptr;
+            pinned_capacity = 0;
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&pinned), count*sizeof(double),
+                                  hipHostMallocDefault));
+            pinned_capacity = count;
+        }
+        return pinned;
+    }
+    void upload(size_t count, hipStream_t stream)
+    {
+        tables.reserve(count);
+        HIP_TRY(hipMemcpyAsync(tables.data, pinned, count*sizeof(double), hipMemcpyHostToDevice,
+                               stream));
+        if (copied == nullptr) HIP_TRY(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(copied, stream));
+        in_flight = true;
+    }
+    ~PathWorkspace()
+    {
+        if (copied != nullptr) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
+        if (pinned != nullptr) (void)hipHostFree(pinned);
+    }
+    PathWorkspace() = default;
+    PathWorkspace(const PathWorkspace &) = delete;
+    PathWorkspace & operator=(const PathWorkspace &) = delete;
+};
+
 }  // namespace
 
 struct lbl_engine
@@ -398,6 +446,7 @@ struct lbl_engine
     std::vector<std::unique_ptr<ContinuumGroup>> groups;
     Lane lanes[kAllLanes];
     unsigned next_lane = 0;
+    PathWorkspace path;             // lbl_path_compute
 
     // Options.
     int prep = LBL_PREP_DEVICE;

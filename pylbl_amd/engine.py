@@ -23,6 +23,9 @@ RANGE_REFERENCE, RANGE_SKIP = 0, 1
 PREP_DEVICE, PREP_HOST = 0, 1
 OUT_DEVICE, ASYNC, SCALE_DENSITY, ACCUMULATE, FARFIELD, DEFER_FINISH = 1, 2, 4, 8, 16, 32
 RANGE_POLICIES = {"reference": RANGE_REFERENCE, "skip": RANGE_SKIP}
+# lbl_path_compute flags: a namespace of their own, clear of the call flags above.
+PATH_OPTICAL_DEPTH, PATH_TRANSMITTANCE, PATH_CUMULATIVE, PATH_FROM_LAST, PATH_CONTINUE = \
+    0x100, 0x200, 0x400, 0x800, 0x1000
 
 EXPORTED_SYMBOLS = (
     "lbl_engine_create", "lbl_engine_destroy", "lbl_last_error", "lbl_molecule_load",
@@ -38,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "lbl_continuum_load", "lbl_continuum_free", "lbl_grid_load", "lbl_grid_free",
     "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
-    "lbl_wing_batches",
+    "lbl_wing_batches", "lbl_path_compute",
 )
 
 VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
@@ -167,6 +170,9 @@ def library():
                                      c_void_p, c_int32, c_void_p, c_int64]
     lib.lbl_xsec_bands.argtypes = [c_void_p, c_int32, c_double, c_double, c_void_p]
     lib.lbl_wing_batches.argtypes = [c_void_p]
+    lib.lbl_path_compute.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                     c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int32]
     for name in EXPORTED_SYMBOLS:
         if name not in ("lbl_last_error", "lbl_stream", "lbl_version"):
             getattr(lib, name).restype = c_int32
@@ -257,6 +263,13 @@ class DeviceSpectra(object):
             columns*8, self.shape[0], ASYNC if asynchronous else 0))
         return target
 
+    def rows(self, count):
+        """The first `count` rows of this block, as a DeviceSpectra that owns no memory (valid
+        while this block is)."""
+        if not 0 < int(count) <= self.shape[0]:
+            raise ValueError(f"rows({count}) of a block of {self.shape[0]} rows.")
+        return _DeviceRows(self, int(count))
+
     def free(self):
         if self.pointer:
             self.engine.lib.lbl_device_free(self.engine.handle, self.pointer)
@@ -267,6 +280,18 @@ class DeviceSpectra(object):
             self.free()
         except Exception:
             pass
+
+
+class _DeviceRows(DeviceSpectra):
+    """DeviceSpectra.rows: leading rows of a block; freeing it frees nothing."""
+    def __init__(self, block, count):
+        self.engine = block.engine
+        self.block = block
+        self.shape = (count, block.shape[1])
+        self.pointer = block.pointer
+
+    def free(self):
+        pass
 
 
 class DevicePool(object):
@@ -609,6 +634,44 @@ class Engine(object):
             self.handle, int(continuum), int(grid), t.size, t.ctypes.data, p.ctypes.data,
             x.ctypes.data, flags, pointer, stride))
         return out
+
+    def path_compute(self, beta, columns, n_paths, levels_per_path, level_begin, lengths, carry,
+                     optical_depth=None, transmittance=None, band_start=None, cumulative=False,
+                     from_last=False, asynchronous=False):
+        """Optical depth / transmittance along paths through the DeviceSpectra `beta` (its rows
+        are the flat levels level_begin, level_begin + 1, ... of n_paths paths of levels_per_path
+        levels; `lengths` [m] one per row) -- lbl_path_compute.  carry: DeviceSpectra
+        [n_paths, >= beta's row length] holding each path's running tau between runs.
+        optical_depth / transmittance: DeviceSpectra outputs (None: not wanted) --
+        [n_paths or rows, row length] without bands, [n_paths or rows, bands] with them.
+        band_start: int64 column starts of the bands (n_bands + 1 values) or None."""
+        lengths = _f64(np.atleast_1d(lengths))
+        rows, stride = int(beta.shape[0]), int(beta.shape[1])
+        if lengths.shape != (rows,):
+            raise ValueError("one path length per row of beta.")
+        if tuple(carry.shape) != (int(n_paths), stride):
+            raise ValueError("carry must be [n_paths, row length of beta].")
+        starts = None if band_start is None else \
+            np.ascontiguousarray(band_start, dtype=np.int64)
+        n_bands = 0 if starts is None else starts.size - 1
+        flags = (PATH_OPTICAL_DEPTH if optical_depth is not None else 0) | \
+                (PATH_TRANSMITTANCE if transmittance is not None else 0) | \
+                (PATH_CUMULATIVE if cumulative else 0) | (PATH_FROM_LAST if from_last else 0) | \
+                (ASYNC if asynchronous else 0)
+        end = int(level_begin) + rows
+        if (end % int(levels_per_path) if from_last else int(level_begin) % int(levels_per_path)):
+            flags |= PATH_CONTINUE
+        width = n_bands if n_bands > 0 else stride
+        for out in (optical_depth, transmittance):
+            if out is not None and (out.shape[1] != width or
+                                    out.shape[0] < (rows if cumulative else int(n_paths))):
+                raise ValueError(f"an output has shape {out.shape}, need rows x {width}.")
+        self._check(self.lib.lbl_path_compute(
+            self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
+            int(level_begin), rows, lengths.ctypes.data, n_bands,
+            starts.ctypes.data if starts is not None else None, carry.pointer,
+            optical_depth.pointer if optical_depth is not None else None,
+            transmittance.pointer if transmittance is not None else None, flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):

@@ -27,6 +27,14 @@ kb = 1.38064852e-23  # Boltzmann constant [J K-1] (pyLBL/spectroscopy.py:15).
 
 MECHANISMS = ["lines", "continuum", "cross_section"]
 
+# Levels of one run of compute_path at most: what one call of the continuum group kernels takes
+# (lbl_continuum_compute_many), so that atmospheres of any size can be integrated.
+_MAX_RUN_LEVELS = 65535
+
+# What compute_path checked and derived from its arguments.
+_PathRequest = namedtuple("_PathRequest", ["lengths", "shape", "quantities", "edges", "starts",
+                                           "cumulative"])
+
 
 def number_density(temperature, pressure, volume_mixing_ratio):
     """Ideal-gas number density [m-3] (pyLBL/spectroscopy.py:18-29)."""
@@ -53,6 +61,22 @@ def _optional_xarray():
         except ImportError:
             _XARRAY.append(None)
     return _XARRAY[0]
+
+
+PATH_QUANTITIES = ("optical_depth", "transmittance")
+PATH_CUMULATIVE = (None, "from_first", "from_last")
+
+
+def band_columns(grid, band_edges):
+    """Column starts of the bands [e_b, e_b+1) of strictly increasing, finite edges on an
+    ascending grid: int64 [B + 1]; band b is the columns starts[b] <= j < starts[b + 1], i.e. the
+    points with e_b <= grid[j] < e_b+1 (a band without points has starts[b] == starts[b + 1])."""
+    edges = np.asarray(band_edges, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2:
+        raise ValueError("band_edges must be a 1-d array of at least two edges.")
+    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.):
+        raise ValueError("band_edges must be finite and strictly increasing.")
+    return np.searchsorted(np.asarray(grid, dtype=np.float64), edges, side="left").astype(np.int64)
 
 
 class Atmosphere(object):
@@ -135,10 +159,12 @@ class MoleculeCache(object):
 
 
 class _Sum(object):
-    """A [levels, n] block in HBM that kernels write first and add into afterwards."""
-    def __init__(self, engine, levels, n):
+    """A [levels, n] block in HBM that kernels write first and add into afterwards (`buffer`: one
+    the caller holds, else one taken from the engine's pool)."""
+    def __init__(self, engine, levels, n, buffer=None):
         self.engine = engine
-        self.buffer = engine.blocks.take(levels, n)     # recycled (engine.DevicePool)
+        # recycled (engine.DevicePool)
+        self.buffer = engine.blocks.take(levels, n) if buffer is None else buffer
         self.written = False
 
     def take(self):
@@ -152,6 +178,49 @@ class _Sum(object):
         the kernels queued so far and beside those queued later."""
         self.buffer.to_host_into(target, target.shape[1], asynchronous=True)
         return self
+
+
+class _Queue(object):
+    """Queues the kernels of one (molecule, mechanism) into a block in HBM, for a flat list of
+    levels: what Spectroscopy._compute_levels and compute_path share."""
+    def __init__(self, spec, temperature, pressure, mole_fractions, remove_pedestal, range_policy,
+                 pieces):
+        self.spec = spec
+        self.temperature, self.pressure, self.mole_fractions = temperature, pressure, mole_fractions
+        self.remove_pedestal, self.range_policy, self.pieces = remove_pedestal, range_policy, pieces
+
+    def lines_into(self, name, gas, block, deliver=None, defer=False):
+        gas.absorption_coefficients(
+            self.temperature, self.pressure, self.mole_fractions[name], self.spec.grid,
+            remove_pedestal=self.remove_pedestal, range_policy=self.range_policy,
+            scale_density=True, out=block.buffer, accumulate=block.take(),
+            asynchronous=True, farfield=self.spec.farfield, deliver=deliver,
+            pieces=self.pieces, defer_finish=defer)
+
+    def continua_into(self, continua_list, continuum_sum):
+        # All of them in one pass over the grid where they are this package's (one launch that
+        # writes the block once instead of a read-modify-write pass per continuum; the same
+        # bits: csrc/continuum.h, group kernels); anything else one by one.
+        if not continua_list:
+            return
+        from .mt_ckd import BandedContinuum, spectra_levels_many
+        if all(isinstance(c, BandedContinuum) for c in continua_list):
+            spectra_levels_many(continua_list, self.temperature, self.pressure,
+                                self.mole_fractions, self.spec.grid, continuum_sum.buffer,
+                                accumulate=continuum_sum.take(), asynchronous=True)
+            return
+        for continuum in continua_list:
+            continuum.spectra_levels(self.temperature, self.pressure, self.mole_fractions,
+                                     self.spec.grid, out=continuum_sum.buffer,
+                                     accumulate=continuum_sum.take(), asynchronous=True)
+
+    def slots_into(self, name, continua_here, cross, continuum_sum, cross_sum):
+        self.continua_into(continua_here, continuum_sum)
+        if cross is not None:
+            cross.absorption_coefficients(self.spec.grid, self.temperature, self.pressure,
+                                          volume_mixing_ratio=self.mole_fractions[name],
+                                          out=cross_sum.buffer, accumulate=cross_sum.take(),
+                                          asynchronous=True)
 
 
 def _zero_in_background(views):
@@ -284,36 +353,198 @@ class Spectroscopy(object):
         return self._create_output_dataset(
             {name: values.reshape(shape + tail) for name, values in flat.items()}, output_format)
 
-    def _compute_levels(self, temperature, pressure, mole_fractions, mode, remove_pedestal,
-                        range_policy):
-        """The three mechanism slots for a flat list of levels: {variable name: array with the
-        levels as leading dimension} ("total" under mode "total")."""
+    def compute_path(self, path_length, quantities=PATH_QUANTITIES, band_edges=None,
+                     cumulative=None, remove_pedestal=None, range_policy="reference"):
+        """Optical depth and transmittance along the paths of the atmosphere, formed on the GPU
+        from the "total" absorption block without handing that block to the host.
+
+        The path axis is the last dimension of the atmosphere: flat level i = p*L + l.  With
+        beta the absorption coefficient [m-1] of compute_absorption("total", remove_pedestal,
+        range_policy) and s the path lengths,
+            tau_p = sum_l s_{p,l} beta_{p,l}, added as tau = tau + s*beta from l = 0 upward,
+            transmittance = exp(-tau) (not clamped).
+
+        Args:
+            path_length: [m], shaped like the atmosphere's temperature, finite and >= 0: each
+                         level's geometric length along its path (slant paths: times the secant).
+            quantities: any of "optical_depth", "transmittance".
+            band_edges: None (every grid point) or strictly increasing finite edges e_0 < ... <
+                        e_B: band b holds the points e_b <= grid < e_b+1, and the result is the
+                        arithmetic mean of tau or of exp(-tau) over them (NaN without points).
+            cumulative: None (one result per path), "from_first" (tau over levels 0 .. l) or
+                        "from_last" (tau over levels l .. L-1, summed from L-1 down).
+
+        Returns:
+            Like compute_absorption: an xarray Dataset when xarray is installed, else a dict of
+            numpy arrays -- "optical_depth" / "transmittance" with the atmosphere's dims (without
+            the last unless cumulative) and "wavenumber" or "band"; coordinates "wavenumber", or
+            "band_lower", "band_upper" and "band_points".
+        """
+        request = self._path_request(path_length, quantities, band_edges, cumulative,
+                                     range_policy)
+        if remove_pedestal is None:
+            remove_pedestal = self.continua_backend == "mt_ckd"
+        values = self._compute_path_levels(request, remove_pedestal, range_policy)
+        return self._create_path_dataset(values, request)
+
+    def _path_request(self, path_length, quantities, band_edges, cumulative, range_policy):
+        """Checks every argument of compute_path (before anything touches the GPU)."""
+        if self.group is not None:
+            raise NotImplementedError("compute_path does not split paths over processes yet "
+                                      "(group is set): the levels of a path would need a sum "
+                                      "over ranks before exp(-tau).")
+        shape = tuple(self.atmosphere.temperature.shape)
+        lengths = np.asarray(path_length, dtype=np.float64)
+        if lengths.shape != shape:
+            raise ValueError(f"path_length has shape {lengths.shape}, the atmosphere {shape}.")
+        if not np.all(np.isfinite(lengths)) or np.any(lengths < 0.):
+            raise ValueError("path lengths must be finite and >= 0.")
+        if lengths.size == 0:
+            raise ValueError("the atmosphere has no levels.")
+        if isinstance(quantities, str):
+            quantities = (quantities,)
+        quantities = tuple(quantities)
+        unknown = [q for q in quantities if q not in PATH_QUANTITIES]
+        if unknown or not quantities:
+            raise ValueError(f"quantities must be a non-empty selection of {PATH_QUANTITIES}, "
+                             f"not {quantities}.")
+        quantities = tuple(q for q in PATH_QUANTITIES if q in quantities)
+        if not (cumulative is None or (isinstance(cumulative, str) and
+                                       cumulative in PATH_CUMULATIVE)):
+            raise ValueError(f"cumulative must be one of {PATH_CUMULATIVE}, not {cumulative!r}.")
+        if range_policy not in ("reference", "skip"):
+            raise ValueError(f"unknown range_policy {range_policy!r}.")
+        edges = starts = None
+        if band_edges is not None:
+            if self.grid.size > 1 and not np.all(np.diff(self.grid) > 0.):
+                raise ValueError("band means need an increasing grid.")
+            starts = band_columns(self.grid, band_edges)
+            edges = np.asarray(band_edges, dtype=np.float64)
+        return _PathRequest(lengths=np.ascontiguousarray(lengths.ravel()), shape=shape,
+                            quantities=quantities, edges=edges, starts=starts,
+                            cumulative=cumulative)
+
+    def _compute_path_levels(self, request, remove_pedestal, range_policy):
+        """{quantity: array [paths or levels, columns or bands]}: the "total" block of a run of
+        levels at a time, queued like _compute_levels queues it, then the path kernels on it."""
+        temperature = self.atmosphere.temperature.ravel()
+        pressure = self.atmosphere.pressure.ravel()
+        mole_fractions = {name: x.ravel() for name, x in self.atmosphere.gases.items()}
         levels = temperature.size
+        per_path = request.shape[-1] if request.shape else 1
+        paths = levels//per_path
         v0, vn, n_per_v = grid_arguments(self.grid)
         n = (vn - v0)*n_per_v
         columns = self.grid.size
-        if levels == 0:
-            # A rank without levels (fewer levels than GPUs): empty blocks of the right shape.
-            if mode == "total":
-                return {"total": np.zeros((0, columns))}
-            tail = (len(MECHANISMS), columns) if mode == "all" else (columns,)
-            return {"{}_absorption".format(name): np.zeros((0,) + tail)
-                    for name in self.atmosphere.gases}
-        in_hbm = levels*n*8 <= self.device_output_limit
-        engine = None
+        # Runs of consecutive levels when the block would not fit: tau carries over in HBM.
+        run = levels if levels*n*8 <= self.device_output_limit else \
+            max(1, self.device_output_limit//(n*8))
+        run = min(run, _MAX_RUN_LEVELS)
+        from_last = request.cumulative == "from_last"
+        cumulative = request.cumulative is not None
+        starts = request.starts
+        width = columns if starts is None else starts.size - 1
+        runs = [(a, min(a + run, levels)) for a in range(0, levels, run)]
+        if from_last:
+            runs.reverse()
 
-        # Queue every kernel before waiting: one batched call per (molecule, mechanism) for
-        # all levels, n*k applied in the kernel epilogue, spectra left in HBM until the end;
-        # the sums over mechanisms ("gas") and over gases ("total") happen on the device.
-        # Within a block the short continuum and cross-section kernels go first and the lines
-        # last: the lines call that completes the LAST block of the whole call hands its result
-        # to the host itself, piece by piece while it computes (lbl_compute_streamed), so no
-        # copy is left standing behind the last kernel.
-        blocks = {}             # (gas, mechanism) -> host array (only when too large for HBM)
-        zero_fills = []         # row views of results that no mechanism writes
-        results = {}            # gas -> its finished array, being filled by queued copies
-        in_flight = []          # blocks in HBM to release once everything has arrived
-        total = None
+        engine, present, heavy = self._present_gases(temperature, pressure, mole_fractions)
+        if engine is None:
+            from .engine import default_engine
+            engine = default_engine(self.device)
+        if heavy is not None:
+            present = [heavy] + present[:-1]
+        results = {q: engine.host_array((levels if cumulative else paths, width))
+                   for q in request.quantities}
+        # One block of `run` levels for beta (and, cumulative, for each output) serves every run;
+        # the shorter last run uses its leading rows.  Together with the carry and per-path outputs
+        # that is all this call holds in HBM.
+        band_width = width if starts is not None else n
+        taken = []
+        with engine.pipeline:
+            try:
+                carry = engine.blocks.take(paths, n)
+                taken.append(carry)
+                beta = engine.blocks.take(run, n)
+                taken.append(beta)
+                outputs = {}
+                for q in request.quantities:
+                    outputs[q] = engine.blocks.take(run if cumulative else paths, band_width)
+                    taken.append(outputs[q])
+                for index, (a, b) in enumerate(runs):
+                    if index > 0:
+                        # The previous run's block and outputs are written again below: what still
+                        # reads them -- its sweep, its copies to the host -- is done first.
+                        engine.synchronize()
+                    queue = _Queue(self, temperature[a:b], pressure[a:b],
+                                   {k: v[a:b] for k, v in mole_fractions.items()},
+                                   remove_pedestal, range_policy, self.delivery_pieces)
+                    total = _Sum(engine, b - a, n,
+                                 buffer=beta if b - a == run else beta.rows(b - a))
+                    if present:
+                        self._queue_total(queue, engine, present, heavy, total, None)
+                    else:
+                        engine.fill_zero(total.buffer, asynchronous=True)
+                    run_outputs = outputs if not cumulative or b - a == run else \
+                        {q: block.rows(b - a) for q, block in outputs.items()}
+                    engine.path_compute(
+                        total.buffer, columns, paths, per_path, a, request.lengths[a:b], carry,
+                        optical_depth=run_outputs.get("optical_depth"),
+                        transmittance=run_outputs.get("transmittance"), band_start=starts,
+                        cumulative=cumulative, from_last=from_last, asynchronous=True)
+                    if cumulative:
+                        for q in request.quantities:
+                            run_outputs[q].to_host_into(results[q][a:b], width, asynchronous=True)
+                if not cumulative:
+                    for q in request.quantities:
+                        outputs[q].to_host_into(results[q], width, asynchronous=True)
+                engine.synchronize()
+            except BaseException:
+                try:
+                    engine.cancel_deferred()
+                    engine.synchronize()
+                except Exception:       # the first error is the one to report
+                    pass
+                raise
+            finally:
+                for block in taken:
+                    engine.blocks.give(block)
+        return results
+
+    def _create_path_dataset(self, values, request):
+        """compute_path's result from {quantity: [paths or levels, columns or bands]}, in the
+        conventions of _create_output_dataset."""
+        dims = list(self.atmosphere.dims)
+        shape = list(request.shape)
+        if request.cumulative is None:
+            dims, shape = dims[:-1], shape[:-1]
+        if request.edges is None:
+            dims.append("wavenumber")
+            coords = {"wavenumber": (self.grid, {"units": "cm-1"})}
+        else:
+            dims.append("band")
+            coords = {"band_lower": (request.edges[:-1], {"units": "cm-1"}),
+                      "band_upper": (request.edges[1:], {"units": "cm-1"}),
+                      "band_points": (np.diff(request.starts), {})}
+        variables = {q: np.asarray(values[q]).reshape(shape + [-1]) for q in request.quantities}
+        units = {"optical_depth": {"units": "1"}, "transmittance": {"units": "1"}}
+        xarray = _optional_xarray()
+        if xarray is None:
+            out = {name: value for name, (value, _) in coords.items()}
+            out.update(variables)
+            return out
+        DataArray, Dataset = xarray.DataArray, xarray.Dataset
+        axis = dims[-1]
+        return Dataset(
+            data_vars={q: DataArray(v, dims=dims, attrs=units[q]) for q, v in variables.items()},
+            coords={name: DataArray(value, dims=(axis,), attrs=attrs)
+                    for name, (value, attrs) in coords.items()})
+
+    def _present_gases(self, temperature, pressure, mole_fractions):
+        """(engine, gases, heaviest): the gases of the atmosphere that some mechanism computes, as
+        (name, Gas or None, continua, cross-section or None), lightest lines table first; the
+        last entry when it has lines; the engine they share (None without any)."""
+        engine = None
         present = []
         for name in self.atmosphere.gases:
             data = self._molecule(name)
@@ -346,6 +577,96 @@ class Spectroscopy(object):
         # (profiles/r03_ab_api.txt).
         present.sort(key=lambda entry: entry[1].num_lines if entry[1] is not None else -1)
         heavy = present[-1] if present and present[-1][1] is not None else None
+        return engine, present, heavy
+
+    def _queue_total(self, queue, engine, present, heavy, total, deliver):
+        """Queues every gas's kernels into the one block `total` (a _Sum; `present` in "total"
+        order: the heavy gas first).  deliver: the page-locked [levels, columns] view the last
+        lines call hands the finished block to, piece by piece -- or None: the block stays in
+        HBM, complete behind what is queued.  Returns True when `deliver` was not handed the
+        finished block (the caller copies it behind everything)."""
+        lines_into, slots_into = queue.lines_into, queue.slots_into
+        # Every gas adds into one block.  The heavy gas's slot kernels go first (the first of them
+        # writes the block -- or the engine clears it), then its lines call, kept back; the other
+        # gases' lines with their short continuum and cross-section kernels behind them; then the
+        # heavy gas's last kernels and the delivery of the finished block.
+        kept_back = False
+        if heavy is not None and self.total_order == "heavy_last":
+            # The short continuum and cross-section kernels of every gas first, the lighter gases'
+            # lines behind them, the heaviest gas last: each run of tiles it finishes completes
+            # that part of the block, which goes to the host while the next run computes (its
+            # pedestal pass is short since round 4, so the first copy starts a third of the way
+            # into the call instead of behind everything).  (Lines first and the slot kernels
+            # behind them was tried: the slot kernels then wait for the first gas's pedestal to be
+            # applied and the heaviest gas is queued later, 1.58 -> 1.70 ms.)
+            # (every continuum of every gas in ONE pass -- the block is written once -- then the
+            # cross-sections.  The additions into the block therefore run c(g1), c(g2), ..., x(g1),
+            # x(g2), ..., lines -- not the reference's gas-by-gas order, spectroscopy.py:225-234:
+            # the continua are bit-identical to the one-by-one sum among themselves, the total may
+            # differ from the reference's order of additions in its last bits, within the parity
+            # bar: tests/test_gpu_api.py::test_total_with_continuum_and_cross_section_of_two_gases)
+            queue.continua_into([c for _, _, continua_here, _ in present
+                                 for c in continua_here], total)
+            for name, gas, continua_here, cross in present:
+                slots_into(name, [], cross, total, total)
+            if not total.written:
+                engine.fill_zero(total.buffer, asynchronous=True)
+                total.take()
+            for name, gas, continua_here, cross in present[1:]:
+                if gas is not None:
+                    lines_into(name, gas, total)
+            lines_into(heavy[0], heavy[1], total, deliver=deliver)
+            return False
+        for index, (name, gas, continua_here, cross) in enumerate(present):
+            if heavy is not None and index == 0:
+                slots_into(name, continua_here, cross, total, total)
+                if not total.written:
+                    engine.fill_zero(total.buffer, asynchronous=True)
+                    total.take()
+                lines_into(name, gas, total, deliver=deliver, defer=deliver is not None)
+                kept_back = deliver is not None and engine.deferred()
+                continue
+            if gas is not None:
+                lines_into(name, gas, total)
+            slots_into(name, continua_here, cross, total, total)
+        if kept_back:
+            engine.finish_deferred()
+            return False
+        # (No gas with lines -- or a call the engine could not keep back, e.g. without a pedestal
+        # pass: it added at once and delivered a block that was not complete; the copy the caller
+        # queues behind everything is the one that counts.)
+        return True
+
+    def _compute_levels(self, temperature, pressure, mole_fractions, mode, remove_pedestal,
+                        range_policy):
+        """The three mechanism slots for a flat list of levels: {variable name: array with the
+        levels as leading dimension} ("total" under mode "total")."""
+        levels = temperature.size
+        v0, vn, n_per_v = grid_arguments(self.grid)
+        n = (vn - v0)*n_per_v
+        columns = self.grid.size
+        if levels == 0:
+            # A rank without levels (fewer levels than GPUs): empty blocks of the right shape.
+            if mode == "total":
+                return {"total": np.zeros((0, columns))}
+            tail = (len(MECHANISMS), columns) if mode == "all" else (columns,)
+            return {"{}_absorption".format(name): np.zeros((0,) + tail)
+                    for name in self.atmosphere.gases}
+        in_hbm = levels*n*8 <= self.device_output_limit
+
+        # Queue every kernel before waiting: one batched call per (molecule, mechanism) for
+        # all levels, n*k applied in the kernel epilogue, spectra left in HBM until the end;
+        # the sums over mechanisms ("gas") and over gases ("total") happen on the device.
+        # Within a block the short continuum and cross-section kernels go first and the lines
+        # last: the lines call that completes the LAST block of the whole call hands its result
+        # to the host itself, piece by piece while it computes (lbl_compute_streamed), so no
+        # copy is left standing behind the last kernel.
+        blocks = {}             # (gas, mechanism) -> host array (only when too large for HBM)
+        zero_fills = []         # row views of results that no mechanism writes
+        results = {}            # gas -> its finished array, being filled by queued copies
+        in_flight = []          # blocks in HBM to release once everything has arrived
+        total = None
+        engine, present, heavy = self._present_gases(temperature, pressure, mole_fractions)
         if heavy is not None and mode == "total":
             present = [heavy] + present[:-1]
 
@@ -354,38 +675,9 @@ class Spectroscopy(object):
         # puts gaps into that queue, 3.6 -> 4.1 ms per call.)
         pieces = 1 if mode == "all" else self.delivery_pieces
 
-        def lines_into(name, gas, block, deliver=None, defer=False):
-            gas.absorption_coefficients(
-                temperature, pressure, mole_fractions[name], self.grid,
-                remove_pedestal=remove_pedestal, range_policy=range_policy,
-                scale_density=True, out=block.buffer, accumulate=block.take(),
-                asynchronous=True, farfield=self.farfield, deliver=deliver,
-                pieces=pieces, defer_finish=defer)
-
-        def continua_into(continua_list, continuum_sum):
-            # All of them in one pass over the grid where they are this package's (one launch that
-            # writes the block once instead of a read-modify-write pass per continuum; the same
-            # bits: csrc/continuum.h, group kernels); anything else one by one.
-            if not continua_list:
-                return
-            from .mt_ckd import BandedContinuum, spectra_levels_many
-            if all(isinstance(c, BandedContinuum) for c in continua_list):
-                spectra_levels_many(continua_list, temperature, pressure, mole_fractions,
-                                    self.grid, continuum_sum.buffer,
-                                    accumulate=continuum_sum.take(), asynchronous=True)
-                return
-            for continuum in continua_list:
-                continuum.spectra_levels(temperature, pressure, mole_fractions, self.grid,
-                                         out=continuum_sum.buffer,
-                                         accumulate=continuum_sum.take(), asynchronous=True)
-
-        def slots_into(name, continua_here, cross, continuum_sum, cross_sum):
-            continua_into(continua_here, continuum_sum)
-            if cross is not None:
-                cross.absorption_coefficients(self.grid, temperature, pressure,
-                                              volume_mixing_ratio=mole_fractions[name],
-                                              out=cross_sum.buffer, accumulate=cross_sum.take(),
-                                              asynchronous=True)
+        queue = _Queue(self, temperature, pressure, mole_fractions, remove_pedestal, range_policy,
+                       pieces)
+        lines_into, slots_into = queue.lines_into, queue.slots_into
 
         # Everything from the first queued call to the final wait is one pipeline on the engine:
         # calls add into shared blocks in a fixed order and one of them may be kept back, so
@@ -415,66 +707,12 @@ class Spectroscopy(object):
                                 self.grid, temperature, pressure,
                                 volume_mixing_ratio=mole_fractions[name])
                 elif mode == "total" and present:
-                    # Every gas adds into one block.  The heavy gas's slot kernels go first (the
-                    # first of them writes the block -- or the engine clears it), then its lines
-                    # call, kept back; the other gases' lines with their short continuum and cross-
-                    # section kernels behind them; then the heavy gas's last kernels and the
-                    # delivery of the finished block.
                     total = _Sum(engine, levels, n)
                     results["total"] = engine.host_array((levels, columns))
-                    kept_back = False
-                    if heavy is not None and self.total_order == "heavy_last":
-                        # The short continuum and cross-section kernels of every gas first, the
-                        # lighter gases' lines behind them, the heaviest gas last: each run of tiles
-                        # it finishes completes that part of the block, which goes to the host while
-                        # the next run computes (its pedestal pass is short since round 4, so the
-                        # first copy starts a third of the way into the call instead of behind
-                        # everything).  (Lines first and the slot kernels behind them was tried: the
-                        # slot kernels then wait for the first gas's pedestal to be applied and the
-                        # heaviest gas is queued later, 1.58 -> 1.70 ms.)
-                        # (every continuum of every gas in ONE pass -- the block is written once --
-                        # then the cross-sections.  The additions into the block therefore run
-                        # c(g1), c(g2), ..., x(g1), x(g2), ..., lines -- not the reference's
-                        # gas-by-gas order, spectroscopy.py:225-234: the continua are bit-identical
-                        # to the one-by-one sum among themselves, the total may differ from the
-                        # reference's order of additions in its last bits, within the parity bar:
-                        # tests/test_gpu_api.py::test_total_with_continuum_and_cross_section_of_two_gases)
-                        continua_into([c for _, _, continua_here, _ in present
-                                       for c in continua_here], total)
-                        for name, gas, continua_here, cross in present:
-                            slots_into(name, [], cross, total, total)
-                        if not total.written:
-                            engine.fill_zero(total.buffer, asynchronous=True)
-                            total.take()
-                        for name, gas, continua_here, cross in present[1:]:
-                            if gas is not None:
-                                lines_into(name, gas, total)
-                        lines_into(heavy[0], heavy[1], total, deliver=results["total"])
-                        in_flight.append(total)
-                        present = []
-                    for index, (name, gas, continua_here, cross) in enumerate(present):
-                        if heavy is not None and index == 0:
-                            slots_into(name, continua_here, cross, total, total)
-                            if not total.written:
-                                engine.fill_zero(total.buffer, asynchronous=True)
-                                total.take()
-                            lines_into(name, gas, total, deliver=results["total"], defer=True)
-                            kept_back = engine.deferred()
-                            continue
-                        if gas is not None:
-                            lines_into(name, gas, total)
-                        slots_into(name, continua_here, cross, total, total)
-                    if heavy is not None and kept_back:
-                        engine.finish_deferred()
-                        in_flight.append(total)
-                    elif self.total_order == "heavy_last" and heavy is not None:
-                        pass
-                    else:
-                        # (No gas with lines -- or a call the engine could not keep back, e.g.
-                        # without a pedestal pass: it added at once and delivered a block that was
-                        # not complete; this copy, queued behind everything, is the one that
-                        # counts.)
+                    if self._queue_total(queue, engine, present, heavy, total, results["total"]):
                         in_flight.append(total.into(results["total"]))
+                    else:
+                        in_flight.append(total)
                 else:
                     for index, (name, gas, continua_here, cross) in enumerate(present):
                         last = index + 1 == len(present)
