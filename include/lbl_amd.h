@@ -215,6 +215,45 @@ int lbl_path_compute(lbl_engine *engine, double *beta, int64_t row_stride, int64
                      const int64_t *band_start, double *carry, double *optical_depth,
                      double *transmittance, int32_t flags);
 
+/* Thermal emission along paths (Spectroscopy.compute_radiance): the radiance that leaves each
+ * path, with the levels as isothermal layers.  beta, row_stride, columns, n_paths,
+ * levels_per_path, level_begin, level_count, path_length, carry, band_start / n_bands,
+ * LBL_PATH_CUMULATIVE, LBL_PATH_CONTINUE and LBL_ASYNC as for lbl_path_compute; a path's
+ * running radiance lives in its carry row between runs.
+ *   grid: a handle of lbl_grid_load with at least `columns` points; nu_j is its value j [cm-1].
+ *   temperature (host, level_count values [K], finite and > 0): each level's temperature.
+ *   boundary_temperature / boundary_emissivity (host, n_paths values each, or NULL for all 0 /
+ *   all 1): what enters path p before its first level in sweep order; a boundary temperature of
+ *   0 means no source behind the path, emissivities lie in [0, 1].
+ * With C1 = LBL_PLANCK_C1 and C2 = LBL_PLANCK_C2 (CODATA 2018 h, c, k, exactly):
+ *   B(nu, T) = (((C1*nu)*nu)*nu) / expm1((C2*nu)/T), 0 for nu <= 0  [W m-2 sr-1 (cm-1)-1]
+ *   level l, x = s_l*beta_l: t = exp(-x), a = -expm1(-x), source B(nu, T_l) (isothermal layer)
+ *   I = eps*B(nu, T_boundary) (0 without a boundary), then I = I*t + B_l*a for every level in
+ *   sweep order: upward from the path's first level, or with LBL_PATH_FROM_LAST (allowed here
+ *   without LBL_PATH_CUMULATIVE) downward from its last.  Each product and sum rounded as written.
+ *   brightness temperature = (C2*nu) / log1p((((C1*nu)*nu)*nu) / I), 0 where I <= 0 or nu <= 0.
+ * Outputs (device; LBL_PATH_RADIANCE -> radiance, LBL_PATH_BRIGHTNESS -> brightness_temperature):
+ *   n_bands == 0: row p of [n_paths][row_stride], written by the run that finishes path p, or
+ *                 with LBL_PATH_CUMULATIVE row r of [level_count][row_stride]: I just after level
+ *                 level_begin + r;
+ *   n_bands > 0:  the arithmetic mean of I over each band, NaN for an empty band, as
+ *                 lbl_path_compute forms it (radiance only: LBL_PATH_BRIGHTNESS with bands is
+ *                 LBL_BAD_ARGUMENT).  With LBL_PATH_CUMULATIVE the run's rows of beta are
+ *                 overwritten by the cumulative radiance, which the means then read.
+ * LBL_BAD_ARGUMENT (message in lbl_last_error) as for lbl_path_compute, and for an unknown or
+ * short grid, temperatures that are not finite and > 0, boundary temperatures that are negative
+ * or not finite, emissivities outside [0, 1]; the engine stays usable. */
+#define LBL_PLANCK_C1  1.1910429723971885e-08  /* 2 h c^2 1e8 [W m-2 sr-1 (cm-1)-4]          */
+#define LBL_PLANCK_C2  1.4387768775039338      /* h c / k 1e2 [cm K]                          */
+#define LBL_PATH_RADIANCE      0x2000
+#define LBL_PATH_BRIGHTNESS    0x4000   /* brightness temperature [K]                        */
+int lbl_path_radiance(lbl_engine *engine, double *beta, int64_t row_stride, int64_t columns,
+                      int32_t grid, int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                      int32_t level_count, const double *path_length, const double *temperature,
+                      const double *boundary_temperature, const double *boundary_emissivity,
+                      int32_t n_bands, const int64_t *band_start, double *carry, double *radiance,
+                      double *brightness_temperature, int32_t flags);
+
 /* Options (thirteen; anything else is LBL_BAD_ARGUMENT):
  *   "prep"                LBL_PREP_DEVICE (default) / LBL_PREP_HOST: where the per-line scalars are formed
  *   "points_per_lane"     0 = by the grid (default), 1/2/4/8 grid points per lane of the accumulate kernel

@@ -32,6 +32,7 @@
 #include "line_prep.h"
 #include "path.h"
 #include "pedestal.h"
+#include "radiance.h"
 #include "tile_schedule.h"
 
 #include "engine_core.h"
@@ -543,5 +544,6 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 }  // extern "C"
 
 #include "continuum_entry.inc"
+#include "radiance_entry.inc"
 #include "xsec_entry.inc"
 #include "sqlite_entry.inc"

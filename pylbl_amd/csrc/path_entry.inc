@@ -25,6 +25,114 @@ bool aligned16(const void * p)
     return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
 
+// The bands of a call: band b is columns [band_start[b], band_start[b + 1]), cut at multiples of
+// kPathSegment into segments.  Staged as 8-byte words after the call's other tables: band_start
+// [n_bands + 1], each band's first segment [n_bands + 1], then the segments (begin, end).
+struct PathBands
+{
+    int n_bands = 0;
+    std::vector<long long> band_segment;
+    long long n_segments = 0;
+
+    // nullptr, or what is wrong with the bands.
+    const char * check(int32_t bands, const int64_t * band_start, int64_t columns)
+    {
+        if (bands < 0 || (bands > 0 && band_start == nullptr))
+        {
+            return "n_bands < 0, or band_start is NULL.";
+        }
+        n_bands = bands;
+        if (n_bands == 0) return nullptr;
+        if (band_start[0] < 0 || band_start[n_bands] > columns)
+        {
+            return "band_start out of [0, columns].";
+        }
+        for (int b = 0; b < n_bands; ++b)
+        {
+            if (band_start[b + 1] < band_start[b]) return "band_start must not decrease.";
+        }
+        band_segment.resize((size_t)n_bands + 1);
+        for (int b = 0; b < n_bands; ++b)
+        {
+            band_segment[b] = n_segments;
+            for (long long c = band_start[b]; c < band_start[b + 1];
+                 c = (c/kPathSegment + 1)*kPathSegment)
+            {
+                n_segments += 1;
+            }
+        }
+        band_segment[n_bands] = n_segments;
+        if (n_segments > std::numeric_limits<int32_t>::max()) return "too many segments.";
+        return nullptr;
+    }
+
+    size_t words() const
+    {
+        return n_bands > 0 ? 2*((size_t)n_bands + 1) + 2*(size_t)n_segments : 0;
+    }
+
+    void stage(long long * table, const int64_t * band_start) const
+    {
+        if (n_bands == 0) return;
+        long long * segments = table + 2*((size_t)n_bands + 1);
+        long long s = 0;
+        for (int b = 0; b <= n_bands; ++b)
+        {
+            table[b] = band_start[b];
+            table[n_bands + 1 + b] = band_segment[b];
+        }
+        for (int b = 0; b < n_bands; ++b)
+        {
+            for (long long c = band_start[b]; c < band_start[b + 1];)
+            {
+                const long long next = std::min<long long>((c/kPathSegment + 1)*kPathSegment,
+                                                           band_start[b + 1]);
+                segments[2*s] = c;
+                segments[2*s + 1] = next;
+                s += 1;
+                c = next;
+            }
+        }
+    }
+
+    // Queues out[r][b] = the mean over band b of row r of `values` (of exp(-value) with
+    // `transmittance`) for `rows` rows `row_stride` apart.  d_table: the staged words on the device.
+    void means(PathWorkspace & w, const long long * d_table, const double * values,
+               long long row_stride, int rows, bool transmittance, double * out,
+               hipStream_t stream) const
+    {
+        // Rows go in the grid's y dimension, at most kPathGridY per launch; the chunks run one
+        // after the other on this stream and share the partial sums.
+        const int chunk_rows = std::min(rows, kPathGridY);
+        w.partial.reserve((size_t)chunk_rows*(size_t)std::max<long long>(n_segments, 1));
+        const long long * d_band_start = d_table;
+        const long long * d_band_segment = d_table + n_bands + 1;
+        const PathSegment * d_segments =
+            reinterpret_cast<const PathSegment *>(d_table + 2*((long long)n_bands + 1));
+        for (int r0 = 0; r0 < rows; r0 += kPathGridY)
+        {
+            const int chunk = std::min(rows - r0, kPathGridY);
+            if (n_segments > 0)
+            {
+                const dim3 partial_grid(
+                    (unsigned)((n_segments + kPathWaves - 1)/kPathWaves), (unsigned)chunk);
+                hipLaunchKernelGGL(path_band_partial_kernel, partial_grid,
+                                   dim3(kPathThreads), 0, stream,
+                                   values + (long long)r0*row_stride, row_stride,
+                                   d_segments, (int)n_segments, transmittance ? 1 : 0,
+                                   w.partial.data);
+                HIP_TRY(hipGetLastError());
+            }
+            const dim3 mean_grid((unsigned)((n_bands + kPathThreads - 1)/kPathThreads),
+                                 (unsigned)chunk);
+            hipLaunchKernelGGL(path_band_mean_kernel, mean_grid, dim3(kPathThreads), 0,
+                               stream, w.partial.data, (int)n_segments, d_band_segment,
+                               d_band_start, (int)n_bands, out + (long long)r0*n_bands);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -79,41 +187,8 @@ int lbl_path_compute(lbl_engine * engine, double * beta, int64_t row_stride, int
             return bad("path lengths must be finite and >= 0.");
         }
     }
-    if (n_bands < 0 || (n_bands > 0 && band_start == nullptr))
-    {
-        return bad("n_bands < 0, or band_start is NULL.");
-    }
-    if (n_bands > 0)
-    {
-        if (band_start[0] < 0 || band_start[n_bands] > columns)
-        {
-            return bad("band_start out of [0, columns].");
-        }
-        for (int b = 0; b < n_bands; ++b)
-        {
-            if (band_start[b + 1] < band_start[b]) return bad("band_start must not decrease.");
-        }
-    }
-
-    // The tables: lengths [level_count], then (bands) band_start [n_bands + 1], band_segment
-    // [n_bands + 1] and the segments, as 8-byte words.
-    std::vector<long long> band_segment;
-    long long n_segments = 0;
-    if (n_bands > 0)
-    {
-        band_segment.resize((size_t)n_bands + 1);
-        for (int b = 0; b < n_bands; ++b)
-        {
-            band_segment[b] = n_segments;
-            for (long long c = band_start[b]; c < band_start[b + 1];
-                 c = (c/kPathSegment + 1)*kPathSegment)
-            {
-                n_segments += 1;
-            }
-        }
-        band_segment[n_bands] = n_segments;
-        if (n_segments > std::numeric_limits<int32_t>::max()) return bad("too many segments.");
-    }
+    PathBands bands;
+    if (const char * problem = bands.check(n_bands, band_start, columns)) return bad(problem);
     // Rows whose band means this call forms: every level of the run (cumulative) or the paths
     // the run finishes.
     int band_rows = 0, band_row0 = 0;
@@ -134,33 +209,11 @@ int lbl_path_compute(lbl_engine * engine, double * beta, int64_t row_stride, int
     {
         HIP_TRY(hipSetDevice(engine->device));
         PathWorkspace & w = engine->path;
-        const size_t words = (size_t)level_count +
-                             (n_bands > 0 ? 2*((size_t)n_bands + 1) + 2*(size_t)n_segments : 0);
+        // The tables: lengths [level_count], then the bands' words.
+        const size_t words = (size_t)level_count + bands.words();
         double * staged = w.stage(words);
         std::memcpy(staged, path_length, (size_t)level_count*8);
-        long long * table = reinterpret_cast<long long *>(staged + level_count);
-        if (n_bands > 0)
-        {
-            long long * segments = table + 2*((size_t)n_bands + 1);
-            long long s = 0;
-            for (int b = 0; b <= n_bands; ++b)
-            {
-                table[b] = band_start[b];
-                table[n_bands + 1 + b] = band_segment[b];
-            }
-            for (int b = 0; b < n_bands; ++b)
-            {
-                for (long long c = band_start[b]; c < band_start[b + 1];)
-                {
-                    const long long next = std::min<long long>((c/kPathSegment + 1)*kPathSegment,
-                                                               band_start[b + 1]);
-                    segments[2*s] = c;
-                    segments[2*s + 1] = next;
-                    s += 1;
-                    c = next;
-                }
-            }
-        }
+        bands.stage(reinterpret_cast<long long *>(staged + level_count), band_start);
         hipStream_t stream = engine->stream;
         // Ordered like a plain compute call: after everything queued on the other lanes (the
         // block's writers among them) -- by events when the caller does not wait, so that the
@@ -259,40 +312,13 @@ int lbl_path_compute(lbl_engine * engine, double * beta, int64_t row_stride, int
             // rows; outputs [rows][n_bands] from the first row this call forms.
             const double * values = cumulative ? beta : carry + (long long)band_row0*row_stride;
             const long long out_row0 = cumulative ? 0 : band_row0;
-            // Rows go in the grid's y dimension, at most kPathGridY per launch; the chunks run one
-            // after the other on this stream and share the partial sums.
-            const int chunk_rows = std::min(band_rows, kPathGridY);
-            w.partial.reserve((size_t)chunk_rows*(size_t)std::max<long long>(n_segments, 1));
-            const long long * d_band_start = d_table;
-            const long long * d_band_segment = d_table + n_bands + 1;
-            const PathSegment * d_segments =
-                reinterpret_cast<const PathSegment *>(d_table + 2*((long long)n_bands + 1));
             for (int q = 0; q < 2; ++q)
             {
                 const bool trans = q == 1;
                 if (!(trans ? want_trans : want_tau)) continue;
                 double * out = (trans ? transmittance : optical_depth) + out_row0*n_bands;
-                for (int r0 = 0; r0 < band_rows; r0 += kPathGridY)
-                {
-                    const int rows = std::min(band_rows - r0, kPathGridY);
-                    if (n_segments > 0)
-                    {
-                        const dim3 partial_grid(
-                            (unsigned)((n_segments + kPathWaves - 1)/kPathWaves), (unsigned)rows);
-                        hipLaunchKernelGGL(path_band_partial_kernel, partial_grid,
-                                           dim3(kPathThreads), 0, stream,
-                                           values + (long long)r0*row_stride, (long long)row_stride,
-                                           d_segments, (int)n_segments, trans ? 1 : 0,
-                                           w.partial.data);
-                        HIP_TRY(hipGetLastError());
-                    }
-                    const dim3 mean_grid((unsigned)((n_bands + kPathThreads - 1)/kPathThreads),
-                                         (unsigned)rows);
-                    hipLaunchKernelGGL(path_band_mean_kernel, mean_grid, dim3(kPathThreads), 0,
-                                       stream, w.partial.data, (int)n_segments, d_band_segment,
-                                       d_band_start, (int)n_bands, out + (long long)r0*n_bands);
-                    HIP_TRY(hipGetLastError());
-                }
+                bands.means(w, d_table, values, (long long)row_stride, band_rows, trans, out,
+                            stream);
                 engine->lanes[0].note_write(out, (long long)band_rows*n_bands*8, stream);
             }
         }

@@ -26,6 +26,8 @@ RANGE_POLICIES = {"reference": RANGE_REFERENCE, "skip": RANGE_SKIP}
 # lbl_path_compute flags: a namespace of their own, clear of the call flags above.
 PATH_OPTICAL_DEPTH, PATH_TRANSMITTANCE, PATH_CUMULATIVE, PATH_FROM_LAST, PATH_CONTINUE = \
     0x100, 0x200, 0x400, 0x800, 0x1000
+# lbl_path_radiance adds two outputs to them.
+PATH_RADIANCE, PATH_BRIGHTNESS = 0x2000, 0x4000
 
 EXPORTED_SYMBOLS = (
     "lbl_engine_create", "lbl_engine_destroy", "lbl_last_error", "lbl_molecule_load",
@@ -41,7 +43,7 @@ EXPORTED_SYMBOLS = (
     "lbl_continuum_load", "lbl_continuum_free", "lbl_grid_load", "lbl_grid_free",
     "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
-    "lbl_wing_batches", "lbl_path_compute",
+    "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance",
 )
 
 VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
@@ -173,6 +175,10 @@ def library():
     lib.lbl_path_compute.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
                                      c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int32]
+    lib.lbl_path_radiance.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                      c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int32]
     for name in EXPORTED_SYMBOLS:
         if name not in ("lbl_last_error", "lbl_stream", "lbl_version"):
             getattr(lib, name).restype = c_int32
@@ -672,6 +678,53 @@ class Engine(object):
             starts.ctypes.data if starts is not None else None, carry.pointer,
             optical_depth.pointer if optical_depth is not None else None,
             transmittance.pointer if transmittance is not None else None, flags))
+
+    def path_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
+                      temperature, carry, boundary_temperature=None, boundary_emissivity=None,
+                      radiance=None, brightness_temperature=None, band_start=None,
+                      cumulative=False, from_last=False, asynchronous=False):
+        """Thermal emission along paths through the DeviceSpectra `beta` -- lbl_path_radiance.
+        Rows, lengths, carry, band_start, cumulative, from_last and asynchronous as for
+        path_compute; grid: handle of load_grid (the wavenumbers of the columns); temperature
+        [K] one per row; boundary_temperature [K] (0: none) / boundary_emissivity one per path
+        (None: no boundary / 1).  radiance / brightness_temperature: DeviceSpectra outputs (None:
+        not wanted), shaped as path_compute's."""
+        lengths = _f64(np.atleast_1d(lengths))
+        temperature = _f64(np.atleast_1d(temperature))
+        rows, stride = int(beta.shape[0]), int(beta.shape[1])
+        if lengths.shape != (rows,) or temperature.shape != (rows,):
+            raise ValueError("one path length and one temperature per row of beta.")
+        if tuple(carry.shape) != (int(n_paths), stride):
+            raise ValueError("carry must be [n_paths, row length of beta].")
+        boundary = []
+        for values in (boundary_temperature, boundary_emissivity):
+            if values is not None:
+                values = _f64(np.atleast_1d(values))
+                if values.shape != (int(n_paths),):
+                    raise ValueError("one boundary value per path.")
+            boundary.append(values)
+        starts = None if band_start is None else \
+            np.ascontiguousarray(band_start, dtype=np.int64)
+        n_bands = 0 if starts is None else starts.size - 1
+        flags = (PATH_RADIANCE if radiance is not None else 0) | \
+                (PATH_BRIGHTNESS if brightness_temperature is not None else 0) | \
+                (PATH_CUMULATIVE if cumulative else 0) | (PATH_FROM_LAST if from_last else 0) | \
+                (ASYNC if asynchronous else 0)
+        end = int(level_begin) + rows
+        if (end % int(levels_per_path) if from_last else int(level_begin) % int(levels_per_path)):
+            flags |= PATH_CONTINUE
+        width = n_bands if n_bands > 0 else stride
+        for out in (radiance, brightness_temperature):
+            if out is not None and (out.shape[1] != width or
+                                    out.shape[0] < (rows if cumulative else int(n_paths))):
+                raise ValueError(f"an output has shape {out.shape}, need rows x {width}.")
+        self._check(self.lib.lbl_path_radiance(
+            self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
+            int(levels_per_path), int(level_begin), rows, lengths.ctypes.data,
+            temperature.ctypes.data, *(b.ctypes.data if b is not None else None for b in boundary),
+            n_bands, starts.ctypes.data if starts is not None else None, carry.pointer,
+            radiance.pointer if radiance is not None else None,
+            brightness_temperature.pointer if brightness_temperature is not None else None, flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):

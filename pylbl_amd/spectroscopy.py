@@ -34,6 +34,9 @@ _MAX_RUN_LEVELS = 65535
 # What compute_path checked and derived from its arguments.
 _PathRequest = namedtuple("_PathRequest", ["lengths", "shape", "quantities", "edges", "starts",
                                            "cumulative"])
+# compute_radiance's: the same, with `cumulative` a bool, and one boundary value per path.
+_RadianceRequest = namedtuple("_RadianceRequest", _PathRequest._fields + (
+    "from_last", "boundary_temperature", "boundary_emissivity"))
 
 
 def number_density(temperature, pressure, volume_mixing_ratio):
@@ -65,6 +68,23 @@ def _optional_xarray():
 
 PATH_QUANTITIES = ("optical_depth", "transmittance")
 PATH_CUMULATIVE = (None, "from_first", "from_last")
+RADIANCE_QUANTITIES = ("radiance", "brightness_temperature")
+RADIANCE_DIRECTIONS = ("toward_last", "toward_first")
+
+# Planck's function per wavenumber, B(nu, T) = C1 nu^3 / expm1(C2 nu / T) [W m-2 sr-1 (cm-1)-1]
+# for nu in cm-1: from the exact CODATA 2018 h, c and k (the same literals as LBL_PLANCK_C1 and
+# LBL_PLANCK_C2 in include/lbl_amd.h).
+PLANCK_C1 = 1.1910429723971885e-08     # 2 h c^2 1e8 [W m-2 sr-1 (cm-1)-4]
+PLANCK_C2 = 1.4387768775039338         # h c / k 1e2 [cm K]
+
+_PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
+               "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K"}
+
+
+def _path_layout(shape):
+    """(levels per path, paths) of an atmosphere of this shape: paths run along its last axis."""
+    per_path = shape[-1] if shape else 1
+    return per_path, int(np.prod(shape, dtype=np.int64))//per_path
 
 
 def band_columns(grid, band_edges):
@@ -387,10 +407,78 @@ class Spectroscopy(object):
         values = self._compute_path_levels(request, remove_pedestal, range_policy)
         return self._create_path_dataset(values, request)
 
-    def _path_request(self, path_length, quantities, band_edges, cumulative, range_policy):
-        """Checks every argument of compute_path (before anything touches the GPU)."""
+    def compute_radiance(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
+                         direction="toward_last", quantities=("radiance",), band_edges=None,
+                         cumulative=False, remove_pedestal=None, range_policy="reference"):
+        """Thermal emission along the paths of the atmosphere: the radiance that leaves each
+        path, formed on the GPU from the "total" absorption block like compute_path's optical
+        depth.  Every level is an isothermal layer at its own temperature.
+
+        Paths as in compute_path: the last dimension of the atmosphere, flat level i = p*L + l.
+        With beta the absorption coefficient [m-1] of compute_absorption("total",
+        remove_pedestal, range_policy), s the path lengths, T_l the level temperatures and nu the
+        grid [cm-1], in this order of operations (each product and sum rounded as written):
+            B(nu, T) = (((C1*nu)*nu)*nu) / expm1((C2*nu)/T), 0 for nu <= 0,
+                       [W m-2 sr-1 (cm-1)-1], C1 = PLANCK_C1, C2 = PLANCK_C2;
+            level l, x = s_l*beta_l: t = exp(-x), a = -expm1(-x), source B(nu, T_l);
+            I = eps*B(nu, T_boundary) (I = 0 without a boundary), then I = I*t + B_l*a for
+            each level in sweep order;
+            brightness temperature = (C2*nu) / log1p((((C1*nu)*nu)*nu) / I), 0 where I <= 0 or
+            nu <= 0.
+        For an atmosphere whose paths start at the surface, "toward_last" with the surface as
+        the boundary is the upwelling radiance at the top, "toward_first" the downwelling
+        radiance at the surface.
+
+        Args:
+            path_length: [m], shaped like the atmosphere's temperature, finite and >= 0.
+            boundary_temperature: None (no source behind the paths), a scalar or one per path
+                         (shaped like the atmosphere without its last dimension) [K], finite and
+                         > 0: the source the radiation starts from.
+            boundary_emissivity: a scalar or one per path, in [0, 1].
+            direction: "toward_last" (levels 0 .. L-1: the radiation leaves after level L-1) or
+                       "toward_first" (levels L-1 .. 0).
+            quantities: any of "radiance", "brightness_temperature".
+            band_edges: as in compute_path: the arithmetic mean of the radiance over each band
+                        (NaN without points).  Not with "brightness_temperature".
+            cumulative: True: one result per level, I just after that level in sweep order.
+
+        Returns:
+            Like compute_path: an xarray Dataset when xarray is installed, else a dict --
+            "radiance" ("W m-2 sr-1 (cm-1)-1") / "brightness_temperature" ("K") with the
+            atmosphere's dims (without the last unless cumulative) and "wavenumber" or "band".
+        """
+        request = self._radiance_request(path_length, boundary_temperature, boundary_emissivity,
+                                         direction, quantities, band_edges, cumulative,
+                                         range_policy)
+        if remove_pedestal is None:
+            remove_pedestal = self.continua_backend == "mt_ckd"
+        per_path, paths = _path_layout(request.shape)
+        temperature = np.ascontiguousarray(self.atmosphere.temperature.ravel(), dtype=np.float64)
+        columns = self.grid.size
+
+        def sweeper(engine):
+            from .mt_ckd import resident_grid
+            grid = resident_grid(engine, self.grid)
+
+            def sweep(beta, a, b, carry, outputs):
+                engine.path_radiance(
+                    beta, columns, grid, paths, per_path, a, request.lengths[a:b],
+                    temperature[a:b], carry, boundary_temperature=request.boundary_temperature,
+                    boundary_emissivity=request.boundary_emissivity,
+                    radiance=outputs.get("radiance"),
+                    brightness_temperature=outputs.get("brightness_temperature"),
+                    band_start=request.starts, cumulative=request.cumulative,
+                    from_last=request.from_last, asynchronous=True)
+            return sweep
+        values = self._sweep_runs(request, request.cumulative, request.from_last, remove_pedestal,
+                                  range_policy, sweeper)
+        return self._create_path_dataset(values, request)
+
+    def _path_geometry(self, path_length, name):
+        """(flat lengths, atmosphere shape): the checks of the path lengths that compute_path and
+        compute_radiance share, made before anything touches the GPU."""
         if self.group is not None:
-            raise NotImplementedError("compute_path does not split paths over processes yet "
+            raise NotImplementedError(f"{name} does not split paths over processes yet "
                                       "(group is set): the levels of a path would need a sum "
                                       "over ranks before exp(-tau).")
         shape = tuple(self.atmosphere.temperature.shape)
@@ -401,6 +489,20 @@ class Spectroscopy(object):
             raise ValueError("path lengths must be finite and >= 0.")
         if lengths.size == 0:
             raise ValueError("the atmosphere has no levels.")
+        return np.ascontiguousarray(lengths.ravel()), shape
+
+    def _path_bands(self, band_edges):
+        """(edges, column starts) of band_edges, or (None, None)."""
+        if band_edges is None:
+            return None, None
+        if self.grid.size > 1 and not np.all(np.diff(self.grid) > 0.):
+            raise ValueError("band means need an increasing grid.")
+        starts = band_columns(self.grid, band_edges)
+        return np.asarray(band_edges, dtype=np.float64), starts
+
+    def _path_request(self, path_length, quantities, band_edges, cumulative, range_policy):
+        """Checks every argument of compute_path (before anything touches the GPU)."""
+        lengths, shape = self._path_geometry(path_length, "compute_path")
         if isinstance(quantities, str):
             quantities = (quantities,)
         quantities = tuple(quantities)
@@ -414,34 +516,93 @@ class Spectroscopy(object):
             raise ValueError(f"cumulative must be one of {PATH_CUMULATIVE}, not {cumulative!r}.")
         if range_policy not in ("reference", "skip"):
             raise ValueError(f"unknown range_policy {range_policy!r}.")
-        edges = starts = None
-        if band_edges is not None:
-            if self.grid.size > 1 and not np.all(np.diff(self.grid) > 0.):
-                raise ValueError("band means need an increasing grid.")
-            starts = band_columns(self.grid, band_edges)
-            edges = np.asarray(band_edges, dtype=np.float64)
-        return _PathRequest(lengths=np.ascontiguousarray(lengths.ravel()), shape=shape,
-                            quantities=quantities, edges=edges, starts=starts,
-                            cumulative=cumulative)
+        edges, starts = self._path_bands(band_edges)
+        return _PathRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                            starts=starts, cumulative=cumulative)
+
+    def _radiance_request(self, path_length, boundary_temperature, boundary_emissivity,
+                          direction, quantities, band_edges, cumulative, range_policy):
+        """Checks every argument of compute_radiance (before anything touches the GPU)."""
+        lengths, shape = self._path_geometry(path_length, "compute_radiance")
+        temperature = self.atmosphere.temperature
+        if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
+            raise ValueError("the atmosphere's temperatures must be finite and > 0.")
+        per_path_shape = shape[:-1]
+
+        def per_path(value, name):
+            values = np.asarray(value, dtype=np.float64)
+            if values.shape not in ((), per_path_shape):
+                raise ValueError(f"{name} has shape {values.shape}: give a scalar or one value "
+                                 f"per path, shaped {per_path_shape}.")
+            return np.ascontiguousarray(np.broadcast_to(values, per_path_shape).ravel())
+        if boundary_temperature is None:
+            boundary = None
+        else:
+            boundary = per_path(boundary_temperature, "boundary_temperature")
+            if not np.all(np.isfinite(boundary)) or np.any(boundary <= 0.):
+                raise ValueError("boundary temperatures must be finite and > 0.")
+        emissivity = per_path(boundary_emissivity, "boundary_emissivity")
+        if not np.all((emissivity >= 0.) & (emissivity <= 1.)):
+            raise ValueError("boundary emissivities must lie in [0, 1].")
+        if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
+            raise ValueError(f"direction must be one of {RADIANCE_DIRECTIONS}, not {direction!r}.")
+        if isinstance(quantities, str):
+            quantities = (quantities,)
+        quantities = tuple(quantities)
+        unknown = [q for q in quantities if q not in RADIANCE_QUANTITIES]
+        if unknown or not quantities:
+            raise ValueError(f"quantities must be a non-empty selection of "
+                             f"{RADIANCE_QUANTITIES}, not {quantities}.")
+        quantities = tuple(q for q in RADIANCE_QUANTITIES if q in quantities)
+        if not isinstance(cumulative, (bool, np.bool_)):
+            raise ValueError(f"cumulative must be True or False, not {cumulative!r}.")
+        if range_policy not in ("reference", "skip"):
+            raise ValueError(f"unknown range_policy {range_policy!r}.")
+        if band_edges is not None and "brightness_temperature" in quantities:
+            raise ValueError("brightness_temperature is only available on the grid: band means "
+                             "are formed of the radiance alone.")
+        edges, starts = self._path_bands(band_edges)
+        return _RadianceRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                                starts=starts, cumulative=bool(cumulative),
+                                from_last=direction == "toward_first",
+                                boundary_temperature=boundary, boundary_emissivity=emissivity)
 
     def _compute_path_levels(self, request, remove_pedestal, range_policy):
+        """{quantity: array [paths or levels, columns or bands]} of compute_path."""
+        per_path, paths = _path_layout(request.shape)
+        from_last = request.cumulative == "from_last"
+        cumulative = request.cumulative is not None
+        columns = self.grid.size
+
+        def sweeper(engine):
+            def sweep(beta, a, b, carry, outputs):
+                engine.path_compute(
+                    beta, columns, paths, per_path, a, request.lengths[a:b], carry,
+                    optical_depth=outputs.get("optical_depth"),
+                    transmittance=outputs.get("transmittance"), band_start=request.starts,
+                    cumulative=cumulative, from_last=from_last, asynchronous=True)
+            return sweep
+        return self._sweep_runs(request, cumulative, from_last, remove_pedestal, range_policy,
+                                sweeper)
+
+    def _sweep_runs(self, request, cumulative, from_last, remove_pedestal, range_policy,
+                    sweeper):
         """{quantity: array [paths or levels, columns or bands]}: the "total" block of a run of
-        levels at a time, queued like _compute_levels queues it, then the path kernels on it."""
+        levels at a time, queued like _compute_levels queues it, then the path kernels on it.
+        sweeper(engine) returns sweep(beta, a, b, carry, outputs), which queues the path kernels
+        of the levels [a, b) on their block `beta`, with `outputs` {quantity: DeviceSpectra}."""
         temperature = self.atmosphere.temperature.ravel()
         pressure = self.atmosphere.pressure.ravel()
         mole_fractions = {name: x.ravel() for name, x in self.atmosphere.gases.items()}
         levels = temperature.size
-        per_path = request.shape[-1] if request.shape else 1
-        paths = levels//per_path
+        per_path, paths = _path_layout(request.shape)
         v0, vn, n_per_v = grid_arguments(self.grid)
         n = (vn - v0)*n_per_v
         columns = self.grid.size
-        # Runs of consecutive levels when the block would not fit: tau carries over in HBM.
+        # Runs of consecutive levels when the block would not fit: the sweep carries over in HBM.
         run = levels if levels*n*8 <= self.device_output_limit else \
             max(1, self.device_output_limit//(n*8))
         run = min(run, _MAX_RUN_LEVELS)
-        from_last = request.cumulative == "from_last"
-        cumulative = request.cumulative is not None
         starts = request.starts
         width = columns if starts is None else starts.size - 1
         runs = [(a, min(a + run, levels)) for a in range(0, levels, run)]
@@ -454,6 +615,7 @@ class Spectroscopy(object):
             engine = default_engine(self.device)
         if heavy is not None:
             present = [heavy] + present[:-1]
+        sweep = sweeper(engine)
         results = {q: engine.host_array((levels if cumulative else paths, width))
                    for q in request.quantities}
         # One block of `run` levels for beta (and, cumulative, for each output) serves every run;
@@ -487,11 +649,7 @@ class Spectroscopy(object):
                         engine.fill_zero(total.buffer, asynchronous=True)
                     run_outputs = outputs if not cumulative or b - a == run else \
                         {q: block.rows(b - a) for q, block in outputs.items()}
-                    engine.path_compute(
-                        total.buffer, columns, paths, per_path, a, request.lengths[a:b], carry,
-                        optical_depth=run_outputs.get("optical_depth"),
-                        transmittance=run_outputs.get("transmittance"), band_start=starts,
-                        cumulative=cumulative, from_last=from_last, asynchronous=True)
+                    sweep(total.buffer, a, b, carry, run_outputs)
                     if cumulative:
                         for q in request.quantities:
                             run_outputs[q].to_host_into(results[q][a:b], width, asynchronous=True)
@@ -512,11 +670,11 @@ class Spectroscopy(object):
         return results
 
     def _create_path_dataset(self, values, request):
-        """compute_path's result from {quantity: [paths or levels, columns or bands]}, in the
-        conventions of _create_output_dataset."""
+        """compute_path's and compute_radiance's result from {quantity: [paths or levels,
+        columns or bands]}, in the conventions of _create_output_dataset."""
         dims = list(self.atmosphere.dims)
         shape = list(request.shape)
-        if request.cumulative is None:
+        if not request.cumulative:
             dims, shape = dims[:-1], shape[:-1]
         if request.edges is None:
             dims.append("wavenumber")
@@ -527,7 +685,6 @@ class Spectroscopy(object):
                       "band_upper": (request.edges[1:], {"units": "cm-1"}),
                       "band_points": (np.diff(request.starts), {})}
         variables = {q: np.asarray(values[q]).reshape(shape + [-1]) for q in request.quantities}
-        units = {"optical_depth": {"units": "1"}, "transmittance": {"units": "1"}}
         xarray = _optional_xarray()
         if xarray is None:
             out = {name: value for name, (value, _) in coords.items()}
@@ -536,7 +693,8 @@ class Spectroscopy(object):
         DataArray, Dataset = xarray.DataArray, xarray.Dataset
         axis = dims[-1]
         return Dataset(
-            data_vars={q: DataArray(v, dims=dims, attrs=units[q]) for q, v in variables.items()},
+            data_vars={q: DataArray(v, dims=dims, attrs={"units": _PATH_UNITS[q]})
+                       for q, v in variables.items()},
             coords={name: DataArray(value, dims=(axis,), attrs=attrs)
                     for name, (value, attrs) in coords.items()})
 
