@@ -254,6 +254,41 @@ int lbl_path_radiance(lbl_engine *engine, double *beta, int64_t row_stride, int6
                       int32_t n_bands, const int64_t *band_start, double *carry, double *radiance,
                       double *brightness_temperature, int32_t flags);
 
+/* Longwave fluxes (Spectroscopy.compute_flux): one sweep of n_angles radiances (1..8) through a
+ * run of levels, down from space or, with LBL_PATH_FLUX_UP, up from a Lambertian surface.  beta,
+ * row_stride, columns, grid, n_paths, levels_per_path, level_begin, level_count, temperature,
+ * band_start / n_bands, LBL_PATH_FROM_LAST, LBL_PATH_CONTINUE and LBL_ASYNC as for
+ * lbl_path_radiance (the sweep order sets LBL_PATH_FROM_LAST: the down sweep of a path whose
+ * surface is its first level runs from its last).
+ *   path_length (host, [level_count][n_angles], finite and >= 0): s_l/mu_k, each level's
+ *   length along angle k [m]; weight (host, n_angles values, finite and >= 0): w_k.
+ *   surface_temperature / surface_emissivity (host, n_paths values each; read by the up sweep
+ *   alone, may be NULL on the down sweep): T_s finite and > 0, eps in [0, 1].
+ * With B as in lbl_path_radiance, each product and sum rounded as written, sums from k = 0:
+ *   x = s_{l,k}*beta_l, I_k = I_k*exp(-x) + B(nu, T_l)*(-expm1(-x)) for every level in sweep order;
+ *   down: I_k = 0 at the path's start; the run that finishes a path writes R = sum_k w_k*I_k to
+ *   its row of reflection (device, [n_paths][row_stride]);
+ *   up: I_k = eps*B(nu, T_s) + (1 - eps)*R at the path's start, and the run that starts a path
+ *   replaces R in its row of reflection by the flux at the surface interface;
+ *   F = pi*(sum_k w_k*I_k), pi = 3.141592653589793.
+ * The K radiances of a path live in carry (device, [n_paths][n_angles][row_stride]) between runs.
+ * Outputs (device): level_flux [level_count][row_stride] (not beta): row r is F just after level
+ * level_begin + r.  With n_bands > 0 also the band means of lbl_path_compute: of the level rows
+ * in flux [level_count][n_bands], and on the up sweep of the surface rows of the paths the run
+ * starts in surface_flux [n_paths][n_bands].
+ * LBL_BAD_ARGUMENT (message in lbl_last_error) as for lbl_path_radiance, and for n_angles outside
+ * 1..8, lengths or weights that are negative or not finite, surface temperatures that are not
+ * finite and > 0 or emissivities outside [0, 1] on the up sweep, level_flux == beta, or a band
+ * output that is NULL; the engine stays usable. */
+#define LBL_PATH_FLUX_UP      0x8000    /* the up sweep: from the surface toward space        */
+int lbl_path_flux(lbl_engine *engine, double *beta, int64_t row_stride, int64_t columns,
+                  int32_t grid, int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                  int32_t level_count, int32_t n_angles, const double *path_length,
+                  const double *weight, const double *temperature,
+                  const double *surface_temperature, const double *surface_emissivity,
+                  int32_t n_bands, const int64_t *band_start, double *carry, double *reflection,
+                  double *level_flux, double *flux, double *surface_flux, int32_t flags);
+
 /* Options (thirteen; anything else is LBL_BAD_ARGUMENT):
  *   "prep"                LBL_PREP_DEVICE (default) / LBL_PREP_HOST: where the per-line scalars are formed
  *   "points_per_lane"     0 = by the grid (default), 1/2/4/8 grid points per lane of the accumulate kernel

@@ -29,6 +29,7 @@
 #include "continuum.h"
 #include "xsec.h"
 #include "farfield.h"
+#include "flux.h"
 #include "line_prep.h"
 #include "path.h"
 #include "pedestal.h"
@@ -545,5 +546,6 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 
 #include "continuum_entry.inc"
 #include "radiance_entry.inc"
+#include "flux_entry.inc"
 #include "xsec_entry.inc"
 #include "sqlite_entry.inc"

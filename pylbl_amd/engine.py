@@ -28,6 +28,8 @@ PATH_OPTICAL_DEPTH, PATH_TRANSMITTANCE, PATH_CUMULATIVE, PATH_FROM_LAST, PATH_CO
     0x100, 0x200, 0x400, 0x800, 0x1000
 # lbl_path_radiance adds two outputs to them.
 PATH_RADIANCE, PATH_BRIGHTNESS = 0x2000, 0x4000
+# lbl_path_flux: the up sweep.
+PATH_FLUX_UP = 0x8000
 
 EXPORTED_SYMBOLS = (
     "lbl_engine_create", "lbl_engine_destroy", "lbl_last_error", "lbl_molecule_load",
@@ -43,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "lbl_continuum_load", "lbl_continuum_free", "lbl_grid_load", "lbl_grid_free",
     "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
-    "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance",
+    "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
 )
 
 VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
@@ -179,6 +181,10 @@ def library():
                                       c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_int32]
+    lib.lbl_path_flux.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                  c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_int32]
     for name in EXPORTED_SYMBOLS:
         if name not in ("lbl_last_error", "lbl_stream", "lbl_version"):
             getattr(lib, name).restype = c_int32
@@ -725,6 +731,56 @@ class Engine(object):
             n_bands, starts.ctypes.data if starts is not None else None, carry.pointer,
             radiance.pointer if radiance is not None else None,
             brightness_temperature.pointer if brightness_temperature is not None else None, flags))
+
+    def path_flux(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
+                  weight, temperature, carry, reflection, level_flux, surface_temperature=None,
+                  surface_emissivity=None, flux=None, surface_flux=None, band_start=None,
+                  up=False, from_last=False, asynchronous=False):
+        """One sweep of K angles through the DeviceSpectra `beta` -- lbl_path_flux.  Rows,
+        columns, grid, temperature, band_start, from_last and asynchronous as for path_radiance;
+        lengths [rows, K]: s_l/mu_k [m]; weight [K]; carry [n_paths*K, row length];
+        reflection [n_paths, row length]; level_flux [>= rows, row length] (F after each level);
+        surface_temperature / surface_emissivity one per path (up sweep); flux [>= rows, bands]
+        and, up, surface_flux [n_paths, bands]: the band means (with band_start only)."""
+        lengths = _f64(lengths)
+        weight = _f64(np.atleast_1d(weight))
+        temperature = _f64(np.atleast_1d(temperature))
+        rows, stride = int(beta.shape[0]), int(beta.shape[1])
+        angles = weight.size
+        if weight.ndim != 1 or lengths.shape != (rows, angles) or temperature.shape != (rows,):
+            raise ValueError("lengths [rows, K], weight [K] and temperature [rows] disagree.")
+        if tuple(carry.shape) != (int(n_paths)*angles, stride) or \
+                tuple(reflection.shape) != (int(n_paths), stride):
+            raise ValueError("carry must be [n_paths*K, row length], reflection [n_paths, "
+                             "row length].")
+        if level_flux.shape[1] != stride or level_flux.shape[0] < rows:
+            raise ValueError(f"level_flux has shape {level_flux.shape}, need rows x {stride}.")
+        surface = []
+        for values in (surface_temperature, surface_emissivity):
+            if values is not None:
+                values = _f64(np.atleast_1d(values))
+                if values.shape != (int(n_paths),):
+                    raise ValueError("one surface value per path.")
+            surface.append(values)
+        starts = None if band_start is None else \
+            np.ascontiguousarray(band_start, dtype=np.int64)
+        n_bands = 0 if starts is None else starts.size - 1
+        for out, count in ((flux, rows), (surface_flux, int(n_paths))):
+            if out is not None and (out.shape[1] != n_bands or out.shape[0] < count):
+                raise ValueError(f"a band output has shape {out.shape}, need {count} x {n_bands}.")
+        flags = (PATH_FLUX_UP if up else 0) | (PATH_FROM_LAST if from_last else 0) | \
+                (ASYNC if asynchronous else 0)
+        end = int(level_begin) + rows
+        if (end % int(levels_per_path) if from_last else int(level_begin) % int(levels_per_path)):
+            flags |= PATH_CONTINUE
+        self._check(self.lib.lbl_path_flux(
+            self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
+            int(levels_per_path), int(level_begin), rows, angles, lengths.ctypes.data,
+            weight.ctypes.data, temperature.ctypes.data,
+            *(s.ctypes.data if s is not None else None for s in surface),
+            n_bands, starts.ctypes.data if starts is not None else None, carry.pointer,
+            reflection.pointer, level_flux.pointer, flux.pointer if flux is not None else None,
+            surface_flux.pointer if surface_flux is not None else None, flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):

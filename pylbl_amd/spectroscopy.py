@@ -37,6 +37,12 @@ _PathRequest = namedtuple("_PathRequest", ["lengths", "shape", "quantities", "ed
 # compute_radiance's: the same, with `cumulative` a bool, and one boundary value per path.
 _RadianceRequest = namedtuple("_RadianceRequest", _PathRequest._fields + (
     "from_last", "boundary_temperature", "boundary_emissivity"))
+# compute_flux's: per-level lengths, the angles, the surface of every path.
+_FluxRequest = namedtuple("_FluxRequest", ["lengths", "shape", "quantities", "edges", "starts",
+                                           "surface", "mu", "weight", "surface_temperature",
+                                           "surface_emissivity"])
+# One pass of _sweep_runs over the levels: its order, and what it returns per level and per path.
+_Pass = namedtuple("_Pass", ["from_last", "level_quantities", "path_quantities"])
 
 
 def number_density(temperature, pressure, volume_mixing_ratio):
@@ -76,9 +82,21 @@ RADIANCE_DIRECTIONS = ("toward_last", "toward_first")
 # LBL_PLANCK_C2 in include/lbl_amd.h).
 PLANCK_C1 = 1.1910429723971885e-08     # 2 h c^2 1e8 [W m-2 sr-1 (cm-1)-4]
 PLANCK_C2 = 1.4387768775039338         # h c / k 1e2 [cm K]
+# Dry air for heating rates: R_d = R/M_d from the CODATA 2018 molar gas constant and the molar
+# mass of dry air, and c_p = (7/2) R_d of an ideal diatomic gas.
+R_DRY = 8.314462618/0.0289644          # [J kg-1 K-1]
+CP_DRY = 3.5*R_DRY                     # [J kg-1 K-1]
+
+FLUX_QUANTITIES = ("upward_flux", "downward_flux", "heating_rate")
+FLUX_SURFACES = ("first", "last")
+MAX_FLUX_ANGLES = 8
 
 _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
                "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K"}
+# compute_flux: on the grid, per band.
+_FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
+               "downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
+               "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
 
 
 def _path_layout(shape):
@@ -97,6 +115,60 @@ def band_columns(grid, band_edges):
     if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.):
         raise ValueError("band_edges must be finite and strictly increasing.")
     return np.searchsorted(np.asarray(grid, dtype=np.float64), edges, side="left").astype(np.int64)
+
+
+def flux_angles(angles):
+    """(mu, weight) of compute_flux's `angles`, checked: an int K in 1..8 gives Gauss-Legendre
+    on mu in (0, 1] -- x, w = leggauss(K), mu = (x + 1)/2, weight = mu*w -- so that
+    sum_k weight_k*mu_k^n = integral over (0, 1] of 2 mu mu^n for n <= 2K - 2; a pair
+    (mu, weight) of equal 1-d arrays of 1..8 values is taken as it is, with 0 < mu <= 1, weights
+    finite and >= 0 that sum to 1 within 1e-12 (an isotropic I then gives F = pi I)."""
+    if isinstance(angles, (int, np.integer)) and not isinstance(angles, (bool, np.bool_)):
+        count = int(angles)
+        if not 1 <= count <= MAX_FLUX_ANGLES:
+            raise ValueError(f"angles must be an int in 1..{MAX_FLUX_ANGLES}, not {count}.")
+        x, w = np.polynomial.legendre.leggauss(count)
+        mu = (x + 1.)/2.
+        return mu, mu*w
+    try:
+        mu, weight = angles
+    except (TypeError, ValueError):
+        raise ValueError("angles must be an int in 1..8 or a pair (mu, weight).") from None
+    mu = np.asarray(mu, dtype=np.float64)
+    weight = np.asarray(weight, dtype=np.float64)
+    if mu.ndim != 1 or weight.shape != mu.shape or not 1 <= mu.size <= MAX_FLUX_ANGLES:
+        raise ValueError(f"angles: mu and weight must be 1-d arrays of the same length in "
+                         f"1..{MAX_FLUX_ANGLES}.")
+    if not np.all((mu > 0.) & (mu <= 1.)):
+        raise ValueError("angles: mu must lie in (0, 1].")
+    if not np.all(np.isfinite(weight)) or np.any(weight < 0.):
+        raise ValueError("angles: weights must be finite and >= 0.")
+    if not abs(float(np.sum(weight)) - 1.) <= 1.e-12:
+        raise ValueError("angles: the weights must sum to 1 (they include the factor mu).")
+    return np.ascontiguousarray(mu), np.ascontiguousarray(weight)
+
+
+def heating_rate(upward_flux, downward_flux, pressure, temperature, thickness, surface="first"):
+    """H_l = 86400*(Fnet[i_lower] - Fnet[i_upper]) / ((rho_l*c_p)*s_l) [K day-1, per cm-1 on the
+    grid], in fp64: fluxes [..., L + 1, W] at the interfaces, pressure [Pa], temperature [K] and
+    thickness [m] [..., L]; Fnet = up - down; i_lower is the interface of level l nearer the
+    surface (l for surface "first", l + 1 for "last"); rho_l = p_l/(R_DRY*T_l); c_p = CP_DRY.
+    NaN where s_l = 0."""
+    net = np.asarray(upward_flux, dtype=np.float64) - np.asarray(downward_flux, dtype=np.float64)
+    lower, upper = (net[..., :-1, :], net[..., 1:, :]) if surface == "first" else \
+        (net[..., 1:, :], net[..., :-1, :])
+    thickness = np.asarray(thickness, dtype=np.float64)
+    density = np.asarray(pressure, dtype=np.float64)/(R_DRY*np.asarray(temperature, np.float64))
+    capacity = (density*CP_DRY)*thickness
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rate = (86400.*(lower - upper))/capacity[..., None]
+    return np.where((thickness == 0.)[..., None], np.nan, rate)
+
+
+def _sweep_pass(quantities, cumulative, from_last):
+    """The one pass of compute_path and compute_radiance."""
+    return _Pass(from_last, tuple(quantities) if cumulative else (),
+                 () if cumulative else tuple(quantities))
 
 
 class Atmosphere(object):
@@ -456,11 +528,12 @@ class Spectroscopy(object):
         temperature = np.ascontiguousarray(self.atmosphere.temperature.ravel(), dtype=np.float64)
         columns = self.grid.size
 
-        def sweeper(engine):
+        def sweeper(engine, take, run):
             from .mt_ckd import resident_grid
             grid = resident_grid(engine, self.grid)
+            carry = take(paths)
 
-            def sweep(beta, a, b, carry, outputs):
+            def sweep(index, beta, a, b, outputs):
                 engine.path_radiance(
                     beta, columns, grid, paths, per_path, a, request.lengths[a:b],
                     temperature[a:b], carry, boundary_temperature=request.boundary_temperature,
@@ -470,13 +543,190 @@ class Spectroscopy(object):
                     band_start=request.starts, cumulative=request.cumulative,
                     from_last=request.from_last, asynchronous=True)
             return sweep
-        values = self._sweep_runs(request, request.cumulative, request.from_last, remove_pedestal,
-                                  range_policy, sweeper)
+        step = _sweep_pass(request.quantities, request.cumulative, request.from_last)
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper)
         return self._create_path_dataset(values, request)
 
-    def _path_geometry(self, path_length, name):
-        """(flat lengths, atmosphere shape): the checks of the path lengths that compute_path and
-        compute_radiance share, made before anything touches the GPU."""
+    def compute_flux(self, layer_thickness, surface_temperature, surface_emissivity=1.,
+                     surface="first", angles=3, quantities=("upward_flux", "downward_flux"),
+                     band_edges=None, remove_pedestal=None, range_policy="reference"):
+        """Upward and downward longwave fluxes at every layer interface, and heating rates,
+        formed on the GPU from the "total" absorption block: the radiance of K angles swept
+        down from space and back up from a Lambertian surface, in two passes over the block.
+
+        Paths as in compute_path: the last dimension of the atmosphere, level l of a path an
+        isothermal layer at T_l of vertical thickness s_l.  With beta the absorption coefficient
+        [m-1] of compute_absorption("total", remove_pedestal, range_policy), nu the grid [cm-1]
+        and B(nu, T) as in compute_radiance, each product and sum rounded as written:
+            s_{l,k} = s_l/mu_k (fp64), one per level and angle;
+            down: I_k = 0 at space, then for each level toward the surface, x = s_{l,k}*beta_l,
+                  I_k = I_k*exp(-x) + B(nu, T_l)*(-expm1(-x)) (compute_radiance's update);
+            surface: R = sum_k w_k*I_k (from k = 0) of the down sweep's I_k at the surface; the
+                  up sweep starts from I_k = eps*B(nu, T_s) + (1 - eps)*R for every k;
+            up: the same update, levels from the surface toward space;
+            F = pi*(sum_k w_k*I_k) at an interface, from k = 0, pi = numpy.pi: F_down is 0 at
+                  space, F_up at the surface comes from the starting I_k;
+            band flux F_b = (band mean of F)*(n_b/n_per_v): compute_path's ordered mean times
+                  the band's width in grid steps (NaN without points);
+            heating rate H_l = 86400*(Fnet[i_lower] - Fnet[i_upper]) / ((rho_l*c_p)*s_l) in fp64
+                  from the returned fluxes, Fnet = F_up - F_down, i_lower the interface of level
+                  l nearer the surface, rho_l = p_l/(R_DRY*T_l), c_p = CP_DRY; NaN where s_l = 0
+                  (see heating_rate).
+        When the absorption of every level fits device_output_limit (two blocks of it per level:
+        beta and the fluxes of a level) it is computed once and both sweeps read it.  Otherwise
+        each pass computes its runs again, save the one the down pass ends on: beyond that limit
+        the line cost doubles.
+
+        Args:
+            layer_thickness: [m], shaped like the atmosphere's temperature, finite and >= 0.
+            surface_temperature: [K], a scalar or one per path, finite and > 0.
+            surface_emissivity: a scalar or one per path, in [0, 1].
+            surface: "first" (level 0 touches the surface) or "last" (level L-1 does); the other
+                     end faces space, from which nothing comes in.
+            angles: an int K in 1..8 (Gauss-Legendre on mu in (0, 1], see flux_angles) or a pair
+                    (mu, weight) of 1..8 values, 0 < mu <= 1, weights >= 0 summing to 1 (the
+                    diffusivity approximation is ([1/1.66], [1.])).
+            quantities: any of "upward_flux", "downward_flux", "heating_rate" (net flux is
+                        up - down).
+            band_edges: as in compute_path.
+
+        Returns:
+            Like compute_path: an xarray Dataset when xarray is installed, else a dict -- the
+            fluxes with the atmosphere's dims, the last replaced by "interface" (L + 1: interface
+            i lies between levels i-1 and i), then "wavenumber" ("W m-2 (cm-1)-1") or "band"
+            ("W m-2"); "heating_rate" with the level dim ("K day-1 (cm-1)-1" / "K day-1").
+        """
+        request = self._flux_request(layer_thickness, surface_temperature, surface_emissivity,
+                                     surface, angles, quantities, band_edges, range_policy)
+        if remove_pedestal is None:
+            remove_pedestal = self.continua_backend == "mt_ckd"
+        per_path, paths = _path_layout(request.shape)
+        temperature = np.ascontiguousarray(self.atmosphere.temperature.ravel(), dtype=np.float64)
+        columns = self.grid.size
+        angles = request.mu.size
+        lengths = request.lengths[:, None]/request.mu[None, :]
+        bands = request.starts is not None
+        # Down from space, then up from the surface: "first" has its surface at level 0.
+        passes = [_Pass(request.surface == "first", ("downward_flux",), ()),
+                  _Pass(request.surface == "last", ("upward_flux",), ("surface_flux",))]
+
+        def sweeper(engine, take, run):
+            from .mt_ckd import resident_grid
+            grid = resident_grid(engine, self.grid)
+            carry = take(paths*angles)
+            # The fluxes of a run's levels (with bands: before their means) and R, then the flux
+            # at the surface: without bands those are the outputs themselves.
+            level = take(run) if bands else None
+            reflection = take(paths) if bands else None
+
+            def sweep(index, beta, a, b, outputs):
+                up = index == 1
+                out = outputs["upward_flux" if up else "downward_flux"]
+                engine.path_flux(
+                    beta, columns, grid, paths, per_path, a, lengths[a:b], request.weight,
+                    temperature[a:b], carry,
+                    reflection if bands else outputs["surface_flux"],
+                    (level if b - a == run else level.rows(b - a)) if bands else out,
+                    surface_temperature=request.surface_temperature,
+                    surface_emissivity=request.surface_emissivity,
+                    flux=out if bands else None,
+                    surface_flux=outputs["surface_flux"] if bands and up else None,
+                    band_start=request.starts, up=up, from_last=passes[index].from_last,
+                    asynchronous=True)
+            return sweep
+        values = self._sweep_runs(request, passes, remove_pedestal, range_policy, sweeper,
+                                  level_blocks=2)
+        return self._create_flux_dataset(self._flux_interfaces(values, request), request)
+
+    def _flux_interfaces(self, values, request):
+        """{quantity: [..., L + 1 or L, W]} of compute_flux from the sweeps' per-level rows (the
+        flux just after each level in sweep order) and the surface rows."""
+        shape = list(request.shape)
+        per_path, paths = _path_layout(request.shape)
+        width = values["downward_flux"].shape[-1]
+        down = np.asarray(values["downward_flux"]).reshape(paths, per_path, width)
+        up = np.asarray(values["upward_flux"]).reshape(paths, per_path, width)
+        surface = np.asarray(values["surface_flux"]).reshape(paths, 1, width)
+        space = np.zeros((paths, 1, width))
+        if request.starts is not None:
+            points = np.diff(request.starts)
+            space[..., points == 0] = np.nan
+        # Sweeping toward level 0 the flux after level l is at interface l, toward level L-1 at
+        # interface l + 1.
+        if request.surface == "first":
+            fluxes = {"downward_flux": np.concatenate([down, space], axis=1),
+                      "upward_flux": np.concatenate([surface, up], axis=1)}
+        else:
+            fluxes = {"downward_flux": np.concatenate([space, down], axis=1),
+                      "upward_flux": np.concatenate([up, surface], axis=1)}
+        if request.starts is not None:
+            _, _, n_per_v = grid_arguments(self.grid)
+            widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
+            fluxes = {q: f*widths for q, f in fluxes.items()}
+        out = {}
+        lead = shape[:-1] + [per_path + 1, width]
+        for q in ("upward_flux", "downward_flux"):
+            if q in request.quantities:
+                out[q] = fluxes[q].reshape(lead)
+        if "heating_rate" in request.quantities:
+            out["heating_rate"] = heating_rate(
+                fluxes["upward_flux"], fluxes["downward_flux"],
+                self.atmosphere.pressure.reshape(paths, per_path),
+                self.atmosphere.temperature.reshape(paths, per_path),
+                request.lengths.reshape(paths, per_path),
+                request.surface).reshape(shape + [width])
+        return out
+
+    def _flux_request(self, layer_thickness, surface_temperature, surface_emissivity, surface,
+                      angles, quantities, band_edges, range_policy):
+        """Checks every argument of compute_flux (before anything touches the GPU)."""
+        lengths, shape = self._path_geometry(layer_thickness, "compute_flux", "layer_thickness",
+                                            "layer thicknesses")
+        temperature = self.atmosphere.temperature
+        if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
+            raise ValueError("the atmosphere's temperatures must be finite and > 0.")
+        if "heating_rate" in (quantities if not isinstance(quantities, str) else (quantities,)):
+            pressure = self.atmosphere.pressure
+            if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
+                raise ValueError("heating rates need pressures that are finite and > 0.")
+        ts = self._per_path(surface_temperature, "surface_temperature", shape)
+        if not np.all(np.isfinite(ts)) or np.any(ts <= 0.):
+            raise ValueError("surface temperatures must be finite and > 0.")
+        es = self._per_path(surface_emissivity, "surface_emissivity", shape)
+        if not np.all((es >= 0.) & (es <= 1.)):
+            raise ValueError("surface emissivities must lie in [0, 1].")
+        if not (isinstance(surface, str) and surface in FLUX_SURFACES):
+            raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
+        mu, weight = flux_angles(angles)
+        if isinstance(quantities, str):
+            quantities = (quantities,)
+        quantities = tuple(quantities)
+        unknown = [q for q in quantities if q not in FLUX_QUANTITIES]
+        if unknown or not quantities:
+            raise ValueError(f"quantities must be a non-empty selection of {FLUX_QUANTITIES}, "
+                             f"not {quantities}.")
+        quantities = tuple(q for q in FLUX_QUANTITIES if q in quantities)
+        if range_policy not in ("reference", "skip"):
+            raise ValueError(f"unknown range_policy {range_policy!r}.")
+        edges, starts = self._path_bands(band_edges)
+        return _FluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                            starts=starts, surface=surface, mu=mu, weight=weight,
+                            surface_temperature=ts, surface_emissivity=es)
+
+    @staticmethod
+    def _per_path(value, name, shape):
+        """A scalar or one value per path (shaped like the atmosphere without its last
+        dimension), as a flat float64 array of one value per path."""
+        per_path_shape = shape[:-1]
+        values = np.asarray(value, dtype=np.float64)
+        if values.shape not in ((), per_path_shape):
+            raise ValueError(f"{name} has shape {values.shape}: give a scalar or one value "
+                             f"per path, shaped {per_path_shape}.")
+        return np.ascontiguousarray(np.broadcast_to(values, per_path_shape).ravel())
+
+    def _path_geometry(self, path_length, name, argument="path_length", what="path lengths"):
+        """(flat lengths, atmosphere shape): the checks of the path lengths that compute_path,
+        compute_radiance and compute_flux share, made before anything touches the GPU."""
         if self.group is not None:
             raise NotImplementedError(f"{name} does not split paths over processes yet "
                                       "(group is set): the levels of a path would need a sum "
@@ -484,9 +734,9 @@ class Spectroscopy(object):
         shape = tuple(self.atmosphere.temperature.shape)
         lengths = np.asarray(path_length, dtype=np.float64)
         if lengths.shape != shape:
-            raise ValueError(f"path_length has shape {lengths.shape}, the atmosphere {shape}.")
+            raise ValueError(f"{argument} has shape {lengths.shape}, the atmosphere {shape}.")
         if not np.all(np.isfinite(lengths)) or np.any(lengths < 0.):
-            raise ValueError("path lengths must be finite and >= 0.")
+            raise ValueError(f"{what} must be finite and >= 0.")
         if lengths.size == 0:
             raise ValueError("the atmosphere has no levels.")
         return np.ascontiguousarray(lengths.ravel()), shape
@@ -527,21 +777,13 @@ class Spectroscopy(object):
         temperature = self.atmosphere.temperature
         if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
             raise ValueError("the atmosphere's temperatures must be finite and > 0.")
-        per_path_shape = shape[:-1]
-
-        def per_path(value, name):
-            values = np.asarray(value, dtype=np.float64)
-            if values.shape not in ((), per_path_shape):
-                raise ValueError(f"{name} has shape {values.shape}: give a scalar or one value "
-                                 f"per path, shaped {per_path_shape}.")
-            return np.ascontiguousarray(np.broadcast_to(values, per_path_shape).ravel())
         if boundary_temperature is None:
             boundary = None
         else:
-            boundary = per_path(boundary_temperature, "boundary_temperature")
+            boundary = self._per_path(boundary_temperature, "boundary_temperature", shape)
             if not np.all(np.isfinite(boundary)) or np.any(boundary <= 0.):
                 raise ValueError("boundary temperatures must be finite and > 0.")
-        emissivity = per_path(boundary_emissivity, "boundary_emissivity")
+        emissivity = self._per_path(boundary_emissivity, "boundary_emissivity", shape)
         if not np.all((emissivity >= 0.) & (emissivity <= 1.)):
             raise ValueError("boundary emissivities must lie in [0, 1].")
         if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
@@ -574,23 +816,32 @@ class Spectroscopy(object):
         cumulative = request.cumulative is not None
         columns = self.grid.size
 
-        def sweeper(engine):
-            def sweep(beta, a, b, carry, outputs):
+        def sweeper(engine, take, run):
+            carry = take(paths)
+
+            def sweep(index, beta, a, b, outputs):
                 engine.path_compute(
                     beta, columns, paths, per_path, a, request.lengths[a:b], carry,
                     optical_depth=outputs.get("optical_depth"),
                     transmittance=outputs.get("transmittance"), band_start=request.starts,
                     cumulative=cumulative, from_last=from_last, asynchronous=True)
             return sweep
-        return self._sweep_runs(request, cumulative, from_last, remove_pedestal, range_policy,
-                                sweeper)
+        return self._sweep_runs(request, [_sweep_pass(request.quantities, cumulative, from_last)],
+                                remove_pedestal, range_policy, sweeper)
 
-    def _sweep_runs(self, request, cumulative, from_last, remove_pedestal, range_policy,
-                    sweeper):
-        """{quantity: array [paths or levels, columns or bands]}: the "total" block of a run of
-        levels at a time, queued like _compute_levels queues it, then the path kernels on it.
-        sweeper(engine) returns sweep(beta, a, b, carry, outputs), which queues the path kernels
-        of the levels [a, b) on their block `beta`, with `outputs` {quantity: DeviceSpectra}."""
+    def _sweep_runs(self, request, passes, remove_pedestal, range_policy, sweeper,
+                    level_blocks=1):
+        """{quantity: array [levels or paths, columns or bands]}: the "total" block of a run of
+        levels at a time, queued like _compute_levels queues it, then the path kernels on it --
+        for each of `passes` (_Pass: its order, and the quantities it returns per level and per
+        path) in turn, every pass over all levels.
+        sweeper(engine, take, run) returns sweep(index, beta, a, b, outputs), which queues the
+        path kernels of pass `index` on the levels [a, b) and their block `beta`, with `outputs`
+        {quantity of any pass: DeviceSpectra}; take(rows, n=n) hands it blocks of its own for the
+        call (carries, scratch).  level_blocks: blocks of [run, n] counted against
+        device_output_limit.  A pass that starts on the run the previous pass ended on finds
+        that run's block still in HBM and does not compute it again: sweeps of a call with
+        several passes must leave beta as they found it."""
         temperature = self.atmosphere.temperature.ravel()
         pressure = self.atmosphere.pressure.ravel()
         mole_fractions = {name: x.ravel() for name, x in self.atmosphere.gases.items()}
@@ -599,15 +850,16 @@ class Spectroscopy(object):
         v0, vn, n_per_v = grid_arguments(self.grid)
         n = (vn - v0)*n_per_v
         columns = self.grid.size
-        # Runs of consecutive levels when the block would not fit: the sweep carries over in HBM.
-        run = levels if levels*n*8 <= self.device_output_limit else \
-            max(1, self.device_output_limit//(n*8))
+        # Runs of consecutive levels when the blocks would not fit: the sweep carries over in HBM.
+        level_bytes = level_blocks*n*8
+        run = levels if levels*level_bytes <= self.device_output_limit else \
+            max(1, self.device_output_limit//level_bytes)
         run = min(run, _MAX_RUN_LEVELS)
         starts = request.starts
         width = columns if starts is None else starts.size - 1
         runs = [(a, min(a + run, levels)) for a in range(0, levels, run)]
-        if from_last:
-            runs.reverse()
+        level_quantities = [q for step in passes for q in step.level_quantities]
+        path_quantities = [q for step in passes for q in step.path_quantities]
 
         engine, present, heavy = self._present_gases(temperature, pressure, mole_fractions)
         if engine is None:
@@ -615,47 +867,52 @@ class Spectroscopy(object):
             engine = default_engine(self.device)
         if heavy is not None:
             present = [heavy] + present[:-1]
-        sweep = sweeper(engine)
-        results = {q: engine.host_array((levels if cumulative else paths, width))
-                   for q in request.quantities}
-        # One block of `run` levels for beta (and, cumulative, for each output) serves every run;
-        # the shorter last run uses its leading rows.  Together with the carry and per-path outputs
-        # that is all this call holds in HBM.
+        results = {q: engine.host_array((levels, width)) for q in level_quantities}
+        results.update({q: engine.host_array((paths, width)) for q in path_quantities})
+        # One block of `run` levels for beta (and for each per-level output) serves every run;
+        # the shorter last run uses its leading rows.  Together with the sweeper's blocks and the
+        # per-path outputs that is all this call holds in HBM.
         band_width = width if starts is not None else n
         taken = []
+
+        def take(rows, columns=n):
+            block = engine.blocks.take(rows, columns)
+            taken.append(block)
+            return block
         with engine.pipeline:
             try:
-                carry = engine.blocks.take(paths, n)
-                taken.append(carry)
-                beta = engine.blocks.take(run, n)
-                taken.append(beta)
-                outputs = {}
-                for q in request.quantities:
-                    outputs[q] = engine.blocks.take(run if cumulative else paths, band_width)
-                    taken.append(outputs[q])
-                for index, (a, b) in enumerate(runs):
-                    if index > 0:
-                        # The previous run's block and outputs are written again below: what still
-                        # reads them -- its sweep, its copies to the host -- is done first.
-                        engine.synchronize()
-                    queue = _Queue(self, temperature[a:b], pressure[a:b],
-                                   {k: v[a:b] for k, v in mole_fractions.items()},
-                                   remove_pedestal, range_policy, self.delivery_pieces)
-                    total = _Sum(engine, b - a, n,
-                                 buffer=beta if b - a == run else beta.rows(b - a))
-                    if present:
-                        self._queue_total(queue, engine, present, heavy, total, None)
-                    else:
-                        engine.fill_zero(total.buffer, asynchronous=True)
-                    run_outputs = outputs if not cumulative or b - a == run else \
-                        {q: block.rows(b - a) for q, block in outputs.items()}
-                    sweep(total.buffer, a, b, carry, run_outputs)
-                    if cumulative:
-                        for q in request.quantities:
+                sweep = sweeper(engine, take, run)
+                beta = take(run, n)
+                outputs = {q: take(run, band_width) for q in level_quantities}
+                outputs.update({q: take(paths, band_width) for q in path_quantities})
+                resident = None
+                for index, step in enumerate(passes):
+                    for a, b in (runs[::-1] if step.from_last else runs):
+                        kept = (a, b) == resident
+                        if resident is not None and not kept:
+                            # The previous run's block and outputs are written again below: what
+                            # still reads them -- its sweep, its copies to the host -- is done
+                            # first.
+                            engine.synchronize()
+                        rows = beta if b - a == run else beta.rows(b - a)
+                        if not kept:
+                            queue = _Queue(self, temperature[a:b], pressure[a:b],
+                                           {k: v[a:b] for k, v in mole_fractions.items()},
+                                           remove_pedestal, range_policy, self.delivery_pieces)
+                            total = _Sum(engine, b - a, n, buffer=rows)
+                            if present:
+                                self._queue_total(queue, engine, present, heavy, total, None)
+                            else:
+                                engine.fill_zero(total.buffer, asynchronous=True)
+                        resident = (a, b)
+                        run_outputs = {q: outputs[q] if b - a == run else outputs[q].rows(b - a)
+                                       for q in level_quantities}
+                        run_outputs.update({q: outputs[q] for q in path_quantities})
+                        sweep(index, rows, a, b, run_outputs)
+                        for q in step.level_quantities:
                             run_outputs[q].to_host_into(results[q][a:b], width, asynchronous=True)
-                if not cumulative:
-                    for q in request.quantities:
-                        outputs[q].to_host_into(results[q], width, asynchronous=True)
+                for q in path_quantities:
+                    outputs[q].to_host_into(results[q], width, asynchronous=True)
                 engine.synchronize()
             except BaseException:
                 try:
@@ -676,25 +933,41 @@ class Spectroscopy(object):
         shape = list(request.shape)
         if not request.cumulative:
             dims, shape = dims[:-1], shape[:-1]
+        dims.append("wavenumber" if request.edges is None else "band")
+        variables = {q: (dims, np.asarray(values[q]).reshape(shape + [-1]), _PATH_UNITS[q])
+                     for q in request.quantities}
+        return self._path_variables(variables, request)
+
+    def _create_flux_dataset(self, values, request):
+        """compute_flux's result from {quantity: [..., interfaces or levels, columns or bands]}:
+        fluxes on the "interface" dim in place of the atmosphere's last, heating rates on it."""
+        dims = list(self.atmosphere.dims)
+        axis = "wavenumber" if request.edges is None else "band"
+        variables = {}
+        for q in request.quantities:
+            here = dims + [axis] if q == "heating_rate" else dims[:-1] + ["interface", axis]
+            variables[q] = (here, values[q], _FLUX_UNITS[q][request.edges is not None])
+        return self._path_variables(variables, request)
+
+    def _path_variables(self, variables, request):
+        """{name: (dims, values, units)} with the grid's or the bands' coordinates, in the
+        conventions of _create_output_dataset."""
         if request.edges is None:
-            dims.append("wavenumber")
             coords = {"wavenumber": (self.grid, {"units": "cm-1"})}
         else:
-            dims.append("band")
             coords = {"band_lower": (request.edges[:-1], {"units": "cm-1"}),
                       "band_upper": (request.edges[1:], {"units": "cm-1"}),
                       "band_points": (np.diff(request.starts), {})}
-        variables = {q: np.asarray(values[q]).reshape(shape + [-1]) for q in request.quantities}
         xarray = _optional_xarray()
         if xarray is None:
             out = {name: value for name, (value, _) in coords.items()}
-            out.update(variables)
+            out.update({q: v for q, (_, v, _) in variables.items()})
             return out
         DataArray, Dataset = xarray.DataArray, xarray.Dataset
-        axis = dims[-1]
+        axis = "wavenumber" if request.edges is None else "band"
         return Dataset(
-            data_vars={q: DataArray(v, dims=dims, attrs={"units": _PATH_UNITS[q]})
-                       for q, v in variables.items()},
+            data_vars={q: DataArray(v, dims=dims, attrs={"units": units})
+                       for q, (dims, v, units) in variables.items()},
             coords={name: DataArray(value, dims=(axis,), attrs=attrs)
                     for name, (value, attrs) in coords.items()})
 
