@@ -87,6 +87,12 @@ extern "C" {
                                  * One deferred call at a time; ignored where it cannot apply
                                  * (no pedestal, several level passes, host output). */
 
+/* The largest cut_off a call with remove_pedestal accepts (others fail with LBL_BAD_ARGUMENT
+ * before any GPU work): the pedestal pre-pass stages 2 x 16 runs of 2 cut_off + 3 slot sums in
+ * one workgroup's LDS, 256 (2 cut_off + 3) + 2048 bytes plus 4608 of its own, and a CU has
+ * 160 KiB.  Without the pedestal any cut_off >= 0 is accepted. */
+#define LBL_MAX_PEDESTAL_CUT_OFF 305
+
 typedef struct lbl_engine lbl_engine;
 
 /* Creates an engine bound to HIP device `device`.  Fails with LBL_NO_DEVICE when the HIP
@@ -289,7 +295,7 @@ int lbl_path_flux(lbl_engine *engine, double *beta, int64_t row_stride, int64_t 
                   int32_t n_bands, const int64_t *band_start, double *carry, double *reflection,
                   double *level_flux, double *flux, double *surface_flux, int32_t flags);
 
-/* Options (thirteen; anything else is LBL_BAD_ARGUMENT):
+/* Options (fourteen; anything else is LBL_BAD_ARGUMENT):
  *   "prep"                LBL_PREP_DEVICE (default) / LBL_PREP_HOST: where the per-line scalars are formed
  *   "points_per_lane"     0 = by the grid (default), 1/2/4/8 grid points per lane of the accumulate kernel
  *   "timing"              0/1/2: HIP events around every kernel; 2 = only around the accumulate and
@@ -311,6 +317,11 @@ int lbl_path_flux(lbl_engine *engine, double *beta, int64_t row_stride, int64_t 
  *   "small_points"        grids of up to so many points x levels count as short calls (default 2^20)
  *   "skip_delivery_lanes" 0/1: lbl_compute_streamed avoids the internal streams that share a
  *                         hardware queue with the copy stream; default 1
+ *   "poison_workspace"    0/1: a test hook; 1 = every call's pedestal pre-pass first fills its
+ *                         floating-point buffers (the relaxation's pedestals, the runs' slot sums,
+ *                         the serial chain's slots, the bins' totals) with 0xFF bytes, a NaN, so that
+ *                         a value read before the call wrote it cannot pass for a right one; the
+ *                         results do not change by a bit; default 0
  * A library built with -DLBL_ABLATE (scripts/ablate_*.sh; never the shipped one) also takes "ablate":
  * parts of the accumulate kernel switched off for timing, results wrong. */
 int lbl_set_option(lbl_engine *engine, const char *name, int64_t value);

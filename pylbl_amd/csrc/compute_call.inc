@@ -169,7 +169,8 @@ int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_fo
                 }
                 engine->timed(kTimePedestal, ped_stream, [&] {
                     pedestal_find_runs(lane.pedestal, ped_stream, m->view(), lane.wing.data, g,
-                                       count, n_cells, engine->scan_chain != 0);
+                                       count, n_cells, engine->scan_chain != 0,
+                                       engine->poison_workspace != 0);
                 }, 0);
                 if (engine->overlap_pedestal)
                 {
@@ -266,7 +267,7 @@ int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_fo
                 engine->timed(kTimePedestal, ped_stream, [&] {
                     pedestal_finish(lane.pedestal, ped_stream, m->view(), lane.wing.data,
                                     lane.core.data, g, count, n_cells, engine->scan_chain != 0,
-                                    engine->relax_launches);
+                                    engine->relax_launches, engine->poison_workspace != 0);
                 });
             };
             // (Chaining the accumulate launches of successive calls by events -- one grid after the

@@ -35,6 +35,16 @@ int shape_of(lbl_engine * engine, const ComputeRequest & rq, CallShape & s)
                     "need vn > v0, n_per_v >= 1 and cut_off >= 0 (grid must start on an "
                     "integer wavenumber with spacing 1/integer).");
     }
+    static_assert(LBL_MAX_PEDESTAL_CUT_OFF == pedestal_cut_off_limit(),
+                  "LBL_MAX_PEDESTAL_CUT_OFF follows the pre-pass's LDS (pedestal.h)");
+    if (rq.remove_pedestal && rq.cut_off > LBL_MAX_PEDESTAL_CUT_OFF)
+    {
+        return fail(engine, LBL_BAD_ARGUMENT,
+                    "cut_off " + std::to_string(rq.cut_off) + " with remove_pedestal: the largest "
+                    "supported is LBL_MAX_PEDESTAL_CUT_OFF = " +
+                    std::to_string(LBL_MAX_PEDESTAL_CUT_OFF) +
+                    " (the pedestal pre-pass's LDS); call without remove_pedestal for wider windows.");
+    }
     s.n_long = (long long)(rq.vn - rq.v0)*rq.n_per_v;
     if (s.n_long > 0x3fffffff)
     {

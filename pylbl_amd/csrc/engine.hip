@@ -436,6 +436,10 @@ int lbl_set_option(lbl_engine * engine, const char * name, int64_t value)
     {
         engine->scan_chain = (int)value;
     }
+    else if (key == "poison_workspace" && (value == 0 || value == 1))
+    {
+        engine->poison_workspace = (int)value;
+    }
     else if (key == "skip_delivery_lanes" && (value == 0 || value == 1))
     {
         engine->skip_delivery_lanes = (int)value;

@@ -460,6 +460,7 @@ struct lbl_engine
     int farfield = 0;               // sum distant lines by their power series (farfield.h)
     int scan_chain = 1;             // pedestal chain by relaxation (pedestal.h), serial chain behind it
     int relax_launches = 0;         // relaxation launches before the serial chain (2 ... 7; 0: by the table)
+    int poison_workspace = 0;       // test hook: NaN-fill the pre-pass's double buffers first (pedestal.h)
     int lanes_in_use = 0;           // lanes the asynchronous calls rotate over; 0: by kind of call
     long long small_points = 1ll << 20;    // grids (points x levels) up to this size count as small
     int overlap_plain = 1;          // plain asynchronous calls on larger grids take turns on two lanes too

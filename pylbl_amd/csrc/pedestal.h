@@ -117,6 +117,14 @@ struct PedestalWorkspace
     std::vector<int> host_counts;
 };
 
+inline void pedestal_check(hipError_t status, const char * what)
+{
+    if (status != hipSuccess)
+    {
+        throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(status));
+    }
+}
+
 constexpr int kRunCut = 1024;     // see opens_run
 constexpr int kPedestalSweepBuffers = 7;    // kMaxRelaxLaunches (pedestal_chain.h)
 
@@ -132,6 +140,39 @@ inline long long pedestal_bytes_per_level(long long n_lines, int n_cells, int cu
 
 #include "pedestal_runs.h"
 #include "pedestal_chain.h"
+
+namespace lbl {
+
+// LDS of the pre-pass's launches whose dynamic part grows with cut_off: run_solve_kernel and
+// run_chain_kernel<false, *> (two chunks of staged slot sums and the ring), run_solve_kernel's own
+// arrays beside them.  A CU has 160 KiB; above 64 KiB a launch must opt in
+// (hipFuncAttributeMaxDynamicSharedMemorySize).  LBL_MAX_PEDESTAL_CUT_OFF (include/lbl_amd.h) is
+// the largest cut_off whose run_solve_kernel fits.
+constexpr size_t kLdsPerCu = 160*1024;
+constexpr size_t kLdsWithoutOptIn = 64*1024;
+constexpr size_t kSolveStaticLds = kHistoryTile*(sizeof(double) + sizeof(int2)) + 64*sizeof(double);
+
+constexpr size_t pedestal_chain_lds_bytes(int cut_off)
+{
+    return (size_t)2*kChainChunk*(2*cut_off + 3)*sizeof(double) + (size_t)kChainRing*sizeof(double);
+}
+
+constexpr int pedestal_cut_off_limit()
+{
+    int c = 0;
+    while (pedestal_chain_lds_bytes(c + 1) + kSolveStaticLds <= kLdsPerCu) ++c;
+    return c;
+}
+
+// Every dynamic-LDS launch of a call that may exceed 64 KiB asks for what it needs first.
+inline void pedestal_lds_opt_in(const void * kernel, size_t bytes)
+{
+    if (bytes <= kLdsWithoutOptIn) return;
+    pedestal_check(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
+                   "LDS opt-in");
+}
+
+}  // namespace lbl
 
 namespace lbl {
 
@@ -217,18 +258,33 @@ inline int pedestal_apply_span(int n_per_v)
     return 256*kApplyPoints/std::max(n_per_v, 1) + 2;
 }
 
-inline size_t pedestal_apply_lds_bytes(int cut_off, int n_per_v)
+constexpr size_t pedestal_apply_lds_bytes(int cut_off, int n_per_v)
 {
-    return (size_t)(3*pedestal_apply_span(n_per_v) + 2*cut_off + 2)*sizeof(double);
+    return (size_t)(3*(256*kApplyPoints/(n_per_v > 1 ? n_per_v : 1) + 2) + 2*cut_off + 2)*sizeof(double);
 }
+// (so its launch needs no opt-in: n_per_v = 1 is its widest span)
+static_assert(pedestal_apply_lds_bytes(pedestal_cut_off_limit(), 1) <= kLdsWithoutOptIn,
+              "pedestal_apply_kernel: LDS at the largest cut_off");
 
 // The pedestal pre-pass for `count` levels whose LineWing/LineCore arrays are already in
 // HBM, in two halves (pedestal_find_runs, pedestal_finish) on the same stream.
-inline void pedestal_check(hipError_t status, const char * what)
+
+// Engine option poison_workspace = 1 (a test hook): the pre-pass's double buffers -- every sweep's
+// pedestals, slot_sums, the serial chain's slots, bin_sum -- are filled with 0xFF bytes (a NaN)
+// over their whole reserved size before the pass writes them, so that a value read before this
+// call wrote it shows up as a NaN or a changed bit instead of the previous call's value.  None of
+// them decides where or how long anything runs: their readers (run_links_kernel: gs / ge,
+// run_chain: the staged sums, the slots and the bins' totals, run_solve_kernel: the earlier
+// chunks' pedestals and the bins' totals, pedestal_apply_kernel: the bins' totals) only add,
+// subtract, compare or store them; every index, loop bound and wait comes from the integer
+// arrays (runs, links, run_slots, run_bin, bin_end, bin_first, run_start, prefix_bin, run_count)
+// and the sync words (progress, state, scan), which are not poisoned: run_find_kernel and
+// run_links_kernel reset those on every call.
+inline void pedestal_poison(hipStream_t stream, double * data, size_t capacity)
 {
-    if (status != hipSuccess)
+    if (data != nullptr)
     {
-        throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(status));
+        pedestal_check(hipMemsetAsync(data, 0xFF, capacity*sizeof(double), stream), "workspace poison");
     }
 }
 
@@ -237,7 +293,7 @@ inline void pedestal_check(hipError_t status, const char * what)
 // another call does not hold it up, see kScanThreads).
 inline void pedestal_find_runs(PedestalWorkspace & ws, hipStream_t stream, const LineTableView & t,
                                const LineWing * wing, const GridSpec & g, int count, int n_cells,
-                               bool parallel_chain)
+                               bool parallel_chain, bool poison = false)
 {
     auto check = pedestal_check;
     const long long n_lines = t.n_lines;
@@ -262,6 +318,13 @@ inline void pedestal_find_runs(PedestalWorkspace & ws, hipStream_t stream, const
     ws.bin_end.reserve((size_t)count*n_bins);
     ws.bin_first.reserve((size_t)count*n_bins);
     ws.state.reserve((size_t)count*kChainState);
+    if (poison)
+    {
+        pedestal_poison(stream, ws.pedestals.data, ws.pedestals.capacity);
+        pedestal_poison(stream, ws.slot_sums.data, ws.slot_sums.capacity);
+        pedestal_poison(stream, ws.slots.data, ws.slots.capacity);
+        pedestal_poison(stream, ws.bin_sum.data, ws.bin_sum.capacity);
+    }
     unsigned long long * now = ws.scan[ws.scan_turn].data;
     unsigned long long * next = ws.scan[ws.scan_turn ^ 1].data;
     ws.scan_turn ^= 1;
@@ -281,7 +344,8 @@ inline void pedestal_find_runs(PedestalWorkspace & ws, hipStream_t stream, const
 // chain inside it for the levels it leaves; else the serial chain alone.
 inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const LineTableView & t,
                             const LineWing * wing, const LineCore * core, const GridSpec & g,
-                            int count, int n_cells, bool parallel_chain = true, int relax_launches = 0)
+                            int count, int n_cells, bool parallel_chain = true, int relax_launches = 0,
+                            bool poison = false)
 {
     auto check = pedestal_check;
     const long long n_lines = t.n_lines;
@@ -311,6 +375,18 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
     relax_launches = std::min(std::max(relax_launches, 2), kMaxRelaxLaunches);
     ws.runs.reserve((size_t)count*max_runs);
     ws.slot_sums.reserve((size_t)count*max_runs*slot_stride);
+    if (parallel_chain)
+    {
+        ws.pedestals.reserve((size_t)relax_launches*count*max_runs);
+        ws.slots.reserve((size_t)count*(n_cells + 1));
+    }
+    if (poison)
+    {
+        // (again: buffers reserved afresh for this call; bin_sum is run_find_kernel's by now)
+        pedestal_poison(stream, ws.pedestals.data, ws.pedestals.capacity);
+        pedestal_poison(stream, ws.slot_sums.data, ws.slot_sums.capacity);
+        pedestal_poison(stream, ws.slots.data, ws.slots.capacity);
+    }
     hipLaunchKernelGGL(run_sums_kernel, dim3(std::min(max_runs, 65535), count), dim3(64), 0,
                        stream, wing, core, t.sorted_of_row, n_lines, g, n_cells,
                        ws.run_start.data, ws.run_count.data, max_runs, slot_stride,
@@ -326,9 +402,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
         ws.links.reserve((size_t)count*max_runs);
         ws.run_slots.reserve((size_t)count*max_runs);
         ws.run_bin.reserve((size_t)count*max_runs);
-        ws.pedestals.reserve((size_t)relax_launches*count*max_runs);
         ws.progress.reserve((size_t)count*max_chunks);
-        ws.slots.reserve((size_t)count*(n_cells + 1));
         hipLaunchKernelGGL(run_links_kernel, dim3(std::min(max_runs, 65535), count), dim3(64), 0,
                            stream, ws.run_count.data, max_runs, slot_stride, n_bins, ws.runs.data,
                            ws.slot_sums.data, ws.prefix_bin.data, n_lines, ws.bin_end.data,
@@ -337,6 +411,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
         check(hipGetLastError(), "run_links_kernel");
         // Windows of at most 64 slots (cut_off <= 30) keep the active slots in registers.
         auto solve = slot_stride <= 64 ? run_solve_kernel<true> : run_solve_kernel<false>;
+        pedestal_lds_opt_in(reinterpret_cast<const void *>(solve), staged_bytes + ring_bytes);
         hipLaunchKernelGGL(solve, dim3(max_chunks, count), dim3(64), staged_bytes + ring_bytes,
                            stream, ws.run_count.data, max_runs, max_chunks, n_bins, relax_launches,
                            ws.links.data, ws.run_slots.data, ws.run_bin.data, ws.bin_end.data,
@@ -369,6 +444,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
     {
         ws.slots.reserve((size_t)count*(n_cells + 1));
         auto chain = slot_stride <= 64 ? run_chain_kernel<false, true> : run_chain_kernel<false, false>;
+        pedestal_lds_opt_in(reinterpret_cast<const void *>(chain), staged_bytes + ring_bytes);
         hipLaunchKernelGGL(chain, dim3(count), dim3(64), staged_bytes + ring_bytes, stream,
                            ws.run_count.data, max_runs, slot_stride, g, n_cells, n_bins,
                            ws.runs.data, ws.slot_sums.data, ws.slots.data, ws.bin_sum.data);

@@ -477,11 +477,15 @@ __device__ __forceinline__ int load_agent(const int * p)
 }
 
 // A pedestal total another chunk (on any XCD, each with an L2 of its own) has written / will read
-// during this launch: device-scope accesses, coherent by themselves.  The order against the count
-// that announces them is kept by a workgroup-scope fence (the stores have completed before the
-// count is stored), not by an agent-scope one -- that would write the XCD's whole L2 back, every
-// sweep of every chunk, under the accumulate grid that is filling it (profiles/r06_ab_combine_in_kernel.txt
-// is what such fences cost).
+// during this launch: device-scope accesses (global_store / global_load ... sc1: write-through
+// stores, loads that bypass the CU's L1), coherent by themselves.  What orders them against the
+// count that announces them is the wave's own `s_waitcnt vmcnt(0)` (publish_wait) between the
+// last such store or flag atomic and the count: every one has been acknowledged before the count
+// is stored.  A workgroup-scope fence does not do that -- it waits for LDS only, nothing another
+// CU can observe -- and an agent-scope release would write the XCD's whole L2 back, every sweep of
+// every chunk, under the accumulate grid that is filling it (profiles/r06_ab_combine_in_kernel.txt
+// is what such fences cost).  Readers poll the count and read the values with sc1 loads
+// (load_agent, load_shared) only, so no acquire fence is needed on their side either.
 __device__ __forceinline__ double load_shared(const double * p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -490,6 +494,13 @@ __device__ __forceinline__ double load_shared(const double * p)
 __device__ __forceinline__ void store_shared(double * p, double value)
 {
     __hip_atomic_store(p, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// This wave's stores and atomics have all completed (see above).  Inline asm: the compiler may
+// not drop or move it, which it may do with its own waits in front of a release.
+__device__ __forceinline__ void publish_wait()
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // Waits until the chunks [first, last) of the level have completed `needed` sweeps.  false: given up
@@ -634,6 +645,7 @@ __global__ __launch_bounds__(64) void run_solve_kernel(const int * __restrict__ 
             }
             // this sweep's values (and flags) before the count that says so
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            publish_wait();
             if (lane == 0) __hip_atomic_store(&done[chunk], sweep + 1, __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -669,9 +681,10 @@ __global__ __launch_bounds__(64) void run_solve_kernel(const int * __restrict__ 
         }
     }
     // Whoever leaves last looks at the flags (every chunk's are in by then: device-scope atomics,
-    // like the bin totals above, completed before the chunk counts itself out) and, where the sweeps
-    // did not apply or have not settled, runs the serial chain for the level.
+    // like the bin totals above, completed -- publish_wait -- before the chunk counts itself out)
+    // and, where the sweeps did not apply or have not settled, runs the serial chain for the level.
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    publish_wait();
     int left = 0;
     if (lane == 0) left = atomicAdd(&flags[kStateFinished], 1);
     left = __builtin_amdgcn_readfirstlane(left);
