@@ -43,7 +43,6 @@
 
 // (calibrate_delivery_lanes, used by lbl_engine_create)
 #include "delivery.inc"
-#include "path_entry.inc"
 
 extern "C" {
 
@@ -549,6 +548,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 }  // extern "C"
 
 #include "continuum_entry.inc"
+#include "path_entry.inc"
 #include "radiance_entry.inc"
 #include "flux_entry.inc"
 #include "xsec_entry.inc"

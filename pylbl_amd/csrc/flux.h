@@ -9,11 +9,11 @@
 // The TU builds with -ffp-contract=off: every product and sum is rounded as written, and with
 // K = 1 and w_0 = 1 the radiances are bit for bit path_radiance_kernel's.
 //
-// path_flux_kernel<kVector, K> is path_radiance_kernel with K radiances per column: a lane owns
-// kPathWidth consecutive columns, has kFluxAhead<K> rows in flight and keeps its K*kPathWidth
-// radiances in registers; nu, C2*nu and C1*nu^3 are formed once, and B(nu, T_l) once per element
-// and level for all K angles (the two divisions and the expm1 of Planck are what one angle of
-// the radiance sweep spends most on).  s_{l,k}, T_l and w_k are the same for the whole wavefront.
+// path_flux_kernel<kVector, K> runs on path.h's sweep skeleton with kFluxAhead<K> rows in flight:
+// radiance.h's update for K radiances per column, a lane's K*kPathWidth radiances in registers;
+// nu, C2*nu and C1*nu^3 are formed once, and B(nu, T_l) once per element and level for all K
+// angles (the two divisions and the expm1 of Planck are what one angle of the radiance sweep
+// spends most on).  s_{l,k}, T_l and w_k are the same for the whole wavefront.
 // After each level the lane writes F to its level row; band means go through path.h's kernels.
 #pragma once
 
@@ -33,25 +33,16 @@ constexpr double kFluxPi = 3.141592653589793;       // numpy.pi
 template <int K>
 constexpr int kFluxAhead = K <= 4 ? kPathAhead : 4;
 
-struct PathFlux
+struct PathFlux : PathLevels
 {
-    const double * beta;        // row of flat level `row_base`; rows `stride` apart
-    long long stride;           // row stride of beta, carry, reflection and level_flux [values]
-    long long columns;
     const double * nu;          // [columns]: the grid [cm-1]
     const double * length;      // [count][K]: s_l/mu_k of flat level first + i [m]
     const double * weight;      // [K]: the angles' weights
     const double * temperature; // [count]: temperature of flat level first + i [K]
     const double * surface_t;   // [paths of the run]: surface temperature [K] (up sweep)
     const double * surface_e;   // [paths of the run]: surface emissivity (up sweep)
-    int first, count;           // the flat levels of this launch
-    int row_base;               // flat level of row 0 of beta and level_flux
-    int levels_per_path;
-    int first_path;             // path of blockIdx.y == 0
     int table_path;             // path of surface_t[0] / surface_e[0]
-    int from_last;              // sweep each path from its last level down
     int up;                     // up sweep: starts from the surface, not from space
-    double * carry;             // [paths][K][stride]: the I_k of a path between runs
     double * reflection;        // [paths][stride]: R (down sweep writes, up sweep reads), then
                                 // the up sweep's flux at the surface interface
     double * level_flux;        // F after each level
@@ -108,34 +99,20 @@ __device__ __forceinline__ void flux_level(const double * length, double t,
     }
 }
 
-// grid (columns / (kPathThreads*kPathWidth), paths touched by [first, first + count)).
-// kVector: every row starts 16-byte aligned (even stride, aligned bases).
+// grid and kVector as for path_sweep_kernel.
 template <bool kVector, int K>
 __global__ __launch_bounds__(kPathThreads) void path_flux_kernel(PathFlux a)
 {
-    constexpr int kAhead = kFluxAhead<K>;
-    const long long j = ((long long)blockIdx.x*kPathThreads + threadIdx.x)*kPathWidth;
-    if (j >= a.columns) return;
-    const int width = (int)(a.columns - j < kPathWidth ? a.columns - j : kPathWidth);
-    const int p = a.first_path + (int)blockIdx.y;
-    const int path_lo = p*a.levels_per_path, path_hi = path_lo + a.levels_per_path;
-    const int lo = max(a.first, path_lo), hi = min(a.first + a.count, path_hi);
-    if (lo >= hi) return;
-    const bool starts = a.from_last ? hi == path_hi : lo == path_lo;
-    const bool finishes = a.from_last ? lo == path_lo : hi == path_hi;
-    const int n = hi - lo;
-    // Level of the k-th step: lo + k upward, hi - 1 - k downward.
-    const int origin = a.from_last ? hi - 1 : lo;
-    const int direction = a.from_last ? -1 : 1;
-    const long long row_step = (long long)direction*a.stride;
-    const double * beta = a.beta + (long long)(origin - a.row_base)*a.stride + j;
-    const double * length = a.length + (long long)(origin - a.first)*K;
-    const double * temperature = a.temperature + (origin - a.first);
-    const long long row = (long long)p*a.stride + j;
-    double * carry = a.carry + (long long)p*K*a.stride + j;
+    const PathLane l = path_lane(a);
+    if (l.idle) return;
+    const double * length = a.length + (long long)l.index0*K;
+    const double * temperature = a.temperature + l.index0;
+    const int width = l.width;
+    const long long row = (long long)l.p*a.stride + l.j;
+    double * carry = a.carry + (long long)l.p*K*a.stride + l.j;
 
     double nu[kPathWidth], c1nu3[kPathWidth], c2nu[kPathWidth];
-    path_load<kVector>(a.nu + j, width, nu);
+    path_load<kVector>(a.nu + l.j, width, nu);
 #pragma unroll
     for (int i = 0; i < kPathWidth; ++i)
     {
@@ -144,10 +121,10 @@ __global__ __launch_bounds__(kPathThreads) void path_flux_kernel(PathFlux a)
     }
 
     double rad[K][kPathWidth];
-    if (starts && a.up)
+    if (l.starts && a.up)
     {
-        const double ts = a.surface_t[p - a.table_path];
-        const double es = a.surface_e[p - a.table_path];
+        const double ts = a.surface_t[l.p - a.table_path];
+        const double es = a.surface_e[l.p - a.table_path];
         double r[kPathWidth];
         path_load<kVector>(a.reflection + row, width, r);
 #pragma unroll
@@ -160,7 +137,7 @@ __global__ __launch_bounds__(kPathThreads) void path_flux_kernel(PathFlux a)
         // The flux at the surface interface replaces R in the same lane's columns.
         flux_store<kVector, K>(a.reflection, row, width, a.weight, rad);
     }
-    else if (starts)
+    else if (l.starts)
     {
 #pragma unroll
         for (int k = 0; k < K; ++k)
@@ -174,36 +151,14 @@ __global__ __launch_bounds__(kPathThreads) void path_flux_kernel(PathFlux a)
 #pragma unroll
         for (int k = 0; k < K; ++k) path_load<kVector>(carry + (long long)k*a.stride, width, rad[k]);
     }
-    const long long level0 = (long long)(origin - a.row_base)*a.stride + j;
+    path_levels<kFluxAhead<K>, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
+                                                  long long at) {
+        flux_level<K>(length + (long long)k*l.direction*K, temperature[k*l.direction], b, nu,
+                      c1nu3, c2nu, rad);
+        flux_store<kVector, K>(a.level_flux, at, width, a.weight, rad);
+    });
 
-    int k = 0;
-    for (; k + kAhead <= n; k += kAhead)
-    {
-        double b[kAhead][kPathWidth];
-#pragma unroll
-        for (int u = 0; u < kAhead; ++u)
-        {
-            path_load<kVector>(beta + (long long)(k + u)*row_step, width, b[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < kAhead; ++u)
-        {
-            flux_level<K>(length + (long long)(k + u)*direction*K,
-                          temperature[(k + u)*direction], b[u], nu, c1nu3, c2nu, rad);
-            flux_store<kVector, K>(a.level_flux, level0 + (long long)(k + u)*row_step, width,
-                                   a.weight, rad);
-        }
-    }
-    for (; k < n; ++k)
-    {
-        double b[kPathWidth];
-        path_load<kVector>(beta + (long long)k*row_step, width, b);
-        flux_level<K>(length + (long long)k*direction*K, temperature[k*direction], b, nu, c1nu3,
-                      c2nu, rad);
-        flux_store<kVector, K>(a.level_flux, level0 + (long long)k*row_step, width, a.weight, rad);
-    }
-
-    if (!finishes)
+    if (!l.finishes)
     {
 #pragma unroll
         for (int q = 0; q < K; ++q) path_store<kVector>(carry + (long long)q*a.stride, width, rad[q]);

@@ -5,10 +5,13 @@
 //   tau = tau + s*beta from tau = 0 (the TU builds with -ffp-contract=off: no FMA), so that the
 //   result is bit for bit the numpy loop in the same order.
 //
-// path_sweep_kernel: one pass over the levels of a run.  A lane owns kPathWidth consecutive
-// columns (one 16-byte load per row), keeps tau in registers, has kPathAhead rows in flight, and
-// writes per-level (cumulative) and final results as they are formed.  The block is read once:
-// the kernel is bound by HBM.
+// The sweep skeleton, shared with path_radiance_kernel (radiance.h) and path_flux_kernel (flux.h):
+// path_lane places a lane -- kPathWidth consecutive columns (one 16-byte load per row) of one path
+// -- and path_levels runs its levels of the launch in sweep order with kAhead rows in flight,
+// handing each row to the kernel's per-level update.  A kernel adds its state, its start, the
+// update with its per-level stores, and its finish.
+// path_sweep_kernel: tau in registers, per-level (cumulative) and final results written as they
+// are formed.  The block is read once: the kernel is bound by HBM.
 // path_band_partial_kernel / path_band_mean_kernel: arithmetic means over runs of columns.  The
 // host cuts every band at multiples of kPathSegment columns; one wavefront sums one segment (each
 // lane a fixed stride, then a fixed DPP scan), a second kernel adds a band's segment partials in
@@ -28,18 +31,24 @@ constexpr int kPathSegment = 4096;      // columns per band segment at most (64 
 constexpr int kPathWaves = kPathThreads/64;
 constexpr int kPathGridY = 65535;       // paths or rows per launch (the grid's y limit)
 
-struct PathSweep
+// What the three sweeps (path_sweep_kernel, path_radiance_kernel in radiance.h,
+// path_flux_kernel in flux.h) share of their arguments.
+struct PathLevels
 {
     const double * beta;        // row of flat level `row_base`; rows `stride` apart
-    long long stride;           // row stride of beta, carry, level and final outputs [values]
+    long long stride;           // row stride of beta, carry and the row outputs [values]
     long long columns;
-    const double * length;      // [count]: path length of flat level first + i
     int first, count;           // the flat levels of this launch
     int row_base;               // flat level of row 0 of beta and the level outputs
     int levels_per_path;
     int first_path;             // path of blockIdx.y == 0
     int from_last;              // sweep each path from its last level down
-    double * carry;             // [paths][stride]: tau of a path between runs
+    double * carry;             // [paths][stride] (flux: [paths][K][stride]): state between runs
+};
+
+struct PathSweep : PathLevels
+{
+    const double * length;      // [count]: path length of flat level first + i
     double * level_tau;         // cumulative: tau after each level (may be beta itself), or null
     double * level_trans;       // cumulative: exp(-tau) after each level, or null
     double * final_tau;         // [paths][stride]: tau of a finished path, or null
@@ -85,82 +94,105 @@ __device__ __forceinline__ void path_store_exp(double * p, int width, const doub
     path_store<kVector>(p, width, t);
 }
 
+// A lane's part of a sweep launch: columns [j, j + width) of path p, whose levels in the launch
+// it takes in n steps -- step k is flat level lo + k upward, hi - 1 - k downward.
+struct PathLane
+{
+    bool idle;                  // no columns, or no level of path p in the launch: nothing to do
+    long long j;
+    int width, p, n;
+    bool starts, finishes;      // the path's first / last level in sweep order is in the launch
+    int direction;              // +1 upward, -1 downward
+    long long row_step;         // from one step's row to the next [values]
+    long long level0;           // offset of step 0's row in beta and the level outputs
+    int index0;                 // index of step 0 in the per-level tables (flat level - first)
+};
+
 // grid (columns / (kPathThreads*kPathWidth), paths touched by [first, first + count)).
+__device__ __forceinline__ PathLane path_lane(const PathLevels & a)
+{
+    PathLane l;
+    l.j = ((long long)blockIdx.x*kPathThreads + threadIdx.x)*kPathWidth;
+    l.width = (int)(a.columns - l.j < kPathWidth ? a.columns - l.j : kPathWidth);
+    l.p = a.first_path + (int)blockIdx.y;
+    const int path_lo = l.p*a.levels_per_path, path_hi = path_lo + a.levels_per_path;
+    const int lo = max(a.first, path_lo), hi = min(a.first + a.count, path_hi);
+    l.idle = l.j >= a.columns || lo >= hi;
+    l.starts = a.from_last ? hi == path_hi : lo == path_lo;
+    l.finishes = a.from_last ? lo == path_lo : hi == path_hi;
+    l.n = hi - lo;
+    const int origin = a.from_last ? hi - 1 : lo;
+    l.direction = a.from_last ? -1 : 1;
+    l.row_step = (long long)l.direction*a.stride;
+    l.level0 = (long long)(origin - a.row_base)*a.stride + l.j;
+    l.index0 = origin - a.first;
+    return l;
+}
+
+// The lane's levels in sweep order, kAhead rows in flight: step(k, b, at) with the step index,
+// the lane's columns of its row of beta and the offset of that row in the level outputs.
+template <int kAhead, bool kVector, typename Step>
+__device__ __forceinline__ void path_levels(const PathLevels & a, const PathLane & l, Step step)
+{
+    const double * beta = a.beta + l.level0;
+    int k = 0;
+    for (; k + kAhead <= l.n; k += kAhead)
+    {
+        double b[kAhead][kPathWidth];
+#pragma unroll
+        for (int u = 0; u < kAhead; ++u)
+        {
+            path_load<kVector>(beta + (long long)(k + u)*l.row_step, l.width, b[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kAhead; ++u)
+        {
+            step(k + u, b[u], l.level0 + (long long)(k + u)*l.row_step);
+        }
+    }
+    for (; k < l.n; ++k)
+    {
+        double b[kPathWidth];
+        path_load<kVector>(beta + (long long)k*l.row_step, l.width, b);
+        step(k, b, l.level0 + (long long)k*l.row_step);
+    }
+}
+
 // kVector: every row starts 16-byte aligned (even stride, aligned bases).
 template <bool kVector>
 __global__ __launch_bounds__(kPathThreads) void path_sweep_kernel(PathSweep a)
 {
-    const long long j = ((long long)blockIdx.x*kPathThreads + threadIdx.x)*kPathWidth;
-    if (j >= a.columns) return;
-    const int width = (int)(a.columns - j < kPathWidth ? a.columns - j : kPathWidth);
-    const int p = a.first_path + (int)blockIdx.y;
-    const int path_lo = p*a.levels_per_path, path_hi = path_lo + a.levels_per_path;
-    const int lo = max(a.first, path_lo), hi = min(a.first + a.count, path_hi);
-    if (lo >= hi) return;
-    const bool starts = a.from_last ? hi == path_hi : lo == path_lo;
-    const bool finishes = a.from_last ? lo == path_lo : hi == path_hi;
-    const int n = hi - lo;
-    // Level of the k-th step: lo + k upward, hi - 1 - k downward.
-    const int origin = a.from_last ? hi - 1 : lo;
-    const int direction = a.from_last ? -1 : 1;
-    const long long row_step = (long long)direction*a.stride;
-    const double * beta = a.beta + (long long)(origin - a.row_base)*a.stride + j;
-    const double * length = a.length + (origin - a.first);
+    const PathLane l = path_lane(a);
+    if (l.idle) return;
+    const double * length = a.length + l.index0;
+    const int width = l.width;
 
     double tau[kPathWidth];
-    if (starts)
+    if (l.starts)
     {
 #pragma unroll
         for (int i = 0; i < kPathWidth; ++i) tau[i] = 0.;
     }
     else
     {
-        path_load<kVector>(a.carry + (long long)p*a.stride + j, width, tau);
+        path_load<kVector>(a.carry + (long long)l.p*a.stride + l.j, width, tau);
     }
     const bool per_level = a.level_tau != nullptr || a.level_trans != nullptr;
-    const long long level0 = (long long)(origin - a.row_base)*a.stride + j;
-
-    int k = 0;
-    for (; k + kPathAhead <= n; k += kPathAhead)
-    {
-        double b[kPathAhead][kPathWidth];
-#pragma unroll
-        for (int u = 0; u < kPathAhead; ++u)
-        {
-            path_load<kVector>(beta + (long long)(k + u)*row_step, width, b[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < kPathAhead; ++u)
-        {
-            const double s = length[(k + u)*direction];
-#pragma unroll
-            for (int i = 0; i < kPathWidth; ++i) tau[i] = tau[i] + s*b[u][i];
-            if (per_level)
-            {
-                const long long at = level0 + (long long)(k + u)*row_step;
-                if (a.level_tau != nullptr) path_store<kVector>(a.level_tau + at, width, tau);
-                if (a.level_trans != nullptr) path_store_exp<kVector>(a.level_trans + at, width, tau);
-            }
-        }
-    }
-    for (; k < n; ++k)
-    {
-        double b[kPathWidth];
-        path_load<kVector>(beta + (long long)k*row_step, width, b);
-        const double s = length[k*direction];
+    path_levels<kPathAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth], long long at)
+                                                 {
+        const double s = length[k*l.direction];
 #pragma unroll
         for (int i = 0; i < kPathWidth; ++i) tau[i] = tau[i] + s*b[i];
         if (per_level)
         {
-            const long long at = level0 + (long long)k*row_step;
             if (a.level_tau != nullptr) path_store<kVector>(a.level_tau + at, width, tau);
             if (a.level_trans != nullptr) path_store_exp<kVector>(a.level_trans + at, width, tau);
         }
-    }
+    });
 
-    const long long row = (long long)p*a.stride + j;
-    if (!finishes || a.keep_final) path_store<kVector>(a.carry + row, width, tau);
-    if (finishes)
+    const long long row = (long long)l.p*a.stride + l.j;
+    if (!l.finishes || a.keep_final) path_store<kVector>(a.carry + row, width, tau);
+    if (l.finishes)
     {
         if (a.final_tau != nullptr) path_store<kVector>(a.final_tau + row, width, tau);
         if (a.final_trans != nullptr) path_store_exp<kVector>(a.final_trans + row, width, tau);

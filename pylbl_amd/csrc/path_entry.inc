@@ -1,5 +1,7 @@
+// What the path entries share (lbl_path_compute here, lbl_path_radiance, lbl_path_flux), and
 // lbl_path_compute: optical depth and transmittance along paths through a block of absorption
-// coefficients in HBM (kernels: path.h).  Included by engine.hip after delivery.inc.
+// coefficients in HBM (kernels: path.h).  Included by engine.hip after continuum_entry.inc (grid
+// handles).
 namespace {
 
 // Where a run of flat levels [begin, end) leaves the paths it touches: the first path, how many,
@@ -20,13 +22,46 @@ PathRun path_run(int begin, int end, int levels_per_path, bool from_last)
     return r;
 }
 
-bool aligned16(const void * p)
+// Rows [first, first + count): the paths whose first level p L (or, with `last`, whose last level
+// (p + 1) L - 1) in storage order lies in [begin, end).
+struct PathRows
 {
-    return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+    int first, count;
+};
+
+PathRows path_rows(int begin, int end, int levels_per_path, bool last)
+{
+    const int shift = last ? 0 : levels_per_path - 1;
+    PathRows r;
+    r.first = (begin + shift)/levels_per_path;
+    r.count = std::max((end + shift)/levels_per_path - r.first, 0);
+    return r;
+}
+
+// Whether all `count` values are finite and >= 0 (with `positive`: > 0).
+bool finite_at_least_zero(const double * values, long long count, bool positive)
+{
+    for (long long i = 0; i < count; ++i)
+    {
+        const double v = values[i];
+        if (!(positive ? v > 0. : v >= 0.) || !std::isfinite(v)) return false;
+    }
+    return true;
+}
+
+// Every row starts 16-byte aligned: an even stride and aligned bases (null: not used).
+bool path_vector(int64_t row_stride, std::initializer_list<const void *> bases)
+{
+    if (row_stride % 2 != 0) return false;
+    for (const void * p : bases)
+    {
+        if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return false;
+    }
+    return true;
 }
 
 // The bands of a call: band b is columns [band_start[b], band_start[b + 1]), cut at multiples of
-// kPathSegment into segments.  Staged as 8-byte words after the call's other tables: band_start
+// kPathSegment into segments.  Staged as 8-byte words among the call's tables: band_start
 // [n_bands + 1], each band's first segment [n_bands + 1], then the segments (begin, end).
 struct PathBands
 {
@@ -96,11 +131,14 @@ struct PathBands
     }
 
     // Queues out[r][b] = the mean over band b of row r of `values` (of exp(-value) with
-    // `transmittance`) for `rows` rows `row_stride` apart.  d_table: the staged words on the device.
-    void means(PathWorkspace & w, const long long * d_table, const double * values,
-               long long row_stride, int rows, bool transmittance, double * out,
-               hipStream_t stream) const
+    // `transmittance`) for `rows` rows `row_stride` apart, and records the write of `out`.
+    // d_table: the staged words on the device.
+    void means(lbl_engine * engine, const long long * d_table, const double * values,
+               long long row_stride, int rows, bool transmittance, double * out) const
     {
+        if (rows <= 0) return;
+        PathWorkspace & w = engine->path;
+        hipStream_t stream = engine->stream;
         // Rows go in the grid's y dimension, at most kPathGridY per launch; the chunks run one
         // after the other on this stream and share the partial sums.
         const int chunk_rows = std::min(rows, kPathGridY);
@@ -130,8 +168,157 @@ struct PathBands
                                d_band_start, (int)n_bands, out + (long long)r0*n_bands);
             HIP_TRY(hipGetLastError());
         }
+        engine->lanes[0].note_write(out, (long long)rows*n_bands*8, stream);
     }
 };
+
+// The tables of a call, staged as 8-byte words in one block (one copy to the device per call).
+struct PathTables
+{
+    std::vector<double> words;
+
+    // Appends `count` words (copies of `values`, or zeros) and returns their offset.
+    size_t add(size_t count, const void * values = nullptr)
+    {
+        const size_t at = words.size();
+        words.resize(at + count);
+        if (values != nullptr) std::memcpy(words.data() + at, values, count*8);
+        return at;
+    }
+
+    size_t add(const PathBands & bands, const int64_t * band_start)
+    {
+        const size_t at = add(bands.words());
+        bands.stage(reinterpret_cast<long long *>(words.data() + at), band_start);
+        return at;
+    }
+};
+
+// One call of a path entry: its run, its checks and the steps every entry takes in order.
+struct PathCall
+{
+    lbl_engine * engine;
+    const char * name;          // the entry, the prefix of its messages
+    int64_t row_stride, columns;
+    int32_t n_paths, levels_per_path, level_begin, level_count, flags;
+    const SpectralGrid * grid = nullptr;
+    PathRun run = {};
+
+    int bad(const char * what) const
+    {
+        return fail(engine, LBL_BAD_ARGUMENT, std::string(name) + ": " + what);
+    }
+
+    bool from_last() const { return (flags & LBL_PATH_FROM_LAST) != 0; }
+    int level_end() const { return level_begin + level_count; }
+
+    // nullptr, or what is wrong with the grid handle.
+    const char * find_grid(int32_t handle)
+    {
+        grid = find_slot(engine->grids, handle);
+        return grid == nullptr ? "unknown grid handle." : nullptr;
+    }
+
+    // nullptr, or what is wrong with the run, its LBL_PATH_CONTINUE flag or its lengths
+    // [level_count][angles].  Fills `run`.
+    const char * check(const double * length, int angles)
+    {
+        if (columns < 1 || row_stride < columns) return "need 1 <= columns <= row_stride.";
+        if (grid != nullptr && grid->n < columns)
+        {
+            return "the grid has fewer than `columns` points.";
+        }
+        if (n_paths < 1 || levels_per_path < 1 ||
+            (int64_t)n_paths*levels_per_path > (int64_t)std::numeric_limits<int32_t>::max() ||
+            (int64_t)n_paths*angles > (int64_t)std::numeric_limits<int32_t>::max())
+        {
+            return "need n_paths >= 1 and levels_per_path >= 1.";
+        }
+        const int levels = n_paths*levels_per_path;
+        if (level_begin < 0 || level_count < 1 || level_count > levels - level_begin)
+        {
+            return "the run [level_begin, level_begin + level_count) is not inside the levels.";
+        }
+        run = path_run(level_begin, level_end(), levels_per_path, from_last());
+        if (run.continues != ((flags & LBL_PATH_CONTINUE) != 0))
+        {
+            return run.continues ? "the run starts inside a path: LBL_PATH_CONTINUE is needed."
+                                 : "the run starts a path: LBL_PATH_CONTINUE must not be set.";
+        }
+        if (!finite_at_least_zero(length, (long long)level_count*angles, false))
+        {
+            return "path lengths must be finite and >= 0.";
+        }
+        return nullptr;
+    }
+
+    // Stages the tables and queues their copy to the device, ordered like a plain compute call:
+    // after everything queued on the other lanes (the block's writers among them) -- by events
+    // when the caller does not wait, so that the host keeps queueing.  A call kept back
+    // (LBL_DEFER_FINISH) may still have the block to write: it is queued first.  Returns the
+    // tables on the device.
+    const double * begin(const PathTables & tables)
+    {
+        HIP_TRY(hipSetDevice(engine->device));
+        PathWorkspace & w = engine->path;
+        const size_t words = tables.words.size();
+        std::memcpy(w.stage(words), tables.words.data(), words*8);
+        engine->finish_deferred();
+        if (flags & LBL_ASYNC)
+        {
+            engine->join_lanes(engine->stream);
+        }
+        else
+        {
+            for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
+        }
+        w.upload(words, engine->stream);
+        return w.tables.data;
+    }
+
+    // Queues launch(grid, first path) for every kPathGridY paths of the run (the grid's y limit).
+    template <typename Launch>
+    void launch(Launch launch_one) const
+    {
+        const long long per_block = (long long)kPathThreads*kPathWidth;
+        for (int y0 = 0; y0 < run.paths; y0 += kPathGridY)
+        {
+            const dim3 grid((unsigned)((columns + per_block - 1)/per_block),
+                            (unsigned)std::min(run.paths - y0, kPathGridY));
+            launch_one(grid, run.first_path + y0);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+
+    // Records the write of `rows` rows of `p` (null: none) on the engine's stream.  The block
+    // counts as written even where it is only read: the next call that writes it (the lines of
+    // the next run, on another lane) must wait for the sweep.
+    void note_rows(const double * p, long long rows) const
+    {
+        if (p == nullptr) return;
+        engine->lanes[0].note_write(p, ((rows - 1)*row_stride + columns)*8, engine->stream);
+    }
+};
+
+// The frame of a path entry: the lock, HIP failures as LBL_ERROR and, without LBL_ASYNC, the wait
+// for the call's work.  body() returns the entry's status.
+template <typename Body>
+int path_entry(lbl_engine * engine, int32_t flags, Body body)
+{
+    if (engine == nullptr) return LBL_BAD_ARGUMENT;
+    EngineLock lock(engine->mutex);
+    try
+    {
+        const int status = body();
+        if (status != LBL_OK) return status;
+        if (!(flags & LBL_ASYNC)) HIP_TRY(hipStreamSynchronize(engine->stream));
+    }
+    catch (const HipFailure & f)
+    {
+        return fail(engine, LBL_ERROR, f.message);
+    }
+    return LBL_OK;
+}
 
 }  // namespace
 
@@ -143,106 +330,47 @@ int lbl_path_compute(lbl_engine * engine, double * beta, int64_t row_stride, int
                      const int64_t * band_start, double * carry, double * optical_depth,
                      double * transmittance, int32_t flags)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    auto bad = [&](const char * what) {
-        return fail(engine, LBL_BAD_ARGUMENT, std::string("lbl_path_compute: ") + what);
-    };
-    const bool want_tau = (flags & LBL_PATH_OPTICAL_DEPTH) != 0;
-    const bool want_trans = (flags & LBL_PATH_TRANSMITTANCE) != 0;
-    const bool cumulative = (flags & LBL_PATH_CUMULATIVE) != 0;
-    const bool from_last = (flags & LBL_PATH_FROM_LAST) != 0;
-    if (beta == nullptr || path_length == nullptr || carry == nullptr)
-    {
-        return bad("beta, path_length and carry must not be NULL.");
-    }
-    if (!want_tau && !want_trans) return bad("no quantity requested.");
-    if ((want_tau && optical_depth == nullptr) || (want_trans && transmittance == nullptr))
-    {
-        return bad("an output requested by the flags is NULL.");
-    }
-    if (from_last && !cumulative) return bad("LBL_PATH_FROM_LAST needs LBL_PATH_CUMULATIVE.");
-    if (columns < 1 || row_stride < columns) return bad("need 1 <= columns <= row_stride.");
-    if (n_paths < 1 || levels_per_path < 1 ||
-        (int64_t)n_paths*levels_per_path > (int64_t)std::numeric_limits<int32_t>::max())
-    {
-        return bad("need n_paths >= 1 and levels_per_path >= 1.");
-    }
-    const int levels = n_paths*levels_per_path;
-    if (level_begin < 0 || level_count < 1 || level_count > levels - level_begin)
-    {
-        return bad("the run [level_begin, level_begin + level_count) is not inside the levels.");
-    }
-    const int level_end = level_begin + level_count;
-    const PathRun run = path_run(level_begin, level_end, levels_per_path, from_last);
-    if (run.continues != ((flags & LBL_PATH_CONTINUE) != 0))
-    {
-        return bad(run.continues ? "the run starts inside a path: LBL_PATH_CONTINUE is needed."
-                                 : "the run starts a path: LBL_PATH_CONTINUE must not be set.");
-    }
-    for (int i = 0; i < level_count; ++i)
-    {
-        if (!(path_length[i] >= 0.) || !std::isfinite(path_length[i]))
+    return path_entry(engine, flags, [&] {
+        PathCall call{engine, "lbl_path_compute", row_stride, columns, n_paths, levels_per_path,
+                      level_begin, level_count, flags};
+        const bool want_tau = (flags & LBL_PATH_OPTICAL_DEPTH) != 0;
+        const bool want_trans = (flags & LBL_PATH_TRANSMITTANCE) != 0;
+        const bool cumulative = (flags & LBL_PATH_CUMULATIVE) != 0;
+        if (beta == nullptr || path_length == nullptr || carry == nullptr)
         {
-            return bad("path lengths must be finite and >= 0.");
+            return call.bad("beta, path_length and carry must not be NULL.");
         }
-    }
-    PathBands bands;
-    if (const char * problem = bands.check(n_bands, band_start, columns)) return bad(problem);
-    // Rows whose band means this call forms: every level of the run (cumulative) or the paths
-    // the run finishes.
-    int band_rows = 0, band_row0 = 0;
-    if (n_bands > 0)
-    {
-        if (cumulative)
+        if (!want_tau && !want_trans) return call.bad("no quantity requested.");
+        if ((want_tau && optical_depth == nullptr) || (want_trans && transmittance == nullptr))
         {
-            band_rows = level_count;
+            return call.bad("an output requested by the flags is NULL.");
         }
-        else
+        if (call.from_last() && !cumulative)
         {
-            // (upward: path p finishes here when its last level, (p + 1) L - 1, is in the run)
-            band_row0 = level_begin/levels_per_path;
-            band_rows = std::max(level_end/levels_per_path - band_row0, 0);
+            return call.bad("LBL_PATH_FROM_LAST needs LBL_PATH_CUMULATIVE.");
         }
-    }
-    try
-    {
-        HIP_TRY(hipSetDevice(engine->device));
-        PathWorkspace & w = engine->path;
-        // The tables: lengths [level_count], then the bands' words.
-        const size_t words = (size_t)level_count + bands.words();
-        double * staged = w.stage(words);
-        std::memcpy(staged, path_length, (size_t)level_count*8);
-        bands.stage(reinterpret_cast<long long *>(staged + level_count), band_start);
-        hipStream_t stream = engine->stream;
-        // Ordered like a plain compute call: after everything queued on the other lanes (the
-        // block's writers among them) -- by events when the caller does not wait, so that the
-        // host keeps queueing.  A call kept back (LBL_DEFER_FINISH) may still have the block to
-        // write: it is queued first.
-        engine->finish_deferred();
-        if (flags & LBL_ASYNC)
+        if (const char * problem = call.check(path_length, 1)) return call.bad(problem);
+        PathBands bands;
+        if (const char * problem = bands.check(n_bands, band_start, columns))
         {
-            engine->join_lanes(stream);
+            return call.bad(problem);
         }
-        else
-        {
-            for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
-        }
-        w.upload(words, stream);
-        const double * d_length = w.tables.data;
-        const long long * d_table = reinterpret_cast<const long long *>(w.tables.data + level_count);
+
+        PathTables tables;
+        const size_t length_at = tables.add(level_count, path_length);
+        const size_t band_at = tables.add(bands, band_start);
+        const double * d_tables = call.begin(tables);
 
         PathSweep a;
         a.beta = beta;
         a.stride = row_stride;
         a.columns = columns;
-        a.length = d_length;
+        a.length = d_tables + length_at;
         a.first = level_begin;
         a.count = level_count;
         a.row_base = level_begin;
         a.levels_per_path = levels_per_path;
-        a.first_path = run.first_path;
-        a.from_last = from_last ? 1 : 0;
+        a.from_last = call.from_last() ? 1 : 0;
         a.carry = carry;
         a.level_tau = a.level_trans = a.final_tau = a.final_trans = nullptr;
         a.keep_final = 0;
@@ -264,71 +392,48 @@ int lbl_path_compute(lbl_engine * engine, double * beta, int64_t row_stride, int
             a.final_tau = want_tau ? optical_depth : nullptr;
             a.final_trans = want_trans ? transmittance : nullptr;
         }
-        const bool vector = row_stride % 2 == 0 && aligned16(beta) && aligned16(carry) &&
-                            aligned16(a.level_tau) && aligned16(a.level_trans) &&
-                            aligned16(a.final_tau) && aligned16(a.final_trans);
-        const long long per_block = (long long)kPathThreads*kPathWidth;
-        // Paths go in the grid's y dimension, at most kPathGridY of them per launch.
-        for (int y0 = 0; y0 < run.paths; y0 += kPathGridY)
-        {
-            a.first_path = run.first_path + y0;
-            const dim3 grid((unsigned)((columns + per_block - 1)/per_block),
-                            (unsigned)std::min(run.paths - y0, kPathGridY));
+        const bool vector = path_vector(row_stride, {beta, carry, a.level_tau, a.level_trans,
+                                                     a.final_tau, a.final_trans});
+        call.launch([&](const dim3 & grid, int first_path) {
+            a.first_path = first_path;
             if (vector)
             {
-                hipLaunchKernelGGL(path_sweep_kernel<true>, grid, dim3(kPathThreads), 0, stream, a);
+                hipLaunchKernelGGL(path_sweep_kernel<true>, grid, dim3(kPathThreads), 0,
+                                   engine->stream, a);
             }
             else
             {
-                hipLaunchKernelGGL(path_sweep_kernel<false>, grid, dim3(kPathThreads), 0, stream, a);
+                hipLaunchKernelGGL(path_sweep_kernel<false>, grid, dim3(kPathThreads), 0,
+                                   engine->stream, a);
             }
-            HIP_TRY(hipGetLastError());
-        }
-        const long long last_row = (long long)(level_count - 1)*row_stride + columns;
-        // The block counts as written even where it is only read: the next call that writes it
-        // (the lines of the next run, on another lane) must wait for this sweep.
-        engine->lanes[0].note_write(beta, last_row*8, stream);
-        if (a.level_tau != nullptr && a.level_tau != beta)
-        {
-            engine->lanes[0].note_write(a.level_tau, last_row*8, stream);
-        }
-        if (a.level_trans != nullptr) engine->lanes[0].note_write(a.level_trans, last_row*8, stream);
-        engine->lanes[0].note_write(carry, ((long long)(n_paths - 1)*row_stride + columns)*8,
-                                    stream);
-        if (a.final_tau != nullptr)
-        {
-            engine->lanes[0].note_write(a.final_tau, ((long long)(n_paths - 1)*row_stride + columns)*8,
-                                        stream);
-        }
-        if (a.final_trans != nullptr)
-        {
-            engine->lanes[0].note_write(a.final_trans, ((long long)(n_paths - 1)*row_stride + columns)*8,
-                                        stream);
-        }
+        });
+        call.note_rows(beta, level_count);
+        call.note_rows(a.level_tau != beta ? a.level_tau : nullptr, level_count);
+        call.note_rows(a.level_trans, level_count);
+        call.note_rows(carry, n_paths);
+        call.note_rows(a.final_tau, n_paths);
+        call.note_rows(a.final_trans, n_paths);
 
-        if (n_bands > 0 && band_rows > 0)
+        if (n_bands > 0)
         {
-            // Values: the run's rows of beta (cumulative, in place) or the finished paths' carry
-            // rows; outputs [rows][n_bands] from the first row this call forms.
-            const double * values = cumulative ? beta : carry + (long long)band_row0*row_stride;
-            const long long out_row0 = cumulative ? 0 : band_row0;
+            // Rows: every level of the run (cumulative, in place in beta) or the paths the run
+            // finishes (upward: those whose last level is in the run), from their carry rows.
+            const PathRows rows = cumulative ? PathRows{0, level_count}
+                                             : path_rows(level_begin, call.level_end(),
+                                                         levels_per_path, true);
+            const double * values = cumulative ? beta : carry + (long long)rows.first*row_stride;
+            const long long * d_bands = reinterpret_cast<const long long *>(d_tables + band_at);
             for (int q = 0; q < 2; ++q)
             {
                 const bool trans = q == 1;
                 if (!(trans ? want_trans : want_tau)) continue;
-                double * out = (trans ? transmittance : optical_depth) + out_row0*n_bands;
-                bands.means(w, d_table, values, (long long)row_stride, band_rows, trans, out,
-                            stream);
-                engine->lanes[0].note_write(out, (long long)band_rows*n_bands*8, stream);
+                double * out = (trans ? transmittance : optical_depth) +
+                               (cumulative ? 0 : (long long)rows.first*n_bands);
+                bands.means(engine, d_bands, values, (long long)row_stride, rows.count, trans, out);
             }
         }
-        if (!(flags & LBL_ASYNC)) HIP_TRY(hipStreamSynchronize(stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 }  // extern "C"

@@ -196,6 +196,19 @@ def _f64(array):
     return np.ascontiguousarray(array, dtype=np.float64)
 
 
+def _path_run(band_start, level_begin, rows, levels_per_path, from_last, asynchronous):
+    """(int64 band starts or None, n_bands, flags) of a path call on the levels [level_begin,
+    level_begin + rows): PATH_FROM_LAST, ASYNC and PATH_CONTINUE when the run's first level in
+    sweep order lies inside a path."""
+    starts = None if band_start is None else np.ascontiguousarray(band_start, dtype=np.int64)
+    n_bands = 0 if starts is None else starts.size - 1
+    flags = (PATH_FROM_LAST if from_last else 0) | (ASYNC if asynchronous else 0)
+    end = int(level_begin) + rows
+    if (end % int(levels_per_path) if from_last else int(level_begin) % int(levels_per_path)):
+        flags |= PATH_CONTINUE
+    return starts, n_bands, flags
+
+
 # Status codes of lbl_table_read (include/lbl_amd.h).
 TABLE_OPEN_FAILED, TABLE_NO_ALIAS, TABLE_NO_TIPS, TABLE_NOT_RECTANGULAR, TABLE_NO_ISOTOPOLOGUES, \
     TABLE_NO_TRANSITIONS = 10, 11, 12, 13, 14, 15
@@ -663,16 +676,11 @@ class Engine(object):
             raise ValueError("one path length per row of beta.")
         if tuple(carry.shape) != (int(n_paths), stride):
             raise ValueError("carry must be [n_paths, row length of beta].")
-        starts = None if band_start is None else \
-            np.ascontiguousarray(band_start, dtype=np.int64)
-        n_bands = 0 if starts is None else starts.size - 1
-        flags = (PATH_OPTICAL_DEPTH if optical_depth is not None else 0) | \
-                (PATH_TRANSMITTANCE if transmittance is not None else 0) | \
-                (PATH_CUMULATIVE if cumulative else 0) | (PATH_FROM_LAST if from_last else 0) | \
-                (ASYNC if asynchronous else 0)
-        end = int(level_begin) + rows
-        if (end % int(levels_per_path) if from_last else int(level_begin) % int(levels_per_path)):
-            flags |= PATH_CONTINUE
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
+                                           from_last, asynchronous)
+        flags |= (PATH_OPTICAL_DEPTH if optical_depth is not None else 0) | \
+                 (PATH_TRANSMITTANCE if transmittance is not None else 0) | \
+                 (PATH_CUMULATIVE if cumulative else 0)
         width = n_bands if n_bands > 0 else stride
         for out in (optical_depth, transmittance):
             if out is not None and (out.shape[1] != width or
@@ -709,16 +717,11 @@ class Engine(object):
                 if values.shape != (int(n_paths),):
                     raise ValueError("one boundary value per path.")
             boundary.append(values)
-        starts = None if band_start is None else \
-            np.ascontiguousarray(band_start, dtype=np.int64)
-        n_bands = 0 if starts is None else starts.size - 1
-        flags = (PATH_RADIANCE if radiance is not None else 0) | \
-                (PATH_BRIGHTNESS if brightness_temperature is not None else 0) | \
-                (PATH_CUMULATIVE if cumulative else 0) | (PATH_FROM_LAST if from_last else 0) | \
-                (ASYNC if asynchronous else 0)
-        end = int(level_begin) + rows
-        if (end % int(levels_per_path) if from_last else int(level_begin) % int(levels_per_path)):
-            flags |= PATH_CONTINUE
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
+                                           from_last, asynchronous)
+        flags |= (PATH_RADIANCE if radiance is not None else 0) | \
+                 (PATH_BRIGHTNESS if brightness_temperature is not None else 0) | \
+                 (PATH_CUMULATIVE if cumulative else 0)
         width = n_bands if n_bands > 0 else stride
         for out in (radiance, brightness_temperature):
             if out is not None and (out.shape[1] != width or
@@ -762,17 +765,12 @@ class Engine(object):
                 if values.shape != (int(n_paths),):
                     raise ValueError("one surface value per path.")
             surface.append(values)
-        starts = None if band_start is None else \
-            np.ascontiguousarray(band_start, dtype=np.int64)
-        n_bands = 0 if starts is None else starts.size - 1
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
+                                           from_last, asynchronous)
         for out, count in ((flux, rows), (surface_flux, int(n_paths))):
             if out is not None and (out.shape[1] != n_bands or out.shape[0] < count):
                 raise ValueError(f"a band output has shape {out.shape}, need {count} x {n_bands}.")
-        flags = (PATH_FLUX_UP if up else 0) | (PATH_FROM_LAST if from_last else 0) | \
-                (ASYNC if asynchronous else 0)
-        end = int(level_begin) + rows
-        if (end % int(levels_per_path) if from_last else int(level_begin) % int(levels_per_path)):
-            flags |= PATH_CONTINUE
+        flags |= PATH_FLUX_UP if up else 0
         self._check(self.lib.lbl_path_flux(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, angles, lengths.ctypes.data,

@@ -171,6 +171,22 @@ def _sweep_pass(quantities, cumulative, from_last):
                  () if cumulative else tuple(quantities))
 
 
+def _selection(quantities, names):
+    """A non-empty selection of `names` (one name or several) as a tuple in the order of `names`."""
+    if isinstance(quantities, str):
+        quantities = (quantities,)
+    quantities = tuple(quantities)
+    unknown = [q for q in quantities if q not in names]
+    if unknown or not quantities:
+        raise ValueError(f"quantities must be a non-empty selection of {names}, not {quantities}.")
+    return tuple(q for q in names if q in quantities)
+
+
+def _check_range_policy(range_policy):
+    if range_policy not in ("reference", "skip"):
+        raise ValueError(f"unknown range_policy {range_policy!r}.")
+
+
 class Atmosphere(object):
     """Pressure, temperature and gas mole fractions as numpy arrays.
 
@@ -476,7 +492,23 @@ class Spectroscopy(object):
                                      range_policy)
         if remove_pedestal is None:
             remove_pedestal = self.continua_backend == "mt_ckd"
-        values = self._compute_path_levels(request, remove_pedestal, range_policy)
+        per_path, paths = _path_layout(request.shape)
+        from_last = request.cumulative == "from_last"
+        cumulative = request.cumulative is not None
+        columns = self.grid.size
+
+        def sweeper(engine, take, run):
+            carry = take(paths)
+
+            def sweep(index, beta, a, b, outputs):
+                engine.path_compute(
+                    beta, columns, paths, per_path, a, request.lengths[a:b], carry,
+                    optical_depth=outputs.get("optical_depth"),
+                    transmittance=outputs.get("transmittance"), band_start=request.starts,
+                    cumulative=cumulative, from_last=from_last, asynchronous=True)
+            return sweep
+        step = _sweep_pass(request.quantities, cumulative, from_last)
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper)
         return self._create_path_dataset(values, request)
 
     def compute_radiance(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
@@ -682,9 +714,7 @@ class Spectroscopy(object):
         """Checks every argument of compute_flux (before anything touches the GPU)."""
         lengths, shape = self._path_geometry(layer_thickness, "compute_flux", "layer_thickness",
                                             "layer thicknesses")
-        temperature = self.atmosphere.temperature
-        if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
-            raise ValueError("the atmosphere's temperatures must be finite and > 0.")
+        self._check_level_temperatures()
         if "heating_rate" in (quantities if not isinstance(quantities, str) else (quantities,)):
             pressure = self.atmosphere.pressure
             if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
@@ -698,16 +728,8 @@ class Spectroscopy(object):
         if not (isinstance(surface, str) and surface in FLUX_SURFACES):
             raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
         mu, weight = flux_angles(angles)
-        if isinstance(quantities, str):
-            quantities = (quantities,)
-        quantities = tuple(quantities)
-        unknown = [q for q in quantities if q not in FLUX_QUANTITIES]
-        if unknown or not quantities:
-            raise ValueError(f"quantities must be a non-empty selection of {FLUX_QUANTITIES}, "
-                             f"not {quantities}.")
-        quantities = tuple(q for q in FLUX_QUANTITIES if q in quantities)
-        if range_policy not in ("reference", "skip"):
-            raise ValueError(f"unknown range_policy {range_policy!r}.")
+        quantities = _selection(quantities, FLUX_QUANTITIES)
+        _check_range_policy(range_policy)
         edges, starts = self._path_bands(band_edges)
         return _FluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
                             starts=starts, surface=surface, mu=mu, weight=weight,
@@ -741,6 +763,11 @@ class Spectroscopy(object):
             raise ValueError("the atmosphere has no levels.")
         return np.ascontiguousarray(lengths.ravel()), shape
 
+    def _check_level_temperatures(self):
+        temperature = self.atmosphere.temperature
+        if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
+            raise ValueError("the atmosphere's temperatures must be finite and > 0.")
+
     def _path_bands(self, band_edges):
         """(edges, column starts) of band_edges, or (None, None)."""
         if band_edges is None:
@@ -753,19 +780,11 @@ class Spectroscopy(object):
     def _path_request(self, path_length, quantities, band_edges, cumulative, range_policy):
         """Checks every argument of compute_path (before anything touches the GPU)."""
         lengths, shape = self._path_geometry(path_length, "compute_path")
-        if isinstance(quantities, str):
-            quantities = (quantities,)
-        quantities = tuple(quantities)
-        unknown = [q for q in quantities if q not in PATH_QUANTITIES]
-        if unknown or not quantities:
-            raise ValueError(f"quantities must be a non-empty selection of {PATH_QUANTITIES}, "
-                             f"not {quantities}.")
-        quantities = tuple(q for q in PATH_QUANTITIES if q in quantities)
+        quantities = _selection(quantities, PATH_QUANTITIES)
         if not (cumulative is None or (isinstance(cumulative, str) and
                                        cumulative in PATH_CUMULATIVE)):
             raise ValueError(f"cumulative must be one of {PATH_CUMULATIVE}, not {cumulative!r}.")
-        if range_policy not in ("reference", "skip"):
-            raise ValueError(f"unknown range_policy {range_policy!r}.")
+        _check_range_policy(range_policy)
         edges, starts = self._path_bands(band_edges)
         return _PathRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
                             starts=starts, cumulative=cumulative)
@@ -774,9 +793,7 @@ class Spectroscopy(object):
                           direction, quantities, band_edges, cumulative, range_policy):
         """Checks every argument of compute_radiance (before anything touches the GPU)."""
         lengths, shape = self._path_geometry(path_length, "compute_radiance")
-        temperature = self.atmosphere.temperature
-        if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
-            raise ValueError("the atmosphere's temperatures must be finite and > 0.")
+        self._check_level_temperatures()
         if boundary_temperature is None:
             boundary = None
         else:
@@ -788,18 +805,10 @@ class Spectroscopy(object):
             raise ValueError("boundary emissivities must lie in [0, 1].")
         if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
             raise ValueError(f"direction must be one of {RADIANCE_DIRECTIONS}, not {direction!r}.")
-        if isinstance(quantities, str):
-            quantities = (quantities,)
-        quantities = tuple(quantities)
-        unknown = [q for q in quantities if q not in RADIANCE_QUANTITIES]
-        if unknown or not quantities:
-            raise ValueError(f"quantities must be a non-empty selection of "
-                             f"{RADIANCE_QUANTITIES}, not {quantities}.")
-        quantities = tuple(q for q in RADIANCE_QUANTITIES if q in quantities)
+        quantities = _selection(quantities, RADIANCE_QUANTITIES)
         if not isinstance(cumulative, (bool, np.bool_)):
             raise ValueError(f"cumulative must be True or False, not {cumulative!r}.")
-        if range_policy not in ("reference", "skip"):
-            raise ValueError(f"unknown range_policy {range_policy!r}.")
+        _check_range_policy(range_policy)
         if band_edges is not None and "brightness_temperature" in quantities:
             raise ValueError("brightness_temperature is only available on the grid: band means "
                              "are formed of the radiance alone.")
@@ -808,26 +817,6 @@ class Spectroscopy(object):
                                 starts=starts, cumulative=bool(cumulative),
                                 from_last=direction == "toward_first",
                                 boundary_temperature=boundary, boundary_emissivity=emissivity)
-
-    def _compute_path_levels(self, request, remove_pedestal, range_policy):
-        """{quantity: array [paths or levels, columns or bands]} of compute_path."""
-        per_path, paths = _path_layout(request.shape)
-        from_last = request.cumulative == "from_last"
-        cumulative = request.cumulative is not None
-        columns = self.grid.size
-
-        def sweeper(engine, take, run):
-            carry = take(paths)
-
-            def sweep(index, beta, a, b, outputs):
-                engine.path_compute(
-                    beta, columns, paths, per_path, a, request.lengths[a:b], carry,
-                    optical_depth=outputs.get("optical_depth"),
-                    transmittance=outputs.get("transmittance"), band_start=request.starts,
-                    cumulative=cumulative, from_last=from_last, asynchronous=True)
-            return sweep
-        return self._sweep_runs(request, [_sweep_pass(request.quantities, cumulative, from_last)],
-                                remove_pedestal, range_policy, sweeper)
 
     def _sweep_runs(self, request, passes, remove_pedestal, range_policy, sweeper,
                     level_blocks=1):
