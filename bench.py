@@ -1,6 +1,6 @@
 """Benchmark of the molecular-lines hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: either under a launcher -- python -m torch.distributed.run --nproc-per-node N ...
      bench.py --gpus N ... -- or bare: without WORLD_SIZE in the environment bench.py starts its
      N ranks itself as child processes, before anything touches the GPU: launch_ranks)
@@ -18,7 +18,11 @@ H2O + CO2, grid 1-5000 cm-1 at 0.001 cm-1 (5 M points), synthetic HITRAN-like li
 HITRAN database exists offline).  --config selects the other BASELINE configs.  Weak scaling:
 every rank gets --levels-per-gpu levels (default 1).
 
-Besides the contract's keys the line carries (N = 1): `roofline` (the resource that binds the
+A plain run does what the headline needs and no more: it sets up, warms up, times the steps,
+writes --dump-outputs and prints the line (the contract's keys, the workload, the kernel times
+the engine's events read inside the timed steps, per-rank records for N > 1).
+
+With --full the line carries besides (N = 1): `roofline` (the resource that binds the
 dominant kernel: the fp64 vector ALU), `roofline_hbm_algorithmic` (SURVEY 8d's 24 B/eval figure,
 for the record), `cpu_baseline` (+ `_parallel`), and untimed legs that measure what users run:
 `sustained`, `single_lane_option`, `pedestal_option`, `standard_atmosphere_option`,
@@ -48,7 +52,7 @@ if ROOT not in sys.path:
 from benchlegs.common import CONFIGS, atmosphere_for                     # noqa: E402
 from benchlegs.compact import compact, write_full_record                                # noqa: E402
 from benchlegs.cpu import closed_form_evals, cpu_legs                    # noqa: E402,F401
-from benchlegs.headline import headline                                  # noqa: E402
+from benchlegs.headline import headline, roofline                        # noqa: E402
 from benchlegs.launcher import device_identity, launch_ranks            # noqa: E402,F401
 from benchlegs.lines import (farfield_legs, lines_option_legs, other_config_legs,     # noqa: E402
                              small_grid_legs)
@@ -78,12 +82,20 @@ def parse():
     parser.add_argument("--points-per-lane", type=int, default=0)
     parser.add_argument("--engine-option", action="append", default=[], metavar="NAME=VALUE",
                         help="lbl_set_option before anything is computed (experiments)")
-    parser.add_argument("--no-cpu-baseline", action="store_true")
+    parser.add_argument("--full", action="store_true",
+                        help="besides the headline: the roofline (launches run alone after the "
+                             "timed steps), the untimed legs, the CPU baselines and, for N > 1, "
+                             "one un-overlapped exchange.  Without it a run sets up, warms up, "
+                             "times the steps, dumps (--dump-outputs) and prints its line")
+    parser.add_argument("--no-cpu-baseline", action="store_true",
+                        help="with --full: no CPU baseline")
     parser.add_argument("--no-extras", action="store_true",
-                        help="only the timed steps (what scripts/profile_bench.sh profiles)")
+                        help="with --full: no untimed legs and no CPU baseline, only the roofline "
+                             "(what scripts/profile_bench.sh profiles)")
     parser.add_argument("--extras", default="all",
-                        help="comma list of untimed legs: all, none, or any of sustained, "
-                             "overlap, pedestal, atmosphere, banded, dense, small, farfield, api, continuum")
+                        help="with --full, comma list of untimed legs: all, none, or any of "
+                             "sustained, overlap, pedestal, atmosphere, banded, dense, small, "
+                             "farfield, api, continuum")
     parser.add_argument("--farfield", action="store_true",
                         help="engine option farfield=1: distant lines through their power "
                              "series (an algorithmic shortcut; never the headline value)")
@@ -423,15 +435,6 @@ def run():
 
     per_rank = None
     if grouped and not args.host_output:
-        # The exchange by itself, once, outside the timed region: kernels first (host waits),
-        # then the collection alone -- what a step would pay if nothing overlapped it.
-        fence()
-        begin = time.perf_counter()
-        alone = sharded.run(atmos.t, atmos.p, vmr, dst=0, output=args.output, async_op=True)
-        engine.synchronize()
-        computed = time.perf_counter()
-        alone.wait(timeout=args.exchange_timeout)
-        finished = time.perf_counter()
         mine = dict(identity, seconds=elapsed, ms_per_step=elapsed/args.steps*1e3,
                     spectra_per_s=len(plan.levels_of(rank))*args.steps/elapsed,
                     evals_per_step=int(evals_per_step_local),
@@ -441,9 +444,19 @@ def run():
                     bytes_received_per_step=exchange["received"]/max(exchange["count"], 1),
                     exchange_wait_ms_per_step=exchange["wait_s"]/args.steps*1e3,
                     exchange_in_flight_ms=exchange["in_flight_s"]/max(exchange["count"], 1)*1e3,
-                    unoverlapped_compute_ms=(computed - begin)*1e3,
-                    unoverlapped_exchange_ms=(finished - computed)*1e3,
                     accumulate_ms_per_step=kernel_ms[2]/args.steps)
+        if args.full:
+            # The exchange by itself, once, outside the timed region: kernels first (host waits),
+            # then the collection alone -- what a step would pay if nothing overlapped it.
+            fence()
+            begin = time.perf_counter()
+            alone = sharded.run(atmos.t, atmos.p, vmr, dst=0, output=args.output, async_op=True)
+            engine.synchronize()
+            computed = time.perf_counter()
+            alone.wait(timeout=args.exchange_timeout)
+            finished = time.perf_counter()
+            mine.update(unoverlapped_compute_ms=(computed - begin)*1e3,
+                        unoverlapped_exchange_ms=(finished - computed)*1e3)
         per_rank = [None]*world
         dist.all_gather_object(per_rank, mine)
         fence()
@@ -470,17 +483,20 @@ def run():
                           levels_total=levels_total, make_tables=make_tables, rank=rank,
                           world=world, plan=plan, sharded=sharded, vmr=vmr, workload=None)
     if rank == 0:
-        line = headline(job, SimpleNamespace(
+        measured = SimpleNamespace(
             elapsed=elapsed, evals_per_step=evals_per_step,
             evals_per_step_local=evals_per_step_local, kernel_ms=kernel_ms, launches=launches,
             busy_ms=busy_ms,
-            per_rank=per_rank, grouped=grouped, everyone=everyone, shared=shared))
+            per_rank=per_rank, grouped=grouped, everyone=everyone, shared=shared)
+        line = headline(job, measured)
         job.workload = line["config"]["workload"]
+        if args.full:
+            roofline(job, measured, line)
 
-    # ---- untimed legs, one GPU only -----------------------------------------------------------
-    plain = world == 1 and not args.force_group and not args.ablate and not args.host_output
+    # ---- untimed legs (--full), one GPU only --------------------------------------------------
+    alone_on_gpu = world == 1 and not args.force_group and not args.ablate and not args.host_output
     shared_db = None
-    if plain and rank == 0 and args.extras != "none":
+    if args.full and alone_on_gpu and rank == 0 and args.extras != "none":
         lines_option_legs(job, line, leg)
         if leg("small") and args.config == "target":
             small_grid_legs(job, line)
@@ -500,7 +516,7 @@ def run():
         other_config_legs(job, line, leg)
         api_and_slot_legs(job, line, leg)
     if rank == 0:
-        if plain and not args.no_cpu_baseline and args.extras != "none":
+        if args.full and alone_on_gpu and not args.no_cpu_baseline and args.extras != "none":
             cpu_legs(job, line, shared_db)
         line["environment"] = {
             "variables": {k: v for k, v in sorted(os.environ.items())

@@ -1,6 +1,6 @@
-"""The ONE line bench.py prints: the contract's keys, `roofline`, `cpu_baseline` and one short
-record per untimed leg -- numbers only, no prose -- small enough for a driver that keeps the last
-few KB of stdout.  Everything else (notes, per-rank device identities, splits, sources) is in the
+"""The ONE line bench.py prints: the contract's keys and, with --full, `roofline`, `cpu_baseline`
+and one short record per untimed leg -- numbers only, no prose -- small enough for a driver that
+keeps the last few KB of stdout.  Everything else (notes, per-rank device identities, splits, sources) is in the
 full record written beside bench.py (`full_record`)."""
 import json
 import os
@@ -96,10 +96,11 @@ def compact(line, full_record=None):
     out["config"]["parallelism"] = config.get("parallelism", "").split(":")[-1].strip()[:80]
     out.update(pick(line, ("evals_per_step", "evals_per_s_per_gpu", "spectra_per_s", "INVALID",
                            "non_default_engine_options", "kernel_ms_per_step")))
-    roofline = pick(line["roofline"], ROOFLINE)
-    if isinstance(line["roofline"].get("issue"), dict):
-        roofline["issue"] = pick(line["roofline"]["issue"], ISSUE)
-    out["roofline"] = roofline
+    if "roofline" in line:                  # (bench.py --full)
+        roofline = pick(line["roofline"], ROOFLINE)
+        if isinstance(line["roofline"].get("issue"), dict):
+            roofline["issue"] = pick(line["roofline"]["issue"], ISSUE)
+        out["roofline"] = roofline
     if "cpu_baseline" in line:
         base = line["cpu_baseline"]
         out["cpu_baseline"] = pick(base, CPU)

@@ -1,4 +1,4 @@
-"""Rank 0's full record of the timed region."""
+"""Rank 0's record of the timed region, and (--full) the roofline of its dominant kernel."""
 import os
 
 from .common import (BOOST_CLOCK_GHZ, BYTES_PER_EVAL, FLOPS_PER_EVAL, FP64_VECTOR_PEAK_TFLOPS,
@@ -8,27 +8,22 @@ from .profiled import PROFILED_RAW, profiled_issue, profiled_traffic
 
 
 def headline(job, m):
-    """Rank 0's JSON line from the timed region: value, the contract's keys, who ran where, and
-    the roofline of the accumulate kernel -- from the same launches run alone after the region
-    (asynchronous calls take turns on two lanes, so inside it a launch is never alone), with the
-    PMC passes committed under profiles/ for traffic and issue slots.
+    """Rank 0's JSON line from the timed region: value, the contract's keys, the workload, who
+    ran where, and the kernel times the engine's events read inside the region.  Nothing is run
+    for it (the roofline, which runs launches of its own, is added by `roofline` with --full).
 
     m: what the timed region measured (elapsed = max over ranks, evals_per_step = sum over ranks,
     this rank's kernel_ms / launches from the engine's events, per_rank records)."""
     import torch.distributed as dist
-    args, engine, tables, handles, molecules = job.args, job.engine, job.tables, job.handles, job.molecules
-    atmos, grid_args, v_lo, v_hi, dv = job.atmos, job.grid_args, job.v_lo, job.v_hi, job.dv
+    args, tables, molecules = job.args, job.tables, job.molecules
+    v_lo, v_hi, dv = job.v_lo, job.v_hi, job.dv
     levels_local, levels_total, n = job.levels_local, job.levels_total, job.n
-    rank, world, plan, sharded, vmr = job.rank, job.world, job.plan, job.sharded, job.vmr
-    elapsed, evals_per_step, evals_per_step_local = m.elapsed, m.evals_per_step, m.evals_per_step_local
-    kernel_ms, launches, per_rank, busy_ms = m.kernel_ms, m.launches, m.per_rank, m.busy_ms
+    world, plan, sharded = job.world, job.plan, job.sharded
+    elapsed, evals_per_step = m.elapsed, m.evals_per_step
+    kernel_ms, per_rank = m.kernel_ms, m.per_rank
     grouped, everyone, shared = m.grouped, m.everyone, m.shared
     ms_per_step = elapsed/args.steps*1e3
     value = evals_per_step*args.steps/elapsed
-    accumulate_ms = kernel_ms[2]/max(launches[2], 1)
-    evals_per_launch = evals_per_step_local/max(launches[2]/args.steps, 1)
-    tflops = evals_per_launch*FLOPS_PER_EVAL/(accumulate_ms*1e-3)/1e12
-    algorithmic = evals_per_launch*BYTES_PER_EVAL/(accumulate_ms*1e-3)/1e9
     workload = (f"BASELINE config '{args.config}': {levels_local} level(s) per GPU, "
                 f"{'+'.join(molecules)}, grid {v_lo:g}-{v_hi:g} cm-1 at {dv:g} cm-1 "
                 f"({n} points), cut_off 25, remove_pedestal={args.pedestal}"
@@ -63,19 +58,47 @@ def headline(job, m):
             "exchange_timeout_s": args.exchange_timeout,
             "rccl_mapped": rccl_libraries(),
             "bytes_to_rank0_per_step": (per_rank or [{}])[0].get("bytes_received_per_step"),
-            "exchange_alone_ms_max": max((r["unoverlapped_exchange_ms"]
-                                          for r in per_rank), default=None)
+            "exchange_alone_ms_max": max((r["unoverlapped_exchange_ms"] for r in per_rank
+                                          if "unoverlapped_exchange_ms" in r), default=None)
             if per_rank else None,
             "note": "per rank: the device it ran on, its own wall time for the timed steps, "
                     "bytes it sent/received per step, host time it spent waiting for an "
                     "exchange inside the timed steps (exchange_wait_ms_per_step; 0 = fully "
-                    "hidden behind the next step's kernels) and one un-overlapped step "
-                    "(kernels, then the collection alone) measured after the timed region",
+                    "hidden behind the next step's kernels) and, with --full, one un-overlapped "
+                    "step (kernels, then the collection alone) measured after the timed region",
             "ranks": per_rank if per_rank else everyone,
         },
         "evals_per_step": evals_per_step,
         "evals_per_s_per_gpu": value/world,
         "spectra_per_s": levels_total*args.steps/elapsed,
+        "kernel_ms_per_step": {
+            "prepare": kernel_ms[0]/args.steps, "schedule": kernel_ms[1]/args.steps,
+            "accumulate": kernel_ms[2]/args.steps, "pedestal": kernel_ms[3]/args.steps},
+    }
+    if args.host_output:
+        line["INVALID"] = "host output: PCIe copies inside the step (reported for DESIGN.md)"
+    if args.ablate:
+        line["INVALID"] = f"ablation {args.ablate}: part of the work was skipped"
+    return line
+
+
+def roofline(job, m, line):
+    """--full: the roofline of the accumulate kernel, added to rank 0's line -- from the same
+    launches run alone after the region (asynchronous calls take turns on two lanes, so inside it
+    a launch is never alone), with the PMC passes committed under profiles/ for traffic and issue
+    slots."""
+    args, engine, handles, molecules = job.args, job.engine, job.handles, job.molecules
+    atmos, grid_args, n = job.atmos, job.grid_args, job.n
+    rank, plan, vmr = job.rank, job.plan, job.vmr
+    evals_per_step_local, kernel_ms, launches, busy_ms = \
+        m.evals_per_step_local, m.kernel_ms, m.launches, m.busy_ms
+    ms_per_step = line["ms_per_step"]
+    workload = line["config"]["workload"]
+    accumulate_ms = kernel_ms[2]/max(launches[2], 1)
+    evals_per_launch = evals_per_step_local/max(launches[2]/args.steps, 1)
+    tflops = evals_per_launch*FLOPS_PER_EVAL/(accumulate_ms*1e-3)/1e12
+    algorithmic = evals_per_launch*BYTES_PER_EVAL/(accumulate_ms*1e-3)/1e9
+    line.update({
         "roofline": {
             "bound": "valu_fp64", "achieved": tflops, "peak": FP64_VECTOR_PEAK_TFLOPS,
             "unit": "TFLOP/s", "frac": tflops/FP64_VECTOR_PEAK_TFLOPS, "traffic": None,
@@ -97,10 +120,7 @@ def headline(job, m):
                     "(register accumulation), so the 'fraction' exceeds 1 and is not a "
                     "bandwidth; north_star's '>= 40 % of the HBM roofline' is 1.33e11 evals/s",
         },
-        "kernel_ms_per_step": {
-            "prepare": kernel_ms[0]/args.steps, "schedule": kernel_ms[1]/args.steps,
-            "accumulate": kernel_ms[2]/args.steps, "pedestal": kernel_ms[3]/args.steps},
-    }
+    })
     if not args.host_output and launches[2] > 0:
         # Asynchronous calls that leave their spectra in HBM take turns on the engine's lanes:
         # the tail of one accumulate grid and the head of the next overlap in time, and an
@@ -114,11 +134,11 @@ def headline(job, m):
         # (3 to 10 launches per molecule: about 50 ms of them, so that the mean does not hang
         # on one launch's clock)
         alone_repeats = int(min(10, max(3, 50./max(ms_per_step, 1e-3))))
-        for m, levels in plan.by_molecule(rank).items():
+        for index, levels in plan.by_molecule(rank).items():
             scratch = DeviceSpectra(engine, len(levels), n)
             for _ in range(alone_repeats):
-                engine.compute(handles[molecules[m]], atmos.t[levels], atmos.p[levels],
-                               vmr[molecules[m]][levels], *grid_args,
+                engine.compute(handles[molecules[index]], atmos.t[levels], atmos.p[levels],
+                               vmr[molecules[index]][levels], *grid_args,
                                remove_pedestal=args.pedestal, out=scratch)
             scratch.free()
         alone_ms, alone_launches = engine.timing(reset=True)
@@ -199,9 +219,4 @@ def headline(job, m):
         line["roofline"]["note"] += ("; far-field series on: most of the evaluations counted in "
                                      "`value` are not executed one by one, so `achieved` is not "
                                      "a rate of executed flops and no fraction is given")
-    if args.host_output:
-        line["INVALID"] = "host output: PCIe copies inside the step (reported for DESIGN.md)"
-    if args.ablate:
-        line["INVALID"] = f"ablation {args.ablate}: part of the work was skipped"
-    return line
 

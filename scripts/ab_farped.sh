@@ -8,7 +8,7 @@ for round in 1 2 3; do
   for opts in "$@"; do
     args=""
     for o in $opts; do args="$args --engine-option $o"; done
-    line=$(python bench.py ${BENCH_ARGS:---farfield --pedestal} --no-extras --no-cpu-baseline --steps 40 --warmup 6 $args 2>/dev/null | tail -1)
+    line=$(python bench.py --full ${BENCH_ARGS:---farfield --pedestal} --no-extras --no-cpu-baseline --steps 40 --warmup 6 $args 2>/dev/null | tail -1)
     ms=$(echo "$line" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.4f ms/step  acc_alone %.4f ms' % (d['ms_per_step'], d['roofline']['avg_launch_ms']))")
     echo "round $round  [${opts:-defaults}]  $ms" | tee -a $OUT
   done

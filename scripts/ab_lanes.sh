@@ -11,7 +11,7 @@ done
 done
 done
 for lanes in 2 4 8; do
-python bench.py --steps 5 --warmup 2 --extras small --no-cpu-baseline --engine-option lanes=$lanes 2>/dev/null | python -c "
+python bench.py --full --steps 5 --warmup 2 --extras small --no-cpu-baseline --engine-option lanes=$lanes 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())['small_grid_options']
 print('lanes $lanes in flight: config0 %.4f ms %.4g evals/s   config1 %.4f ms %.4g evals/s' % (d['config0']['ms_per_step'], d['config0']['value'], d['config1']['ms_per_step'], d['config1']['value']))"

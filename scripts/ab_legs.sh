@@ -8,7 +8,7 @@ OUT=$1; VARIANT=$2; ROUNDS=${3:-3}
 for round in $(seq 1 $ROUNDS); do
   for which in main variant; do
     if [ $which = main ]; then unset PYLBL_AMD_LIBRARY; else export PYLBL_AMD_LIBRARY=$(realpath $VARIANT); fi
-    python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --extras ${EXTRAS:-api,farfield,pedestal} --full-record /tmp/ab_full.json 2>/dev/null | python -c "
+    python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --extras ${EXTRAS:-api,farfield,pedestal} --full-record /tmp/ab_full.json 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 legs = d.get('legs', {})

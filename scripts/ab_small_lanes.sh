@@ -5,7 +5,7 @@ for round in 1 2; do
   for opts in "$@"; do
     args=""
     for o in $opts; do args="$args --engine-option $o"; done
-    python bench.py --extras small --no-cpu-baseline --steps 3 --warmup 1 $args 2>/dev/null | python -c "
+    python bench.py --full --extras small --no-cpu-baseline --steps 3 --warmup 1 $args 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 s = d['small_grid_options']

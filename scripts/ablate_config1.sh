@@ -11,7 +11,7 @@ OUT=gpurun_out/ablate_config1_$TAG.txt
 : > $OUT
 for extra in "--config 1" "--config 1 --points-per-lane 2" "--config 1 --points-per-lane 8"; do
   for a in 0 1 2 3 4 8 16 32 64; do
-    line=$(python bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline --ablate $a $extra 2>/dev/null | tail -1)
+    line=$(python bench.py --full --steps 40 --warmup 5 --no-extras --no-cpu-baseline --ablate $a $extra 2>/dev/null | tail -1)
     ms=$(python -c "import json,sys; d=json.loads(sys.argv[1]); print('%.4f %.4f launch alone %.4f' % (d['ms_per_step'], d['kernel_ms_per_step']['accumulate'], d['roofline']['avg_launch_ms']))" "$line")
     echo "args='$extra' ablate=$a ms_per_step,accumulate_ms_in_step= $ms" | tee -a $OUT
   done

@@ -4,7 +4,7 @@
 # (parts of the kernel can only be switched off in the diagnostics build: python -m pylbl_amd.build ablate)
 export PYLBL_AMD_LIBRARY=$(pwd)/pylbl_amd/liblbl_amd_ablate.so
 for ablate in 0 1 2 3 4 16 32 48 0; do
-  python bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline --levels-per-gpu 8 --profile standard --ablate $ablate 2>/dev/null | python -c "
+  python bench.py --full --steps 5 --warmup 2 --no-extras --no-cpu-baseline --levels-per-gpu 8 --profile standard --ablate $ablate 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('ablate %-3s ms/step %.3f accumulate launch alone %.3f ms' % ('$ablate', d['ms_per_step'], d['roofline']['avg_launch_ms']))"

@@ -22,7 +22,7 @@ line = json.loads(open(f"{src}/bench1.json").read().strip().splitlines()[-1])
 evals_per_launch = line["roofline"]["evals_per_launch"]
 summary = {
     "tag": tag,
-    "command": "rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --steps 3 --warmup 1 "
+    "command": "rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --full --steps 3 --warmup 1 "
                "--no-cpu-baseline --extras $EXTRAS (one pass per group, scripts/profile_counters.sh)",
     "workload": line["config"]["workload"],
     "evals_per_accumulate_launch": evals_per_launch,

@@ -13,7 +13,7 @@ tag = sys.argv[1]
 src = f"gpurun_out/prof_{tag}"
 stats = glob.glob(f"{src}/stats/*/*_kernel_stats.csv")[0]
 shutil.copy(stats, f"profiles/{tag}_kernel_stats.csv")
-summary = {"tag": tag, "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 "
+summary = {"tag": tag, "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 "
            "--warmup 2 --no-cpu-baseline --extras " + os.environ.get("EXTRAS", "none") + " " +
            " ".join(sys.argv[2:]), "kernels": {}, "counters": {}}
 for row in csv.DictReader(open(stats)):

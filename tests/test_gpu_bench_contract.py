@@ -1,19 +1,28 @@
 """bench.py's contract with the driver, checked on the GPU: ONE short JSON line (<= 8 KB: the
-driver keeps only the tail of stdout) with the agreed keys, a roofline fraction in (0, 1], a CPU
-baseline, the whole record in the file the line names, and the same from the two-rank launch
-(gloo, both ranks on GPU 0: the flow the driver starts with torch.distributed.run over RCCL)."""
+driver keeps only the tail of stdout) with the agreed keys and the whole record in the file the
+line names; a plain run carries the headline alone, and with --full a roofline fraction in (0, 1],
+a CPU baseline and the untimed legs; the same from the two-rank launch (gloo, both ranks on GPU 0:
+the flow the driver starts with torch.distributed.run over RCCL)."""
 import json
 import os
 import socket
 import subprocess
 import sys
+import time
 
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-        "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"}
+HEADLINE = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+            "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"}
+KEYS = HEADLINE | {"roofline"}          # (--full)
+MOVED = {"roofline", "roofline_hbm_algorithmic", "cpu_baseline", "cpu_baseline_parallel",
+         "cpu_baseline_all_cores", "legs", "ingest", "sustained", "single_lane_option",
+         "pedestal_option", "standard_atmosphere_option", "banded_table_option",
+         "dense_table_option", "small_grid_options", "farfield_option", "api_call",
+         "continuum_slot", "cross_section_slot", "config2_option", "config3_share_option",
+         "config4_share_option"}
 
 
 LIMIT = 8192            # bytes of stdout the driver is known to keep
@@ -40,8 +49,8 @@ def run(command, env=None, tmp_path=None):
     return line, full
 
 
-def check(line, n_gpus, steps, warmup):
-    assert KEYS <= set(line)
+def check_headline(line, n_gpus, steps, warmup):
+    assert HEADLINE <= set(line)
     assert line["n_gpus"] == n_gpus and line["steps"] == steps and line["warmup"] == warmup
     assert line["unit"] == "evals/s" and line["dtype"] == "f64" and line["data"] == "synthetic"
     assert line["higher_is_better"] is True and line["scaling"] == "weak"
@@ -50,6 +59,12 @@ def check(line, n_gpus, steps, warmup):
     assert line["value"] > 1.e9*n_gpus               # north_star's floor, per GPU
     assert abs(line["value"] - line["evals_per_step"]*steps/(line["ms_per_step"]*1e-3*steps)) \
         <= 1e-3*line["value"]               # (the short line carries five significant digits)
+
+
+def check(line, n_gpus, steps, warmup):
+    """A --full line: the headline and the roofline of the accumulate kernel."""
+    assert KEYS <= set(line)
+    check_headline(line, n_gpus, steps, warmup)
     roofline = line["roofline"]
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(roofline)
     assert 0. < roofline["frac"] <= 1.
@@ -69,9 +84,31 @@ def check_issue(roofline):
     assert 3. < issue["fp64_wave_instructions_per_64_evals"] < 8.
 
 
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """`python3 bench.py --gpus 1 --steps 20 --warmup 5`, the driver's plain command: set-up,
+    warm-up, the timed steps, the dump and the line -- no roofline, leg or CPU baseline, in the
+    line or the record -- and at most 30 s of the run outside its steps."""
+    outputs = tmp_path / "outputs"
+    begin = time.perf_counter()
+    line, full = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5",
+                      "--dump-outputs", str(outputs)], tmp_path=tmp_path)
+    seconds = time.perf_counter() - begin
+    check_headline(line, 1, 20, 5)
+    assert line["config"]["workload"].startswith("BASELINE config 'target'")
+    assert line["kernel_ms_per_step"]["accumulate"] > 0.
+    assert not MOVED & set(line) and not MOVED & set(full), (MOVED & set(full))
+    assert seconds - 25*line["ms_per_step"]*1e-3 <= 30., seconds
+    with open(outputs / "outputs.json") as handle:
+        record = json.load(handle)
+    assert set(record["arrays"]) == {"H2O", "CO2"}
+    for name, entry in record["arrays"].items():
+        assert entry["shape"] == [1, 5000000]
+        assert (outputs / f"{name}.npy").is_file()
+
+
 def test_single_gpu_line(tmp_path):
-    line, full = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--extras",
-                      "pedestal", "--cpu-sample-cm", "200"], tmp_path=tmp_path)
+    line, full = run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1",
+                      "--extras", "pedestal", "--cpu-sample-cm", "200"], tmp_path=tmp_path)
     check(line, 1, 3, 1)
     assert line["config"]["workload"].startswith("BASELINE config 'target'")
     baseline = line["cpu_baseline"]
@@ -83,11 +120,12 @@ def test_single_gpu_line(tmp_path):
 
 
 def test_the_drivers_own_command_prints_a_line_it_can_keep():
-    """`python3 bench.py --gpus 1 --steps 20 --warmup 5` -- what the driver runs at round end,
-    every leg on (only the CPU legs' sample is cut short here): the last line of stdout is the
-    whole of stdout, fits the driver's tail, and carries roofline + cpu_baseline + every leg."""
+    """`python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` -- what the driver runs once per
+    change besides the plain command, every leg on (only the CPU legs' sample is cut short here):
+    the last line of stdout is the whole of stdout, fits the driver's tail, and carries roofline +
+    cpu_baseline + every leg."""
     line, full = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5",
-                      "--cpu-sample-cm", "100"])
+                      "--full", "--cpu-sample-cm", "100"])
     check(line, 1, 20, 5)
     check_issue(line["roofline"])
     assert {"value", "unit", "cores", "kind", "sample", "cpu", "host_cores"} <= set(line["cpu_baseline"])
@@ -112,7 +150,7 @@ def test_two_rank_line(launcher, ordering, tmp_path):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     arguments = ["bench.py", "--gpus", "2", "--backend", "gloo", "--config", "1", "--steps", "2",
-                 "--warmup", "1"]
+                 "--warmup", "1", "--full"]
     # ordering "device": kernels and exchange ordered by events on the GPU as on the RCCL path
     # (PYLBL_AMD_ORDER_ON_DEVICE, distributed.ShardedLines), gloo carrying the blocks.
     environment = dict(os.environ, PYLBL_AMD_ORDER_ON_DEVICE="1" if ordering == "device" else "0")
@@ -151,6 +189,26 @@ def test_two_rank_line(launcher, ordering, tmp_path):
     assert report["bytes_to_rank0_per_step"] == 2*n*8
 
 
+def test_two_rank_plain_line(tmp_path):
+    """`python bench.py --gpus 2` without --full: every rank's own record of the timed steps,
+    and no roofline or un-overlapped exchange."""
+    environment = dict(os.environ, PYLBL_AMD_ORDER_ON_DEVICE="0")
+    for name in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        environment.pop(name, None)
+    line, full = run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--config",
+                      "1", "--steps", "2", "--warmup", "1"], env=environment, tmp_path=tmp_path)
+    check_headline(line, 2, 2, 1)
+    assert not MOVED & set(full)
+    assert line["distributed"]["launcher"] == "bench.py"
+    assert [r["rank"] for r in line["distributed"]["ranks"]] == [0, 1]
+    report = full["distributed"]
+    assert report["exchange_alone_ms_max"] is None
+    for r in report["ranks"]:
+        assert r["ms_per_step"] > 0. and r["exchanges"] >= 2
+        assert "unoverlapped_exchange_ms" not in r
+    assert report["bytes_to_rank0_per_step"] == 2*500000*8
+
+
 def test_one_rank_line_with_the_process_group_over_rccl(tmp_path):
     """`bench.py --gpus 1 --backend nccl --force-group`: the N-GPU flow with N = 1 -- RCCL
     loaded, a communicator on the device, the step's blocks collected through the grouped
@@ -160,7 +218,7 @@ def test_one_rank_line_with_the_process_group_over_rccl(tmp_path):
     for name in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         environment.pop(name, None)
     line, full = run([sys.executable, "bench.py", "--gpus", "1", "--backend", "nccl",
-                      "--force-group", "--steps", "3", "--warmup", "1"], env=environment,
+                      "--force-group", "--steps", "3", "--warmup", "1", "--full"], env=environment,
                      tmp_path=tmp_path)
     check(line, 1, 3, 1)
     assert line["distributed"]["ranks"][0]["spectra_per_s"] > 0.

@@ -482,6 +482,31 @@ def test_bench_short_line_fits_the_drivers_tail_also_for_eight_ranks():
     assert "uuid" not in line8["distributed"]["ranks"][0]
 
 
+def test_bench_short_line_of_a_plain_run_is_the_headline():
+    """A run without --full records no roofline, leg or CPU baseline (and, for N > 1, no
+    un-overlapped exchange): its short line keeps the contract's keys and the in-region kernel
+    times, and is no more than that."""
+    import json
+    import sys
+    sys.path.insert(0, str(ROOT))
+    from benchlegs import compact
+    records = sorted((ROOT / "profiles").glob("bench_r??[a-z]_full.json"), key=lambda p: p.name)
+    if not records:
+        pytest.skip("no whole bench record under profiles/")
+    full = json.loads(records[-1].read_text())
+    keep = set(compact.CONTRACT) | {"config", "distributed", "evals_per_step",
+                                    "evals_per_s_per_gpu", "spectra_per_s", "kernel_ms_per_step",
+                                    "environment"}
+    plain = {k: v for k, v in full.items() if k in keep}
+    line = compact.compact(plain, full_record="bench_full.json")
+    for key in compact.CONTRACT:
+        assert line[key] == full[key], key
+    assert set(line) == set(compact.CONTRACT) | {"config", "evals_per_step", "evals_per_s_per_gpu",
+                                                 "spectra_per_s", "kernel_ms_per_step",
+                                                 "full_record"}
+    assert line["kernel_ms_per_step"]["accumulate"] > 0.
+
+
 def test_banded_tables_inside_the_grid_drop_what_falls_outside():
     a = synthetic.banded_line_table("CO2", 1., 5000., num_lines=20000, bands=8, seed=5)
     b = synthetic.banded_line_table("CO2", 1., 5000., num_lines=20000, bands=8, seed=5, inside=True)
