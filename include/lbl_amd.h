@@ -295,6 +295,53 @@ int lbl_path_flux(lbl_engine *engine, double *beta, int64_t row_stride, int64_t 
                   int32_t n_bands, const int64_t *band_start, double *carry, double *reflection,
                   double *level_flux, double *flux, double *surface_flux, int32_t flags);
 
+/* Instrument line shapes (Spectroscopy.compute_path / compute_radiance with `instrument`): N
+ * channels, each a weighted mean of a row of fine-grid values under its line shape.
+ * lbl_instrument_create binds an instrument to a grid (a handle of lbl_grid_load, ascending):
+ * it checks the arguments, computes every channel's window columns on the host in fp64 and
+ * uploads its tables with a copy of the grid in one staged copy.  The handle holds no reference
+ * to the grid afterwards.  With Delta = nu_j - nu_c (host arrays of n_channels values, the
+ * per-channel `parameter` and `half_width` finite and > 0):
+ *   LBL_INSTRUMENT_BOXCAR     w = 1,                          window nu_c -/+ parameter/2
+ *   LBL_INSTRUMENT_TRIANGLE   w = 1 - |Delta|/parameter,      window nu_c -/+ parameter
+ *   LBL_INSTRUMENT_GAUSSIAN   w = exp(-G*((Delta/parameter)*(Delta/parameter))), G = 4 ln 2,
+ *                                                             window nu_c -/+ half_width
+ *   LBL_INSTRUMENT_FTS        w = S(Delta) = sinc(2 L Delta), L = parameter (max path
+ *                             difference [cm]), sinc(x) = sin(pi x)/(pi x), sinc(0) = 1,
+ *                                                             window nu_c -/+ half_width
+ *   LBL_INSTRUMENT_FTS_HAMMING w = 0.54 S(Delta) + 0.23 (S(Delta - 1/(2L)) + S(Delta + 1/(2L)))
+ *   LBL_INSTRUMENT_TABULATED  w = linear interpolation of response at Delta on offsets (n_table
+ *                             >= 2 finite, strictly increasing values; response [response_rows]
+ *                             [n_table], response_rows 1 (shared) or n_channels), window
+ *                             [nu_c + offsets[0], nu_c + offsets[n_table - 1]]; parameter and
+ *                             half_width may be NULL.
+ * Channel c covers the columns searchsorted(grid, lo, "left") <= j < searchsorted(grid, hi,
+ * "right") of its window [lo, hi].
+ * lbl_instrument_apply writes out[r][c] (device, [rows][n_channels], in the order of the centers)
+ *   R_c = (sum_j w_j v_j) / (sum_j w_j) over the window, v_j = values[r*row_stride + j] (device,
+ *   row_stride >= the grid's points), or exp(-v_j) with LBL_PATH_TRANSMITTANCE;
+ * NaN where the window holds no points, lies not wholly inside [grid[0], grid[n - 1]], or its
+ * weights do not sum to > 0.  The sums are formed in a fixed order without atomics: the same
+ * bits for every call and however the rows are split between calls.  Queued on the engine
+ * stream like lbl_path_compute, behind whatever wrote `values`, and recorded as a write of `out`;
+ * LBL_ASYNC returns after queueing.  LBL_BAD_ARGUMENT (message in lbl_last_error) for an unknown
+ * grid or instrument handle, a descending grid, bad shapes, centers, widths or tables, NULL
+ * pointers, rows < 1, a short row_stride or unknown flags; the engine stays usable.
+ * lbl_instrument_free releases the handle. */
+#define LBL_INSTRUMENT_BOXCAR        0
+#define LBL_INSTRUMENT_TRIANGLE      1
+#define LBL_INSTRUMENT_GAUSSIAN      2
+#define LBL_INSTRUMENT_FTS           3
+#define LBL_INSTRUMENT_FTS_HAMMING   4
+#define LBL_INSTRUMENT_TABULATED     5
+int lbl_instrument_create(lbl_engine *engine, int32_t grid, int32_t shape, int32_t n_channels,
+                          const double *centers, const double *parameter,
+                          const double *half_width, int32_t n_table, const double *offsets,
+                          const double *response, int32_t response_rows, int32_t *handle);
+int lbl_instrument_free(lbl_engine *engine, int32_t handle);
+int lbl_instrument_apply(lbl_engine *engine, const double *values, int64_t row_stride,
+                         int32_t rows, int32_t handle, int32_t flags, double *out);
+
 /* Options (fourteen; anything else is LBL_BAD_ARGUMENT):
  *   "prep"                LBL_PREP_DEVICE (default) / LBL_PREP_HOST: where the per-line scalars are formed
  *   "points_per_lane"     0 = by the grid (default), 1/2/4/8 grid points per lane of the accumulate kernel

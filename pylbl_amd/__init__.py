@@ -14,11 +14,12 @@ from .errors import AliasNotFoundError, CrossSectionNotFoundError, EngineError, 
 from .engine import DeviceSpectra, Engine, default_engine
 from .arts_crossfit import CrossSection
 from .gas_optics import Gas
+from .instrument import Instrument
 from .plugins import continua, cross_sections, models, molecular_lines, register
 from .spectroscopy import Atmosphere, Spectroscopy, number_density
 
 __all__ = ["Gas", "CrossSection", "Database", "MemoryDatabase", "LineTable", "TotalPartitionFunction", "write_database",
-           "Engine", "DeviceSpectra", "default_engine", "Spectroscopy", "Atmosphere",
+           "Engine", "DeviceSpectra", "default_engine", "Spectroscopy", "Atmosphere", "Instrument",
            "number_density", "molecular_lines", "continua", "cross_sections", "models",
            "register", "AliasNotFoundError", "CrossSectionNotFoundError", "EngineError", "IsotopologuesNotFoundError",
            "TipsDataNotFoundError", "TransitionsNotFoundError"]

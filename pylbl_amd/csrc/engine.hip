@@ -30,6 +30,7 @@
 #include "xsec.h"
 #include "farfield.h"
 #include "flux.h"
+#include "instrument.h"
 #include "line_prep.h"
 #include "path.h"
 #include "pedestal.h"
@@ -115,6 +116,7 @@ int lbl_engine_destroy(lbl_engine * engine)
     engine->continua.clear();
     engine->xsecs.clear();
     engine->grids.clear();
+    engine->instruments.clear();
     for (auto & lane : engine->lanes) lane.destroy();
     if (engine->copy_stream != nullptr) (void)hipStreamDestroy(engine->copy_stream);
     if (engine->copies_handed_over != nullptr) (void)hipEventDestroy(engine->copies_handed_over);
@@ -551,5 +553,6 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "path_entry.inc"
 #include "radiance_entry.inc"
 #include "flux_entry.inc"
+#include "instrument_entry.inc"
 #include "xsec_entry.inc"
 #include "sqlite_entry.inc"

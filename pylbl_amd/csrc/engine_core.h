@@ -353,6 +353,21 @@ struct SpectralGrid
     }
 };
 
+// An instrument bound to a grid: its channels, tiles and items, the tables of its shape and a
+// copy of the grid's wavenumbers, all on the device in one block of 8-byte words.
+struct Instrument
+{
+    int shape = 0, n_channels = 0, n_items = 0, n_table = 0;
+    long long grid_points = 0;
+    DeviceBuffer<double> words;
+    const InstrChannel * channel = nullptr;
+    const InstrItem * item = nullptr;
+    const long long * tile_channel = nullptr;
+    const double * offsets = nullptr;
+    const double * response = nullptr;
+    const double * nu = nullptr;
+};
+
 // Several continua evaluated in one pass (continuum.h, group kernels): the bands of all of them
 // in one list on the device, one workspace of coarse spectra, one block of level scalars
 // [continuum][level].  Kept per list of handles; dropped when one of them is freed.
@@ -444,6 +459,7 @@ struct lbl_engine
     std::vector<std::unique_ptr<SpectralGrid>> grids;
     std::vector<std::unique_ptr<XsecData>> xsecs;
     std::vector<std::unique_ptr<ContinuumGroup>> groups;
+    std::vector<std::unique_ptr<Instrument>> instruments;
     Lane lanes[kAllLanes];
     unsigned next_lane = 0;
     PathWorkspace path;             // lbl_path_compute

@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
     "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
+    "lbl_instrument_create", "lbl_instrument_free", "lbl_instrument_apply",
 )
 
 VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
@@ -185,6 +186,11 @@ def library():
                                   c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_int32]
+    lib.lbl_instrument_create.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                          c_void_p, c_int32, c_void_p, c_void_p, c_int32, i32p]
+    lib.lbl_instrument_free.argtypes = [c_void_p, c_int32]
+    lib.lbl_instrument_apply.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                         c_void_p]
     for name in EXPORTED_SYMBOLS:
         if name not in ("lbl_last_error", "lbl_stream", "lbl_version"):
             getattr(lib, name).restype = c_int32
@@ -734,6 +740,41 @@ class Engine(object):
             n_bands, starts.ctypes.data if starts is not None else None, carry.pointer,
             radiance.pointer if radiance is not None else None,
             brightness_temperature.pointer if brightness_temperature is not None else None, flags))
+
+    def instrument_create(self, grid, shape, centers, parameter=None, half_width=None,
+                          offsets=None, response=None):
+        """Binds an instrument (pylbl_amd.instrument: its shape code, centres [N] and per-channel
+        parameter / half_width [N], or the offsets [K] and response [K] or [N, K] of a table) to
+        the grid handle `grid` -- lbl_instrument_create.  Returns the instrument handle."""
+        centers = _f64(np.atleast_1d(centers))
+        arrays = [None if x is None else _f64(x) for x in (parameter, half_width, offsets,
+                                                            response)]
+        parameter, half_width, offsets, response = arrays
+        n_table = 0 if offsets is None else offsets.size
+        rows = 0 if response is None else (1 if response.ndim == 1 else response.shape[0])
+        handle = c_int32(-1)
+        self._check(self.lib.lbl_instrument_create(
+            self.handle, int(grid), int(shape), centers.size, centers.ctypes.data,
+            *(x.ctypes.data if x is not None else None for x in (parameter, half_width)),
+            n_table, *(x.ctypes.data if x is not None else None for x in (offsets, response)),
+            rows, byref(handle)))
+        return handle.value
+
+    def instrument_free(self, instrument):
+        self._check(self.lib.lbl_instrument_free(self.handle, int(instrument)))
+
+    def instrument_apply(self, values, rows, instrument, out, transmittance=False,
+                         asynchronous=False):
+        """out[r][c] = channel c's weighted mean of row r of the DeviceSpectra `values` (of
+        exp(-value) with `transmittance`) for its first `rows` rows -- lbl_instrument_apply.
+        out: DeviceSpectra [>= rows, channels]."""
+        rows = int(rows)
+        if not 0 < rows <= values.shape[0] or out.shape[0] < rows:
+            raise ValueError(f"{rows} rows of values {values.shape} into {out.shape}.")
+        flags = (PATH_TRANSMITTANCE if transmittance else 0) | (ASYNC if asynchronous else 0)
+        self._check(self.lib.lbl_instrument_apply(
+            self.handle, values.pointer, int(values.shape[1]), rows, int(instrument), flags,
+            out.pointer))
 
     def path_flux(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                   weight, temperature, carry, reflection, level_flux, surface_temperature=None,

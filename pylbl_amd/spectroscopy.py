@@ -33,7 +33,7 @@ _MAX_RUN_LEVELS = 65535
 
 # What compute_path checked and derived from its arguments.
 _PathRequest = namedtuple("_PathRequest", ["lengths", "shape", "quantities", "edges", "starts",
-                                           "cumulative"])
+                                           "cumulative", "instrument"])
 # compute_radiance's: the same, with `cumulative` a bool, and one boundary value per path.
 _RadianceRequest = namedtuple("_RadianceRequest", _PathRequest._fields + (
     "from_last", "boundary_temperature", "boundary_emissivity"))
@@ -163,6 +163,13 @@ def heating_rate(upward_flux, downward_flux, pressure, temperature, thickness, s
     with np.errstate(divide="ignore", invalid="ignore"):
         rate = (86400.*(lower - upper))/capacity[..., None]
     return np.where((thickness == 0.)[..., None], np.nan, rate)
+
+
+def _spectral_axis(request):
+    """The last dim of a path result: "channel", "band" or "wavenumber"."""
+    if getattr(request, "instrument", None) is not None:
+        return "channel"
+    return "wavenumber" if request.edges is None else "band"
 
 
 def _sweep_pass(quantities, cumulative, from_last):
@@ -462,7 +469,8 @@ class Spectroscopy(object):
             {name: values.reshape(shape + tail) for name, values in flat.items()}, output_format)
 
     def compute_path(self, path_length, quantities=PATH_QUANTITIES, band_edges=None,
-                     cumulative=None, remove_pedestal=None, range_policy="reference"):
+                     cumulative=None, remove_pedestal=None, range_policy="reference",
+                     instrument=None):
         """Optical depth and transmittance along the paths of the atmosphere, formed on the GPU
         from the "total" absorption block without handing that block to the host.
 
@@ -481,15 +489,20 @@ class Spectroscopy(object):
                         arithmetic mean of tau or of exp(-tau) over them (NaN without points).
             cumulative: None (one result per path), "from_first" (tau over levels 0 .. l) or
                         "from_last" (tau over levels l .. L-1, summed from L-1 down).
+            instrument: None, or an Instrument (pylbl_amd.instrument): the channel means of tau
+                        or of exp(-tau) under its line shapes (not exp of the mean tau); NaN for
+                        a channel without points or not wholly inside the grid.  Not with
+                        band_edges.
 
         Returns:
             Like compute_absorption: an xarray Dataset when xarray is installed, else a dict of
             numpy arrays -- "optical_depth" / "transmittance" with the atmosphere's dims (without
-            the last unless cumulative) and "wavenumber" or "band"; coordinates "wavenumber", or
-            "band_lower", "band_upper" and "band_points".
+            the last unless cumulative) and "wavenumber", "band" or "channel"; coordinates
+            "wavenumber", or "band_lower", "band_upper" and "band_points", or "channel_center",
+            "channel_lower", "channel_upper" and "channel_points".
         """
         request = self._path_request(path_length, quantities, band_edges, cumulative,
-                                     range_policy)
+                                     range_policy, instrument)
         if remove_pedestal is None:
             remove_pedestal = self.continua_backend == "mt_ckd"
         per_path, paths = _path_layout(request.shape)
@@ -507,13 +520,21 @@ class Spectroscopy(object):
                     transmittance=outputs.get("transmittance"), band_start=request.starts,
                     cumulative=cumulative, from_last=from_last, asynchronous=True)
             return sweep
-        step = _sweep_pass(request.quantities, cumulative, from_last)
-        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper)
+        reductions = None
+        if request.instrument is None:
+            step = _sweep_pass(request.quantities, cumulative, from_last)
+        else:
+            # The sweep leaves tau on the grid; both quantities are channel means of it.
+            step = _sweep_pass(("optical_depth",), cumulative, from_last)
+            reductions = [(q, "optical_depth", q == "transmittance") for q in request.quantities]
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                  reductions=reductions)
         return self._create_path_dataset(values, request)
 
     def compute_radiance(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
                          direction="toward_last", quantities=("radiance",), band_edges=None,
-                         cumulative=False, remove_pedestal=None, range_policy="reference"):
+                         cumulative=False, remove_pedestal=None, range_policy="reference",
+                         instrument=None):
         """Thermal emission along the paths of the atmosphere: the radiance that leaves each
         path, formed on the GPU from the "total" absorption block like compute_path's optical
         depth.  Every level is an isothermal layer at its own temperature.
@@ -545,15 +566,21 @@ class Spectroscopy(object):
             band_edges: as in compute_path: the arithmetic mean of the radiance over each band
                         (NaN without points).  Not with "brightness_temperature".
             cumulative: True: one result per level, I just after that level in sweep order.
+            instrument: None, or an Instrument (pylbl_amd.instrument): the channel radiances R_c
+                        under its line shapes (NaN for a channel without points or not wholly
+                        inside the grid); "brightness_temperature" is then that of R_c at the
+                        channel centre, (C2*nu_c)/log1p((((C1*nu_c)*nu_c)*nu_c)/R_c), 0 where
+                        R_c <= 0.  Not with band_edges.
 
         Returns:
             Like compute_path: an xarray Dataset when xarray is installed, else a dict --
             "radiance" ("W m-2 sr-1 (cm-1)-1") / "brightness_temperature" ("K") with the
-            atmosphere's dims (without the last unless cumulative) and "wavenumber" or "band".
+            atmosphere's dims (without the last unless cumulative) and "wavenumber", "band" or
+            "channel".
         """
         request = self._radiance_request(path_length, boundary_temperature, boundary_emissivity,
                                          direction, quantities, band_edges, cumulative,
-                                         range_policy)
+                                         range_policy, instrument)
         if remove_pedestal is None:
             remove_pedestal = self.continua_backend == "mt_ckd"
         per_path, paths = _path_layout(request.shape)
@@ -575,8 +602,18 @@ class Spectroscopy(object):
                     band_start=request.starts, cumulative=request.cumulative,
                     from_last=request.from_last, asynchronous=True)
             return sweep
-        step = _sweep_pass(request.quantities, request.cumulative, request.from_last)
-        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper)
+        if request.instrument is None:
+            step = _sweep_pass(request.quantities, request.cumulative, request.from_last)
+            values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper)
+        else:
+            # Channel radiances on the GPU; their brightness temperatures at the centres here.
+            step = _sweep_pass(("radiance",), request.cumulative, request.from_last)
+            values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                      reductions=[("radiance", "radiance", False)])
+            if "brightness_temperature" in request.quantities:
+                from .instrument import brightness_temperature
+                values["brightness_temperature"] = brightness_temperature(
+                    values["radiance"], request.instrument.centers)
         return self._create_path_dataset(values, request)
 
     def compute_flux(self, layer_thickness, surface_temperature, surface_emissivity=1.,
@@ -768,8 +805,16 @@ class Spectroscopy(object):
         if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
             raise ValueError("the atmosphere's temperatures must be finite and > 0.")
 
-    def _path_bands(self, band_edges):
-        """(edges, column starts) of band_edges, or (None, None)."""
+    def _path_bands(self, band_edges, instrument=None):
+        """(edges, column starts) of band_edges, or (None, None); checks `instrument` too."""
+        if instrument is not None:
+            from .instrument import Instrument
+            if band_edges is not None:
+                raise ValueError("give band_edges or instrument, not both.")
+            if not isinstance(instrument, Instrument):
+                raise ValueError(f"instrument must be an Instrument, not {type(instrument)}.")
+            if self.grid.size > 1 and not np.all(np.diff(self.grid) > 0.):
+                raise ValueError("instrument channels need an increasing grid.")
         if band_edges is None:
             return None, None
         if self.grid.size > 1 and not np.all(np.diff(self.grid) > 0.):
@@ -777,7 +822,8 @@ class Spectroscopy(object):
         starts = band_columns(self.grid, band_edges)
         return np.asarray(band_edges, dtype=np.float64), starts
 
-    def _path_request(self, path_length, quantities, band_edges, cumulative, range_policy):
+    def _path_request(self, path_length, quantities, band_edges, cumulative, range_policy,
+                      instrument=None):
         """Checks every argument of compute_path (before anything touches the GPU)."""
         lengths, shape = self._path_geometry(path_length, "compute_path")
         quantities = _selection(quantities, PATH_QUANTITIES)
@@ -785,12 +831,13 @@ class Spectroscopy(object):
                                        cumulative in PATH_CUMULATIVE)):
             raise ValueError(f"cumulative must be one of {PATH_CUMULATIVE}, not {cumulative!r}.")
         _check_range_policy(range_policy)
-        edges, starts = self._path_bands(band_edges)
+        edges, starts = self._path_bands(band_edges, instrument)
         return _PathRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
-                            starts=starts, cumulative=cumulative)
+                            starts=starts, cumulative=cumulative, instrument=instrument)
 
     def _radiance_request(self, path_length, boundary_temperature, boundary_emissivity,
-                          direction, quantities, band_edges, cumulative, range_policy):
+                          direction, quantities, band_edges, cumulative, range_policy,
+                          instrument=None):
         """Checks every argument of compute_radiance (before anything touches the GPU)."""
         lengths, shape = self._path_geometry(path_length, "compute_radiance")
         self._check_level_temperatures()
@@ -812,14 +859,14 @@ class Spectroscopy(object):
         if band_edges is not None and "brightness_temperature" in quantities:
             raise ValueError("brightness_temperature is only available on the grid: band means "
                              "are formed of the radiance alone.")
-        edges, starts = self._path_bands(band_edges)
+        edges, starts = self._path_bands(band_edges, instrument)
         return _RadianceRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
-                                starts=starts, cumulative=bool(cumulative),
+                                starts=starts, cumulative=bool(cumulative), instrument=instrument,
                                 from_last=direction == "toward_first",
                                 boundary_temperature=boundary, boundary_emissivity=emissivity)
 
     def _sweep_runs(self, request, passes, remove_pedestal, range_policy, sweeper,
-                    level_blocks=1):
+                    level_blocks=1, reductions=None):
         """{quantity: array [levels or paths, columns or bands]}: the "total" block of a run of
         levels at a time, queued like _compute_levels queues it, then the path kernels on it --
         for each of `passes` (_Pass: its order, and the quantities it returns per level and per
@@ -830,7 +877,12 @@ class Spectroscopy(object):
         call (carries, scratch).  level_blocks: blocks of [run, n] counted against
         device_output_limit.  A pass that starts on the run the previous pass ended on finds
         that run's block still in HBM and does not compute it again: sweeps of a call with
-        several passes must leave beta as they found it."""
+        several passes must leave beta as they found it.
+        reductions: with request.instrument, [(result, quantity of a pass, transmittance)]: the
+        sweeps write their quantities on the grid into blocks of their own, and
+        lbl_instrument_apply reduces those rows into [rows, channels] blocks (of exp(-value)
+        with `transmittance`), which alone go to the host as `result`.  Each per-level grid
+        block counts against device_output_limit."""
         temperature = self.atmosphere.temperature.ravel()
         pressure = self.atmosphere.pressure.ravel()
         mole_fractions = {name: x.ravel() for name, x in self.atmosphere.gases.items()}
@@ -839,6 +891,11 @@ class Spectroscopy(object):
         v0, vn, n_per_v = grid_arguments(self.grid)
         n = (vn - v0)*n_per_v
         columns = self.grid.size
+        instrument = getattr(request, "instrument", None)
+        level_quantities = [q for step in passes for q in step.level_quantities]
+        path_quantities = [q for step in passes for q in step.path_quantities]
+        if instrument is not None:
+            level_blocks += len(level_quantities)
         # Runs of consecutive levels when the blocks would not fit: the sweep carries over in HBM.
         level_bytes = level_blocks*n*8
         run = levels if levels*level_bytes <= self.device_output_limit else \
@@ -846,9 +903,9 @@ class Spectroscopy(object):
         run = min(run, _MAX_RUN_LEVELS)
         starts = request.starts
         width = columns if starts is None else starts.size - 1
+        if instrument is not None:
+            width = len(instrument)
         runs = [(a, min(a + run, levels)) for a in range(0, levels, run)]
-        level_quantities = [q for step in passes for q in step.level_quantities]
-        path_quantities = [q for step in passes for q in step.path_quantities]
 
         engine, present, heavy = self._present_gases(temperature, pressure, mole_fractions)
         if engine is None:
@@ -856,8 +913,16 @@ class Spectroscopy(object):
             engine = default_engine(self.device)
         if heavy is not None:
             present = [heavy] + present[:-1]
-        results = {q: engine.host_array((levels, width)) for q in level_quantities}
-        results.update({q: engine.host_array((paths, width)) for q in path_quantities})
+        if instrument is None:
+            results = {q: engine.host_array((levels, width)) for q in level_quantities}
+            results.update({q: engine.host_array((paths, width)) for q in path_quantities})
+        else:
+            from .instrument import resident_instrument
+            handle = resident_instrument(engine, instrument, self.grid)
+            level_reductions = [r for r in reductions if r[1] in level_quantities]
+            path_reductions = [r for r in reductions if r[1] in path_quantities]
+            results = {r[0]: engine.host_array((levels, width)) for r in level_reductions}
+            results.update({r[0]: engine.host_array((paths, width)) for r in path_reductions})
         # One block of `run` levels for beta (and for each per-level output) serves every run;
         # the shorter last run uses its leading rows.  Together with the sweeper's blocks and the
         # per-path outputs that is all this call holds in HBM.
@@ -874,6 +939,9 @@ class Spectroscopy(object):
                 beta = take(run, n)
                 outputs = {q: take(run, band_width) for q in level_quantities}
                 outputs.update({q: take(paths, band_width) for q in path_quantities})
+                if instrument is not None:
+                    channels = {r[0]: take(run, width) for r in level_reductions}
+                    channels.update({r[0]: take(paths, width) for r in path_reductions})
                 resident = None
                 for index, step in enumerate(passes):
                     for a, b in (runs[::-1] if step.from_last else runs):
@@ -898,9 +966,24 @@ class Spectroscopy(object):
                                        for q in level_quantities}
                         run_outputs.update({q: outputs[q] for q in path_quantities})
                         sweep(index, rows, a, b, run_outputs)
+                        if instrument is not None:
+                            for q, source, transmittance in level_reductions:
+                                if source not in step.level_quantities:
+                                    continue
+                                engine.instrument_apply(run_outputs[source], b - a, handle,
+                                                        channels[q], transmittance=transmittance,
+                                                        asynchronous=True)
+                                channels[q].rows(b - a).to_host_into(results[q][a:b], width,
+                                                                     asynchronous=True)
+                            continue
                         for q in step.level_quantities:
                             run_outputs[q].to_host_into(results[q][a:b], width, asynchronous=True)
-                for q in path_quantities:
+                if instrument is not None:
+                    for q, source, transmittance in path_reductions:
+                        engine.instrument_apply(outputs[source], paths, handle, channels[q],
+                                                transmittance=transmittance, asynchronous=True)
+                        channels[q].to_host_into(results[q], width, asynchronous=True)
+                for q in path_quantities if instrument is None else ():
                     outputs[q].to_host_into(results[q], width, asynchronous=True)
                 engine.synchronize()
             except BaseException:
@@ -922,7 +1005,7 @@ class Spectroscopy(object):
         shape = list(request.shape)
         if not request.cumulative:
             dims, shape = dims[:-1], shape[:-1]
-        dims.append("wavenumber" if request.edges is None else "band")
+        dims.append(_spectral_axis(request))
         variables = {q: (dims, np.asarray(values[q]).reshape(shape + [-1]), _PATH_UNITS[q])
                      for q in request.quantities}
         return self._path_variables(variables, request)
@@ -939,9 +1022,17 @@ class Spectroscopy(object):
         return self._path_variables(variables, request)
 
     def _path_variables(self, variables, request):
-        """{name: (dims, values, units)} with the grid's or the bands' coordinates, in the
-        conventions of _create_output_dataset."""
-        if request.edges is None:
+        """{name: (dims, values, units)} with the grid's, the bands' or the channels'
+        coordinates, in the conventions of _create_output_dataset."""
+        instrument = getattr(request, "instrument", None)
+        if instrument is not None:
+            lower, upper = instrument.window()
+            start, end = instrument.columns(self.grid)
+            coords = {"channel_center": (instrument.centers, {"units": "cm-1"}),
+                      "channel_lower": (lower, {"units": "cm-1"}),
+                      "channel_upper": (upper, {"units": "cm-1"}),
+                      "channel_points": (end - start, {})}
+        elif request.edges is None:
             coords = {"wavenumber": (self.grid, {"units": "cm-1"})}
         else:
             coords = {"band_lower": (request.edges[:-1], {"units": "cm-1"}),
@@ -953,7 +1044,7 @@ class Spectroscopy(object):
             out.update({q: v for q, (_, v, _) in variables.items()})
             return out
         DataArray, Dataset = xarray.DataArray, xarray.Dataset
-        axis = "wavenumber" if request.edges is None else "band"
+        axis = _spectral_axis(request)
         return Dataset(
             data_vars={q: DataArray(v, dims=dims, attrs={"units": units})
                        for q, (dims, v, units) in variables.items()},
