@@ -1,27 +1,8 @@
 // Host side of the continuum entry points of include/lbl_amd.h (kernels: continuum.h).
-// Included at the end of engine.hip.  Like the lines path there is no CPU compute here.
+// Included at the end of engine.hip after slot_entry.inc.  Like the lines path there is no CPU
+// compute here.
 
 namespace {
-
-template <typename T>
-T * find_slot(std::vector<std::unique_ptr<T>> & slots, int32_t handle)
-{
-    if (handle < 0 || (size_t)handle >= slots.size()) return nullptr;
-    return slots[handle].get();
-}
-
-template <typename T>
-int32_t store_slot(std::vector<std::unique_ptr<T>> & slots, std::unique_ptr<T> value)
-{
-    size_t slot = slots.size();
-    for (size_t i = 0; i < slots.size(); ++i)
-    {
-        if (!slots[i]) { slot = i; break; }
-    }
-    if (slot == slots.size()) slots.emplace_back();
-    slots[slot] = std::move(value);
-    return (int32_t)slot;
-}
 
 const int kBandColumns[kBandKinds] = {2, 2, 3, 4, 3, 1, 2, 1, 1, 1, 1, 1, 1, 3, 3, 1};
 
@@ -57,15 +38,12 @@ extern "C" {
 int lbl_continuum_load(lbl_engine * engine, int32_t n_bands, const lbl_band * bands,
                        const double * table, int64_t table_size, int32_t * continuum)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (continuum == nullptr || bands == nullptr || table == nullptr || n_bands < 1 ||
-        n_bands > kMaxBands || table_size < 1)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_load: bad argument.");
-    }
-    try
-    {
+    return entry(engine, [&] {
+        if (continuum == nullptr || bands == nullptr || table == nullptr || n_bands < 1 ||
+            n_bands > kMaxBands || table_size < 1)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_load: bad argument.");
+        }
         HIP_TRY(hipSetDevice(engine->device));
         std::unique_ptr<ContinuumSet> c(new ContinuumSet());
         c->set.n_bands = n_bands;
@@ -105,51 +83,41 @@ int lbl_continuum_load(lbl_engine * engine, int32_t n_bands, const lbl_band * ba
         c->table.upload(table, (size_t)table_size, engine->stream);
         HIP_TRY(hipStreamSynchronize(engine->stream));
         *continuum = store_slot(engine->continua, std::move(c));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    catch (const std::bad_alloc &)
-    {
-        return fail(engine, LBL_ERROR, "host allocation failed.");
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_continuum_free(lbl_engine * engine, int32_t continuum)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (find_slot(engine->continua, continuum) == nullptr)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
-    }
-    (void)hipSetDevice(engine->device);
-    engine->drain_lanes();
-    // (groups that hold the continuum's table go with it)
-    for (auto & group : engine->groups)
-    {
-        if (group && std::find(group->members.begin(), group->members.end(), continuum) !=
-                         group->members.end())
+    return entry(engine, [&] {
+        if (find_slot(engine->continua, continuum) == nullptr)
         {
-            group.reset();
+            return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
         }
-    }
-    engine->continua[continuum].reset();
-    return LBL_OK;
+        (void)hipSetDevice(engine->device);
+        engine->drain_lanes();
+        // (groups that hold the continuum's table go with it)
+        for (auto & group : engine->groups)
+        {
+            if (group && std::find(group->members.begin(), group->members.end(), continuum) !=
+                             group->members.end())
+            {
+                group.reset();
+            }
+        }
+        engine->continua[continuum].reset();
+        return LBL_OK;
+    });
 }
 
 int lbl_grid_load(lbl_engine * engine, int64_t n, const double * wavenumber, int32_t * grid)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (grid == nullptr || wavenumber == nullptr || n < 1 || n > 0x7fffffff)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_grid_load: bad argument (1 ... 2^31 - 1 points).");
-    }
-    try
-    {
+    return entry(engine, [&] {
+        if (grid == nullptr || wavenumber == nullptr || n < 1 || n > 0x7fffffff)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT,
+                        "lbl_grid_load: bad argument (1 ... 2^31 - 1 points).");
+        }
         HIP_TRY(hipSetDevice(engine->device));
         std::unique_ptr<SpectralGrid> g(new SpectralGrid());
         g->n = n;
@@ -172,26 +140,22 @@ int lbl_grid_load(lbl_engine * engine, int64_t n, const double * wavenumber, int
         g->wavenumber.upload(wavenumber, (size_t)n, engine->stream);
         HIP_TRY(hipStreamSynchronize(engine->stream));
         *grid = store_slot(engine->grids, std::move(g));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_grid_free(lbl_engine * engine, int32_t grid)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (find_slot(engine->grids, grid) == nullptr)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "unknown grid handle.");
-    }
-    (void)hipSetDevice(engine->device);
-    engine->drain_lanes();
-    engine->grids[grid].reset();
-    return LBL_OK;
+    return entry(engine, [&] {
+        if (find_slot(engine->grids, grid) == nullptr)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "unknown grid handle.");
+        }
+        (void)hipSetDevice(engine->device);
+        engine->drain_lanes();
+        engine->grids[grid].reset();
+        return LBL_OK;
+    });
 }
 
 int lbl_continuum_compute(lbl_engine * engine, int32_t continuum, int32_t grid,
@@ -199,129 +163,42 @@ int lbl_continuum_compute(lbl_engine * engine, int32_t continuum, int32_t grid,
                           const double * vmr, int32_t flags, double * extinction,
                           int64_t level_stride)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    ContinuumSet * c = find_slot(engine->continua, continuum);
-    SpectralGrid * g = find_slot(engine->grids, grid);
-    if (c == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
-    if (g == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown grid handle.");
-    if (n_levels < 0 || extinction == nullptr ||
-        (n_levels > 0 && (temperature == nullptr || pressure == nullptr || vmr == nullptr)))
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_compute: bad argument.");
-    }
-    const long long n = g->n;
-    const long long stride = level_stride > 0 ? level_stride : n;
-    if (stride < n) return fail(engine, LBL_BAD_ARGUMENT, "level_stride < grid points.");
-    if (n_levels == 0) return LBL_OK;
-    const bool out_device = (flags & LBL_OUT_DEVICE) != 0;
-    const bool add_into = (flags & LBL_ACCUMULATE) != 0;
-    try
-    {
-        HIP_TRY(hipSetDevice(engine->device));
-        // Lane 0; a call that adds into its output first lets the other lanes finish, the
-        // ordering rule of lbl_compute.
-        // Queued device-to-device calls run on the slot lane's urgent stream, behind whatever
-        // the other lanes have queued for this block; everything else on lane 0 with the other
-        // lanes drained.
-        const bool queued = out_device && (flags & LBL_ASYNC);
-        Lane & lane = engine->lanes[queued ? kSlotLane : 0];
-        hipStream_t stream = lane.main;
-        const long long out_bytes = ((long long)(n_levels - 1)*stride + n)*8;
-        if (queued)
-        {
-            lane.used = true;
-            engine->order_after_writers(stream, extinction, out_bytes, &lane);
-        }
-        else
-        {
-            for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
-        }
-        c->wait();      // the previous call's copy may still read the pinned level block
-        long long chunk = std::min<long long>(n_levels, 65535);
-        if (!out_device)
-        {
-            chunk = std::max(1ll, std::min(chunk, engine->workspace_bytes/(n*8)));
-        }
-        c->reserve_pinned((size_t)chunk);
-        ContinuumLevel * host = c->pinned;
-        c->levels.reserve((size_t)chunk);
-        c->coarse.reserve((size_t)(chunk*c->set.coarse_points));
-        c->slopes.reserve((size_t)(chunk*c->set.coarse_points));
-        if (!out_device) c->staging.reserve((size_t)(chunk*n));
-        for (long long base = 0; base < n_levels; base += chunk)
-        {
-            const int count = (int)std::min<long long>(chunk, n_levels - base);
-            for (int l = 0; l < count; ++l)
-            {
-                host[l] = continuum_level(temperature[base + l], pressure[base + l]*0.01,
-                                          vmr + (base + l)*LBL_VMR_COUNT);  // utils.py:13,172
-            }
-            HIP_TRY(hipMemcpyAsync(c->levels.data, host, count*sizeof(ContinuumLevel),
-                                   hipMemcpyHostToDevice, stream));
-            c->copied_on(stream);
-            engine->timed(kTimeBandSpectra, stream, [&] {
-                launch_band_spectra(*c, count, stream);
-            });
-            double * target = out_device ? extinction + base*stride : c->staging.data;
-            const long long target_stride = out_device ? stride : n;
-            engine->timed(kTimeContinuum, stream, [&] {
+    return entry(engine, [&] {
+        ContinuumSet * c = find_slot(engine->continua, continuum);
+        if (c == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
+        SlotCall call{engine, n_levels, flags, extinction};
+        const int status = call.check(
+            grid, level_stride,
+            n_levels < 0 || extinction == nullptr ||
+            (n_levels > 0 && (temperature == nullptr || pressure == nullptr || vmr == nullptr)),
+            "lbl_continuum_compute: bad argument.");
+        if (status != LBL_OK || n_levels == 0) return status;
+        const SpectralGrid * g = call.g;
+        const long long n = call.n;
+        return call.run(*c, c->coarse, c->set.coarse_points, kTimeContinuum,
+            [&](long long l) {      // utils.py:13,172
+                return continuum_level(temperature[l], pressure[l]*0.01, vmr + l*LBL_VMR_COUNT);
+            },
+            [&](int count) {
+                engine->timed(kTimeBandSpectra, call.stream, [&] {
+                    launch_band_spectra(*c, count, call.stream);
+                });
+            },
+            [&](int count, double * target, long long target_stride, int add) {
                 // Measured on 5 M points (scripts/perf_continuum.py): 4 points x 1 level for a
                 // single level, 2 points x 4 levels for a batch.
                 const int pt = count == 1 ? 4 : 2, lv = count == 1 ? 1 : 4;
                 const long long per_block = 256*pt;
                 dim3 blocks((unsigned)((n + per_block - 1)/per_block),
                             (unsigned)((count + lv - 1)/lv));
-                const int add = (out_device && add_into) ? 1 : 0;
 #define LBL_INTERP(PT, LV)                                                                 \
                 hipLaunchKernelGGL((continuum_interp_kernel<PT, LV>), blocks, dim3(256), 0, \
-                                   stream, c->set, c->coarse.data, c->slopes.data,          \
+                                   call.stream, c->set, c->coarse.data, c->slopes.data,     \
                                    g->form(), n, count, target, target_stride, add)
                 if (count == 1) LBL_INTERP(4, 1); else LBL_INTERP(2, 4);
 #undef LBL_INTERP
-                HIP_TRY(hipGetLastError());
             });
-            c->mark(stream);
-            if (!out_device)
-            {
-                std::vector<double> rows;
-                for (int l = 0; l < count; ++l)
-                {
-                    double * dst = extinction + (base + l)*stride;
-                    const double * src = c->staging.data + (size_t)l*n;
-                    if (add_into)
-                    {
-                        rows.resize((size_t)n);
-                        HIP_TRY(hipMemcpyAsync(rows.data(), src, (size_t)n*8,
-                                               hipMemcpyDeviceToHost, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        for (long long i = 0; i < n; ++i) dst[i] += rows[i];
-                    }
-                    else
-                    {
-                        HIP_TRY(hipMemcpyAsync(dst, src, (size_t)n*8, hipMemcpyDeviceToHost,
-                                               stream));
-                    }
-                }
-                HIP_TRY(hipStreamSynchronize(stream));
-            }
-            else if (base + count < n_levels)
-            {
-                c->wait();
-            }
-        }
-        if (out_device) lane.note_write(extinction, out_bytes, stream);
-        if (!(flags & LBL_ASYNC)) HIP_TRY(hipStreamSynchronize(stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    catch (const std::bad_alloc &)
-    {
-        return fail(engine, LBL_ERROR, "host allocation failed.");
-    }
-    return LBL_OK;
+    });
 }
 
 int lbl_continuum_compute_many(lbl_engine * engine, int32_t n_continua,
@@ -330,57 +207,35 @@ int lbl_continuum_compute_many(lbl_engine * engine, int32_t n_continua,
                                const double * vmr, int32_t flags, double * extinction,
                                int64_t level_stride)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (n_continua < 1 || continua == nullptr)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_compute_many: no continua.");
-    }
-    SpectralGrid * g = find_slot(engine->grids, grid);
-    if (g == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown grid handle.");
-    if (n_levels < 0 || extinction == nullptr || !(flags & LBL_OUT_DEVICE) ||
-        (n_levels > 0 && (temperature == nullptr || pressure == nullptr || vmr == nullptr)))
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_compute_many: bad argument (the "
-                                              "output is a device block: LBL_OUT_DEVICE).");
-    }
-    const long long n = g->n;
-    const long long stride = level_stride > 0 ? level_stride : n;
-    if (stride < n) return fail(engine, LBL_BAD_ARGUMENT, "level_stride < grid points.");
-    if (n_levels == 0) return LBL_OK;
-    if (n_levels > 65535) return fail(engine, LBL_BAD_ARGUMENT, "more than 65535 levels.");
-    std::vector<ContinuumSet *> sets;
-    int total_bands = 0;
-    for (int m = 0; m < n_continua; ++m)
-    {
-        ContinuumSet * c = find_slot(engine->continua, continua[m]);
-        if (c == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
-        sets.push_back(c);
-        total_bands += c->set.n_bands;
-    }
-    if (total_bands > kMaxGroupBands)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "more than 64 bands in one group of continua.");
-    }
-    const bool add_into = (flags & LBL_ACCUMULATE) != 0;
-    try
-    {
-        HIP_TRY(hipSetDevice(engine->device));
-        // Ordered like lbl_continuum_compute: queued calls on the slot lane's urgent stream behind
-        // whoever wrote the block last, blocking ones on lane 0 with the other lanes drained.
-        const bool queued = (flags & LBL_ASYNC) != 0;
-        Lane & lane = engine->lanes[queued ? kSlotLane : 0];
-        hipStream_t stream = lane.main;
-        const long long out_bytes = ((long long)(n_levels - 1)*stride + n)*8;
-        if (queued)
+    return entry(engine, [&] {
+        if (n_continua < 1 || continua == nullptr)
         {
-            lane.used = true;
-            engine->order_after_writers(stream, extinction, out_bytes, &lane);
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_compute_many: no continua.");
         }
-        else
+        SlotCall call{engine, n_levels, flags, extinction};
+        const int status = call.check(
+            grid, level_stride,
+            n_levels < 0 || extinction == nullptr || !(flags & LBL_OUT_DEVICE) ||
+            (n_levels > 0 && (temperature == nullptr || pressure == nullptr || vmr == nullptr)),
+            "lbl_continuum_compute_many: bad argument (the output is a device block: "
+            "LBL_OUT_DEVICE).");
+        if (status != LBL_OK || n_levels == 0) return status;
+        if (n_levels > 65535) return fail(engine, LBL_BAD_ARGUMENT, "more than 65535 levels.");
+        std::vector<ContinuumSet *> sets;
+        int total_bands = 0;
+        for (int m = 0; m < n_continua; ++m)
         {
-            for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
+            ContinuumSet * c = find_slot(engine->continua, continua[m]);
+            if (c == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
+            sets.push_back(c);
+            total_bands += c->set.n_bands;
         }
+        if (total_bands > kMaxGroupBands)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "more than 64 bands in one group of continua.");
+        }
+        call.open();
+        hipStream_t stream = call.stream;
         // The group of exactly these continua in this order (built at first use).
         ContinuumGroup * group = nullptr;
         const std::vector<int32_t> wanted(continua, continua + n_continua);
@@ -455,45 +310,33 @@ int lbl_continuum_compute_many(lbl_engine * engine, int32_t n_continua,
             // time (table values requested together) only cost registers.
             const int pt = 4, lv = n_levels == 1 ? 1 : 2;
             const long long per_block = 256*pt;
-            dim3 blocks((unsigned)((n + per_block - 1)/per_block),
+            dim3 blocks((unsigned)((call.n + per_block - 1)/per_block),
                         (unsigned)((n_levels + lv - 1)/lv));
 #define LBL_GROUP_INTERP(PT, LV)                                                             \
             hipLaunchKernelGGL((group_interp_kernel<PT, LV>), blocks, dim3(256), 0,          \
                                stream, group->bands.data, group->n_bands,                    \
                                group->level_points, group->coarse.data, group->slopes.data,  \
-                               g->form(), n, n_levels, extinction, stride, add_into ? 1 : 0)
+                               call.g->form(), call.n, n_levels, extinction, call.stride,    \
+                               call.add_into ? 1 : 0)
             if (n_levels == 1) LBL_GROUP_INTERP(4, 1); else LBL_GROUP_INTERP(4, 2);
 #undef LBL_GROUP_INTERP
             HIP_TRY(hipGetLastError());
         });
         group->mark(stream);
-        lane.note_write(extinction, out_bytes, stream);
-        if (!queued) HIP_TRY(hipStreamSynchronize(stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    catch (const std::bad_alloc &)
-    {
-        return fail(engine, LBL_ERROR, "host allocation failed.");
-    }
-    return LBL_OK;
+        return call.close();
+    });
 }
 
 int lbl_continuum_bands(lbl_engine * engine, int32_t continuum, double temperature,
                         double pressure_mb, const double * vmr, double * spectra)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    ContinuumSet * c = find_slot(engine->continua, continuum);
-    if (c == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
-    if (vmr == nullptr || spectra == nullptr)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_bands: bad argument.");
-    }
-    try
-    {
+    return entry(engine, [&] {
+        ContinuumSet * c = find_slot(engine->continua, continuum);
+        if (c == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
+        if (vmr == nullptr || spectra == nullptr)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_continuum_bands: bad argument.");
+        }
         HIP_TRY(hipSetDevice(engine->device));
         for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
         hipStream_t stream = engine->stream;
@@ -508,12 +351,8 @@ int lbl_continuum_bands(lbl_engine * engine, int32_t continuum, double temperatu
         HIP_TRY(hipMemcpyAsync(spectra, c->coarse.data, (size_t)c->set.coarse_points*8,
                                hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 }  // extern "C"

@@ -549,6 +549,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 
 }  // extern "C"
 
+#include "slot_entry.inc"
 #include "continuum_entry.inc"
 #include "path_entry.inc"
 #include "radiance_entry.inc"

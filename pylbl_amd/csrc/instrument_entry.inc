@@ -69,22 +69,20 @@ int lbl_instrument_create(lbl_engine * engine, int32_t grid, int32_t shape, int3
                           const double * half_width, int32_t n_table, const double * offsets,
                           const double * response, int32_t response_rows, int32_t * handle)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    auto bad = [&](const char * what) {
-        return fail(engine, LBL_BAD_ARGUMENT, std::string("lbl_instrument_create: ") + what);
-    };
-    if (handle == nullptr) return bad("handle is NULL.");
-    const SpectralGrid * g = find_slot(engine->grids, grid);
-    if (g == nullptr) return bad("unknown grid handle.");
-    if (!g->ascending) return bad("the grid must be ascending.");
-    if (const char * problem = instrument_check(shape, n_channels, centers, parameter, half_width,
-                                                n_table, offsets, response, response_rows))
-    {
-        return bad(problem);
-    }
-    try
-    {
+    return entry(engine, [&] {
+        auto bad = [&](const char * what) {
+            return fail(engine, LBL_BAD_ARGUMENT, std::string("lbl_instrument_create: ") + what);
+        };
+        if (handle == nullptr) return bad("handle is NULL.");
+        const SpectralGrid * g = find_slot(engine->grids, grid);
+        if (g == nullptr) return bad("unknown grid handle.");
+        if (!g->ascending) return bad("the grid must be ascending.");
+        if (const char * problem = instrument_check(shape, n_channels, centers, parameter,
+                                                    half_width, n_table, offsets, response,
+                                                    response_rows))
+        {
+            return bad(problem);
+        }
         HIP_TRY(hipSetDevice(engine->device));
         std::vector<double> nu((size_t)g->n);
         HIP_TRY(hipMemcpyAsync(nu.data(), g->wavenumber.data, nu.size()*8,
@@ -208,26 +206,23 @@ int lbl_instrument_create(lbl_engine * engine, int32_t grid, int32_t shape, int3
         in->response = base + at_response;
         in->nu = base + at_nu;
         *handle = store_slot(engine->instruments, std::move(in));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_instrument_free(lbl_engine * engine, int32_t handle)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (find_slot(engine->instruments, handle) == nullptr)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_instrument_free: unknown instrument handle.");
-    }
-    (void)hipSetDevice(engine->device);
-    engine->drain_lanes();
-    engine->instruments[handle].reset();
-    return LBL_OK;
+    return entry(engine, [&] {
+        if (find_slot(engine->instruments, handle) == nullptr)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT,
+                        "lbl_instrument_free: unknown instrument handle.");
+        }
+        (void)hipSetDevice(engine->device);
+        engine->drain_lanes();
+        engine->instruments[handle].reset();
+        return LBL_OK;
+    });
 }
 
 int lbl_instrument_apply(lbl_engine * engine, const double * values, int64_t row_stride,

@@ -23,6 +23,27 @@ int fail(lbl_engine * engine, int code, const std::string & message)
 
 typedef std::lock_guard<std::recursive_mutex> EngineLock;
 
+// The frame of an entry point: a null engine, the engine's lock, and HIP failures and failed host
+// allocations as LBL_ERROR.  body() returns the entry's status.
+template <typename Body>
+int entry(lbl_engine * engine, Body body)
+{
+    if (engine == nullptr) return LBL_BAD_ARGUMENT;
+    EngineLock lock(engine->mutex);
+    try
+    {
+        return body();
+    }
+    catch (const HipFailure & f)
+    {
+        return fail(engine, LBL_ERROR, f.message);
+    }
+    catch (const std::bad_alloc &)
+    {
+        return fail(engine, LBL_ERROR, "host allocation failed.");
+    }
+}
+
 Molecule * find_molecule(lbl_engine * engine, int32_t handle)
 {
     if (handle < 0 || (size_t)handle >= engine->molecules.size()) return nullptr;

@@ -1,6 +1,6 @@
 // What the path entries share (lbl_path_compute here, lbl_path_radiance, lbl_path_flux), and
 // lbl_path_compute: optical depth and transmittance along paths through a block of absorption
-// coefficients in HBM (kernels: path.h).  Included by engine.hip after continuum_entry.inc (grid
+// coefficients in HBM (kernels: path.h).  Included by engine.hip after slot_entry.inc (grid
 // handles).
 namespace {
 
@@ -300,24 +300,16 @@ struct PathCall
     }
 };
 
-// The frame of a path entry: the lock, HIP failures as LBL_ERROR and, without LBL_ASYNC, the wait
-// for the call's work.  body() returns the entry's status.
+// The frame of a path entry: entry()'s and, without LBL_ASYNC, the wait for the call's work.
 template <typename Body>
 int path_entry(lbl_engine * engine, int32_t flags, Body body)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    try
-    {
+    return entry(engine, [&] {
         const int status = body();
         if (status != LBL_OK) return status;
         if (!(flags & LBL_ASYNC)) HIP_TRY(hipStreamSynchronize(engine->stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 }  // namespace

@@ -1,20 +1,31 @@
 // Host side of the cross-section entry points of include/lbl_amd.h (kernels: xsec.h).
-// Included at the end of engine.hip after continuum_entry.inc (find_slot, store_slot).
+// Included at the end of engine.hip after slot_entry.inc and continuum_entry.inc.
+
+namespace {
+
+void launch_xsec_model(lbl_engine * engine, XsecData & x, int n_levels, hipStream_t stream)
+{
+    engine->timed(kTimeXsecModel, stream, [&] {
+        dim3 grid((unsigned)x.set.n_bands, (unsigned)n_levels);
+        hipLaunchKernelGGL(xsec_model_kernel, grid, dim3(kModelThreads), 0, stream, x.set, x.fgrid.data,
+                           x.coeffs.data, x.levels.data, x.values.data, x.slopes.data);
+        HIP_TRY(hipGetLastError());
+    });
+}
+
+}  // namespace
 
 extern "C" {
 
 int lbl_xsec_load(lbl_engine * engine, int32_t n_bands, const int32_t * sizes,
                   const double * frequency, const double * coefficients, int32_t * xsec)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (xsec == nullptr || sizes == nullptr || frequency == nullptr || coefficients == nullptr ||
-        n_bands < 1 || n_bands > kMaxXsecBands)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_xsec_load: bad argument.");
-    }
-    try
-    {
+    return entry(engine, [&] {
+        if (xsec == nullptr || sizes == nullptr || frequency == nullptr ||
+            coefficients == nullptr || n_bands < 1 || n_bands > kMaxXsecBands)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_xsec_load: bad argument.");
+        }
         HIP_TRY(hipSetDevice(engine->device));
         std::unique_ptr<XsecData> x(new XsecData());
         x->set.n_bands = n_bands;
@@ -46,194 +57,81 @@ int lbl_xsec_load(lbl_engine * engine, int32_t n_bands, const int32_t * sizes,
         x->coeffs.upload(coefficients, (size_t)(4*total), engine->stream);
         HIP_TRY(hipStreamSynchronize(engine->stream));
         *xsec = store_slot(engine->xsecs, std::move(x));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    catch (const std::bad_alloc &)
-    {
-        return fail(engine, LBL_ERROR, "host allocation failed.");
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_xsec_free(lbl_engine * engine, int32_t xsec)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (find_slot(engine->xsecs, xsec) == nullptr)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "unknown cross-section handle.");
-    }
-    (void)hipSetDevice(engine->device);
-    engine->drain_lanes();
-    engine->xsecs[xsec].reset();
-    return LBL_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-void launch_xsec_model(lbl_engine * engine, XsecData & x, int n_levels, hipStream_t stream)
-{
-    engine->timed(kTimeXsecModel, stream, [&] {
-        dim3 grid((unsigned)x.set.n_bands, (unsigned)n_levels);
-        hipLaunchKernelGGL(xsec_model_kernel, grid, dim3(kModelThreads), 0, stream, x.set, x.fgrid.data,
-                           x.coeffs.data, x.levels.data, x.values.data, x.slopes.data);
-        HIP_TRY(hipGetLastError());
+    return entry(engine, [&] {
+        if (find_slot(engine->xsecs, xsec) == nullptr)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "unknown cross-section handle.");
+        }
+        (void)hipSetDevice(engine->device);
+        engine->drain_lanes();
+        engine->xsecs[xsec].reset();
+        return LBL_OK;
     });
 }
-
-}  // namespace
-
-extern "C" {
 
 int lbl_xsec_compute(lbl_engine * engine, int32_t xsec, int32_t grid, int32_t n_levels,
                      const double * temperature, const double * pressure, const double * vmr,
                      int32_t flags, double * out, int64_t level_stride)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    XsecData * x = find_slot(engine->xsecs, xsec);
-    SpectralGrid * g = find_slot(engine->grids, grid);
-    if (x == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown cross-section handle.");
-    if (g == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown grid handle.");
-    const bool scale = (flags & LBL_SCALE_DENSITY) != 0;
-    if (n_levels < 0 || out == nullptr ||
-        (n_levels > 0 && (temperature == nullptr || pressure == nullptr ||
-                          (scale && vmr == nullptr))))
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_xsec_compute: bad argument.");
-    }
-    const long long n = g->n;
-    const long long stride = level_stride > 0 ? level_stride : n;
-    if (stride < n) return fail(engine, LBL_BAD_ARGUMENT, "level_stride < grid points.");
-    if (n_levels == 0) return LBL_OK;
-    const bool out_device = (flags & LBL_OUT_DEVICE) != 0;
-    const bool add_into = (flags & LBL_ACCUMULATE) != 0;
-    try
-    {
-        HIP_TRY(hipSetDevice(engine->device));
-        // Queued device-to-device calls run on the slot lane's urgent stream, behind whatever
-        // the other lanes have queued for this block; everything else on lane 0 with the other
-        // lanes drained.
-        const bool queued = out_device && (flags & LBL_ASYNC);
-        Lane & lane = engine->lanes[queued ? kSlotLane : 0];
-        hipStream_t stream = lane.main;
-        const long long out_bytes = ((long long)(n_levels - 1)*stride + n)*8;
-        if (queued)
-        {
-            lane.used = true;
-            engine->order_after_writers(stream, out, out_bytes, &lane);
-        }
-        else
-        {
-            for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
-        }
-        x->wait();
-        long long chunk = std::min<long long>(n_levels, 65535);
-        if (!out_device)
-        {
-            chunk = std::max(1ll, std::min(chunk, engine->workspace_bytes/(n*8)));
-        }
-        x->reserve_pinned((size_t)chunk);
-        x->levels.reserve((size_t)chunk);
-        x->values.reserve((size_t)(chunk*x->set.total));
-        x->slopes.reserve((size_t)(chunk*x->set.total));
-        if (!out_device) x->staging.reserve((size_t)(chunk*n));
-        for (long long base = 0; base < n_levels; base += chunk)
-        {
-            const int count = (int)std::min<long long>(chunk, n_levels - base);
-            for (int l = 0; l < count; ++l)
-            {
-                XsecLevel & s = x->pinned[l];
-                s.t = temperature[base + l];
-                s.p = pressure[base + l];
+    return entry(engine, [&] {
+        XsecData * x = find_slot(engine->xsecs, xsec);
+        if (x == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown cross-section handle.");
+        const bool scale = (flags & LBL_SCALE_DENSITY) != 0;
+        SlotCall call{engine, n_levels, flags, out};
+        const int status = call.check(
+            grid, level_stride,
+            n_levels < 0 || out == nullptr ||
+            (n_levels > 0 && (temperature == nullptr || pressure == nullptr ||
+                              (scale && vmr == nullptr))),
+            "lbl_xsec_compute: bad argument.");
+        if (status != LBL_OK || n_levels == 0) return status;
+        const SpectralGrid * g = call.g;
+        const long long n = call.n;
+        return call.run(*x, x->values, x->set.total, kTimeXsec,
+            [&](long long l) {
                 // spectroscopy.py:18-29,199-203: n = P x /(kb T).
-                s.density = scale ? s.p*vmr[base + l]/(kBoltzmann*s.t) : 1.;
-            }
-            HIP_TRY(hipMemcpyAsync(x->levels.data, x->pinned, count*sizeof(XsecLevel),
-                                   hipMemcpyHostToDevice, stream));
-            x->copied_on(stream);
-            launch_xsec_model(engine, *x, count, stream);
-            double * target = out_device ? out + base*stride : x->staging.data;
-            const long long target_stride = out_device ? stride : n;
-            engine->timed(kTimeXsec, stream, [&] {
-                const int add = (out_device && add_into) ? 1 : 0;
+                const double t = temperature[l], p = pressure[l];
+                return XsecLevel{t, p, scale ? p*vmr[l]/(kBoltzmann*t) : 1.};
+            },
+            [&](int count) { launch_xsec_model(engine, *x, count, call.stream); },
+            [&](int count, double * target, long long target_stride, int add) {
                 const int ascending = g->ascending ? 1 : 0;
                 if (count == 1)
                 {
                     dim3 blocks((unsigned)((n + 1023)/1024), 1u);
-                    hipLaunchKernelGGL((xsec_interp_kernel<4, 1>), blocks, dim3(256), 0, stream,
-                                       x->set, x->fgrid.data, x->values.data, x->slopes.data,
-                                       x->levels.data, g->form(), n, count, ascending,
-                                       target, target_stride, add);
+                    hipLaunchKernelGGL((xsec_interp_kernel<4, 1>), blocks, dim3(256), 0,
+                                       call.stream, x->set, x->fgrid.data, x->values.data,
+                                       x->slopes.data, x->levels.data, g->form(), n, count,
+                                       ascending, target, target_stride, add);
                 }
                 else
                 {
                     dim3 blocks((unsigned)((n + 511)/512), (unsigned)((count + 3)/4));
-                    hipLaunchKernelGGL((xsec_interp_kernel<2, 4>), blocks, dim3(256), 0, stream,
-                                       x->set, x->fgrid.data, x->values.data, x->slopes.data,
-                                       x->levels.data, g->form(), n, count, ascending,
-                                       target, target_stride, add);
+                    hipLaunchKernelGGL((xsec_interp_kernel<2, 4>), blocks, dim3(256), 0,
+                                       call.stream, x->set, x->fgrid.data, x->values.data,
+                                       x->slopes.data, x->levels.data, g->form(), n, count,
+                                       ascending, target, target_stride, add);
                 }
-                HIP_TRY(hipGetLastError());
             });
-            x->mark(stream);
-            if (!out_device)
-            {
-                std::vector<double> row;
-                for (int l = 0; l < count; ++l)
-                {
-                    double * dst = out + (base + l)*stride;
-                    const double * src = x->staging.data + (size_t)l*n;
-                    if (add_into)
-                    {
-                        row.resize((size_t)n);
-                        HIP_TRY(hipMemcpyAsync(row.data(), src, (size_t)n*8,
-                                               hipMemcpyDeviceToHost, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        for (long long i = 0; i < n; ++i) dst[i] += row[i];
-                    }
-                    else
-                    {
-                        HIP_TRY(hipMemcpyAsync(dst, src, (size_t)n*8, hipMemcpyDeviceToHost,
-                                               stream));
-                    }
-                }
-                HIP_TRY(hipStreamSynchronize(stream));
-            }
-            else if (base + count < n_levels)
-            {
-                x->wait();
-            }
-        }
-        if (out_device) lane.note_write(out, out_bytes, stream);
-        if (!(flags & LBL_ASYNC)) HIP_TRY(hipStreamSynchronize(stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    catch (const std::bad_alloc &)
-    {
-        return fail(engine, LBL_ERROR, "host allocation failed.");
-    }
-    return LBL_OK;
+    });
 }
 
 int lbl_xsec_bands(lbl_engine * engine, int32_t xsec, double temperature, double pressure,
                    double * values)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    XsecData * x = find_slot(engine->xsecs, xsec);
-    if (x == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown cross-section handle.");
-    if (values == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "lbl_xsec_bands: bad argument.");
-    try
-    {
+    return entry(engine, [&] {
+        XsecData * x = find_slot(engine->xsecs, xsec);
+        if (x == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "unknown cross-section handle.");
+        if (values == nullptr)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_xsec_bands: bad argument.");
+        }
         HIP_TRY(hipSetDevice(engine->device));
         hipStream_t stream = engine->stream;
         x->wait();
@@ -248,12 +146,8 @@ int lbl_xsec_bands(lbl_engine * engine, int32_t xsec, double temperature, double
         HIP_TRY(hipMemcpyAsync(values, x->values.data, (size_t)x->set.total*8,
                                hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 }  // extern "C"

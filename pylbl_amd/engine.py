@@ -202,6 +202,13 @@ def _f64(array):
     return np.ascontiguousarray(array, dtype=np.float64)
 
 
+def _slot_levels(temperature, pressure, accumulate, asynchronous):
+    """(temperature, pressure, flags) of a slot call: float64 arrays [levels] and ACCUMULATE /
+    ASYNC."""
+    t, p = _f64(np.atleast_1d(temperature)), _f64(np.atleast_1d(pressure))
+    return t, p, (ACCUMULATE if accumulate else 0) | (ASYNC if asynchronous else 0)
+
+
 def _path_run(band_start, level_begin, rows, levels_per_path, from_last, asynchronous):
     """(int64 band starts or None, n_bands, flags) of a path call on the levels [level_begin,
     level_begin + rows): PATH_FROM_LAST, ASYNC and PATH_CONTINUE when the run's first level in
@@ -655,11 +662,10 @@ class Engine(object):
                           accumulate=False, asynchronous=False):
         """Continuum extinction [m-1]: float64[levels, n] (or fills `out`, host array or
         DeviceSpectra).  vmr is [levels, VMR_COUNT]; pressure in Pa."""
-        t, p = _f64(np.atleast_1d(temperature)), _f64(np.atleast_1d(pressure))
+        t, p, flags = _slot_levels(temperature, pressure, accumulate, asynchronous)
         x = _f64(vmr).reshape(-1, VMR_COUNT)
         if not (t.ndim == 1 and t.shape == p.shape and x.shape[0] == t.size):
             raise ValueError("temperature, pressure [levels] and vmr [levels, 5] disagree.")
-        flags = (ACCUMULATE if accumulate else 0) | (ASYNC if asynchronous else 0)
         out, pointer, flags, stride = self._output(out, t.size, n, flags)
         self._check(self.lib.lbl_continuum_compute(
             self.handle, int(continuum), int(grid), t.size, t.ctypes.data, p.ctypes.data,
@@ -827,14 +833,13 @@ class Engine(object):
         the order given, into the DeviceSpectra `out` [levels, >= n] -- the same bits as one
         continuum_compute per handle, at a third of the HBM traffic for three of them.
         vmr: [len(continua), levels, VMR_COUNT]."""
-        t, p = _f64(np.atleast_1d(temperature)), _f64(np.atleast_1d(pressure))
+        t, p, flags = _slot_levels(temperature, pressure, accumulate, asynchronous)
         handles = np.ascontiguousarray(continua, dtype=np.int32)
         x = _f64(vmr).reshape(handles.size, -1, VMR_COUNT)
         if not (t.ndim == 1 and t.shape == p.shape and x.shape[1] == t.size):
             raise ValueError("temperature, pressure [levels] and vmr [continua, levels, 5] disagree.")
         if not hasattr(out, "pointer"):
             raise ValueError("continuum_compute_many writes a block in HBM (DeviceSpectra).")
-        flags = (ACCUMULATE if accumulate else 0) | (ASYNC if asynchronous else 0)
         out, pointer, flags, stride = self._output(out, t.size, n, flags)
         self._check(self.lib.lbl_continuum_compute_many(
             self.handle, handles.size, handles.ctypes.data, int(grid), t.size, t.ctypes.data,
@@ -883,10 +888,9 @@ class Engine(object):
     def xsec_compute(self, xsec, grid, n, temperature, pressure, vmr=None, out=None,
                      accumulate=False, asynchronous=False):
         """Cross sections [m2] (or, with vmr, n k [m-1]): float64[levels, n] or fills `out`."""
-        t, p = _f64(np.atleast_1d(temperature)), _f64(np.atleast_1d(pressure))
+        t, p, flags = _slot_levels(temperature, pressure, accumulate, asynchronous)
         if not (t.ndim == 1 and t.shape == p.shape):
             raise ValueError("temperature and pressure must be 1-d and equally long.")
-        flags = (ACCUMULATE if accumulate else 0) | (ASYNC if asynchronous else 0)
         x = None
         if vmr is not None:
             x = _f64(np.atleast_1d(vmr))

@@ -303,3 +303,62 @@ def test_arithmetic_grids_are_recognised_exactly(continua, continuum_oracle):
             got = continua[owner].spectra(temperature, pressure, vmr, grid)
             expect = continuum_oracle.continuum(owner).spectra(temperature, pressure, vmr, grid)
             assert_close(got, expect, f"{owner} on {name}")
+
+
+def test_host_output_in_workspace_chunks(continua, continuum_oracle):
+    """The host-output path of lbl_continuum_compute: with a 1 MiB workspace, 7 levels of 60 000
+    points go through the staging block two levels at a time (the last one alone), are copied
+    into rows longer than the grid, then added on the host onto what those rows hold.  The same
+    bits as the default workspace (one chunk) and as a DeviceSpectra copied back."""
+    grid = np.arange(600., 3600., 0.05)
+    atmos = synthetic.standard_atmosphere(7)
+    continuum = continua["H2OSelf"]
+    engine = default_engine(0)
+    levels, n, padded = atmos.t.size, grid.size, grid.size + 13
+
+    def write_then_add(out):
+        continuum.spectra_levels(atmos.t, atmos.p, atmos.vmr, grid, out=out)
+        written = out[:, :n].copy() if isinstance(out, np.ndarray) else out.to_host()[:, :n]
+        continuum.spectra_levels(atmos.t, atmos.p, atmos.vmr, grid, out=out, accumulate=True)
+        added = out[:, :n].copy() if isinstance(out, np.ndarray) else out.to_host()[:, :n]
+        return written, added
+
+    engine.set_option("workspace_bytes", 1 << 20)
+    try:
+        chunked_out = np.full((levels, padded), -7.)
+        chunked = write_then_add(chunked_out)
+    finally:
+        engine.set_option("workspace_bytes", 4 << 30)
+    assert np.all(chunked_out[:, n:] == -7.)        # the padding is not written
+    whole = write_then_add(np.full((levels, padded), -7.))
+    block = DeviceSpectra(engine, levels, padded)
+    try:
+        device = write_then_add(block)
+    finally:
+        block.free()
+    for reference in (whole, device):
+        for got, expect in zip(chunked, reference):
+            assert np.array_equal(got, expect)
+    dictionaries = level_dictionaries(atmos)
+    expect = np.stack([continuum_oracle.continuum("H2OSelf").spectra(
+        atmos.t[i], atmos.p[i], dictionaries[i], grid) for i in range(levels)])
+    assert_close(chunked[0], expect, "chunked host output")
+    assert_close(chunked[1], 2.*expect, "chunked host accumulate")
+
+
+def test_error_messages(continua):
+    """What a bad lbl_continuum_compute reports, in the order it checks."""
+    engine = default_engine(0)
+    grid = np.arange(1., 10., 1.)
+    handle = engine.load_grid(grid)
+    continuum = continua["CO2"].handle
+    try:
+        for args, message in (((12345, handle, grid.size), "unknown continuum handle."),
+                              ((continuum, 12345, grid.size), "unknown grid handle."),
+                              ((12345, 12345, grid.size), "unknown continuum handle."),
+                              ((continuum, handle, grid.size - 1), "level_stride < grid points.")):
+            with pytest.raises(EngineError) as error:
+                engine.continuum_compute(*args, [250.], [1e4], np.zeros((1, 5)))
+            assert str(error.value) == f"status 2: {message}"
+    finally:
+        engine.free_grid(handle)

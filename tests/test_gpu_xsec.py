@@ -231,3 +231,67 @@ def test_coefficient_file_in_the_reference_layout():
             for i, (temperature, pressure) in enumerate(data["states"]):
                 got = cross.absorption_coefficient(grid, temperature, pressure)
                 assert_close(got, data[f"xsec_{name}_{i}"], f"{name} state {i}")
+
+
+def test_host_output_in_workspace_chunks(molecule):
+    """The host-output path of lbl_xsec_compute: with a 1 MiB workspace, 7 levels of 60 000
+    points go through the staging block two levels at a time (the last one alone), are copied
+    into rows longer than the grid, then added on the host onto what those rows hold.  The same
+    bits as the default workspace (one chunk) and as a DeviceSpectra copied back."""
+    from oracle import xsec_oracle
+    from pylbl_amd import number_density
+    cross, bands = molecule
+    grid = np.arange(500., 1400., 0.015)
+    atmos = synthetic.standard_atmosphere(7)
+    vmr = np.linspace(1e-10, 3e-10, atmos.t.size)
+    engine = default_engine(0)
+    levels, n, padded = atmos.t.size, grid.size, grid.size + 13
+
+    def write_then_add(out):
+        cross.absorption_coefficients(grid, atmos.t, atmos.p, volume_mixing_ratio=vmr, out=out)
+        written = out[:, :n].copy() if isinstance(out, np.ndarray) else out.to_host()[:, :n]
+        cross.absorption_coefficients(grid, atmos.t, atmos.p, volume_mixing_ratio=vmr, out=out,
+                                      accumulate=True)
+        added = out[:, :n].copy() if isinstance(out, np.ndarray) else out.to_host()[:, :n]
+        return written, added
+
+    engine.set_option("workspace_bytes", 1 << 20)
+    try:
+        chunked_out = np.full((levels, padded), -7.)
+        chunked = write_then_add(chunked_out)
+    finally:
+        engine.set_option("workspace_bytes", 4 << 30)
+    assert np.all(chunked_out[:, n:] == -7.)        # the padding is not written
+    whole = write_then_add(np.full((levels, padded), -7.))
+    block = DeviceSpectra(engine, levels, padded)
+    try:
+        device = write_then_add(block)
+    finally:
+        block.free()
+    for reference in (whole, device):
+        for got, expect in zip(chunked, reference):
+            assert np.array_equal(got, expect)
+    expect = np.stack([number_density(atmos.t[i], atmos.p[i], vmr[i]) *
+                       xsec_oracle.absorption_coefficient(bands, grid, atmos.t[i], atmos.p[i])
+                       for i in range(levels)])
+    assert_close(chunked[0], expect, "chunked host output")
+    assert_close(chunked[1], 2.*expect, "chunked host accumulate")
+
+
+def test_error_messages(molecule):
+    """What a bad lbl_xsec_compute reports, in the order it checks."""
+    cross, _ = molecule
+    engine = default_engine(0)
+    grid = np.arange(500., 510., 1.)
+    handle = engine.load_grid(grid)
+    try:
+        for args, message in (((4242, handle, grid.size), "unknown cross-section handle."),
+                              ((cross.handle, 4242, grid.size), "unknown grid handle."),
+                              ((4242, 4242, grid.size), "unknown cross-section handle."),
+                              ((cross.handle, handle, grid.size - 1),
+                               "level_stride < grid points.")):
+            with pytest.raises(EngineError) as error:
+                engine.xsec_compute(*args, [250.], [1e4])
+            assert str(error.value) == f"status 2: {message}"
+    finally:
+        engine.free_grid(handle)
