@@ -448,6 +448,9 @@ class Engine(object):
         # one block in a fixed order, one deferred call per engine).  Single calls need no lock:
         # the C ABI serialises them per handle (include/lbl_amd.h, "Threads").
         self.pipeline = threading.RLock()
+        # Channel count of each instrument handle made by instrument_create: the width of `out`
+        # that instrument_apply checks before anything is launched.
+        self._instrument_channels = {}
         # Options for every engine of the process, for experiments: PYLBL_AMD_OPTIONS="name=value,..."
         # (kept in `environment_options` so that whoever reports numbers can say so: bench.py
         # echoes them).  "ablate" leaves work out -- results are wrong -- and is refused here: a
@@ -764,19 +767,25 @@ class Engine(object):
             *(x.ctypes.data if x is not None else None for x in (parameter, half_width)),
             n_table, *(x.ctypes.data if x is not None else None for x in (offsets, response)),
             rows, byref(handle)))
+        self._instrument_channels[handle.value] = centers.size
         return handle.value
 
     def instrument_free(self, instrument):
         self._check(self.lib.lbl_instrument_free(self.handle, int(instrument)))
+        self._instrument_channels.pop(int(instrument), None)
 
     def instrument_apply(self, values, rows, instrument, out, transmittance=False,
                          asynchronous=False):
         """out[r][c] = channel c's weighted mean of row r of the DeviceSpectra `values` (of
         exp(-value) with `transmittance`) for its first `rows` rows -- lbl_instrument_apply.
-        out: DeviceSpectra [>= rows, channels]."""
+        out: DeviceSpectra [>= rows, channels]: the kernel writes row r at out + r*channels, so
+        for a handle of instrument_create any other width is refused."""
         rows = int(rows)
         if not 0 < rows <= values.shape[0] or out.shape[0] < rows:
             raise ValueError(f"{rows} rows of values {values.shape} into {out.shape}.")
+        channels = self._instrument_channels.get(int(instrument))
+        if channels is not None and out.shape[1] != channels:
+            raise ValueError(f"out has shape {out.shape}, need rows x {channels} channels.")
         flags = (PATH_TRANSMITTANCE if transmittance else 0) | (ASYNC if asynchronous else 0)
         self._check(self.lib.lbl_instrument_apply(
             self.handle, values.pointer, int(values.shape[1]), rows, int(instrument), flags,

@@ -217,3 +217,36 @@ def test_instrument_needs_an_increasing_grid():
     with pytest.raises(ValueError, match="increasing"):
         spec.compute_path(np.ones((3, 5)), instrument=Instrument.boxcar([600.5], 0.5))
     assert spec.cache == {}
+
+
+@pytest.mark.parametrize("kind", ["uniform", "jittered"])
+@pytest.mark.parametrize("name", ["boxcar", "triangle", "gaussian", "fts", "fts-hamming",
+                                  "tabulated"])
+def test_probe_channel_sets_reach_every_tile_and_segment_edge(kind, name):
+    """The channel sets of tests/test_gpu_instrument_limits.py's identity probe, through a numpy
+    mirror of the sort and tiling of lbl_instrument_create: they reach the edges a rewrite of
+    the apply breaks first."""
+    from tests import instrument_cases as cases
+    grid = cases.probe_grid(kind)
+    assert grid.size % 8 != 0 and np.all(np.diff(grid) > 0.)
+    x = cases.probe_instrument(name, grid)
+    need = cases.TABULATED_CASES if name == "tabulated" else cases.CASES
+    missing = [case for case in need if case not in cases.coverage(x, grid)]
+    assert not missing, missing
+    tiles = cases.tiling(x, grid)
+    # every column of a valid window lies in one of its channel's items
+    for c in np.flatnonzero(tiles["valid"]):
+        spans = [tiles["items"][i] for i in range(tiles["first_item"][c],
+                                                  tiles["first_item"][c] + tiles["n_items"][c])]
+        assert all(t == tiles["tile"][c] for t, _, _ in spans)
+        assert spans[0][1] <= tiles["begin"][c] < spans[0][2]
+        assert spans[-1][1] < tiles["end"][c] <= spans[-1][2]
+        assert all(a[2] == b[1] for a, b in zip(spans, spans[1:]))
+
+
+def test_launch_chunk_of_the_apply():
+    from tests import instrument_cases as cases
+    assert cases.launch_chunk(8192, 150) == 64               # the partial-sum cap
+    assert cases.launch_chunk(8191, 150) == 128
+    assert cases.launch_chunk(5, 65535 + 77) == 65535          # the grid's y dimension
+    assert cases.launch_chunk(0, 70) == 70                     # no valid channel
