@@ -1,8 +1,8 @@
-// The stages of one batched lines call that stand on their own: the request put into the engine's
-// terms, the lane an asynchronous call takes, what a level allows the kernel to skip, the per-line
-// scalars made on the host (LBL_PREP_HOST), and the ways results go back to host memory.
-// compute() in compute_call.inc strings them together.  Included by engine.hip after
-// lanes_plans.inc.
+// The stages of one batched lines call, in the order compute() (compute_call.inc) strings them
+// together: the request put into the engine's terms, the lane the call takes and what it waits for
+// there, the level scalars of a pass, the prologue (on the host under LBL_PREP_HOST), the pedestal
+// pre-pass, the launches of a piece, the part that finishes a pass, the ways results go back to
+// host memory, and the end of the call.  Included by engine.hip after lanes_plans.inc.
 namespace {
 
 // A request checked and put into the engine's terms.
@@ -177,14 +177,85 @@ int next_lane_for(lbl_engine * engine, const ComputeRequest & rq, const CallShap
     return lane_index;
 }
 
+// The lane a call runs on, ordered against the calls on the other lanes and a call kept back.
+Lane & take_lane(lbl_engine * engine, const ComputeRequest & rq, const CallShape & s,
+                 const CallTraits & t, long long out_bytes)
+{
+    if ((rq.flags & LBL_DEFER_FINISH) || (!t.alternate && engine->deferred == &engine->lanes[0]))
+    {
+        // There is one deferral at a time; and a call about to reuse lane 0's buffers must not
+        // find a kept-back call still needing them.  (Kept-back calls stay off lane 0,
+        // next_lane_for, so a plain call -- another thread's, say -- leaves a deferral alone: the
+        // order in which a pipeline's calls add into their block does not depend on who else uses
+        // the engine.  The kept-back kernels order themselves behind every write of their block
+        // when they are queued, run_finish.)
+        engine->finish_deferred();
+    }
+    Lane & lane = engine->lanes[t.alternate ? next_lane_for(engine, rq, s, t) : 0];
+    if (!t.alternate)
+    {
+        if ((rq.flags & LBL_ASYNC) && t.out_device)
+        {
+            engine->join_lanes(lane.main);      // the host keeps queueing
+        }
+        else
+        {
+            for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
+        }
+    }
+    else
+    {
+        lane.used = true;
+        if (t.out_device && !t.add_into_block)
+        {
+            // Calls on different lanes run side by side; two that write the same memory must
+            // not: the later one waits for the earlier one's last kernel.  (A call that adds
+            // into the block waits later, in front of the one kernel that does the adding.)
+            engine->order_after_writers(lane.main, rq.k, out_bytes, &lane);
+        }
+    }
+    return lane;
+}
+
+// Levels per pass, bounded by the workspace budget.
+long long levels_per_pass(const lbl_engine * engine, const ComputeRequest & rq,
+                          const CallShape & s, const CallTraits & t, const Molecule::Plan & plan)
+{
+    const long long n_lines = s.m->n_lines;
+    const long long per_level = plan.partial_slots*64*s.points*8 + n_lines*(long long)(sizeof(LineWing) + sizeof(LineCore)) +
+                                (long long)s.tiling.n_tiles*sizeof(TileSchedule) +
+                                (t.out_device ? 0 : s.n_long*8) +
+                                (rq.remove_pedestal ? pedestal_bytes_per_level(n_lines, rq.vn - rq.v0, rq.cut_off) : 0);
+    const long long chunk = std::max(1ll, engine->workspace_bytes/std::max(per_level, 1ll));
+    return std::min<long long>(std::min<long long>(chunk, rq.n_levels), 65535);
+}
+
+// One lines call on its lane: what the stages below share.
+struct LinesCall
+{
+    lbl_engine * engine;
+    const ComputeRequest & rq;
+    const CallShape & shape;
+    const CallTraits & traits;
+    Lane & lane;
+    hipStream_t stream;             // lane.main
+    const Molecule::Plan & plan;
+    bool streamed;                  // lbl_compute_streamed: columns go to host memory piece by piece
+    int pieces;                     // runs of tiles launched one after the other; 1 unless streamed
+    bool with_pedestal;
+    long long out_bytes;            // the caller's block, first byte to last
+    long long chunk;                // levels per pass
+};
+
 // The lane's buffers for passes of `chunk` levels.  (Waits for the copy of the previous call's
 // level scalars out of the pinned block this call is about to fill.)
-void reserve_for_call(Lane & lane, const ComputeRequest & rq, const CallShape & s,
-                      const CallTraits & t, const Molecule::Plan & plan, long long chunk,
-                      hipStream_t stream)
+void reserve_for_call(const LinesCall & c)
 {
-    const long long n_lines = s.m->n_lines, n_tiles = s.tiling.n_tiles;
-    const bool with_pedestal = rq.remove_pedestal && n_lines > 0 && t.want_k;
+    const ComputeRequest & rq = c.rq;
+    const CallShape & s = c.shape;
+    const CallTraits & t = c.traits;
+    Lane & lane = c.lane;
+    const long long n_lines = s.m->n_lines, n_tiles = s.tiling.n_tiles, chunk = c.chunk;
     if (lane.levels_in_flight)
     {
         HIP_TRY(hipEventSynchronize(lane.levels_copied));
@@ -196,7 +267,7 @@ void reserve_for_call(Lane & lane, const ComputeRequest & rq, const CallShape & 
     lane.core.reserve((size_t)(chunk*std::max(n_lines, 1ll)));
     lane.schedule.reserve((size_t)(chunk*n_tiles));
     if (t.want_k && !t.out_device) lane.staging.reserve((size_t)(chunk*s.n_long));
-    if (with_pedestal && t.out_device && t.add_into_block)
+    if (c.with_pedestal && t.out_device && t.add_into_block)
     {
         lane.raw.reserve((size_t)(chunk*s.n_long));
     }
@@ -206,13 +277,13 @@ void reserve_for_call(Lane & lane, const ComputeRequest & rq, const CallShape & 
     }
     if (t.want_k)
     {
-        lane.partial.reserve((size_t)std::max(1ll, chunk*plan.partial_slots*64*s.points));
+        lane.partial.reserve((size_t)std::max(1ll, chunk*c.plan.partial_slots*64*s.points));
     }
     lane.wing_bounds.reserve((size_t)(chunk*kWingBounds));
     if (rq.evals != nullptr)
     {
         lane.evals.reserve(1);
-        HIP_TRY(hipMemsetAsync(lane.evals.data, 0, sizeof(unsigned long long), stream));
+        HIP_TRY(hipMemsetAsync(lane.evals.data, 0, sizeof(unsigned long long), c.stream));
     }
     if (rq.derived != nullptr) lane.derived.reserve((size_t)(std::max(n_lines, 1ll)*8));
 }
@@ -261,6 +332,43 @@ void bound_inner_regions(const Molecule & m, const RangeRule & rule, LevelScalar
             lv.inner_possible = 0.;
         }
     }
+}
+
+// A few levels travel as kernel arguments of the prologue kernel (no copy in front of it); more
+// go through the pinned block.
+bool levels_inline(const lbl_engine * engine, int count)
+{
+    return engine->prep != LBL_PREP_HOST && count <= kInlineLevels;
+}
+
+// The level scalars of a pass into the lane's pinned block and, unless they travel inline, on
+// their way to the device.  Returns LBL_OK or the status fail() recorded.
+int stage_levels(const LinesCall & c, long long base, int count)
+{
+    const ComputeRequest & rq = c.rq;
+    Lane & lane = c.lane;
+    // The previous pass may still be reading the pinned block.
+    if (base > 0) HIP_TRY(hipStreamSynchronize(c.stream));
+    for (int l = 0; l < count; ++l)
+    {
+        std::string why;
+        LevelScalars & lv = lane.pinned_levels[l];
+        if (!fill_level(*c.shape.m, rq.temperature[base + l], rq.pressure[base + l],
+                        rq.vmr[base + l], lv, why))
+        {
+            return fail(c.engine, LBL_OUT_OF_RANGE,
+                        "level " + std::to_string(base + l) + ": " + why);
+        }
+        bound_inner_regions(*c.shape.m, c.shape.rule, lv);
+    }
+    if (!levels_inline(c.engine, count))
+    {
+        HIP_TRY(hipMemcpyAsync(lane.levels.data, lane.pinned_levels, count*sizeof(LevelScalars),
+                               hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(hipEventRecord(lane.levels_copied, c.stream));
+        lane.levels_in_flight = true;
+    }
+    return LBL_OK;
 }
 
 // Can a line outside a tile's core range have its core in the tile?  Only if the window
@@ -352,6 +460,224 @@ void prepare_on_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
     }
 }
 
+// K1: per-line scalars (+ the tile cut points, in the same launch) of a pass.
+void launch_prologue(const LinesCall & c, int count, HostPrep & hp)
+{
+    lbl_engine * engine = c.engine;
+    const ComputeRequest & rq = c.rq;
+    const CallShape & s = c.shape;
+    Lane & lane = c.lane;
+    hipStream_t stream = c.stream;
+    if (engine->prep == LBL_PREP_HOST)
+    {
+        prepare_on_host(engine, lane, rq, s, count, stream, hp);
+        return;
+    }
+    const bool inline_levels = levels_inline(engine, count);
+    InlineLevels packed;
+    if (inline_levels)
+    {
+        std::memcpy(packed.level, lane.pinned_levels, count*sizeof(LevelScalars));
+    }
+    const int prepare_blocks = (int)((s.m->n_lines + 255)/256);
+    const int schedule_blocks = c.traits.want_k ? (int)((8ll*s.tiling.n_tiles + 255)/256) : 0;
+    // (every bound starts at kWingBoundsFill: byte 0x7f)
+    HIP_TRY(hipMemsetAsync(lane.wing_bounds.data, 0x7f, (size_t)count*kWingBounds*sizeof(int),
+                           stream));
+    engine->timed(kTimePrepare, stream, [&] {
+        dim3 grid((unsigned)std::max(prepare_blocks + schedule_blocks, 1), (unsigned)count);
+        hipLaunchKernelGGL(prologue_kernel, grid, dim3(256), 0, stream, s.m->view(),
+                           lane.levels.data, packed, inline_levels ? 1 : 0, s.g, s.rule, s.tiling,
+                           s.farfield, prepare_blocks, lane.wing.data, lane.core.data,
+                           lane.schedule.data,
+                           rq.derived != nullptr ? lane.derived.data : nullptr,
+                           rq.evals != nullptr ? lane.evals.data : nullptr,
+                           lane.wing_bounds.data);
+        HIP_TRY(hipGetLastError());
+    });
+}
+
+// Where the spectra of a pass end up, where the accumulate kernel writes, and the streams of the
+// pedestal pre-pass and of the part that finishes the pieces.
+Lane::Pass pass_of(const LinesCall & c, long long base, int count)
+{
+    const CallTraits & t = c.traits;
+    Lane::Pass p;
+    p.base = base;
+    p.count = count;
+    p.target = t.out_device ? c.rq.k + base*c.shape.stride : c.lane.staging.data;
+    p.target_stride = t.out_device ? c.shape.stride : c.shape.n_long;
+    p.sums = p.target;
+    p.sums_stride = p.target_stride;
+    if (c.with_pedestal && t.out_device && t.add_into_block)
+    {
+        p.sums = c.lane.raw.data;
+        p.sums_stride = c.shape.n_long;
+    }
+    p.ped_stream = c.engine->overlap_pedestal ? c.lane.side : c.stream;
+    // With a pedestal the pieces are finished on the stream the chain runs on (the apply kernels
+    // follow it there, while the main stream goes on with the accumulate launches of the later
+    // pieces), else on the main stream.
+    p.finish_stream = c.with_pedestal ? p.ped_stream : c.stream;
+    return p;
+}
+
+// The pedestal pre-pass only needs the per-line scalars: it runs on the side stream next to the
+// accumulate kernel (its serial chain keeps one CU busy).  Its run-finding kernels go first: once
+// the accumulate grid owns the chip their wide workgroups would wait for it to drain.
+void start_pedestal_search(const LinesCall & c, const Lane::Pass & p)
+{
+    lbl_engine * engine = c.engine;
+    Lane & lane = c.lane;
+    if (engine->overlap_pedestal)
+    {
+        HIP_TRY(hipEventRecord(lane.prepared, c.stream));
+        HIP_TRY(hipStreamWaitEvent(lane.side, lane.prepared, 0));
+    }
+    engine->timed(kTimePedestal, p.ped_stream, [&] {
+        pedestal_find_runs(lane.pedestal, p.ped_stream, c.shape.m->view(), lane.wing.data,
+                           c.shape.g, p.count, c.rq.vn - c.rq.v0, engine->scan_chain != 0,
+                           engine->poison_workspace != 0);
+    }, 0);
+    if (engine->overlap_pedestal)
+    {
+        HIP_TRY(hipEventRecord(lane.runs_found, lane.side));
+    }
+}
+
+AccumulateArgs accumulate_args(const LinesCall & c, const Lane::Pass & p)
+{
+    const ComputeRequest & rq = c.rq;
+    const CallShape & s = c.shape;
+    const GridSpec & g = s.g;
+    const Lane & lane = c.lane;
+    const bool add_into = c.traits.out_device && c.traits.add_into_block;
+    AccumulateArgs args;
+    args.wing = lane.wing.data;
+    args.core = lane.core.data;
+    args.schedule = lane.schedule.data;
+    args.levels = lane.levels.data;
+    args.items = c.plan.items.data;
+    args.far_series = s.farfield ? lane.far_series.data : nullptr;
+    args.wing_bounds = lane.wing_bounds.data;
+    args.wing_batches = c.engine->wing_batches;
+    args.partial = lane.partial.data;
+    args.partial_slots = c.plan.partial_slots;
+    args.level_stride = p.sums_stride;
+    args.k = p.sums;
+    args.n_lines = s.m->n_lines;
+    args.tiling = s.tiling;
+    args.n_tiles = s.tiling.n_tiles;
+    args.n = g.n;
+    args.v0 = g.v0;
+    args.n_per_v = g.n_per_v;
+    args.dv = g.dv;
+    args.v0_real = (double)g.v0;
+    // With a pedestal the kernel stores plain sums; pedestal_apply_kernel finishes.
+    args.scale_density = (!c.with_pedestal && (rq.flags & LBL_SCALE_DENSITY)) ? 1 : 0;
+    args.accumulate = (!c.with_pedestal && add_into) ? 1 : 0;
+    args.inner_everywhere = inner_points_everywhere(lane.pinned_levels, p.count, rq, s);
+#ifdef LBL_ABLATE
+    args.ablate = c.engine->ablate;
+#endif
+    return args;
+}
+
+// The accumulate launch of a piece's work items and the sums of its split tiles.
+void launch_piece(const LinesCall & c, const Lane::Pass & p, const AccumulateArgs & args,
+                  int piece)
+{
+    const Molecule::Plan & plan = c.plan;
+    hipStream_t stream = c.stream;
+    const int points = c.shape.points, count = p.count;
+    const int item0 = plan.item_begin[piece], item1 = plan.item_begin[piece + 1];
+    const int split0 = plan.split_begin[piece], split1 = plan.split_begin[piece + 1];
+    c.engine->timed(kTimeAccumulate, stream, [&] {
+        if (item1 > item0)
+        {
+            // One workgroup per work item, heaviest items first.
+            AccumulateArgs mine = args;
+            mine.items = plan.items.data + item0;
+            dim3 grid((unsigned)(item1 - item0), (unsigned)count);
+            launch_accumulate(points, grid, stream, mine);
+        }
+        if (split1 > split0)
+        {
+            const int units = (split1 - split0)*points;     // (split tile, 64-point row)
+            hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((units + 3)/4), (unsigned)count),
+                               dim3(256), 0, stream, args, plan.split.data + split0,
+                               split1 - split0, 64*points);
+            HIP_TRY(hipGetLastError());
+        }
+    });
+}
+
+// Lane::Finish of a pass: what copy_piece_home and run_finish go by.
+void describe_finish(const LinesCall & c, const Lane::Pass & p)
+{
+    const ComputeRequest & rq = c.rq;
+    const CallTraits & t = c.traits;
+    Lane::Finish & f = c.lane.finish;
+    f.pass = p;
+    f.g = c.shape.g;
+    f.pieces = c.pieces;
+    f.flags = rq.flags;
+    // (a run of tiles may be empty -- few tiles, uneven weights -- and must not move its
+    // neighbours' bounds: entry i is both the end of run i-1 and the start of run i)
+    long long reached = 0;
+    for (int piece = 0; piece < c.pieces; ++piece)
+    {
+        long long q0, q1;
+        c.plan.point_range(piece, c.shape.tiling, c.shape.g, q0, q1);
+        if (q1 <= q0)
+        {
+            q0 = q1 = reached;
+        }
+        f.point_begin[piece] = q0;
+        f.point_begin[piece + 1] = q1;
+        reached = q1;
+    }
+    f.streamed = c.streamed;
+    f.add_into = t.out_device && t.add_into_block;
+    f.order_writers = t.alternate && f.add_into;
+    f.host = rq.host;
+    f.host_pitch = rq.host_pitch;
+    f.columns = rq.columns;
+    // The block's write record: only once, behind the call's last pass.
+    const bool last_pass = p.base + p.count >= rq.n_levels;
+    f.k = (t.out_device && last_pass) ? rq.k : nullptr;
+    f.block = rq.k;
+    f.out_bytes = c.out_bytes;
+}
+
+// Behind the accumulate launches of a pass with a pedestal: the pedestal chain (the host waits for
+// the run counts inside), then what finishes the pieces -- now, or kept back.  (Queueing the chain
+// in front of the accumulate launches of a far-field call: +-0, profiles/r05_ab_chain_first.txt.)
+void finish_with_pedestal(const LinesCall & c, const Lane::Pass & p)
+{
+    lbl_engine * engine = c.engine;
+    const ComputeRequest & rq = c.rq;
+    Lane & lane = c.lane;
+    engine->timed(kTimePedestal, p.ped_stream, [&] {
+        pedestal_finish(lane.pedestal, p.ped_stream, c.shape.m->view(), lane.wing.data,
+                        lane.core.data, c.shape.g, p.count, rq.vn - rq.v0,
+                        engine->scan_chain != 0, engine->relax_launches,
+                        engine->poison_workspace != 0);
+    });
+    lane.finish.pending = true;
+    // Kept back for lbl_finish_deferred only if nothing of this call comes after it: one pass,
+    // spectra in device memory, the host not waiting.
+    if ((rq.flags & LBL_DEFER_FINISH) && (rq.flags & LBL_ASYNC) && c.traits.out_device &&
+        c.traits.alternate && c.chunk >= rq.n_levels && rq.evals == nullptr)
+    {
+        engine->deferred = &lane;
+    }
+    else
+    {
+        engine->run_finish(lane);
+    }
+}
+
 // Spectra of one pass from the lane's staging block into the caller's host memory (a call
 // without LBL_OUT_DEVICE): one copy where the rows are dense and nothing is added, through a
 // temporary otherwise.  Waits, except for the last pass of a blocking call (the end of the call
@@ -410,6 +736,45 @@ void derived_to_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
     {
         std::memcpy(rq.derived + (size_t)s.m->order[j]*8, sorted.data() + (size_t)j*8, 64);
     }
+}
+
+// The end of a call: the block's write record, what goes back by value, and the wait of a call
+// without LBL_ASYNC -- here, or left to the caller as an event (compute()'s wait_for).
+int end_call(const LinesCall & c, const HostPrep & hp, hipEvent_t * wait_for)
+{
+    lbl_engine * engine = c.engine;
+    const ComputeRequest & rq = c.rq;
+    Lane & lane = c.lane;
+    hipStream_t stream = c.stream;
+    if (c.traits.out_device && c.traits.want_k && !c.with_pedestal)
+    {
+        lane.note_write(rq.k, c.out_bytes, stream);     // (with a pedestal: run_finish does)
+    }
+    if (rq.evals != nullptr && !(engine->prep == LBL_PREP_HOST))
+    {
+        unsigned long long total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, lane.evals.data, sizeof(total), hipMemcpyDeviceToHost,
+                               stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        *rq.evals = (int64_t)total;
+    }
+    if (rq.derived != nullptr)
+    {
+        derived_to_host(engine, lane, rq, c.shape, hp, stream);
+    }
+    if (!(rq.flags & LBL_ASYNC))
+    {
+        if (wait_for != nullptr)
+        {
+            *wait_for = engine->take_event();
+            HIP_TRY(hipEventRecord(*wait_for, stream));
+        }
+        else
+        {
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    return LBL_OK;
 }
 
 }  // namespace

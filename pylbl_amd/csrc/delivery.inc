@@ -81,10 +81,7 @@ void * lbl_stream(lbl_engine * engine)
 // handful of event records and stream waits.
 int lbl_order_stream_after_engine(lbl_engine * engine, void * stream)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    try
-    {
+    return entry(engine, [&] {
         HIP_TRY(hipSetDevice(engine->device));
         // "Everything queued so far" includes what a call kept back (LBL_DEFER_FINISH): the
         // caller's stream is about to read the block.
@@ -99,20 +96,13 @@ int lbl_order_stream_after_engine(lbl_engine * engine, void * stream)
         }
         HIP_TRY(hipEventRecord(engine->copies_handed_over, engine->copy_stream));
         HIP_TRY(hipStreamWaitEvent(theirs, engine->copies_handed_over, 0));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_order_engine_after_stream(lbl_engine * engine, void * stream)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    try
-    {
+    return entry(engine, [&] {
         HIP_TRY(hipSetDevice(engine->device));
         HIP_TRY(hipEventRecord(engine->taken_over, reinterpret_cast<hipStream_t>(stream)));
         for (auto & lane : engine->lanes)
@@ -121,12 +111,8 @@ int lbl_order_engine_after_stream(lbl_engine * engine, void * stream)
             HIP_TRY(hipStreamWaitEvent(lane.side, engine->taken_over, 0));
         }
         HIP_TRY(hipStreamWaitEvent(engine->copy_stream, engine->taken_over, 0));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_device_alloc(lbl_engine * engine, int64_t bytes, void ** pointer)
@@ -134,29 +120,33 @@ int lbl_device_alloc(lbl_engine * engine, int64_t bytes, void ** pointer)
     if (engine == nullptr || pointer == nullptr || bytes < 0) return LBL_BAD_ARGUMENT;
     (void)hipSetDevice(engine->device);
     const int64_t size = std::max<int64_t>(bytes, 8);
+    // (the allocation itself outside the lock: only the list of blocks is the engine's state)
     hipError_t status = hipMalloc(pointer, (size_t)size);
     if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
-    EngineLock lock(engine->mutex);
-    engine->device_blocks.push_back(lbl_engine::Block{static_cast<const char *>(*pointer), size});
-    return LBL_OK;
+    return entry(engine, [&] {
+        engine->device_blocks.push_back(lbl_engine::Block{static_cast<const char *>(*pointer), size});
+        return LBL_OK;
+    });
 }
 
 int lbl_device_free(lbl_engine * engine, void * pointer)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    (void)hipSetDevice(engine->device);
-    // A call kept back (LBL_DEFER_FINISH) that still has THIS block to write is finished first,
-    // like in lbl_synchronize -- never left to run into freed memory.  (Any other block: the
-    // deferral stays; a free from a finalizer thread must not reorder a pipeline's additions.)
-    if (engine->deferred_touches(pointer, lbl_engine::forget(engine->device_blocks, pointer)))
-    {
-        try { engine->finish_deferred(); } catch (const HipFailure &) { engine->cancel_deferred(); }
-    }
-    engine->drain_lanes();
-    hipError_t status = hipFree(pointer);
-    if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
-    return LBL_OK;
+    return entry(engine, [&] {
+        (void)hipSetDevice(engine->device);
+        // A call kept back (LBL_DEFER_FINISH) that still has THIS block to write is finished first,
+        // like in lbl_synchronize -- never left to run into freed memory.  (Any other block: the
+        // deferral stays; a free from a finalizer thread must not reorder a pipeline's additions.)
+        if (engine->deferred_touches(pointer, lbl_engine::forget(engine->device_blocks, pointer)))
+        {
+            // (a failure here is not the free's: what cannot be finished is dropped, and the
+            // memory is freed all the same)
+            try { engine->finish_deferred(); } catch (const HipFailure &) { engine->cancel_deferred(); }
+        }
+        engine->drain_lanes();
+        hipError_t status = hipFree(pointer);
+        if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
+        return LBL_OK;
+    });
 }
 
 int lbl_copy_to_host(lbl_engine * engine, void * host, const void * device, int64_t bytes)
@@ -165,45 +155,42 @@ int lbl_copy_to_host(lbl_engine * engine, void * host, const void * device, int6
     {
         return LBL_BAD_ARGUMENT;
     }
-    EngineLock lock(engine->mutex);
-    (void)hipSetDevice(engine->device);
-    try { engine->finish_deferred(); }
-    catch (const HipFailure & f) { return fail(engine, LBL_ERROR, f.message); }
-    // The memory may have been written on any lane (asynchronous calls with a pedestal rotate
-    // over them): wait for all of them, not only for lane 0.
-    hipError_t status = hipSuccess;
-    for (auto & lane : engine->lanes)
-    {
-        if (status == hipSuccess) status = hipStreamSynchronize(lane.main);
-    }
-    if (status == hipSuccess)
-    {
-        status = hipMemcpyAsync(host, device, (size_t)bytes, hipMemcpyDeviceToHost,
-                                engine->stream);
-    }
-    if (status == hipSuccess) status = hipStreamSynchronize(engine->stream);
-    if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
-    return LBL_OK;
+    return entry(engine, [&] {
+        (void)hipSetDevice(engine->device);
+        engine->finish_deferred();
+        // The memory may have been written on any lane (asynchronous calls with a pedestal rotate
+        // over them): wait for all of them, not only for lane 0.
+        hipError_t status = hipSuccess;
+        for (auto & lane : engine->lanes)
+        {
+            if (status == hipSuccess) status = hipStreamSynchronize(lane.main);
+        }
+        if (status == hipSuccess)
+        {
+            status = hipMemcpyAsync(host, device, (size_t)bytes, hipMemcpyDeviceToHost,
+                                    engine->stream);
+        }
+        if (status == hipSuccess) status = hipStreamSynchronize(engine->stream);
+        if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
+        return LBL_OK;
+    });
 }
 
 int lbl_fill_zero(lbl_engine * engine, double * k, int32_t n_levels, int64_t n,
                   int64_t level_stride, int32_t flags)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (k == nullptr || n_levels < 0 || n < 0 || (level_stride != 0 && level_stride < n))
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_fill_zero: bad argument.");
-    }
-    const int64_t stride = level_stride > 0 ? level_stride : n;
-    if (n_levels == 0 || n == 0) return LBL_OK;
-    if (!(flags & LBL_OUT_DEVICE))
-    {
-        for (int32_t l = 0; l < n_levels; ++l) std::memset(k + l*stride, 0, (size_t)n*8);
-        return LBL_OK;
-    }
-    try
-    {
+    return entry(engine, [&] {
+        if (k == nullptr || n_levels < 0 || n < 0 || (level_stride != 0 && level_stride < n))
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_fill_zero: bad argument.");
+        }
+        const int64_t stride = level_stride > 0 ? level_stride : n;
+        if (n_levels == 0 || n == 0) return LBL_OK;
+        if (!(flags & LBL_OUT_DEVICE))
+        {
+            for (int32_t l = 0; l < n_levels; ++l) std::memset(k + l*stride, 0, (size_t)n*8);
+            return LBL_OK;
+        }
         HIP_TRY(hipSetDevice(engine->device));
         // Ordered like a plain compute call: after everything queued on the other lanes --
         // by events when the caller does not wait either, so that the host keeps queueing.
@@ -219,12 +206,8 @@ int lbl_fill_zero(lbl_engine * engine, double * k, int32_t n_levels, int64_t n,
                                  engine->stream));
         engine->lanes[0].note_write(k, ((long long)(n_levels - 1)*stride + n)*8, engine->stream);
         if (!(flags & LBL_ASYNC)) HIP_TRY(hipStreamSynchronize(engine->stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_copy_rows_to_host(lbl_engine * engine, void * host, int64_t host_pitch,
@@ -237,9 +220,7 @@ int lbl_copy_rows_to_host(lbl_engine * engine, void * host, int64_t host_pitch,
         return LBL_BAD_ARGUMENT;
     }
     if (rows == 0 || row_bytes == 0) return LBL_OK;
-    EngineLock lock(engine->mutex);
-    try
-    {
+    return entry(engine, [&] {
         HIP_TRY(hipSetDevice(engine->device));
         engine->finish_deferred();      // the rows may be what a call kept back still has to write
         // The rows may have been written on any lane: the copy stream waits for what each of
@@ -253,12 +234,8 @@ int lbl_copy_rows_to_host(lbl_engine * engine, void * host, int64_t host_pitch,
                                  (size_t)row_bytes, (size_t)rows, hipMemcpyDeviceToHost,
                                  engine->copy_stream));
         if (!(flags & LBL_ASYNC)) HIP_TRY(hipStreamSynchronize(engine->copy_stream));
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_host_alloc(lbl_engine * engine, int64_t bytes, void ** pointer)
@@ -266,30 +243,32 @@ int lbl_host_alloc(lbl_engine * engine, int64_t bytes, void ** pointer)
     if (engine == nullptr || pointer == nullptr || bytes < 0) return LBL_BAD_ARGUMENT;
     (void)hipSetDevice(engine->device);
     const int64_t size = std::max<int64_t>(bytes, 8);
-    hipError_t status = hipHostMalloc(pointer, (size_t)size, hipHostMallocDefault);
+    hipError_t status = hipHostMalloc(pointer, (size_t)size, hipHostMallocDefault);    // (outside the lock)
     if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
-    EngineLock lock(engine->mutex);
-    engine->host_blocks.push_back(lbl_engine::Block{static_cast<const char *>(*pointer), size});
-    return LBL_OK;
+    return entry(engine, [&] {
+        engine->host_blocks.push_back(lbl_engine::Block{static_cast<const char *>(*pointer), size});
+        return LBL_OK;
+    });
 }
 
 int lbl_host_free(lbl_engine * engine, void * pointer)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    (void)hipSetDevice(engine->device);
-    if (engine->deferred_touches(pointer, lbl_engine::forget(engine->host_blocks, pointer)))
-    {
-        // The copies of the streamed call kept back target this memory.  (Any other array --
-        // e.g. one a finalizer thread hands back while a pipeline is between its deferred call
-        // and lbl_finish_deferred -- leaves the deferral alone.)
-        try { engine->finish_deferred(); } catch (const HipFailure &) { engine->cancel_deferred(); }
-        engine->drain_lanes();
-    }
-    if (engine->copy_stream != nullptr) (void)hipStreamSynchronize(engine->copy_stream);
-    hipError_t status = hipHostFree(pointer);
-    if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
-    return LBL_OK;
+    return entry(engine, [&] {
+        (void)hipSetDevice(engine->device);
+        if (engine->deferred_touches(pointer, lbl_engine::forget(engine->host_blocks, pointer)))
+        {
+            // The copies of the streamed call kept back target this memory.  (Any other array --
+            // e.g. one a finalizer thread hands back while a pipeline is between its deferred call
+            // and lbl_finish_deferred -- leaves the deferral alone.)  As in lbl_device_free, a
+            // failure to finish drops the call instead of failing the free.
+            try { engine->finish_deferred(); } catch (const HipFailure &) { engine->cancel_deferred(); }
+            engine->drain_lanes();
+        }
+        if (engine->copy_stream != nullptr) (void)hipStreamSynchronize(engine->copy_stream);
+        hipError_t status = hipHostFree(pointer);
+        if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
+        return LBL_OK;
+    });
 }
 
 }  // extern "C"

@@ -149,18 +149,15 @@ int lbl_molecule_load(lbl_engine * engine, int64_t n_lines,
                       const double * tips_temperature, const double * tips_data,
                       int32_t * molecule)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (molecule == nullptr || n_lines < 0 || n_lines > 0x7fffffff || mass == nullptr ||
-        tips_temperature == nullptr || tips_data == nullptr || num_iso < 1 || num_t < 2 ||
-        (n_lines > 0 && (nu == nullptr || sw == nullptr || gamma_air == nullptr ||
-                         gamma_self == nullptr || n_air == nullptr || elower == nullptr ||
-                         delta_air == nullptr || local_iso_id == nullptr)))
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_molecule_load: bad argument.");
-    }
-    try
-    {
+    return entry(engine, [&] {
+        if (molecule == nullptr || n_lines < 0 || n_lines > 0x7fffffff || mass == nullptr ||
+            tips_temperature == nullptr || tips_data == nullptr || num_iso < 1 || num_t < 2 ||
+            (n_lines > 0 && (nu == nullptr || sw == nullptr || gamma_air == nullptr ||
+                             gamma_self == nullptr || n_air == nullptr || elower == nullptr ||
+                             delta_air == nullptr || local_iso_id == nullptr)))
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_molecule_load: bad argument.");
+        }
         HIP_TRY(hipSetDevice(engine->device));
         std::unique_ptr<Molecule> m(new Molecule());
         m->n_lines = n_lines;
@@ -259,30 +256,22 @@ int lbl_molecule_load(lbl_engine * engine, int64_t n_lines,
         if (slot == engine->molecules.size()) engine->molecules.emplace_back();
         engine->molecules[slot] = std::move(m);
         *molecule = (int32_t)slot;
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    catch (const std::bad_alloc &)
-    {
-        return fail(engine, LBL_ERROR, "host allocation failed.");
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_molecule_free(lbl_engine * engine, int32_t molecule)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (find_molecule(engine, molecule) == nullptr)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "unknown molecule handle.");
-    }
-    (void)hipSetDevice(engine->device);
-    engine->drain_lanes();
-    engine->molecules[molecule].reset();
-    return LBL_OK;
+    return entry(engine, [&] {
+        if (find_molecule(engine, molecule) == nullptr)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "unknown molecule handle.");
+        }
+        (void)hipSetDevice(engine->device);
+        engine->drain_lanes();
+        engine->molecules[molecule].reset();
+        return LBL_OK;
+    });
 }
 
 int lbl_compute(lbl_engine * engine, int32_t molecule, int32_t n_levels,
@@ -306,30 +295,33 @@ int lbl_compute_streamed(lbl_engine * engine, int32_t molecule, int32_t n_levels
                          double * k, int64_t level_stride, void * host, int64_t host_pitch,
                          int64_t columns, int32_t pieces)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (k == nullptr || host == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "k or host is NULL.");
-    if (!(flags & LBL_OUT_DEVICE))
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "lbl_compute_streamed needs LBL_OUT_DEVICE.");
-    }
-    if (columns < 0 || host_pitch < columns*8 || pieces < 1)
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "need columns >= 0, host_pitch >= 8*columns and "
-                                              "pieces >= 1.");
-    }
-    ComputeRequest rq{molecule, n_levels, temperature, pressure, vmr, v0, vn, n_per_v, cut_off,
-                      remove_pedestal, range_policy, flags, k, level_stride, nullptr, nullptr};
-    rq.host = static_cast<char *>(host);
-    rq.host_pitch = host_pitch;
-    rq.columns = columns;
-    rq.pieces = pieces;
-    const int status = compute(engine, rq);
-    if (status == LBL_OK && !(flags & LBL_ASYNC))
-    {
-        (void)hipStreamSynchronize(engine->copy_stream);
-    }
-    return status;
+    return entry(engine, [&] {
+        if (k == nullptr || host == nullptr)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "k or host is NULL.");
+        }
+        if (!(flags & LBL_OUT_DEVICE))
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "lbl_compute_streamed needs LBL_OUT_DEVICE.");
+        }
+        if (columns < 0 || host_pitch < columns*8 || pieces < 1)
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "need columns >= 0, host_pitch >= 8*columns and "
+                                                  "pieces >= 1.");
+        }
+        ComputeRequest rq{molecule, n_levels, temperature, pressure, vmr, v0, vn, n_per_v, cut_off,
+                          remove_pedestal, range_policy, flags, k, level_stride, nullptr, nullptr};
+        rq.host = static_cast<char *>(host);
+        rq.host_pitch = host_pitch;
+        rq.columns = columns;
+        rq.pieces = pieces;
+        const int status = compute(engine, rq);
+        if (status == LBL_OK && !(flags & LBL_ASYNC))
+        {
+            (void)hipStreamSynchronize(engine->copy_stream);
+        }
+        return status;
+    });
 }
 
 int lbl_line_scalars(lbl_engine * engine, int32_t molecule, double temperature,
@@ -337,13 +329,13 @@ int lbl_line_scalars(lbl_engine * engine, int32_t molecule, double temperature,
                      int32_t cut_off, int32_t remove_pedestal, int32_t range_policy,
                      double * derived)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    if (derived == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "derived is NULL.");
-    (void)remove_pedestal;
-    ComputeRequest rq{molecule, 1, &temperature, &pressure, &vmr, v0, vn, n_per_v, cut_off,
-                      0, range_policy, 0, nullptr, 0, nullptr, derived};
-    return compute(engine, rq);
+    return entry(engine, [&] {
+        if (derived == nullptr) return fail(engine, LBL_BAD_ARGUMENT, "derived is NULL.");
+        (void)remove_pedestal;
+        ComputeRequest rq{molecule, 1, &temperature, &pressure, &vmr, v0, vn, n_per_v, cut_off,
+                          0, range_policy, 0, nullptr, 0, nullptr, derived};
+        return compute(engine, rq);
+    });
 }
 
 int lbl_deferred(const lbl_engine * engine)
@@ -355,196 +347,163 @@ int lbl_deferred(const lbl_engine * engine)
 
 int lbl_cancel_deferred(lbl_engine * engine)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    engine->cancel_deferred();
-    return LBL_OK;
+    return entry(engine, [&] {
+        engine->cancel_deferred();
+        return LBL_OK;
+    });
 }
 
 int lbl_finish_deferred(lbl_engine * engine)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    try
-    {
+    return entry(engine, [&] {
         HIP_TRY(hipSetDevice(engine->device));
         engine->finish_deferred();
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_synchronize(lbl_engine * engine)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    (void)hipSetDevice(engine->device);
-    // A call still kept back (LBL_DEFER_FINISH) is finished first: nothing stays unapplied.
-    const int finished = lbl_finish_deferred(engine);
-    if (finished != LBL_OK) return finished;
-    for (auto & lane : engine->lanes)
-    {
-        hipError_t status = hipStreamSynchronize(lane.main);
-        if (status == hipSuccess) status = hipStreamSynchronize(lane.side);
+    return entry(engine, [&] {
+        (void)hipSetDevice(engine->device);
+        // A call still kept back (LBL_DEFER_FINISH) is finished first: nothing stays unapplied.
+        const int finished = lbl_finish_deferred(engine);
+        if (finished != LBL_OK) return finished;
+        for (auto & lane : engine->lanes)
+        {
+            hipError_t status = hipStreamSynchronize(lane.main);
+            if (status == hipSuccess) status = hipStreamSynchronize(lane.side);
+            if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
+        }
+        const hipError_t status = hipStreamSynchronize(engine->copy_stream);
         if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
-    }
-    const hipError_t status = hipStreamSynchronize(engine->copy_stream);
-    if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_set_option(lbl_engine * engine, const char * name, int64_t value)
 {
-    if (engine == nullptr || name == nullptr) return LBL_BAD_ARGUMENT;
+    if (name == nullptr) return LBL_BAD_ARGUMENT;
     // (compute() reads the options under the same lock: none changes in the middle of a call)
-    EngineLock lock(engine->mutex);
-    const std::string key(name);
-    if (key == "prep" && (value == LBL_PREP_DEVICE || value == LBL_PREP_HOST))
-    {
-        engine->prep = (int)value;
-    }
-    else if (key == "points_per_lane" &&
-             (value == 0 || value == 1 || value == 2 || value == 4 || value == 8))
-    {
-        engine->points_per_lane = (int)value;
-    }
-    else if (key == "timing" && value >= 0 && value <= 2)
-    {
-        if (value != 0 && engine->timing == 0)
+    return entry(engine, [&] {
+        const std::string key(name);
+        if (key == "prep" && (value == LBL_PREP_DEVICE || value == LBL_PREP_HOST))
         {
-            // A fresh origin for the positions of the spans to come, behind everything queued so far.
-            try
+            engine->prep = (int)value;
+        }
+        else if (key == "points_per_lane" &&
+                 (value == 0 || value == 1 || value == 2 || value == 4 || value == 8))
+        {
+            engine->points_per_lane = (int)value;
+        }
+        else if (key == "timing" && value >= 0 && value <= 2)
+        {
+            if (value != 0 && engine->timing == 0)
             {
+                // A fresh origin for the positions of the spans to come, behind everything queued so far.
                 HIP_TRY(hipSetDevice(engine->device));
                 engine->drain_lanes();
                 engine->reset_epoch();
             }
-            catch (const HipFailure & f)
-            {
-                return fail(engine, LBL_ERROR, f.message);
-            }
+            engine->timing = (int)value;
         }
-        engine->timing = (int)value;
-    }
-    else if (key == "relax_launches" && (value == 0 || (value >= 2 && value <= 7)))
-    {
-        engine->relax_launches = (int)value;
-    }
-    else if (key == "scan_chain" && (value == 0 || value == 1))
-    {
-        engine->scan_chain = (int)value;
-    }
-    else if (key == "poison_workspace" && (value == 0 || value == 1))
-    {
-        engine->poison_workspace = (int)value;
-    }
-    else if (key == "skip_delivery_lanes" && (value == 0 || value == 1))
-    {
-        engine->skip_delivery_lanes = (int)value;
-    }
-    else if (key == "overlap_plain" && (value == 0 || value == 1))
-    {
-        engine->overlap_plain = (int)value;
-    }
-    else if (key == "small_points" && value >= 0)
-    {
-        engine->small_points = value;
-    }
-    else if (key == "lanes" && (value == 0 || (value >= 2 && value <= kLanes)))
-    {
-        engine->lanes_in_use = (int)value;
-    }
-    else if (key == "farfield" && (value == 0 || value == 1))
-    {
-        engine->farfield = (int)value;
-    }
-    else if (key == "overlap_pedestal" && (value == 0 || value == 1))
-    {
-        engine->overlap_pedestal = (int)value;
-    }
-    else if (key == "aligned_tiles" && (value == 0 || value == 1))
-    {
-        engine->aligned_tiles = (int)value;
-    }
-    else if (key == "wing_batches" && (value == 1 || value == 2 || value == 4 || value == 8))
-    {
-        engine->wing_batches = std::min((int)value, kWingBatchesMax);
-    }
+        else if (key == "relax_launches" && (value == 0 || (value >= 2 && value <= 7)))
+        {
+            engine->relax_launches = (int)value;
+        }
+        else if (key == "scan_chain" && (value == 0 || value == 1))
+        {
+            engine->scan_chain = (int)value;
+        }
+        else if (key == "poison_workspace" && (value == 0 || value == 1))
+        {
+            engine->poison_workspace = (int)value;
+        }
+        else if (key == "skip_delivery_lanes" && (value == 0 || value == 1))
+        {
+            engine->skip_delivery_lanes = (int)value;
+        }
+        else if (key == "overlap_plain" && (value == 0 || value == 1))
+        {
+            engine->overlap_plain = (int)value;
+        }
+        else if (key == "small_points" && value >= 0)
+        {
+            engine->small_points = value;
+        }
+        else if (key == "lanes" && (value == 0 || (value >= 2 && value <= kLanes)))
+        {
+            engine->lanes_in_use = (int)value;
+        }
+        else if (key == "farfield" && (value == 0 || value == 1))
+        {
+            engine->farfield = (int)value;
+        }
+        else if (key == "overlap_pedestal" && (value == 0 || value == 1))
+        {
+            engine->overlap_pedestal = (int)value;
+        }
+        else if (key == "aligned_tiles" && (value == 0 || value == 1))
+        {
+            engine->aligned_tiles = (int)value;
+        }
+        else if (key == "wing_batches" && (value == 1 || value == 2 || value == 4 || value == 8))
+        {
+            engine->wing_batches = std::min((int)value, kWingBatchesMax);
+        }
 #ifdef LBL_ABLATE
-    else if (key == "ablate" && value >= 0 && value <= 127)
-    {
-        engine->ablate = (int)value;    // diagnostics build only: results are wrong when set
-    }
+        else if (key == "ablate" && value >= 0 && value <= 127)
+        {
+            engine->ablate = (int)value;    // diagnostics build only: results are wrong when set
+        }
 #endif
-    else if (key == "workspace_bytes" && value >= (1 << 20))
-    {
-        engine->workspace_bytes = value;
-    }
-    else
-    {
-        return fail(engine, LBL_BAD_ARGUMENT, "unknown option or value: " + key);
-    }
-    return LBL_OK;
+        else if (key == "workspace_bytes" && value >= (1 << 20))
+        {
+            engine->workspace_bytes = value;
+        }
+        else
+        {
+            return fail(engine, LBL_BAD_ARGUMENT, "unknown option or value: " + key);
+        }
+        return LBL_OK;
+    });
 }
 
 int lbl_timing(lbl_engine * engine, double ms[8], int64_t launches[8], int32_t reset)
 {
-    if (engine == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    try
-    {
+    return entry(engine, [&] {
         HIP_TRY(hipSetDevice(engine->device));
         engine->drain_lanes();
         engine->drain_spans();
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    for (int i = 0; i < kTimeKinds; ++i)
-    {
-        if (ms != nullptr) ms[i] = engine->time_ms[i];
-        if (launches != nullptr) launches[i] = engine->launches[i];
-        if (reset)
+        for (int i = 0; i < kTimeKinds; ++i)
         {
-            engine->time_ms[i] = 0.;
-            engine->launches[i] = 0;
-            engine->busy_ms[i] = 0.;
+            if (ms != nullptr) ms[i] = engine->time_ms[i];
+            if (launches != nullptr) launches[i] = engine->launches[i];
+            if (reset)
+            {
+                engine->time_ms[i] = 0.;
+                engine->launches[i] = 0;
+                engine->busy_ms[i] = 0.;
+            }
         }
-    }
-    if (reset && engine->timing != 0)
-    {
-        try
+        if (reset && engine->timing != 0)
         {
             engine->reset_epoch();      // (every stream has just been drained)
         }
-        catch (const HipFailure & f)
-        {
-            return fail(engine, LBL_ERROR, f.message);
-        }
-    }
-    return LBL_OK;
+        return LBL_OK;
+    });
 }
 
 int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 {
-    if (engine == nullptr || busy_ms == nullptr) return LBL_BAD_ARGUMENT;
-    EngineLock lock(engine->mutex);
-    try
-    {
+    if (busy_ms == nullptr) return LBL_BAD_ARGUMENT;
+    return entry(engine, [&] {
         HIP_TRY(hipSetDevice(engine->device));
         engine->drain_lanes();
         engine->drain_spans();
-    }
-    catch (const HipFailure & f)
-    {
-        return fail(engine, LBL_ERROR, f.message);
-    }
-    for (int i = 0; i < kTimeKinds; ++i) busy_ms[i] = engine->busy_ms[i];
-    return LBL_OK;
+        for (int i = 0; i < kTimeKinds; ++i) busy_ms[i] = engine->busy_ms[i];
+        return LBL_OK;
+    });
 }
 
 }  // extern "C"

@@ -104,6 +104,20 @@ struct Molecule
         DeviceBuffer<WorkItem> items;       // piece-major, heaviest first within a piece
         DeviceBuffer<SplitTile> split;      // piece-major
         std::vector<int> item_begin, split_begin, tile_begin;   // [pieces + 1] each
+
+        // The grid points [q0, q1) of a piece's run of tiles; q0 == q1 == 0 where the run is empty.
+        void point_range(int piece, const Tiling & tiling, const GridSpec & g, long long & q0,
+                         long long & q1) const
+        {
+            long long unused = 0;
+            q0 = q1 = 0;
+            if (tile_begin[piece + 1] > tile_begin[piece])
+            {
+                tile_bounds(tiling, tile_begin[piece], g.n_per_v, g.n, q0, unused);
+                tile_bounds(tiling, tile_begin[piece + 1] - 1, g.n_per_v, g.n, unused, q1);
+                q1 += 1;
+            }
+        }
     };
     std::vector<std::unique_ptr<Plan>> plans;
 
@@ -140,27 +154,38 @@ struct Lane
     hipEvent_t handed_over = nullptr;   // what a caller's stream waits for (lbl_order_stream_after_engine)
     hipEvent_t piece_done[8] = {};      // behind the last kernel of each piece of a streamed call
     hipEvent_t piece_summed[8] = {};    // behind a piece's accumulate launch (pedestal: applied elsewhere)
-    // The last part of a call with a pedestal -- the kernels that apply it to the caller's block,
-    // piece by piece, and the copies of a streamed call -- kept back until lbl_finish_deferred
-    // (LBL_DEFER_FINISH): everything before works in the lane's own buffers, so a long call can be
+    // One pass of a lines call (levels [base, base + count) of the request): where its spectra end
+    // up, where the accumulate kernel writes, and the streams its later stages run on.
+    struct Pass
+    {
+        long long base = 0;
+        int count = 0;
+        double * target = nullptr;      // the caller's block, or the lane's staging block
+        long long target_stride = 0;
+        double * sums = nullptr;        // == target unless a pedestal is applied on the way into it
+        long long sums_stride = 0;
+        hipStream_t ped_stream = nullptr;       // the pedestal pre-pass
+        hipStream_t finish_stream = nullptr;    // where the pieces are finished
+    };
+    // How the pieces of a pass are finished (compute_stages.inc, describe_finish).  Without a
+    // pedestal that is the copy of a streamed call's columns, queued behind each piece's launch.
+    // With one it is the last part of the call -- the kernels that apply the pedestal to the
+    // caller's block, piece by piece, and those copies -- which LBL_DEFER_FINISH keeps back until
+    // lbl_finish_deferred: everything before works in the lane's own buffers, so a long call can be
     // queued FIRST and still be the LAST to add into a block other calls write meanwhile.
     struct Finish
     {
         bool pending = false;
-        int pieces = 1, count = 0, n_cells = 0, flags = 0;
+        Pass pass;
+        GridSpec g;
+        int pieces = 1, flags = 0;
         long long point_begin[9] = {};      // piece p covers points [point_begin[p], point_begin[p+1])
-        int n_per_v = 0, cut_off = 0;
-        const double * sums = nullptr;
-        long long sums_stride = 0;
-        double * target = nullptr;
-        long long target_stride = 0;
         bool streamed = false, order_writers = false, add_into = false;
         char * host = nullptr;
-        long long host_pitch = 0, columns = 0, base = 0;
+        long long host_pitch = 0, columns = 0;
         double * k = nullptr;          // the block, for its write record: set by the call's last pass only
         const double * block = nullptr; // the block, for ordering behind its earlier writers: every pass
         long long out_bytes = 0;
-        hipStream_t finish_stream = nullptr;
     } finish;
     // The last few writes of device output queued on this lane: where, and an event behind the
     // kernel that wrote.  A call on another lane that touches the same memory waits for it.
@@ -648,10 +673,30 @@ struct lbl_engine
             const char * q = reinterpret_cast<const char *>(p);
             return p != nullptr && n > 0 && q < e && b < q + n;
         };
-        const long long rows = ((long long)(f.count - 1)*f.target_stride + f.point_begin[f.pieces])*8;
-        return meets(f.k, f.out_bytes) || meets(f.target, rows) ||
-               (f.streamed && meets(f.host + f.base*f.host_pitch,
-                                    (long long)(f.count - 1)*f.host_pitch + f.columns*8));
+        const Lane::Pass & p = f.pass;
+        const long long rows = ((long long)(p.count - 1)*p.target_stride + f.point_begin[f.pieces])*8;
+        return meets(f.k, f.out_bytes) || meets(p.target, rows) ||
+               (f.streamed && meets(f.host + p.base*f.host_pitch,
+                                    (long long)(p.count - 1)*f.host_pitch + f.columns*8));
+    }
+
+    // A streamed call: the columns of a finished piece to page-locked host memory, behind what
+    // `after` holds now, beside the kernels of the next piece.  (The runtime's device-to-host copy
+    // is a kernel of its own here, not a DMA engine; queued beside an accumulate grid it costs the
+    // grid nothing, and a hand-written copy kernel of 8..1024 workgroups did worse:
+    // profiles/r03_perf_deliver.txt.)
+    void copy_piece_home(Lane & lane, int piece, hipStream_t after)
+    {
+        const Lane::Finish & f = lane.finish;
+        const Lane::Pass & p = f.pass;
+        const long long q0 = f.point_begin[piece], q1 = f.point_begin[piece + 1];
+        if (!f.streamed || q1 <= q0 || q0 >= f.columns) return;
+        const long long c1 = std::min<long long>(q1, f.columns);
+        HIP_TRY(hipEventRecord(lane.piece_done[piece], after));
+        HIP_TRY(hipStreamWaitEvent(copy_stream, lane.piece_done[piece], 0));
+        HIP_TRY(hipMemcpy2DAsync(f.host + p.base*f.host_pitch + q0*8, (size_t)f.host_pitch,
+                                 p.target + q0, (size_t)p.target_stride*8, (size_t)(c1 - q0)*8,
+                                 (size_t)p.count, hipMemcpyDeviceToHost, copy_stream));
     }
 
     // Queues what Lane::Finish describes: apply kernels (+ copies) of every piece, then ties the
@@ -659,6 +704,8 @@ struct lbl_engine
     void run_finish(Lane & lane)
     {
         Lane::Finish & f = lane.finish;
+        const Lane::Pass & p = f.pass;
+        const GridSpec & g = f.g;
         hipStream_t stream = lane.main;
         // (what is queued here is queued NOW: a call that joined this lane since the kept-back
         // call was made has to join it again)
@@ -667,46 +714,33 @@ struct lbl_engine
         {
             // (every pass of a call in several passes: the FIRST pass's kernels are the ones that
             // must not add into rows another lane's earlier call is still adding into)
-            order_after_writers(f.finish_stream, f.block, f.out_bytes, &lane);
+            order_after_writers(p.finish_stream, f.block, f.out_bytes, &lane);
         }
         for (int piece = 0; piece < f.pieces; ++piece)
         {
             const long long q0 = f.point_begin[piece], q1 = f.point_begin[piece + 1];
             if (q1 <= q0) continue;
-            if (f.finish_stream != stream)
+            if (p.finish_stream != stream)
             {
                 // (recorded behind this piece's accumulate launch)
-                HIP_TRY(hipStreamWaitEvent(f.finish_stream, lane.piece_summed[piece], 0));
+                HIP_TRY(hipStreamWaitEvent(p.finish_stream, lane.piece_summed[piece], 0));
             }
             constexpr int per_block = 256*kApplyPoints;
-            dim3 grid((unsigned)((q1 - q0 + per_block - 1)/per_block), (unsigned)f.count);
+            dim3 grid((unsigned)((q1 - q0 + per_block - 1)/per_block), (unsigned)p.count);
             hipLaunchKernelGGL(pedestal_apply_kernel, grid, dim3(256),
-                               pedestal_apply_lds_bytes(f.cut_off, f.n_per_v), f.finish_stream,
-                               f.sums, f.sums_stride, f.target, f.target_stride,
+                               pedestal_apply_lds_bytes(g.cut_off, g.n_per_v), p.finish_stream,
+                               p.sums, p.sums_stride, p.target, p.target_stride,
                                lane.pedestal.bin_sum.data, lane.levels.data, (int)q0, (int)q1,
-                               f.n_per_v, f.n_cells + 2*f.cut_off + 3, f.cut_off,
-                               pedestal_apply_span(f.n_per_v),
+                               g.n_per_v, g.vn - g.v0 + 2*g.cut_off + 3, g.cut_off,
+                               pedestal_apply_span(g.n_per_v),
                                (f.flags & LBL_SCALE_DENSITY) ? 1 : 0, f.add_into ? 1 : 0);
             HIP_TRY(hipGetLastError());
-            if (f.streamed && q0 < f.columns)
-            {
-                // This piece's columns go home beside the kernels of the next.  (The runtime's
-                // device-to-host copy is a kernel of its own here, not a DMA engine; queued
-                // beside an accumulate grid it costs the grid nothing, and a hand-written copy
-                // kernel of 8..1024 workgroups did worse: profiles/r03_perf_deliver.txt.)
-                const long long c1 = std::min<long long>(q1, f.columns);
-                HIP_TRY(hipEventRecord(lane.piece_done[piece], f.finish_stream));
-                HIP_TRY(hipStreamWaitEvent(copy_stream, lane.piece_done[piece], 0));
-                HIP_TRY(hipMemcpy2DAsync(f.host + f.base*f.host_pitch + q0*8, (size_t)f.host_pitch,
-                                         f.target + q0, (size_t)f.target_stride*8,
-                                         (size_t)(c1 - q0)*8, (size_t)f.count,
-                                         hipMemcpyDeviceToHost, copy_stream));
-            }
+            copy_piece_home(lane, piece, p.finish_stream);
         }
-        if (f.finish_stream != stream)
+        if (p.finish_stream != stream)
         {
             // Later users of the lane's main stream (and of the block) come after the last apply.
-            HIP_TRY(hipEventRecord(lane.pedestal_done, f.finish_stream));
+            HIP_TRY(hipEventRecord(lane.pedestal_done, p.finish_stream));
             HIP_TRY(hipStreamWaitEvent(stream, lane.pedestal_done, 0));
         }
         if (f.k != nullptr)

@@ -23,8 +23,9 @@ int fail(lbl_engine * engine, int code, const std::string & message)
 
 typedef std::lock_guard<std::recursive_mutex> EngineLock;
 
-// The frame of an entry point: a null engine, the engine's lock, and HIP failures and failed host
-// allocations as LBL_ERROR.  body() returns the entry's status.
+// The frame of an entry point: a null engine, the engine's lock, and HIP failures, failed host
+// allocations and whatever else the standard library throws as LBL_ERROR: nothing leaves through
+// the C ABI.  body() returns the entry's status.
 template <typename Body>
 int entry(lbl_engine * engine, Body body)
 {
@@ -41,6 +42,10 @@ int entry(lbl_engine * engine, Body body)
     catch (const std::bad_alloc &)
     {
         return fail(engine, LBL_ERROR, "host allocation failed.");
+    }
+    catch (const std::exception & e)
+    {
+        return fail(engine, LBL_ERROR, e.what());
     }
 }
 

@@ -521,16 +521,11 @@ extern "C" int lbl_molecule_load_sqlite(lbl_engine * engine, const char * path, 
     {
         return LBL_BAD_ARGUMENT;
     }
-    try
-    {
+    return entry(engine, [&] {
         lbl_table table;
         std::string why;
         const int status = read_table(path, name, table, why);
         if (status != LBL_OK) return fail(engine, status, why);
         return upload_table(engine, table, molecule);
-    }
-    catch (const std::exception & e)
-    {
-        return fail(engine, LBL_ERROR, e.what());
-    }
+    });
 }

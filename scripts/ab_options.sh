@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of bench.py flags (e.g. engine options) on several workloads, interleaved.
-# Usage on the GPU box: scripts/ab_options.sh "--engine-option item_floor=512" "--engine-option item_floor=6000"
+# Usage on the GPU box: scripts/ab_options.sh "--engine-option lanes=2" "--engine-option lanes=4"
 # WORKLOADS (newline-separated bench arguments) overrides the default list.
 DEFAULT_WORKLOADS=$'\n--pedestal\n--banded\n--config 1\n--levels-per-gpu 8 --profile standard'
 IFS=$'\n' read -r -d '' -a workloads <<< "${WORKLOADS-$DEFAULT_WORKLOADS}"
