@@ -295,6 +295,63 @@ int lbl_path_flux(lbl_engine *engine, double *beta, int64_t row_stride, int64_t 
                   int32_t n_bands, const int64_t *band_start, double *carry, double *reflection,
                   double *level_flux, double *flux, double *surface_flux, int32_t flags);
 
+/* Analytic radiance Jacobians (Spectroscopy.compute_jacobian): the derivatives of
+ * lbl_path_radiance's radiance with respect to the state of every level and of the boundary, for
+ * a run of whole paths.  beta (read only), row_stride, columns, grid, n_paths, levels_per_path,
+ * level_begin, level_count, path_length, temperature, boundary_temperature, boundary_emissivity,
+ * band_start / n_bands, LBL_PATH_FROM_LAST and LBL_ASYNC as for lbl_path_radiance.  The run must
+ * consist of whole paths (level_begin and level_count multiples of levels_per_path): there is no
+ * carry, and LBL_PATH_CONTINUE and LBL_PATH_CUMULATIVE must not be set.
+ * For one path and one grid point nu, with the levels numbered k = 0 .. L-1 in sweep order (k = 0
+ * is the path's first level, or with LBL_PATH_FROM_LAST its last), each product and sum rounded
+ * as written:
+ *   x_k = s_k*beta_k, t_k = exp(-x_k), a_k = -expm1(-x_k), B_k = B(nu, T_k);
+ *   forward, exactly lbl_path_radiance's: I_-1 = eps*B(nu, T_b) (0 without a boundary),
+ *     I_k = I_{k-1}*t_k + B_k*a_k; the radiance is I_{L-1};
+ *   trailing optical depth, summed from the observer backwards: tau'_{L-1} = 0, then
+ *     tau'_{k-1} = tau'_k + s_k*beta_k for k = L-1 .. 0; trail_k = exp(-tau'_k),
+ *     trail_b = exp(-tau'_{-1});
+ *   dB(nu, T): with u = (C2*nu)/T and B = B(nu, T), dB = (B*(u/T))*(1. + B/(((C1*nu)*nu)*nu)),
+ *     0 for nu <= 0 (B/(C1 nu^3) is 1/expm1(u): dB/dT without a second expm1).
+ * Outputs (device), each chosen by its flag:
+ *   LBL_PATH_RADIANCE              radiance                      I_{L-1}, bit for bit
+ *                                                                lbl_path_radiance's
+ *   LBL_PATH_JACOBIAN_DEPTH        optical_depth_jacobian        dI/dx_k = (B_k - I_k)*trail_k
+ *   LBL_PATH_JACOBIAN_LOG_DEPTH    log_optical_depth_jacobian    dI/dln x_k
+ *                                                                = x_k*((B_k - I_k)*trail_k)
+ *   LBL_PATH_JACOBIAN_TEMPERATURE  temperature_jacobian          dI/dT_k at fixed beta
+ *                                                                = (a_k*dB(nu, T_k))*trail_k
+ *   LBL_PATH_JACOBIAN_BOUNDARY_T   boundary_temperature_jacobian (eps*dB(nu, T_b))*trail_b
+ *   LBL_PATH_JACOBIAN_BOUNDARY_E   boundary_emissivity_jacobian  B(nu, T_b)*trail_b
+ * The three per-level ones fill row r of [level_count][row_stride] (flat level level_begin + r),
+ * the radiance and the boundary Jacobians row p of [n_paths][row_stride], for the paths of the
+ * run.  The dependence of beta on the state is the caller's to chain: s_k*dbeta_k/dq times
+ * optical_depth_jacobian.
+ *   work (device): n_bands == 0: [level_count][row_stride], the trail_k between the kernel's two
+ *     loops; optical_depth_jacobian or log_optical_depth_jacobian (one of them) may be `work`
+ *     itself.  n_bands > 0: [max(P, 1)*level_count + Q*paths][row_stride] with P the per-level
+ *     and Q the per-path quantities requested and `paths` those of the run: the fine rows of
+ *     every quantity, whose band means (as lbl_path_compute forms them, NaN for an empty band)
+ *     go to row r of [level_count][n_bands] or row p of [n_paths][n_bands] of the outputs.
+ * LBL_BAD_ARGUMENT (message in lbl_last_error) as for lbl_path_radiance, and for a run that does
+ * not consist of whole paths, LBL_PATH_CONTINUE or LBL_PATH_CUMULATIVE, a boundary Jacobian
+ * requested for a path of the run whose boundary temperature is 0, a requested output that is
+ * NULL, an output other than those two that is `work`, or no quantity requested; nothing is
+ * launched and the engine stays usable. */
+#define LBL_PATH_JACOBIAN_DEPTH        0x10000
+#define LBL_PATH_JACOBIAN_LOG_DEPTH    0x20000
+#define LBL_PATH_JACOBIAN_TEMPERATURE  0x40000
+#define LBL_PATH_JACOBIAN_BOUNDARY_T   0x80000
+#define LBL_PATH_JACOBIAN_BOUNDARY_E  0x100000
+int lbl_path_jacobian(lbl_engine *engine, const double *beta, int64_t row_stride, int64_t columns,
+                      int32_t grid, int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                      int32_t level_count, const double *path_length, const double *temperature,
+                      const double *boundary_temperature, const double *boundary_emissivity,
+                      int32_t n_bands, const int64_t *band_start, double *work, double *radiance,
+                      double *optical_depth_jacobian, double *log_optical_depth_jacobian,
+                      double *temperature_jacobian, double *boundary_temperature_jacobian,
+                      double *boundary_emissivity_jacobian, int32_t flags);
+
 /* Instrument line shapes (Spectroscopy.compute_path / compute_radiance with `instrument`): N
  * channels, each a weighted mean of a row of fine-grid values under its line shape.
  * lbl_instrument_create binds an instrument to a grid (a handle of lbl_grid_load, ascending):

@@ -31,6 +31,7 @@
 #include "farfield.h"
 #include "flux.h"
 #include "instrument.h"
+#include "jacobian.h"
 #include "line_prep.h"
 #include "path.h"
 #include "pedestal.h"
@@ -512,6 +513,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "continuum_entry.inc"
 #include "path_entry.inc"
 #include "radiance_entry.inc"
+#include "jacobian_entry.inc"
 #include "flux_entry.inc"
 #include "instrument_entry.inc"
 #include "xsec_entry.inc"

@@ -1,7 +1,7 @@
-// What the path entries share (lbl_path_compute here, lbl_path_radiance, lbl_path_flux), and
-// lbl_path_compute: optical depth and transmittance along paths through a block of absorption
-// coefficients in HBM (kernels: path.h).  Included by engine.hip after slot_entry.inc (grid
-// handles).
+// What the path entries share (lbl_path_compute here, lbl_path_radiance, lbl_path_jacobian,
+// lbl_path_flux), and lbl_path_compute: optical depth and transmittance along paths through a
+// block of absorption coefficients in HBM (kernels: path.h).  Included by engine.hip after
+// slot_entry.inc (grid handles).
 namespace {
 
 // Where a run of flat levels [begin, end) leaves the paths it touches: the first path, how many,

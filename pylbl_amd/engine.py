@@ -30,6 +30,19 @@ PATH_OPTICAL_DEPTH, PATH_TRANSMITTANCE, PATH_CUMULATIVE, PATH_FROM_LAST, PATH_CO
 PATH_RADIANCE, PATH_BRIGHTNESS = 0x2000, 0x4000
 # lbl_path_flux: the up sweep.
 PATH_FLUX_UP = 0x8000
+# lbl_path_jacobian: its five Jacobians, beside PATH_RADIANCE.
+PATH_JACOBIAN_DEPTH, PATH_JACOBIAN_LOG_DEPTH, PATH_JACOBIAN_TEMPERATURE, \
+    PATH_JACOBIAN_BOUNDARY_T, PATH_JACOBIAN_BOUNDARY_E = \
+    0x10000, 0x20000, 0x40000, 0x80000, 0x100000
+# Engine.path_jacobian's outputs and their flags, in the order of lbl_path_jacobian's arguments.
+PATH_JACOBIAN_OUTPUTS = (
+    ("radiance", PATH_RADIANCE), ("optical_depth_jacobian", PATH_JACOBIAN_DEPTH),
+    ("log_optical_depth_jacobian", PATH_JACOBIAN_LOG_DEPTH),
+    ("temperature_jacobian", PATH_JACOBIAN_TEMPERATURE),
+    ("boundary_temperature_jacobian", PATH_JACOBIAN_BOUNDARY_T),
+    ("boundary_emissivity_jacobian", PATH_JACOBIAN_BOUNDARY_E))
+PATH_JACOBIAN_PER_LEVEL = ("optical_depth_jacobian", "log_optical_depth_jacobian",
+                           "temperature_jacobian")
 
 EXPORTED_SYMBOLS = (
     "lbl_engine_create", "lbl_engine_destroy", "lbl_last_error", "lbl_molecule_load",
@@ -46,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
     "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
+    "lbl_path_jacobian",
     "lbl_instrument_create", "lbl_instrument_free", "lbl_instrument_apply",
 )
 
@@ -182,6 +196,10 @@ def library():
                                       c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_int32]
+    lib.lbl_path_jacobian.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                      c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int32]
     lib.lbl_path_flux.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
@@ -749,6 +767,64 @@ class Engine(object):
             n_bands, starts.ctypes.data if starts is not None else None, carry.pointer,
             radiance.pointer if radiance is not None else None,
             brightness_temperature.pointer if brightness_temperature is not None else None, flags))
+
+    def path_jacobian(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
+                      temperature, work, boundary_temperature=None, boundary_emissivity=None,
+                      radiance=None, optical_depth_jacobian=None,
+                      log_optical_depth_jacobian=None, temperature_jacobian=None,
+                      boundary_temperature_jacobian=None, boundary_emissivity_jacobian=None,
+                      band_start=None, from_last=False, asynchronous=False):
+        """Analytic radiance Jacobians along whole paths through the DeviceSpectra `beta` --
+        lbl_path_jacobian.  Rows (whole paths), lengths, temperature, grid, the boundary values,
+        band_start, from_last and asynchronous as for path_radiance.  Outputs (DeviceSpectra,
+        None: not wanted): the three per-level Jacobians [rows, row length], radiance and the
+        two boundary Jacobians [n_paths, row length]; with bands [rows or n_paths, bands].
+        work: DeviceSpectra [>= rows, row length] without bands (optical_depth_jacobian or
+        log_optical_depth_jacobian may be it), with bands [>= max(P, 1)*rows + Q*paths of the
+        run, row length] for P per-level and Q per-path outputs."""
+        lengths = _f64(np.atleast_1d(lengths))
+        temperature = _f64(np.atleast_1d(temperature))
+        rows, stride = int(beta.shape[0]), int(beta.shape[1])
+        if lengths.shape != (rows,) or temperature.shape != (rows,):
+            raise ValueError("one path length and one temperature per row of beta.")
+        boundary = []
+        for values in (boundary_temperature, boundary_emissivity):
+            if values is not None:
+                values = _f64(np.atleast_1d(values))
+                if values.shape != (int(n_paths),):
+                    raise ValueError("one boundary value per path.")
+            boundary.append(values)
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
+                                           from_last, asynchronous)
+        given = dict(radiance=radiance, optical_depth_jacobian=optical_depth_jacobian,
+                     log_optical_depth_jacobian=log_optical_depth_jacobian,
+                     temperature_jacobian=temperature_jacobian,
+                     boundary_temperature_jacobian=boundary_temperature_jacobian,
+                     boundary_emissivity_jacobian=boundary_emissivity_jacobian)
+        width = n_bands if n_bands > 0 else stride
+        work_rows, run_paths = rows, -(-rows//int(levels_per_path))
+        if n_bands > 0:
+            per_level = sum(given[q] is not None for q in PATH_JACOBIAN_PER_LEVEL)
+            per_path = sum(out is not None for out in given.values()) - per_level
+            work_rows = max(per_level, 1)*rows + per_path*run_paths
+        if work.shape[1] != stride or work.shape[0] < work_rows:
+            raise ValueError(f"work has shape {work.shape}, need {work_rows} x {stride}.")
+        pointers = []
+        for name, flag in PATH_JACOBIAN_OUTPUTS:
+            out = given[name]
+            pointers.append(None if out is None else out.pointer)
+            if out is None:
+                continue
+            flags |= flag
+            need = rows if name in PATH_JACOBIAN_PER_LEVEL else int(n_paths)
+            if out.shape[1] != width or out.shape[0] < need:
+                raise ValueError(f"{name} has shape {out.shape}, need {need} x {width}.")
+        self._check(self.lib.lbl_path_jacobian(
+            self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
+            int(levels_per_path), int(level_begin), rows, lengths.ctypes.data,
+            temperature.ctypes.data, *(b.ctypes.data if b is not None else None for b in boundary),
+            n_bands, starts.ctypes.data if starts is not None else None, work.pointer, *pointers,
+            flags))
 
     def instrument_create(self, grid, shape, centers, parameter=None, half_width=None,
                           offsets=None, response=None):

@@ -87,12 +87,24 @@ PLANCK_C2 = 1.4387768775039338         # h c / k 1e2 [cm K]
 R_DRY = 8.314462618/0.0289644          # [J kg-1 K-1]
 CP_DRY = 3.5*R_DRY                     # [J kg-1 K-1]
 
+# compute_jacobian: the radiance and its derivatives, per level and per path.
+JACOBIAN_LEVEL_QUANTITIES = ("optical_depth_jacobian", "log_optical_depth_jacobian",
+                             "temperature_jacobian")
+JACOBIAN_PATH_QUANTITIES = ("radiance", "boundary_temperature_jacobian",
+                            "boundary_emissivity_jacobian")
+JACOBIAN_QUANTITIES = ("radiance",) + JACOBIAN_LEVEL_QUANTITIES + JACOBIAN_PATH_QUANTITIES[1:]
+
 FLUX_QUANTITIES = ("upward_flux", "downward_flux", "heating_rate")
 FLUX_SURFACES = ("first", "last")
 MAX_FLUX_ANGLES = 8
 
 _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
-               "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K"}
+               "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K",
+               "optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
+               "log_optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
+               "temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
+               "boundary_temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
+               "boundary_emissivity_jacobian": "W m-2 sr-1 (cm-1)-1"}
 # compute_flux: on the grid, per band.
 _FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
                "downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
@@ -176,6 +188,25 @@ def _sweep_pass(quantities, cumulative, from_last):
     """The one pass of compute_path and compute_radiance."""
     return _Pass(from_last, tuple(quantities) if cumulative else (),
                  () if cumulative else tuple(quantities))
+
+
+def _cut_runs(levels, per_path, level_bytes, limit, whole_paths=False):
+    """(run, [(a, b)]): the runs of consecutive flat levels of _sweep_runs, `run` levels each but
+    the last, for blocks of level_bytes per level within `limit` bytes and _MAX_RUN_LEVELS
+    levels.  whole_paths: every run is a whole number of paths of per_path levels -- the most
+    that fit; ValueError where one path does not."""
+    if whole_paths:
+        path_bytes = per_path*level_bytes
+        paths = min(limit//path_bytes, _MAX_RUN_LEVELS//per_path)
+        if paths < 1:
+            raise ValueError(f"device_output_limit = {limit} bytes does not hold one path: its "
+                             f"blocks need {path_bytes} bytes ({per_path} levels, and at most "
+                             f"{_MAX_RUN_LEVELS} levels in a run).")
+        run = min(paths*per_path, levels)
+    else:
+        run = levels if levels*level_bytes <= limit else max(1, limit//level_bytes)
+        run = min(run, _MAX_RUN_LEVELS)
+    return run, [(a, min(a + run, levels)) for a in range(0, levels, run)]
 
 
 def _selection(quantities, names):
@@ -616,6 +647,105 @@ class Spectroscopy(object):
                     values["radiance"], request.instrument.centers)
         return self._create_path_dataset(values, request)
 
+    def compute_jacobian(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
+                         direction="toward_last",
+                         quantities=("radiance", "optical_depth_jacobian",
+                                     "temperature_jacobian"),
+                         band_edges=None, instrument=None, remove_pedestal=None,
+                         range_policy="reference"):
+        """Analytic Jacobians (weighting functions) of compute_radiance's radiance: its
+        derivatives with respect to the state of every level and of the boundary, formed on the
+        GPU in one more sweep over the "total" absorption block of a radiance call.
+
+        Paths, beta, s, T_l, nu, B and the arguments as in compute_radiance.  For one path and
+        one grid point, with the levels numbered k = 0 .. L-1 in sweep order (k = 0 is level 0
+        for "toward_last" and level L-1 for "toward_first"), each product and sum rounded as
+        written:
+            x_k = s_k*beta_k, t_k = exp(-x_k), a_k = -expm1(-x_k), B_k = B(nu, T_k);
+            forward, exactly compute_radiance's: I_-1 = eps*B(nu, T_b) (0 without a boundary),
+            I_k = I_{k-1}*t_k + B_k*a_k; "radiance" is I_{L-1};
+            trailing optical depth, summed from the observer backwards: tau'_{L-1} = 0, then
+            tau'_{k-1} = tau'_k + s_k*beta_k for k = L-1 .. 0; trail_k = exp(-tau'_k),
+            trail_b = exp(-tau'_{-1});
+            dB(nu, T): with u = (C2*nu)/T and B = B(nu, T),
+            dB = (B*(u/T))*(1. + B/(((C1*nu)*nu)*nu)), 0 for nu <= 0.
+        Per level (the atmosphere's dims):
+            "optical_depth_jacobian"      dI/dx_k = (B_k - I_k)*trail_k
+                                          [radiance per unit optical depth];
+            "log_optical_depth_jacobian"  dI/dln x_k = x_k*((B_k - I_k)*trail_k) [radiance]: the
+                                          response to a fractional change of the layer's absorber
+                                          amount;
+            "temperature_jacobian"        dI/dT_k at fixed beta = (a_k*dB(nu, T_k))*trail_k
+                                          [radiance K-1].
+        Per path (without the last dim; only with boundary_temperature):
+            "boundary_temperature_jacobian"  (eps*dB(nu, T_b))*trail_b [radiance K-1];
+            "boundary_emissivity_jacobian"   B(nu, T_b)*trail_b [radiance].
+        "temperature_jacobian" is the source-function part alone: how beta depends on T and on
+        the mixing ratios is the caller's to chain, as s_k*dbeta_k/dq times
+        "optical_depth_jacobian".  Jacobians of fluxes and of brightness temperature are not
+        formed.
+
+        Args:
+            path_length, boundary_temperature, boundary_emissivity, direction, remove_pedestal,
+            range_policy: as in compute_radiance.
+            quantities: any of "radiance" and the five names above.
+            band_edges: as in compute_path: the arithmetic mean of every quantity over each band
+                        (the bands' weights do not depend on the state, so the mean of the
+                        Jacobian is the Jacobian of the band radiance).
+            instrument: None, or an Instrument: the same under its line shapes, dR_c/dq =
+                        sum_j w_j dv_j/dq / sum_j w_j.  Not with band_edges.
+
+        Returns:
+            Like compute_radiance: an xarray Dataset when xarray is installed, else a dict.
+        Raises ValueError where the blocks of one path (beta, the work block and one block per
+        per-level quantity) exceed device_output_limit: a run holds whole paths.
+        """
+        request = self._radiance_request(path_length, boundary_temperature, boundary_emissivity,
+                                         direction, quantities, band_edges, False, range_policy,
+                                         instrument, names=JACOBIAN_QUANTITIES,
+                                         caller="compute_jacobian")
+        if request.boundary_temperature is None and any(
+                q.startswith("boundary_") for q in request.quantities):
+            raise ValueError("the boundary Jacobians need a boundary_temperature.")
+        if remove_pedestal is None:
+            remove_pedestal = self.continua_backend == "mt_ckd"
+        per_path, paths = _path_layout(request.shape)
+        temperature = np.ascontiguousarray(self.atmosphere.temperature.ravel(), dtype=np.float64)
+        columns = self.grid.size
+        per_level = [q for q in request.quantities if q in JACOBIAN_LEVEL_QUANTITIES]
+        step = _Pass(request.from_last, tuple(per_level),
+                     tuple(q for q in request.quantities if q in JACOBIAN_PATH_QUANTITIES))
+        # With bands the entry keeps every quantity's fine rows in the work block.
+        banded = request.starts is not None
+        work_blocks = max(len(per_level), 1) if banded else 1
+
+        def sweeper(engine, take, run):
+            from .mt_ckd import resident_grid
+            grid = resident_grid(engine, self.grid)
+            run_paths = run//per_path
+            work = take(work_blocks*run + (len(step.path_quantities)*run_paths if banded else 0))
+
+            def sweep(index, beta, a, b, outputs):
+                engine.path_jacobian(
+                    beta, columns, grid, paths, per_path, a, request.lengths[a:b],
+                    temperature[a:b], work,
+                    boundary_temperature=request.boundary_temperature,
+                    boundary_emissivity=request.boundary_emissivity, band_start=request.starts,
+                    from_last=request.from_last, asynchronous=True,
+                    **{q: outputs[q] for q in request.quantities})
+            return sweep
+        # Per level in HBM: beta, the work block(s) and, on the grid, a block per per-level
+        # quantity (which _sweep_runs counts itself with an instrument).
+        level_blocks = 1 + work_blocks
+        if not banded and request.instrument is None:
+            level_blocks += len(per_level)
+        reductions = None if request.instrument is None else \
+            [(q, q, False) for q in request.quantities]
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                  level_blocks=level_blocks, reductions=reductions,
+                                  whole_paths=True)
+        return self._create_path_dataset(values, request)
+
     def compute_flux(self, layer_thickness, surface_temperature, surface_emissivity=1.,
                      surface="first", angles=3, quantities=("upward_flux", "downward_flux"),
                      band_edges=None, remove_pedestal=None, range_policy="reference"):
@@ -837,9 +967,10 @@ class Spectroscopy(object):
 
     def _radiance_request(self, path_length, boundary_temperature, boundary_emissivity,
                           direction, quantities, band_edges, cumulative, range_policy,
-                          instrument=None):
-        """Checks every argument of compute_radiance (before anything touches the GPU)."""
-        lengths, shape = self._path_geometry(path_length, "compute_radiance")
+                          instrument=None, names=RADIANCE_QUANTITIES, caller="compute_radiance"):
+        """Checks every argument of compute_radiance (before anything touches the GPU);
+        compute_jacobian's too, with its `names`."""
+        lengths, shape = self._path_geometry(path_length, caller)
         self._check_level_temperatures()
         if boundary_temperature is None:
             boundary = None
@@ -852,7 +983,7 @@ class Spectroscopy(object):
             raise ValueError("boundary emissivities must lie in [0, 1].")
         if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
             raise ValueError(f"direction must be one of {RADIANCE_DIRECTIONS}, not {direction!r}.")
-        quantities = _selection(quantities, RADIANCE_QUANTITIES)
+        quantities = _selection(quantities, names)
         if not isinstance(cumulative, (bool, np.bool_)):
             raise ValueError(f"cumulative must be True or False, not {cumulative!r}.")
         _check_range_policy(range_policy)
@@ -866,7 +997,7 @@ class Spectroscopy(object):
                                 boundary_temperature=boundary, boundary_emissivity=emissivity)
 
     def _sweep_runs(self, request, passes, remove_pedestal, range_policy, sweeper,
-                    level_blocks=1, reductions=None):
+                    level_blocks=1, reductions=None, whole_paths=False):
         """{quantity: array [levels or paths, columns or bands]}: the "total" block of a run of
         levels at a time, queued like _compute_levels queues it, then the path kernels on it --
         for each of `passes` (_Pass: its order, and the quantities it returns per level and per
@@ -882,7 +1013,9 @@ class Spectroscopy(object):
         sweeps write their quantities on the grid into blocks of their own, and
         lbl_instrument_apply reduces those rows into [rows, channels] blocks (of exp(-value)
         with `transmittance`), which alone go to the host as `result`.  Each per-level grid
-        block counts against device_output_limit."""
+        block counts against device_output_limit.
+        whole_paths: every run is a whole number of paths (_cut_runs), for sweeps that carry
+        nothing from run to run."""
         temperature = self.atmosphere.temperature.ravel()
         pressure = self.atmosphere.pressure.ravel()
         mole_fractions = {name: x.ravel() for name, x in self.atmosphere.gases.items()}
@@ -897,15 +1030,12 @@ class Spectroscopy(object):
         if instrument is not None:
             level_blocks += len(level_quantities)
         # Runs of consecutive levels when the blocks would not fit: the sweep carries over in HBM.
-        level_bytes = level_blocks*n*8
-        run = levels if levels*level_bytes <= self.device_output_limit else \
-            max(1, self.device_output_limit//level_bytes)
-        run = min(run, _MAX_RUN_LEVELS)
+        run, runs = _cut_runs(levels, per_path, level_blocks*n*8, self.device_output_limit,
+                              whole_paths)
         starts = request.starts
         width = columns if starts is None else starts.size - 1
         if instrument is not None:
             width = len(instrument)
-        runs = [(a, min(a + run, levels)) for a in range(0, levels, run)]
 
         engine, present, heavy = self._present_gases(temperature, pressure, mole_fractions)
         if engine is None:
@@ -999,15 +1129,17 @@ class Spectroscopy(object):
         return results
 
     def _create_path_dataset(self, values, request):
-        """compute_path's and compute_radiance's result from {quantity: [paths or levels,
-        columns or bands]}, in the conventions of _create_output_dataset."""
-        dims = list(self.atmosphere.dims)
-        shape = list(request.shape)
-        if not request.cumulative:
-            dims, shape = dims[:-1], shape[:-1]
-        dims.append(_spectral_axis(request))
-        variables = {q: (dims, np.asarray(values[q]).reshape(shape + [-1]), _PATH_UNITS[q])
-                     for q in request.quantities}
+        """compute_path's, compute_radiance's and compute_jacobian's result from {quantity:
+        [paths or levels, columns or bands]}, in the conventions of _create_output_dataset:
+        per level when cumulative and for the per-level Jacobians."""
+        axis = _spectral_axis(request)
+        variables = {}
+        for q in request.quantities:
+            dims, shape = list(self.atmosphere.dims), list(request.shape)
+            if not (request.cumulative or q in JACOBIAN_LEVEL_QUANTITIES):
+                dims, shape = dims[:-1], shape[:-1]
+            variables[q] = (dims + [axis], np.asarray(values[q]).reshape(shape + [-1]),
+                            _PATH_UNITS[q])
         return self._path_variables(variables, request)
 
     def _create_flux_dataset(self, values, request):
