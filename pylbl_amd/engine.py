@@ -240,6 +240,37 @@ def _path_run(band_start, level_begin, rows, levels_per_path, from_last, asynchr
     return starts, n_bands, flags
 
 
+def _per_row(beta, message, *values):
+    """(rows, row length of the DeviceSpectra `beta`, float64 arrays of one value per row);
+    ValueError(message) where one of `values` is not that."""
+    rows, stride = int(beta.shape[0]), int(beta.shape[1])
+    arrays = [_f64(np.atleast_1d(x)) for x in values]
+    if any(x.shape != (rows,) for x in arrays):
+        raise ValueError(message)
+    return (rows, stride, *arrays)
+
+
+def _per_path(n_paths, message, *values):
+    """Each of `values` as a float64 array of one value per path, None as it is."""
+    arrays = [None if x is None else _f64(np.atleast_1d(x)) for x in values]
+    if any(x is not None and x.shape != (int(n_paths),) for x in arrays):
+        raise ValueError(message)
+    return arrays
+
+
+def _check_outputs(outputs, rows, width):
+    for out in outputs:
+        if out is not None and (out.shape[1] != width or out.shape[0] < rows):
+            raise ValueError(f"an output has shape {out.shape}, need rows x {width}.")
+
+
+def _address(x):
+    """What a C entry takes for a DeviceSpectra or an array: None for None."""
+    if x is None:
+        return None
+    return x.pointer if hasattr(x, "pointer") else x.ctypes.data
+
+
 # Status codes of lbl_table_read (include/lbl_amd.h).
 TABLE_OPEN_FAILED, TABLE_NO_ALIAS, TABLE_NO_TIPS, TABLE_NOT_RECTANGULAR, TABLE_NO_ISOTOPOLOGUES, \
     TABLE_NO_TRANSITIONS = 10, 11, 12, 13, 14, 15
@@ -703,10 +734,7 @@ class Engine(object):
         optical_depth / transmittance: DeviceSpectra outputs (None: not wanted) --
         [n_paths or rows, row length] without bands, [n_paths or rows, bands] with them.
         band_start: int64 column starts of the bands (n_bands + 1 values) or None."""
-        lengths = _f64(np.atleast_1d(lengths))
-        rows, stride = int(beta.shape[0]), int(beta.shape[1])
-        if lengths.shape != (rows,):
-            raise ValueError("one path length per row of beta.")
+        rows, stride, lengths = _per_row(beta, "one path length per row of beta.", lengths)
         if tuple(carry.shape) != (int(n_paths), stride):
             raise ValueError("carry must be [n_paths, row length of beta].")
         starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
@@ -714,17 +742,12 @@ class Engine(object):
         flags |= (PATH_OPTICAL_DEPTH if optical_depth is not None else 0) | \
                  (PATH_TRANSMITTANCE if transmittance is not None else 0) | \
                  (PATH_CUMULATIVE if cumulative else 0)
-        width = n_bands if n_bands > 0 else stride
-        for out in (optical_depth, transmittance):
-            if out is not None and (out.shape[1] != width or
-                                    out.shape[0] < (rows if cumulative else int(n_paths))):
-                raise ValueError(f"an output has shape {out.shape}, need rows x {width}.")
+        _check_outputs((optical_depth, transmittance), rows if cumulative else int(n_paths),
+                       n_bands if n_bands > 0 else stride)
         self._check(self.lib.lbl_path_compute(
             self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
-            int(level_begin), rows, lengths.ctypes.data, n_bands,
-            starts.ctypes.data if starts is not None else None, carry.pointer,
-            optical_depth.pointer if optical_depth is not None else None,
-            transmittance.pointer if transmittance is not None else None, flags))
+            int(level_begin), rows, lengths.ctypes.data, n_bands, _address(starts), carry.pointer,
+            _address(optical_depth), _address(transmittance), flags))
 
     def path_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                       temperature, carry, boundary_temperature=None, boundary_emissivity=None,
@@ -736,37 +759,24 @@ class Engine(object):
         [K] one per row; boundary_temperature [K] (0: none) / boundary_emissivity one per path
         (None: no boundary / 1).  radiance / brightness_temperature: DeviceSpectra outputs (None:
         not wanted), shaped as path_compute's."""
-        lengths = _f64(np.atleast_1d(lengths))
-        temperature = _f64(np.atleast_1d(temperature))
-        rows, stride = int(beta.shape[0]), int(beta.shape[1])
-        if lengths.shape != (rows,) or temperature.shape != (rows,):
-            raise ValueError("one path length and one temperature per row of beta.")
+        rows, stride, lengths, temperature = _per_row(
+            beta, "one path length and one temperature per row of beta.", lengths, temperature)
         if tuple(carry.shape) != (int(n_paths), stride):
             raise ValueError("carry must be [n_paths, row length of beta].")
-        boundary = []
-        for values in (boundary_temperature, boundary_emissivity):
-            if values is not None:
-                values = _f64(np.atleast_1d(values))
-                if values.shape != (int(n_paths),):
-                    raise ValueError("one boundary value per path.")
-            boundary.append(values)
+        boundary = _per_path(n_paths, "one boundary value per path.", boundary_temperature,
+                             boundary_emissivity)
         starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
                                            from_last, asynchronous)
         flags |= (PATH_RADIANCE if radiance is not None else 0) | \
                  (PATH_BRIGHTNESS if brightness_temperature is not None else 0) | \
                  (PATH_CUMULATIVE if cumulative else 0)
-        width = n_bands if n_bands > 0 else stride
-        for out in (radiance, brightness_temperature):
-            if out is not None and (out.shape[1] != width or
-                                    out.shape[0] < (rows if cumulative else int(n_paths))):
-                raise ValueError(f"an output has shape {out.shape}, need rows x {width}.")
+        _check_outputs((radiance, brightness_temperature),
+                       rows if cumulative else int(n_paths), n_bands if n_bands > 0 else stride)
         self._check(self.lib.lbl_path_radiance(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, lengths.ctypes.data,
-            temperature.ctypes.data, *(b.ctypes.data if b is not None else None for b in boundary),
-            n_bands, starts.ctypes.data if starts is not None else None, carry.pointer,
-            radiance.pointer if radiance is not None else None,
-            brightness_temperature.pointer if brightness_temperature is not None else None, flags))
+            temperature.ctypes.data, *map(_address, boundary), n_bands, _address(starts),
+            carry.pointer, _address(radiance), _address(brightness_temperature), flags))
 
     def path_jacobian(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                       temperature, work, boundary_temperature=None, boundary_emissivity=None,
@@ -782,18 +792,10 @@ class Engine(object):
         work: DeviceSpectra [>= rows, row length] without bands (optical_depth_jacobian or
         log_optical_depth_jacobian may be it), with bands [>= max(P, 1)*rows + Q*paths of the
         run, row length] for P per-level and Q per-path outputs."""
-        lengths = _f64(np.atleast_1d(lengths))
-        temperature = _f64(np.atleast_1d(temperature))
-        rows, stride = int(beta.shape[0]), int(beta.shape[1])
-        if lengths.shape != (rows,) or temperature.shape != (rows,):
-            raise ValueError("one path length and one temperature per row of beta.")
-        boundary = []
-        for values in (boundary_temperature, boundary_emissivity):
-            if values is not None:
-                values = _f64(np.atleast_1d(values))
-                if values.shape != (int(n_paths),):
-                    raise ValueError("one boundary value per path.")
-            boundary.append(values)
+        rows, stride, lengths, temperature = _per_row(
+            beta, "one path length and one temperature per row of beta.", lengths, temperature)
+        boundary = _per_path(n_paths, "one boundary value per path.", boundary_temperature,
+                             boundary_emissivity)
         starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
                                            from_last, asynchronous)
         given = dict(radiance=radiance, optical_depth_jacobian=optical_depth_jacobian,
@@ -812,7 +814,7 @@ class Engine(object):
         pointers = []
         for name, flag in PATH_JACOBIAN_OUTPUTS:
             out = given[name]
-            pointers.append(None if out is None else out.pointer)
+            pointers.append(_address(out))
             if out is None:
                 continue
             flags |= flag
@@ -822,9 +824,8 @@ class Engine(object):
         self._check(self.lib.lbl_path_jacobian(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, lengths.ctypes.data,
-            temperature.ctypes.data, *(b.ctypes.data if b is not None else None for b in boundary),
-            n_bands, starts.ctypes.data if starts is not None else None, work.pointer, *pointers,
-            flags))
+            temperature.ctypes.data, *map(_address, boundary), n_bands, _address(starts),
+            work.pointer, *pointers, flags))
 
     def instrument_create(self, grid, shape, centers, parameter=None, half_width=None,
                           offsets=None, response=None):
@@ -840,9 +841,8 @@ class Engine(object):
         handle = c_int32(-1)
         self._check(self.lib.lbl_instrument_create(
             self.handle, int(grid), int(shape), centers.size, centers.ctypes.data,
-            *(x.ctypes.data if x is not None else None for x in (parameter, half_width)),
-            n_table, *(x.ctypes.data if x is not None else None for x in (offsets, response)),
-            rows, byref(handle)))
+            _address(parameter), _address(half_width), n_table, _address(offsets),
+            _address(response), rows, byref(handle)))
         self._instrument_channels[handle.value] = centers.size
         return handle.value
 
@@ -890,13 +890,8 @@ class Engine(object):
                              "row length].")
         if level_flux.shape[1] != stride or level_flux.shape[0] < rows:
             raise ValueError(f"level_flux has shape {level_flux.shape}, need rows x {stride}.")
-        surface = []
-        for values in (surface_temperature, surface_emissivity):
-            if values is not None:
-                values = _f64(np.atleast_1d(values))
-                if values.shape != (int(n_paths),):
-                    raise ValueError("one surface value per path.")
-            surface.append(values)
+        surface = _per_path(n_paths, "one surface value per path.", surface_temperature,
+                            surface_emissivity)
         starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
                                            from_last, asynchronous)
         for out, count in ((flux, rows), (surface_flux, int(n_paths))):
@@ -906,11 +901,9 @@ class Engine(object):
         self._check(self.lib.lbl_path_flux(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, angles, lengths.ctypes.data,
-            weight.ctypes.data, temperature.ctypes.data,
-            *(s.ctypes.data if s is not None else None for s in surface),
-            n_bands, starts.ctypes.data if starts is not None else None, carry.pointer,
-            reflection.pointer, level_flux.pointer, flux.pointer if flux is not None else None,
-            surface_flux.pointer if surface_flux is not None else None, flags))
+            weight.ctypes.data, temperature.ctypes.data, *map(_address, surface), n_bands,
+            _address(starts), carry.pointer, reflection.pointer, level_flux.pointer,
+            _address(flux), _address(surface_flux), flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):

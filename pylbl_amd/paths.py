@@ -1,0 +1,566 @@
+"""The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux and
+compute_jacobian -- on the host: their quantities and units, the checks of their arguments (one
+request per call, made before anything touches the GPU), the run loop that sweeps the "total"
+absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
+cuts (_level_bytes) and the assembly of the results.  The sweeps themselves are the kernels of
+csrc/path.h behind Engine.path_*; the "total" block is queued by Spectroscopy.total_into.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+from .synthetic import grid_arguments
+
+# Levels of one run at most: what one call of the continuum group kernels takes
+# (lbl_continuum_compute_many), so that atmospheres of any size can be integrated.
+_MAX_RUN_LEVELS = 65535
+
+PATH_QUANTITIES = ("optical_depth", "transmittance")
+PATH_CUMULATIVE = (None, "from_first", "from_last")
+RADIANCE_QUANTITIES = ("radiance", "brightness_temperature")
+RADIANCE_DIRECTIONS = ("toward_last", "toward_first")
+
+# Planck's function per wavenumber, B(nu, T) = C1 nu^3 / expm1(C2 nu / T) [W m-2 sr-1 (cm-1)-1]
+# for nu in cm-1: from the exact CODATA 2018 h, c and k (the same literals as LBL_PLANCK_C1 and
+# LBL_PLANCK_C2 in include/lbl_amd.h).
+PLANCK_C1 = 1.1910429723971885e-08     # 2 h c^2 1e8 [W m-2 sr-1 (cm-1)-4]
+PLANCK_C2 = 1.4387768775039338         # h c / k 1e2 [cm K]
+# Dry air for heating rates: R_d = R/M_d from the CODATA 2018 molar gas constant and the molar
+# mass of dry air, and c_p = (7/2) R_d of an ideal diatomic gas.
+R_DRY = 8.314462618/0.0289644          # [J kg-1 K-1]
+CP_DRY = 3.5*R_DRY                     # [J kg-1 K-1]
+
+# compute_jacobian: the radiance and its derivatives, per level and per path.
+JACOBIAN_LEVEL_QUANTITIES = ("optical_depth_jacobian", "log_optical_depth_jacobian",
+                             "temperature_jacobian")
+JACOBIAN_PATH_QUANTITIES = ("radiance", "boundary_temperature_jacobian",
+                            "boundary_emissivity_jacobian")
+JACOBIAN_QUANTITIES = ("radiance",) + JACOBIAN_LEVEL_QUANTITIES + JACOBIAN_PATH_QUANTITIES[1:]
+
+FLUX_QUANTITIES = ("upward_flux", "downward_flux", "heating_rate")
+FLUX_SURFACES = ("first", "last")
+MAX_FLUX_ANGLES = 8
+
+_PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
+               "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K",
+               "optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
+               "log_optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
+               "temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
+               "boundary_temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
+               "boundary_emissivity_jacobian": "W m-2 sr-1 (cm-1)-1"}
+# compute_flux: on the grid, per band.
+_FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
+               "downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
+               "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
+
+# What every product checked and derived from its arguments: flat lengths, the atmosphere's shape,
+# the quantities asked for, band edges and their column starts (or None), the Instrument (or
+# None), and whether the result is per level (compute_path: None, "from_first" or "from_last").
+_COMMON = ("lengths", "shape", "quantities", "edges", "starts", "instrument", "cumulative")
+_PathRequest = namedtuple("_PathRequest", _COMMON)
+# compute_radiance's and compute_jacobian's: the sweep order and one boundary value per path.
+_RadianceRequest = namedtuple("_RadianceRequest", _COMMON + (
+    "from_last", "boundary_temperature", "boundary_emissivity"))
+# compute_flux's: the angles and the surface of every path.
+_FluxRequest = namedtuple("_FluxRequest", _COMMON + (
+    "surface", "mu", "weight", "surface_temperature", "surface_emissivity"))
+
+# One pass of _sweep_runs over the levels: its order, and what it writes per level and per path.
+_Pass = namedtuple("_Pass", ["from_last", "level_quantities", "path_quantities"])
+# One returned array of _sweep_runs: host array `name` is filled from the sweeps' block `source`,
+# per level or per path -- copied as it is without an instrument, reduced to channels (of
+# exp(-source) with `transmittance`) by Engine.instrument_apply with one.
+_Product = namedtuple("_Product", ["name", "source", "per_level", "transmittance"],
+                      defaults=(False,))
+# What _sweep_runs hands a sweeper: the engine, take(rows, columns=n) for blocks of its own for
+# the call (carries, scratch), the layout of the paths, the columns of the grid, the flat level
+# temperatures and grid(), the handle of the grid in HBM.
+_Call = namedtuple("_Call", ["engine", "take", "paths", "per_path", "columns", "temperature",
+                             "grid"])
+
+
+def _path_layout(shape):
+    """(levels per path, paths) of an atmosphere of this shape: paths run along its last axis."""
+    per_path = shape[-1] if shape else 1
+    return per_path, int(np.prod(shape, dtype=np.int64))//per_path
+
+
+def band_columns(grid, band_edges):
+    """Column starts of the bands [e_b, e_b+1) of strictly increasing, finite edges on an
+    ascending grid: int64 [B + 1]; band b is the columns starts[b] <= j < starts[b + 1], i.e. the
+    points with e_b <= grid[j] < e_b+1 (a band without points has starts[b] == starts[b + 1])."""
+    edges = np.asarray(band_edges, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2:
+        raise ValueError("band_edges must be a 1-d array of at least two edges.")
+    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.):
+        raise ValueError("band_edges must be finite and strictly increasing.")
+    return np.searchsorted(np.asarray(grid, dtype=np.float64), edges, side="left").astype(np.int64)
+
+
+def flux_angles(angles):
+    """(mu, weight) of compute_flux's `angles`, checked: an int K in 1..8 gives Gauss-Legendre
+    on mu in (0, 1] -- x, w = leggauss(K), mu = (x + 1)/2, weight = mu*w -- so that
+    sum_k weight_k*mu_k^n = integral over (0, 1] of 2 mu mu^n for n <= 2K - 2; a pair
+    (mu, weight) of equal 1-d arrays of 1..8 values is taken as it is, with 0 < mu <= 1, weights
+    finite and >= 0 that sum to 1 within 1e-12 (an isotropic I then gives F = pi I)."""
+    if isinstance(angles, (int, np.integer)) and not isinstance(angles, (bool, np.bool_)):
+        count = int(angles)
+        if not 1 <= count <= MAX_FLUX_ANGLES:
+            raise ValueError(f"angles must be an int in 1..{MAX_FLUX_ANGLES}, not {count}.")
+        x, w = np.polynomial.legendre.leggauss(count)
+        mu = (x + 1.)/2.
+        return mu, mu*w
+    try:
+        mu, weight = angles
+    except (TypeError, ValueError):
+        raise ValueError("angles must be an int in 1..8 or a pair (mu, weight).") from None
+    mu = np.asarray(mu, dtype=np.float64)
+    weight = np.asarray(weight, dtype=np.float64)
+    if mu.ndim != 1 or weight.shape != mu.shape or not 1 <= mu.size <= MAX_FLUX_ANGLES:
+        raise ValueError(f"angles: mu and weight must be 1-d arrays of the same length in "
+                         f"1..{MAX_FLUX_ANGLES}.")
+    if not np.all((mu > 0.) & (mu <= 1.)):
+        raise ValueError("angles: mu must lie in (0, 1].")
+    if not np.all(np.isfinite(weight)) or np.any(weight < 0.):
+        raise ValueError("angles: weights must be finite and >= 0.")
+    if not abs(float(np.sum(weight)) - 1.) <= 1.e-12:
+        raise ValueError("angles: the weights must sum to 1 (they include the factor mu).")
+    return np.ascontiguousarray(mu), np.ascontiguousarray(weight)
+
+
+def heating_rate(upward_flux, downward_flux, pressure, temperature, thickness, surface="first"):
+    """H_l = 86400*(Fnet[i_lower] - Fnet[i_upper]) / ((rho_l*c_p)*s_l) [K day-1, per cm-1 on the
+    grid], in fp64: fluxes [..., L + 1, W] at the interfaces, pressure [Pa], temperature [K] and
+    thickness [m] [..., L]; Fnet = up - down; i_lower is the interface of level l nearer the
+    surface (l for surface "first", l + 1 for "last"); rho_l = p_l/(R_DRY*T_l); c_p = CP_DRY.
+    NaN where s_l = 0."""
+    net = np.asarray(upward_flux, dtype=np.float64) - np.asarray(downward_flux, dtype=np.float64)
+    lower, upper = (net[..., :-1, :], net[..., 1:, :]) if surface == "first" else \
+        (net[..., 1:, :], net[..., :-1, :])
+    thickness = np.asarray(thickness, dtype=np.float64)
+    density = np.asarray(pressure, dtype=np.float64)/(R_DRY*np.asarray(temperature, np.float64))
+    capacity = (density*CP_DRY)*thickness
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rate = (86400.*(lower - upper))/capacity[..., None]
+    return np.where((thickness == 0.)[..., None], np.nan, rate)
+
+
+def _selection(quantities, names):
+    """A non-empty selection of `names` (one name or several) as a tuple in the order of `names`."""
+    if isinstance(quantities, str):
+        quantities = (quantities,)
+    quantities = tuple(quantities)
+    unknown = [q for q in quantities if q not in names]
+    if unknown or not quantities:
+        raise ValueError(f"quantities must be a non-empty selection of {names}, not {quantities}.")
+    return tuple(q for q in names if q in quantities)
+
+
+# ---------------------------------------------------------------------------------------------
+# The requests: every argument of a product checked before anything touches the GPU.
+def _check_range_policy(range_policy):
+    if range_policy not in ("reference", "skip"):
+        raise ValueError(f"unknown range_policy {range_policy!r}.")
+
+
+def _path_geometry(spec, path_length, name, argument="path_length", what="path lengths"):
+    """(flat lengths, atmosphere shape): the checks of the path lengths that every product
+    shares."""
+    if spec.group is not None:
+        raise NotImplementedError(f"{name} does not split paths over processes yet "
+                                  "(group is set): the levels of a path would need a sum "
+                                  "over ranks before exp(-tau).")
+    shape = tuple(spec.atmosphere.temperature.shape)
+    lengths = np.asarray(path_length, dtype=np.float64)
+    if lengths.shape != shape:
+        raise ValueError(f"{argument} has shape {lengths.shape}, the atmosphere {shape}.")
+    if not np.all(np.isfinite(lengths)) or np.any(lengths < 0.):
+        raise ValueError(f"{what} must be finite and >= 0.")
+    if lengths.size == 0:
+        raise ValueError("the atmosphere has no levels.")
+    return np.ascontiguousarray(lengths.ravel()), shape
+
+
+def _check_level_temperatures(spec):
+    temperature = spec.atmosphere.temperature
+    if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
+        raise ValueError("the atmosphere's temperatures must be finite and > 0.")
+
+
+def _per_path(value, name, shape):
+    """A scalar or one value per path (shaped like the atmosphere without its last dimension), as
+    a flat float64 array of one value per path."""
+    per_path_shape = shape[:-1]
+    values = np.asarray(value, dtype=np.float64)
+    if values.shape not in ((), per_path_shape):
+        raise ValueError(f"{name} has shape {values.shape}: give a scalar or one value "
+                         f"per path, shaped {per_path_shape}.")
+    return np.ascontiguousarray(np.broadcast_to(values, per_path_shape).ravel())
+
+
+def _emitter(temperature, emissivity, what, shape, optional=False):
+    """(temperatures, emissivities), one per path, of what lies behind the paths (`what`:
+    "boundary" or "surface"): a temperature per path, finite and > 0 (None without one, where
+    that is `optional`), and an emissivity per path in [0, 1]."""
+    if temperature is None and optional:
+        temperatures = None
+    else:
+        temperatures = _per_path(temperature, f"{what}_temperature", shape)
+        if not np.all(np.isfinite(temperatures)) or np.any(temperatures <= 0.):
+            raise ValueError(f"{what} temperatures must be finite and > 0.")
+    emissivities = _per_path(emissivity, f"{what}_emissivity", shape)
+    if not np.all((emissivities >= 0.) & (emissivities <= 1.)):
+        raise ValueError(f"{what} emissivities must lie in [0, 1].")
+    return temperatures, emissivities
+
+
+def _path_bands(spec, band_edges, instrument=None):
+    """(edges, column starts) of band_edges, or (None, None); checks `instrument` too."""
+    if instrument is not None:
+        from .instrument import Instrument
+        if band_edges is not None:
+            raise ValueError("give band_edges or instrument, not both.")
+        if not isinstance(instrument, Instrument):
+            raise ValueError(f"instrument must be an Instrument, not {type(instrument)}.")
+        if spec.grid.size > 1 and not np.all(np.diff(spec.grid) > 0.):
+            raise ValueError("instrument channels need an increasing grid.")
+    if band_edges is None:
+        return None, None
+    if spec.grid.size > 1 and not np.all(np.diff(spec.grid) > 0.):
+        raise ValueError("band means need an increasing grid.")
+    starts = band_columns(spec.grid, band_edges)
+    return np.asarray(band_edges, dtype=np.float64), starts
+
+
+def _path_request(spec, path_length, quantities, band_edges, cumulative, range_policy,
+                  instrument=None):
+    """Checks every argument of compute_path."""
+    lengths, shape = _path_geometry(spec, path_length, "compute_path")
+    quantities = _selection(quantities, PATH_QUANTITIES)
+    if not (cumulative is None or (isinstance(cumulative, str) and
+                                   cumulative in PATH_CUMULATIVE)):
+        raise ValueError(f"cumulative must be one of {PATH_CUMULATIVE}, not {cumulative!r}.")
+    _check_range_policy(range_policy)
+    edges, starts = _path_bands(spec, band_edges, instrument)
+    return _PathRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                        starts=starts, instrument=instrument, cumulative=cumulative)
+
+
+def _radiance_request(spec, path_length, boundary_temperature, boundary_emissivity, direction,
+                      quantities, band_edges, cumulative, range_policy, instrument=None,
+                      names=RADIANCE_QUANTITIES, caller="compute_radiance"):
+    """Checks every argument of compute_radiance; compute_jacobian's too, with its `names`."""
+    lengths, shape = _path_geometry(spec, path_length, caller)
+    _check_level_temperatures(spec)
+    boundary, emissivity = _emitter(boundary_temperature, boundary_emissivity, "boundary", shape,
+                                    optional=True)
+    if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
+        raise ValueError(f"direction must be one of {RADIANCE_DIRECTIONS}, not {direction!r}.")
+    quantities = _selection(quantities, names)
+    if not isinstance(cumulative, (bool, np.bool_)):
+        raise ValueError(f"cumulative must be True or False, not {cumulative!r}.")
+    _check_range_policy(range_policy)
+    if band_edges is not None and "brightness_temperature" in quantities:
+        raise ValueError("brightness_temperature is only available on the grid: band means "
+                         "are formed of the radiance alone.")
+    edges, starts = _path_bands(spec, band_edges, instrument)
+    return _RadianceRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                            starts=starts, instrument=instrument, cumulative=bool(cumulative),
+                            from_last=direction == "toward_first",
+                            boundary_temperature=boundary, boundary_emissivity=emissivity)
+
+
+def _flux_request(spec, layer_thickness, surface_temperature, surface_emissivity, surface,
+                  angles, quantities, band_edges, range_policy):
+    """Checks every argument of compute_flux."""
+    lengths, shape = _path_geometry(spec, layer_thickness, "compute_flux", "layer_thickness",
+                                    "layer thicknesses")
+    _check_level_temperatures(spec)
+    if "heating_rate" in (quantities if not isinstance(quantities, str) else (quantities,)):
+        pressure = spec.atmosphere.pressure
+        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
+            raise ValueError("heating rates need pressures that are finite and > 0.")
+    ts, es = _emitter(surface_temperature, surface_emissivity, "surface", shape)
+    if not (isinstance(surface, str) and surface in FLUX_SURFACES):
+        raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
+    mu, weight = flux_angles(angles)
+    quantities = _selection(quantities, FLUX_QUANTITIES)
+    _check_range_policy(range_policy)
+    edges, starts = _path_bands(spec, band_edges)
+    return _FluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                        starts=starts, instrument=None, cumulative=False, surface=surface, mu=mu,
+                        weight=weight, surface_temperature=ts, surface_emissivity=es)
+
+
+# ---------------------------------------------------------------------------------------------
+# The run loop.
+def _sweep_pass(quantities, cumulative, from_last):
+    """The one pass of compute_path and compute_radiance."""
+    return _Pass(from_last, tuple(quantities) if cumulative else (),
+                 () if cumulative else tuple(quantities))
+
+
+def _cut_runs(levels, per_path, level_bytes, limit, whole_paths=False):
+    """(run, [(a, b)]): the runs of consecutive flat levels of _sweep_runs, `run` levels each but
+    the last, for blocks of level_bytes per level within `limit` bytes and _MAX_RUN_LEVELS
+    levels.  whole_paths: every run is a whole number of paths of per_path levels -- the most
+    that fit; ValueError where one path does not."""
+    if whole_paths:
+        path_bytes = per_path*level_bytes
+        paths = min(limit//path_bytes, _MAX_RUN_LEVELS//per_path)
+        if paths < 1:
+            raise ValueError(f"device_output_limit = {limit} bytes does not hold one path: its "
+                             f"blocks need {path_bytes} bytes ({per_path} levels, and at most "
+                             f"{_MAX_RUN_LEVELS} levels in a run).")
+        run = min(paths*per_path, levels)
+    else:
+        run = levels if levels*level_bytes <= limit else max(1, limit//level_bytes)
+        run = min(run, _MAX_RUN_LEVELS)
+    return run, [(a, min(a + run, levels)) for a in range(0, levels, run)]
+
+
+def _level_bytes(n, request, level_quantities, level_blocks, grid_outputs):
+    """Bytes per level of a run that count against device_output_limit (_cut_runs' level_bytes),
+    in blocks of n float64: the caller's `level_blocks` -- beta and what its sweeper takes per
+    level (compute_path and compute_radiance 1, compute_flux 2: the fluxes of a level,
+    compute_jacobian 1 and its work blocks) -- and one block per per-level quantity of the passes
+    where an instrument reduces it from the grid, or where the caller says its `grid_outputs`
+    count (compute_jacobian) and there are no bands.
+    Known undercount, kept because it decides where runs are cut: without an instrument the
+    per-level grid outputs of compute_path and compute_radiance (cumulative=) are not counted,
+    and compute_flux counts one output block where it holds two on the grid; neither are the
+    per-path blocks and carries.  Counting them is a follow-up that changes the run cuts."""
+    blocks = level_blocks
+    if request.instrument is not None or (grid_outputs and request.starts is None):
+        blocks += len(level_quantities)
+    return blocks*n*8
+
+
+def _first_rows(block, count):
+    return block if count == block.shape[0] else block.rows(count)
+
+
+def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, level_blocks=1,
+                products=None, grid_outputs=False, whole_paths=False):
+    """{product: array [levels or paths, columns, bands or channels]}: the "total" block of a run
+    of levels at a time (Spectroscopy.total_into), then the path kernels on it -- for each of
+    `passes` (_Pass) in turn, every pass over all levels.
+    sweeper(call, run) (call: _Call) returns sweep(index, beta, a, b, outputs), which queues the
+    path kernels of pass `index` on the levels [a, b) and their block `beta`, with `outputs`
+    {quantity of any pass: DeviceSpectra}.  A pass that starts on the run the previous pass ended
+    on finds that run's block still in HBM and does not compute it again: sweeps of a call with
+    several passes must leave beta as they found it.
+    products: what goes to the host (_Product); None: every quantity of the passes as it is.
+    With request.instrument the sweeps write their quantities on the grid and only the products,
+    reduced to [rows, channels] by lbl_instrument_apply, travel.
+    level_blocks, grid_outputs: see _level_bytes.  whole_paths: every run is a whole number of
+    paths (_cut_runs), for sweeps that carry nothing from run to run."""
+    if remove_pedestal is None:
+        remove_pedestal = spec.continua_backend == "mt_ckd"
+    temperature = spec.atmosphere.temperature.ravel()
+    pressure = spec.atmosphere.pressure.ravel()
+    mole_fractions = {name: x.ravel() for name, x in spec.atmosphere.gases.items()}
+    levels = temperature.size
+    per_path, paths = _path_layout(request.shape)
+    v0, vn, n_per_v = grid_arguments(spec.grid)
+    n = (vn - v0)*n_per_v
+    instrument, starts = request.instrument, request.starts
+    level_quantities = [q for step in passes for q in step.level_quantities]
+    path_quantities = [q for step in passes for q in step.path_quantities]
+    if products is None:
+        products = [_Product(q, q, True) for q in level_quantities] + \
+            [_Product(q, q, False) for q in path_quantities]
+    products = sorted(products, key=lambda product: not product.per_level)
+    # Runs of consecutive levels when the blocks would not fit: the sweep carries over in HBM.
+    run, runs = _cut_runs(levels, per_path,
+                          _level_bytes(n, request, level_quantities, level_blocks, grid_outputs),
+                          spec.device_output_limit, whole_paths)
+    # What the sweeps write per row, and what goes home per row.
+    band_width = n if starts is None else starts.size - 1
+    width = spec.grid.size if starts is None else starts.size - 1
+
+    gases = spec._present_gases(temperature, pressure, mole_fractions, total=True)
+    engine = gases[0]
+    if engine is None:
+        from .engine import default_engine
+        engine = default_engine(spec.device)
+    if instrument is not None:
+        from .instrument import resident_instrument
+        handle = resident_instrument(engine, instrument, spec.grid)
+        width = len(instrument)
+    results = {product.name: engine.host_array((levels if product.per_level else paths, width))
+               for product in products}
+    # One block of `run` levels for beta (and for each per-level output) serves every run; the
+    # shorter last run uses its leading rows.  Together with the sweeper's blocks and the
+    # per-path outputs that is all this call holds in HBM.
+    taken = []
+
+    def take(rows, columns=n):
+        block = engine.blocks.take(rows, columns)
+        taken.append(block)
+        return block
+
+    def grid_handle():
+        from .mt_ckd import resident_grid
+        return resident_grid(engine, spec.grid)
+
+    def send_home(product, rows, target):
+        """Queues the copy of the first `rows` rows of the product's source to `target`: reduced
+        to channels first with an instrument."""
+        block = _first_rows(outputs[product.source], rows)
+        if instrument is not None:
+            engine.instrument_apply(block, rows, handle, channels[product.name],
+                                    transmittance=product.transmittance, asynchronous=True)
+            block = _first_rows(channels[product.name], rows)
+        block.to_host_into(target, width, asynchronous=True)
+    with engine.pipeline:
+        try:
+            sweep = sweeper(_Call(engine, take, paths, per_path, spec.grid.size, temperature,
+                                  grid_handle), run)
+            beta = take(run, n)
+            outputs = {q: take(run, band_width) for q in level_quantities}
+            outputs.update({q: take(paths, band_width) for q in path_quantities})
+            channels = {} if instrument is None else {
+                product.name: take(run if product.per_level else paths, width)
+                for product in products}
+            resident = None
+            for index, step in enumerate(passes):
+                for a, b in (runs[::-1] if step.from_last else runs):
+                    kept = (a, b) == resident
+                    if resident is not None and not kept:
+                        # The previous run's block and outputs are written again below: what
+                        # still reads them -- its sweep, its copies to the host -- is done first.
+                        engine.synchronize()
+                    rows = _first_rows(beta, b - a)
+                    if not kept:
+                        spec.total_into(rows, a, b, remove_pedestal, range_policy, gases=gases)
+                    resident = (a, b)
+                    sweep(index, rows, a, b,
+                          {q: _first_rows(block, b - a) if q in level_quantities else block
+                           for q, block in outputs.items()})
+                    for product in products:
+                        if product.per_level and product.source in step.level_quantities:
+                            send_home(product, b - a, results[product.name][a:b])
+            for product in products:
+                if not product.per_level:
+                    send_home(product, paths, results[product.name])
+            engine.synchronize()
+        except BaseException:
+            try:
+                engine.cancel_deferred()
+                engine.synchronize()
+            except Exception:       # the first error is the one to report
+                pass
+            raise
+        finally:
+            for block in taken:
+                engine.blocks.give(block)
+    return results
+
+
+# ---------------------------------------------------------------------------------------------
+# The results.
+def _spectral_axis(request):
+    """The last dim of a path result: "channel", "band" or "wavenumber"."""
+    if request.instrument is not None:
+        return "channel"
+    return "wavenumber" if request.edges is None else "band"
+
+
+def _flux_interfaces(spec, values, request):
+    """{quantity: [..., L + 1 or L, W]} of compute_flux from the sweeps' per-level rows (the
+    flux just after each level in sweep order) and the surface rows."""
+    shape = list(request.shape)
+    per_path, paths = _path_layout(request.shape)
+    width = values["downward_flux"].shape[-1]
+    down = np.asarray(values["downward_flux"]).reshape(paths, per_path, width)
+    up = np.asarray(values["upward_flux"]).reshape(paths, per_path, width)
+    surface = np.asarray(values["surface_flux"]).reshape(paths, 1, width)
+    space = np.zeros((paths, 1, width))
+    if request.starts is not None:
+        points = np.diff(request.starts)
+        space[..., points == 0] = np.nan
+    # Sweeping toward level 0 the flux after level l is at interface l, toward level L-1 at
+    # interface l + 1.
+    if request.surface == "first":
+        fluxes = {"downward_flux": np.concatenate([down, space], axis=1),
+                  "upward_flux": np.concatenate([surface, up], axis=1)}
+    else:
+        fluxes = {"downward_flux": np.concatenate([space, down], axis=1),
+                  "upward_flux": np.concatenate([up, surface], axis=1)}
+    if request.starts is not None:
+        _, _, n_per_v = grid_arguments(spec.grid)
+        widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
+        fluxes = {q: f*widths for q, f in fluxes.items()}
+    out = {}
+    lead = shape[:-1] + [per_path + 1, width]
+    for q in ("upward_flux", "downward_flux"):
+        if q in request.quantities:
+            out[q] = fluxes[q].reshape(lead)
+    if "heating_rate" in request.quantities:
+        out["heating_rate"] = heating_rate(
+            fluxes["upward_flux"], fluxes["downward_flux"],
+            spec.atmosphere.pressure.reshape(paths, per_path),
+            spec.atmosphere.temperature.reshape(paths, per_path),
+            request.lengths.reshape(paths, per_path),
+            request.surface).reshape(shape + [width])
+    return out
+
+
+def _create_path_dataset(spec, values, request):
+    """compute_path's, compute_radiance's and compute_jacobian's result from {quantity:
+    [paths or levels, columns, bands or channels]}: per level when cumulative and for the
+    per-level Jacobians."""
+    axis = _spectral_axis(request)
+    variables = {}
+    for q in request.quantities:
+        dims, shape = list(spec.atmosphere.dims), list(request.shape)
+        if not (request.cumulative or q in JACOBIAN_LEVEL_QUANTITIES):
+            dims, shape = dims[:-1], shape[:-1]
+        variables[q] = (dims + [axis], np.asarray(values[q]).reshape(shape + [-1]),
+                        _PATH_UNITS[q])
+    return _path_variables(spec, variables, request)
+
+
+def _create_flux_dataset(spec, values, request):
+    """compute_flux's result from {quantity: [..., interfaces or levels, columns or bands]}:
+    fluxes on the "interface" dim in place of the atmosphere's last, heating rates on it."""
+    dims = list(spec.atmosphere.dims)
+    axis = _spectral_axis(request)
+    variables = {}
+    for q in request.quantities:
+        here = dims + [axis] if q == "heating_rate" else dims[:-1] + ["interface", axis]
+        variables[q] = (here, values[q], _FLUX_UNITS[q][request.edges is not None])
+    return _path_variables(spec, variables, request)
+
+
+def _path_variables(spec, variables, request):
+    """{name: (dims, values, units)} with the grid's, the bands' or the channels' coordinates, in
+    the conventions of Spectroscopy._create_output_dataset."""
+    from .spectroscopy import _optional_xarray
+    axis = _spectral_axis(request)
+    if axis == "channel":
+        instrument = request.instrument
+        lower, upper = instrument.window()
+        start, end = instrument.columns(spec.grid)
+        coords = {"channel_center": (instrument.centers, {"units": "cm-1"}),
+                  "channel_lower": (lower, {"units": "cm-1"}),
+                  "channel_upper": (upper, {"units": "cm-1"}),
+                  "channel_points": (end - start, {})}
+    elif axis == "wavenumber":
+        coords = {"wavenumber": (spec.grid, {"units": "cm-1"})}
+    else:
+        coords = {"band_lower": (request.edges[:-1], {"units": "cm-1"}),
+                  "band_upper": (request.edges[1:], {"units": "cm-1"}),
+                  "band_points": (np.diff(request.starts), {})}
+    xarray = _optional_xarray()
+    if xarray is None:
+        out = {name: value for name, (value, _) in coords.items()}
+        out.update({q: v for q, (_, v, _) in variables.items()})
+        return out
+    DataArray, Dataset = xarray.DataArray, xarray.Dataset
+    return Dataset(
+        data_vars={q: DataArray(v, dims=dims, attrs={"units": units})
+                   for q, (dims, v, units) in variables.items()},
+        coords={name: DataArray(value, dims=(axis,), attrs=attrs)
+                for name, (value, attrs) in coords.items()})

@@ -12,6 +12,15 @@ What is different: all levels of a molecule go to the GPU in one batched call an
 number-density scaling happens in the kernel epilogue; xarray is optional (not installed in
 this image) -- without it the atmosphere is a plain (p, t, vmr) tuple and the result a dict
 of numpy arrays with the same variable names.
+
+What is in this module: Atmosphere, MoleculeCache, the queueing of the kernels of one (molecule,
+mechanism) into blocks in HBM (_Sum, _Queue) and Spectroscopy -- compute_absorption with
+_compute_levels, the "total" block of a range of levels (total_into, _present_gases,
+_queue_total), and the four path products compute_path, compute_radiance, compute_jacobian and
+compute_flux: their documentation and their sweeps.  Everything else of the path products
+(argument checks, the run loop, HBM accounting, results) is in paths.py, whose public names
+stay importable from here and whose request, run-loop and result functions are also Spectroscopy's
+private methods of the same names.
 """
 from collections import namedtuple
 import contextlib
@@ -19,30 +28,19 @@ import os
 
 import numpy as np
 
-from . import errors
+from . import errors, paths
+from .paths import (CP_DRY, FLUX_QUANTITIES, FLUX_SURFACES, JACOBIAN_LEVEL_QUANTITIES,  # noqa: F401
+                    JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
+                    PATH_CUMULATIVE, PATH_QUANTITIES, PLANCK_C1, PLANCK_C2, R_DRY,
+                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, band_columns, flux_angles,
+                    heating_rate, _MAX_RUN_LEVELS, _PATH_UNITS, _Pass, _Product, _cut_runs,
+                    _path_layout, _sweep_pass)
 from .plugins import continua, cross_sections, molecular_lines
 from .synthetic import grid_arguments
 
 kb = 1.38064852e-23  # Boltzmann constant [J K-1] (pyLBL/spectroscopy.py:15).
 
 MECHANISMS = ["lines", "continuum", "cross_section"]
-
-# Levels of one run of compute_path at most: what one call of the continuum group kernels takes
-# (lbl_continuum_compute_many), so that atmospheres of any size can be integrated.
-_MAX_RUN_LEVELS = 65535
-
-# What compute_path checked and derived from its arguments.
-_PathRequest = namedtuple("_PathRequest", ["lengths", "shape", "quantities", "edges", "starts",
-                                           "cumulative", "instrument"])
-# compute_radiance's: the same, with `cumulative` a bool, and one boundary value per path.
-_RadianceRequest = namedtuple("_RadianceRequest", _PathRequest._fields + (
-    "from_last", "boundary_temperature", "boundary_emissivity"))
-# compute_flux's: per-level lengths, the angles, the surface of every path.
-_FluxRequest = namedtuple("_FluxRequest", ["lengths", "shape", "quantities", "edges", "starts",
-                                           "surface", "mu", "weight", "surface_temperature",
-                                           "surface_emissivity"])
-# One pass of _sweep_runs over the levels: its order, and what it returns per level and per path.
-_Pass = namedtuple("_Pass", ["from_last", "level_quantities", "path_quantities"])
 
 
 def number_density(temperature, pressure, volume_mixing_ratio):
@@ -70,159 +68,6 @@ def _optional_xarray():
         except ImportError:
             _XARRAY.append(None)
     return _XARRAY[0]
-
-
-PATH_QUANTITIES = ("optical_depth", "transmittance")
-PATH_CUMULATIVE = (None, "from_first", "from_last")
-RADIANCE_QUANTITIES = ("radiance", "brightness_temperature")
-RADIANCE_DIRECTIONS = ("toward_last", "toward_first")
-
-# Planck's function per wavenumber, B(nu, T) = C1 nu^3 / expm1(C2 nu / T) [W m-2 sr-1 (cm-1)-1]
-# for nu in cm-1: from the exact CODATA 2018 h, c and k (the same literals as LBL_PLANCK_C1 and
-# LBL_PLANCK_C2 in include/lbl_amd.h).
-PLANCK_C1 = 1.1910429723971885e-08     # 2 h c^2 1e8 [W m-2 sr-1 (cm-1)-4]
-PLANCK_C2 = 1.4387768775039338         # h c / k 1e2 [cm K]
-# Dry air for heating rates: R_d = R/M_d from the CODATA 2018 molar gas constant and the molar
-# mass of dry air, and c_p = (7/2) R_d of an ideal diatomic gas.
-R_DRY = 8.314462618/0.0289644          # [J kg-1 K-1]
-CP_DRY = 3.5*R_DRY                     # [J kg-1 K-1]
-
-# compute_jacobian: the radiance and its derivatives, per level and per path.
-JACOBIAN_LEVEL_QUANTITIES = ("optical_depth_jacobian", "log_optical_depth_jacobian",
-                             "temperature_jacobian")
-JACOBIAN_PATH_QUANTITIES = ("radiance", "boundary_temperature_jacobian",
-                            "boundary_emissivity_jacobian")
-JACOBIAN_QUANTITIES = ("radiance",) + JACOBIAN_LEVEL_QUANTITIES + JACOBIAN_PATH_QUANTITIES[1:]
-
-FLUX_QUANTITIES = ("upward_flux", "downward_flux", "heating_rate")
-FLUX_SURFACES = ("first", "last")
-MAX_FLUX_ANGLES = 8
-
-_PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
-               "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K",
-               "optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
-               "log_optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
-               "temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
-               "boundary_temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
-               "boundary_emissivity_jacobian": "W m-2 sr-1 (cm-1)-1"}
-# compute_flux: on the grid, per band.
-_FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
-               "downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
-               "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
-
-
-def _path_layout(shape):
-    """(levels per path, paths) of an atmosphere of this shape: paths run along its last axis."""
-    per_path = shape[-1] if shape else 1
-    return per_path, int(np.prod(shape, dtype=np.int64))//per_path
-
-
-def band_columns(grid, band_edges):
-    """Column starts of the bands [e_b, e_b+1) of strictly increasing, finite edges on an
-    ascending grid: int64 [B + 1]; band b is the columns starts[b] <= j < starts[b + 1], i.e. the
-    points with e_b <= grid[j] < e_b+1 (a band without points has starts[b] == starts[b + 1])."""
-    edges = np.asarray(band_edges, dtype=np.float64)
-    if edges.ndim != 1 or edges.size < 2:
-        raise ValueError("band_edges must be a 1-d array of at least two edges.")
-    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.):
-        raise ValueError("band_edges must be finite and strictly increasing.")
-    return np.searchsorted(np.asarray(grid, dtype=np.float64), edges, side="left").astype(np.int64)
-
-
-def flux_angles(angles):
-    """(mu, weight) of compute_flux's `angles`, checked: an int K in 1..8 gives Gauss-Legendre
-    on mu in (0, 1] -- x, w = leggauss(K), mu = (x + 1)/2, weight = mu*w -- so that
-    sum_k weight_k*mu_k^n = integral over (0, 1] of 2 mu mu^n for n <= 2K - 2; a pair
-    (mu, weight) of equal 1-d arrays of 1..8 values is taken as it is, with 0 < mu <= 1, weights
-    finite and >= 0 that sum to 1 within 1e-12 (an isotropic I then gives F = pi I)."""
-    if isinstance(angles, (int, np.integer)) and not isinstance(angles, (bool, np.bool_)):
-        count = int(angles)
-        if not 1 <= count <= MAX_FLUX_ANGLES:
-            raise ValueError(f"angles must be an int in 1..{MAX_FLUX_ANGLES}, not {count}.")
-        x, w = np.polynomial.legendre.leggauss(count)
-        mu = (x + 1.)/2.
-        return mu, mu*w
-    try:
-        mu, weight = angles
-    except (TypeError, ValueError):
-        raise ValueError("angles must be an int in 1..8 or a pair (mu, weight).") from None
-    mu = np.asarray(mu, dtype=np.float64)
-    weight = np.asarray(weight, dtype=np.float64)
-    if mu.ndim != 1 or weight.shape != mu.shape or not 1 <= mu.size <= MAX_FLUX_ANGLES:
-        raise ValueError(f"angles: mu and weight must be 1-d arrays of the same length in "
-                         f"1..{MAX_FLUX_ANGLES}.")
-    if not np.all((mu > 0.) & (mu <= 1.)):
-        raise ValueError("angles: mu must lie in (0, 1].")
-    if not np.all(np.isfinite(weight)) or np.any(weight < 0.):
-        raise ValueError("angles: weights must be finite and >= 0.")
-    if not abs(float(np.sum(weight)) - 1.) <= 1.e-12:
-        raise ValueError("angles: the weights must sum to 1 (they include the factor mu).")
-    return np.ascontiguousarray(mu), np.ascontiguousarray(weight)
-
-
-def heating_rate(upward_flux, downward_flux, pressure, temperature, thickness, surface="first"):
-    """H_l = 86400*(Fnet[i_lower] - Fnet[i_upper]) / ((rho_l*c_p)*s_l) [K day-1, per cm-1 on the
-    grid], in fp64: fluxes [..., L + 1, W] at the interfaces, pressure [Pa], temperature [K] and
-    thickness [m] [..., L]; Fnet = up - down; i_lower is the interface of level l nearer the
-    surface (l for surface "first", l + 1 for "last"); rho_l = p_l/(R_DRY*T_l); c_p = CP_DRY.
-    NaN where s_l = 0."""
-    net = np.asarray(upward_flux, dtype=np.float64) - np.asarray(downward_flux, dtype=np.float64)
-    lower, upper = (net[..., :-1, :], net[..., 1:, :]) if surface == "first" else \
-        (net[..., 1:, :], net[..., :-1, :])
-    thickness = np.asarray(thickness, dtype=np.float64)
-    density = np.asarray(pressure, dtype=np.float64)/(R_DRY*np.asarray(temperature, np.float64))
-    capacity = (density*CP_DRY)*thickness
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rate = (86400.*(lower - upper))/capacity[..., None]
-    return np.where((thickness == 0.)[..., None], np.nan, rate)
-
-
-def _spectral_axis(request):
-    """The last dim of a path result: "channel", "band" or "wavenumber"."""
-    if getattr(request, "instrument", None) is not None:
-        return "channel"
-    return "wavenumber" if request.edges is None else "band"
-
-
-def _sweep_pass(quantities, cumulative, from_last):
-    """The one pass of compute_path and compute_radiance."""
-    return _Pass(from_last, tuple(quantities) if cumulative else (),
-                 () if cumulative else tuple(quantities))
-
-
-def _cut_runs(levels, per_path, level_bytes, limit, whole_paths=False):
-    """(run, [(a, b)]): the runs of consecutive flat levels of _sweep_runs, `run` levels each but
-    the last, for blocks of level_bytes per level within `limit` bytes and _MAX_RUN_LEVELS
-    levels.  whole_paths: every run is a whole number of paths of per_path levels -- the most
-    that fit; ValueError where one path does not."""
-    if whole_paths:
-        path_bytes = per_path*level_bytes
-        paths = min(limit//path_bytes, _MAX_RUN_LEVELS//per_path)
-        if paths < 1:
-            raise ValueError(f"device_output_limit = {limit} bytes does not hold one path: its "
-                             f"blocks need {path_bytes} bytes ({per_path} levels, and at most "
-                             f"{_MAX_RUN_LEVELS} levels in a run).")
-        run = min(paths*per_path, levels)
-    else:
-        run = levels if levels*level_bytes <= limit else max(1, limit//level_bytes)
-        run = min(run, _MAX_RUN_LEVELS)
-    return run, [(a, min(a + run, levels)) for a in range(0, levels, run)]
-
-
-def _selection(quantities, names):
-    """A non-empty selection of `names` (one name or several) as a tuple in the order of `names`."""
-    if isinstance(quantities, str):
-        quantities = (quantities,)
-    quantities = tuple(quantities)
-    unknown = [q for q in quantities if q not in names]
-    if unknown or not quantities:
-        raise ValueError(f"quantities must be a non-empty selection of {names}, not {quantities}.")
-    return tuple(q for q in names if q in quantities)
-
-
-def _check_range_policy(range_policy):
-    if range_policy not in ("reference", "skip"):
-        raise ValueError(f"unknown range_policy {range_policy!r}.")
 
 
 class Atmosphere(object):
@@ -469,28 +314,23 @@ class Spectroscopy(object):
             same variable names ("wavenumber", "mechanism", "<formula>_absorption" /
             "absorption").
         """
-        temperature = self.atmosphere.temperature.ravel()
-        pressure = self.atmosphere.pressure.ravel()
         shape = list(self.atmosphere.temperature.shape)
+        levels = self.atmosphere.temperature.size
         if remove_pedestal is None:
             remove_pedestal = self.continua_backend == "mt_ckd"
-        # Every gas at every level, the dictionary the continua read (spectroscopy.py:173).
-        mole_fractions = {name: x.ravel() for name, x in self.atmosphere.gases.items()}
         mode = output_format if output_format in ("all", "gas") else "total"
         columns = self.grid.size
         if self.group is None:
-            flat = self._compute_levels(temperature, pressure, mole_fractions, mode,
-                                        remove_pedestal, range_policy)
+            flat = self._compute_levels(0, levels, mode, remove_pedestal, range_policy)
         else:
             # One process per GPU: this rank's block of levels, then one collection per array.
             from . import distributed
             group = None if self.group is True else self.group
             rank, world, _ = distributed._group_info(group)
-            mine = distributed.level_shard(temperature.size, rank, world)
-            local = self._compute_levels(
-                temperature[mine], pressure[mine], {k: v[mine] for k, v in mole_fractions.items()},
-                mode, remove_pedestal, range_policy)
-            flat = {name: distributed.gather_arrays(values, temperature.size, self.gather_to,
+            mine = distributed.level_shard(levels, rank, world)
+            local = self._compute_levels(mine.start, mine.stop, mode, remove_pedestal,
+                                         range_policy)
+            flat = {name: distributed.gather_arrays(values, levels, self.gather_to,
                                                     group, device=self.device)
                     for name, values in local.items()}
             if any(values is None for values in flat.values()):
@@ -533,33 +373,29 @@ class Spectroscopy(object):
             "channel_lower", "channel_upper" and "channel_points".
         """
         request = self._path_request(path_length, quantities, band_edges, cumulative,
-                                     range_policy, instrument)
-        if remove_pedestal is None:
-            remove_pedestal = self.continua_backend == "mt_ckd"
-        per_path, paths = _path_layout(request.shape)
+                                      range_policy, instrument)
         from_last = request.cumulative == "from_last"
         cumulative = request.cumulative is not None
-        columns = self.grid.size
 
-        def sweeper(engine, take, run):
-            carry = take(paths)
+        def sweeper(call, run):
+            carry = call.take(call.paths)
 
             def sweep(index, beta, a, b, outputs):
-                engine.path_compute(
-                    beta, columns, paths, per_path, a, request.lengths[a:b], carry,
+                call.engine.path_compute(
+                    beta, call.columns, call.paths, call.per_path, a, request.lengths[a:b], carry,
                     optical_depth=outputs.get("optical_depth"),
                     transmittance=outputs.get("transmittance"), band_start=request.starts,
                     cumulative=cumulative, from_last=from_last, asynchronous=True)
             return sweep
-        reductions = None
         if request.instrument is None:
-            step = _sweep_pass(request.quantities, cumulative, from_last)
+            step, products = _sweep_pass(request.quantities, cumulative, from_last), None
         else:
             # The sweep leaves tau on the grid; both quantities are channel means of it.
             step = _sweep_pass(("optical_depth",), cumulative, from_last)
-            reductions = [(q, "optical_depth", q == "transmittance") for q in request.quantities]
+            products = [_Product(q, "optical_depth", cumulative, q == "transmittance")
+                        for q in request.quantities]
         values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
-                                  reductions=reductions)
+                                   products=products)
         return self._create_path_dataset(values, request)
 
     def compute_radiance(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
@@ -609,24 +445,19 @@ class Spectroscopy(object):
             atmosphere's dims (without the last unless cumulative) and "wavenumber", "band" or
             "channel".
         """
-        request = self._radiance_request(path_length, boundary_temperature, boundary_emissivity,
-                                         direction, quantities, band_edges, cumulative,
-                                         range_policy, instrument)
-        if remove_pedestal is None:
-            remove_pedestal = self.continua_backend == "mt_ckd"
-        per_path, paths = _path_layout(request.shape)
-        temperature = np.ascontiguousarray(self.atmosphere.temperature.ravel(), dtype=np.float64)
-        columns = self.grid.size
+        request = self._radiance_request(path_length, boundary_temperature,
+                                          boundary_emissivity, direction, quantities, band_edges,
+                                          cumulative, range_policy, instrument)
 
-        def sweeper(engine, take, run):
-            from .mt_ckd import resident_grid
-            grid = resident_grid(engine, self.grid)
-            carry = take(paths)
+        def sweeper(call, run):
+            grid = call.grid()
+            carry = call.take(call.paths)
 
             def sweep(index, beta, a, b, outputs):
-                engine.path_radiance(
-                    beta, columns, grid, paths, per_path, a, request.lengths[a:b],
-                    temperature[a:b], carry, boundary_temperature=request.boundary_temperature,
+                call.engine.path_radiance(
+                    beta, call.columns, grid, call.paths, call.per_path, a, request.lengths[a:b],
+                    call.temperature[a:b], carry,
+                    boundary_temperature=request.boundary_temperature,
                     boundary_emissivity=request.boundary_emissivity,
                     radiance=outputs.get("radiance"),
                     brightness_temperature=outputs.get("brightness_temperature"),
@@ -634,17 +465,18 @@ class Spectroscopy(object):
                     from_last=request.from_last, asynchronous=True)
             return sweep
         if request.instrument is None:
-            step = _sweep_pass(request.quantities, request.cumulative, request.from_last)
-            values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper)
+            quantities, products = request.quantities, None
         else:
             # Channel radiances on the GPU; their brightness temperatures at the centres here.
-            step = _sweep_pass(("radiance",), request.cumulative, request.from_last)
-            values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
-                                      reductions=[("radiance", "radiance", False)])
-            if "brightness_temperature" in request.quantities:
-                from .instrument import brightness_temperature
-                values["brightness_temperature"] = brightness_temperature(
-                    values["radiance"], request.instrument.centers)
+            quantities = ("radiance",)
+            products = [_Product("radiance", "radiance", request.cumulative)]
+        step = _sweep_pass(quantities, request.cumulative, request.from_last)
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                   products=products)
+        if request.instrument is not None and "brightness_temperature" in request.quantities:
+            from .instrument import brightness_temperature
+            values["brightness_temperature"] = brightness_temperature(
+                values["radiance"], request.instrument.centers)
         return self._create_path_dataset(values, request)
 
     def compute_jacobian(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
@@ -700,18 +532,13 @@ class Spectroscopy(object):
         Raises ValueError where the blocks of one path (beta, the work block and one block per
         per-level quantity) exceed device_output_limit: a run holds whole paths.
         """
-        request = self._radiance_request(path_length, boundary_temperature, boundary_emissivity,
-                                         direction, quantities, band_edges, False, range_policy,
-                                         instrument, names=JACOBIAN_QUANTITIES,
-                                         caller="compute_jacobian")
+        request = self._radiance_request(path_length, boundary_temperature,
+                                          boundary_emissivity, direction, quantities, band_edges,
+                                          False, range_policy, instrument,
+                                          names=JACOBIAN_QUANTITIES, caller="compute_jacobian")
         if request.boundary_temperature is None and any(
                 q.startswith("boundary_") for q in request.quantities):
             raise ValueError("the boundary Jacobians need a boundary_temperature.")
-        if remove_pedestal is None:
-            remove_pedestal = self.continua_backend == "mt_ckd"
-        per_path, paths = _path_layout(request.shape)
-        temperature = np.ascontiguousarray(self.atmosphere.temperature.ravel(), dtype=np.float64)
-        columns = self.grid.size
         per_level = [q for q in request.quantities if q in JACOBIAN_LEVEL_QUANTITIES]
         step = _Pass(request.from_last, tuple(per_level),
                      tuple(q for q in request.quantities if q in JACOBIAN_PATH_QUANTITIES))
@@ -719,31 +546,26 @@ class Spectroscopy(object):
         banded = request.starts is not None
         work_blocks = max(len(per_level), 1) if banded else 1
 
-        def sweeper(engine, take, run):
-            from .mt_ckd import resident_grid
-            grid = resident_grid(engine, self.grid)
-            run_paths = run//per_path
-            work = take(work_blocks*run + (len(step.path_quantities)*run_paths if banded else 0))
+        def sweeper(call, run):
+            grid = call.grid()
+            run_paths = run//call.per_path
+            work = call.take(work_blocks*run +
+                             (len(step.path_quantities)*run_paths if banded else 0))
 
             def sweep(index, beta, a, b, outputs):
-                engine.path_jacobian(
-                    beta, columns, grid, paths, per_path, a, request.lengths[a:b],
-                    temperature[a:b], work,
+                call.engine.path_jacobian(
+                    beta, call.columns, grid, call.paths, call.per_path, a, request.lengths[a:b],
+                    call.temperature[a:b], work,
                     boundary_temperature=request.boundary_temperature,
                     boundary_emissivity=request.boundary_emissivity, band_start=request.starts,
                     from_last=request.from_last, asynchronous=True,
                     **{q: outputs[q] for q in request.quantities})
             return sweep
-        # Per level in HBM: beta, the work block(s) and, on the grid, a block per per-level
-        # quantity (which _sweep_runs counts itself with an instrument).
-        level_blocks = 1 + work_blocks
-        if not banded and request.instrument is None:
-            level_blocks += len(per_level)
-        reductions = None if request.instrument is None else \
-            [(q, q, False) for q in request.quantities]
+        products = None if request.instrument is None else \
+            [_Product(q, q, q in JACOBIAN_LEVEL_QUANTITIES) for q in request.quantities]
         values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
-                                  level_blocks=level_blocks, reductions=reductions,
-                                  whole_paths=True)
+                                   level_blocks=1 + work_blocks, products=products,
+                                   grid_outputs=True, whole_paths=True)
         return self._create_path_dataset(values, request)
 
     def compute_flux(self, layer_thickness, surface_temperature, surface_emissivity=1.,
@@ -795,13 +617,9 @@ class Spectroscopy(object):
             i lies between levels i-1 and i), then "wavenumber" ("W m-2 (cm-1)-1") or "band"
             ("W m-2"); "heating_rate" with the level dim ("K day-1 (cm-1)-1" / "K day-1").
         """
-        request = self._flux_request(layer_thickness, surface_temperature, surface_emissivity,
-                                     surface, angles, quantities, band_edges, range_policy)
-        if remove_pedestal is None:
-            remove_pedestal = self.continua_backend == "mt_ckd"
-        per_path, paths = _path_layout(request.shape)
-        temperature = np.ascontiguousarray(self.atmosphere.temperature.ravel(), dtype=np.float64)
-        columns = self.grid.size
+        request = self._flux_request(layer_thickness, surface_temperature,
+                                      surface_emissivity, surface, angles, quantities, band_edges,
+                                      range_policy)
         angles = request.mu.size
         lengths = request.lengths[:, None]/request.mu[None, :]
         bands = request.starts is not None
@@ -809,21 +627,20 @@ class Spectroscopy(object):
         passes = [_Pass(request.surface == "first", ("downward_flux",), ()),
                   _Pass(request.surface == "last", ("upward_flux",), ("surface_flux",))]
 
-        def sweeper(engine, take, run):
-            from .mt_ckd import resident_grid
-            grid = resident_grid(engine, self.grid)
-            carry = take(paths*angles)
+        def sweeper(call, run):
+            grid = call.grid()
+            carry = call.take(call.paths*angles)
             # The fluxes of a run's levels (with bands: before their means) and R, then the flux
             # at the surface: without bands those are the outputs themselves.
-            level = take(run) if bands else None
-            reflection = take(paths) if bands else None
+            level = call.take(run) if bands else None
+            reflection = call.take(call.paths) if bands else None
 
             def sweep(index, beta, a, b, outputs):
                 up = index == 1
                 out = outputs["upward_flux" if up else "downward_flux"]
-                engine.path_flux(
-                    beta, columns, grid, paths, per_path, a, lengths[a:b], request.weight,
-                    temperature[a:b], carry,
+                call.engine.path_flux(
+                    beta, call.columns, grid, call.paths, call.per_path, a, lengths[a:b],
+                    request.weight, call.temperature[a:b], carry,
                     reflection if bands else outputs["surface_flux"],
                     (level if b - a == run else level.rows(b - a)) if bands else out,
                     surface_temperature=request.surface_temperature,
@@ -833,360 +650,23 @@ class Spectroscopy(object):
                     band_start=request.starts, up=up, from_last=passes[index].from_last,
                     asynchronous=True)
             return sweep
+        # Two blocks per level: beta and the fluxes of a level.
         values = self._sweep_runs(request, passes, remove_pedestal, range_policy, sweeper,
-                                  level_blocks=2)
+                                   level_blocks=2)
         return self._create_flux_dataset(self._flux_interfaces(values, request), request)
 
-    def _flux_interfaces(self, values, request):
-        """{quantity: [..., L + 1 or L, W]} of compute_flux from the sweeps' per-level rows (the
-        flux just after each level in sweep order) and the surface rows."""
-        shape = list(request.shape)
-        per_path, paths = _path_layout(request.shape)
-        width = values["downward_flux"].shape[-1]
-        down = np.asarray(values["downward_flux"]).reshape(paths, per_path, width)
-        up = np.asarray(values["upward_flux"]).reshape(paths, per_path, width)
-        surface = np.asarray(values["surface_flux"]).reshape(paths, 1, width)
-        space = np.zeros((paths, 1, width))
-        if request.starts is not None:
-            points = np.diff(request.starts)
-            space[..., points == 0] = np.nan
-        # Sweeping toward level 0 the flux after level l is at interface l, toward level L-1 at
-        # interface l + 1.
-        if request.surface == "first":
-            fluxes = {"downward_flux": np.concatenate([down, space], axis=1),
-                      "upward_flux": np.concatenate([surface, up], axis=1)}
-        else:
-            fluxes = {"downward_flux": np.concatenate([space, down], axis=1),
-                      "upward_flux": np.concatenate([up, surface], axis=1)}
-        if request.starts is not None:
-            _, _, n_per_v = grid_arguments(self.grid)
-            widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
-            fluxes = {q: f*widths for q, f in fluxes.items()}
-        out = {}
-        lead = shape[:-1] + [per_path + 1, width]
-        for q in ("upward_flux", "downward_flux"):
-            if q in request.quantities:
-                out[q] = fluxes[q].reshape(lead)
-        if "heating_rate" in request.quantities:
-            out["heating_rate"] = heating_rate(
-                fluxes["upward_flux"], fluxes["downward_flux"],
-                self.atmosphere.pressure.reshape(paths, per_path),
-                self.atmosphere.temperature.reshape(paths, per_path),
-                request.lengths.reshape(paths, per_path),
-                request.surface).reshape(shape + [width])
-        return out
+    # The host side of the path products is paths.py, whose functions take the Spectroscopy first.
+    _path_request, _radiance_request = paths._path_request, paths._radiance_request
+    _flux_request, _sweep_runs = paths._flux_request, paths._sweep_runs
+    _flux_interfaces = paths._flux_interfaces
+    _create_path_dataset = paths._create_path_dataset
+    _create_flux_dataset = paths._create_flux_dataset
 
-    def _flux_request(self, layer_thickness, surface_temperature, surface_emissivity, surface,
-                      angles, quantities, band_edges, range_policy):
-        """Checks every argument of compute_flux (before anything touches the GPU)."""
-        lengths, shape = self._path_geometry(layer_thickness, "compute_flux", "layer_thickness",
-                                            "layer thicknesses")
-        self._check_level_temperatures()
-        if "heating_rate" in (quantities if not isinstance(quantities, str) else (quantities,)):
-            pressure = self.atmosphere.pressure
-            if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
-                raise ValueError("heating rates need pressures that are finite and > 0.")
-        ts = self._per_path(surface_temperature, "surface_temperature", shape)
-        if not np.all(np.isfinite(ts)) or np.any(ts <= 0.):
-            raise ValueError("surface temperatures must be finite and > 0.")
-        es = self._per_path(surface_emissivity, "surface_emissivity", shape)
-        if not np.all((es >= 0.) & (es <= 1.)):
-            raise ValueError("surface emissivities must lie in [0, 1].")
-        if not (isinstance(surface, str) and surface in FLUX_SURFACES):
-            raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
-        mu, weight = flux_angles(angles)
-        quantities = _selection(quantities, FLUX_QUANTITIES)
-        _check_range_policy(range_policy)
-        edges, starts = self._path_bands(band_edges)
-        return _FluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
-                            starts=starts, surface=surface, mu=mu, weight=weight,
-                            surface_temperature=ts, surface_emissivity=es)
-
-    @staticmethod
-    def _per_path(value, name, shape):
-        """A scalar or one value per path (shaped like the atmosphere without its last
-        dimension), as a flat float64 array of one value per path."""
-        per_path_shape = shape[:-1]
-        values = np.asarray(value, dtype=np.float64)
-        if values.shape not in ((), per_path_shape):
-            raise ValueError(f"{name} has shape {values.shape}: give a scalar or one value "
-                             f"per path, shaped {per_path_shape}.")
-        return np.ascontiguousarray(np.broadcast_to(values, per_path_shape).ravel())
-
-    def _path_geometry(self, path_length, name, argument="path_length", what="path lengths"):
-        """(flat lengths, atmosphere shape): the checks of the path lengths that compute_path,
-        compute_radiance and compute_flux share, made before anything touches the GPU."""
-        if self.group is not None:
-            raise NotImplementedError(f"{name} does not split paths over processes yet "
-                                      "(group is set): the levels of a path would need a sum "
-                                      "over ranks before exp(-tau).")
-        shape = tuple(self.atmosphere.temperature.shape)
-        lengths = np.asarray(path_length, dtype=np.float64)
-        if lengths.shape != shape:
-            raise ValueError(f"{argument} has shape {lengths.shape}, the atmosphere {shape}.")
-        if not np.all(np.isfinite(lengths)) or np.any(lengths < 0.):
-            raise ValueError(f"{what} must be finite and >= 0.")
-        if lengths.size == 0:
-            raise ValueError("the atmosphere has no levels.")
-        return np.ascontiguousarray(lengths.ravel()), shape
-
-    def _check_level_temperatures(self):
-        temperature = self.atmosphere.temperature
-        if not np.all(np.isfinite(temperature)) or np.any(temperature <= 0.):
-            raise ValueError("the atmosphere's temperatures must be finite and > 0.")
-
-    def _path_bands(self, band_edges, instrument=None):
-        """(edges, column starts) of band_edges, or (None, None); checks `instrument` too."""
-        if instrument is not None:
-            from .instrument import Instrument
-            if band_edges is not None:
-                raise ValueError("give band_edges or instrument, not both.")
-            if not isinstance(instrument, Instrument):
-                raise ValueError(f"instrument must be an Instrument, not {type(instrument)}.")
-            if self.grid.size > 1 and not np.all(np.diff(self.grid) > 0.):
-                raise ValueError("instrument channels need an increasing grid.")
-        if band_edges is None:
-            return None, None
-        if self.grid.size > 1 and not np.all(np.diff(self.grid) > 0.):
-            raise ValueError("band means need an increasing grid.")
-        starts = band_columns(self.grid, band_edges)
-        return np.asarray(band_edges, dtype=np.float64), starts
-
-    def _path_request(self, path_length, quantities, band_edges, cumulative, range_policy,
-                      instrument=None):
-        """Checks every argument of compute_path (before anything touches the GPU)."""
-        lengths, shape = self._path_geometry(path_length, "compute_path")
-        quantities = _selection(quantities, PATH_QUANTITIES)
-        if not (cumulative is None or (isinstance(cumulative, str) and
-                                       cumulative in PATH_CUMULATIVE)):
-            raise ValueError(f"cumulative must be one of {PATH_CUMULATIVE}, not {cumulative!r}.")
-        _check_range_policy(range_policy)
-        edges, starts = self._path_bands(band_edges, instrument)
-        return _PathRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
-                            starts=starts, cumulative=cumulative, instrument=instrument)
-
-    def _radiance_request(self, path_length, boundary_temperature, boundary_emissivity,
-                          direction, quantities, band_edges, cumulative, range_policy,
-                          instrument=None, names=RADIANCE_QUANTITIES, caller="compute_radiance"):
-        """Checks every argument of compute_radiance (before anything touches the GPU);
-        compute_jacobian's too, with its `names`."""
-        lengths, shape = self._path_geometry(path_length, caller)
-        self._check_level_temperatures()
-        if boundary_temperature is None:
-            boundary = None
-        else:
-            boundary = self._per_path(boundary_temperature, "boundary_temperature", shape)
-            if not np.all(np.isfinite(boundary)) or np.any(boundary <= 0.):
-                raise ValueError("boundary temperatures must be finite and > 0.")
-        emissivity = self._per_path(boundary_emissivity, "boundary_emissivity", shape)
-        if not np.all((emissivity >= 0.) & (emissivity <= 1.)):
-            raise ValueError("boundary emissivities must lie in [0, 1].")
-        if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
-            raise ValueError(f"direction must be one of {RADIANCE_DIRECTIONS}, not {direction!r}.")
-        quantities = _selection(quantities, names)
-        if not isinstance(cumulative, (bool, np.bool_)):
-            raise ValueError(f"cumulative must be True or False, not {cumulative!r}.")
-        _check_range_policy(range_policy)
-        if band_edges is not None and "brightness_temperature" in quantities:
-            raise ValueError("brightness_temperature is only available on the grid: band means "
-                             "are formed of the radiance alone.")
-        edges, starts = self._path_bands(band_edges, instrument)
-        return _RadianceRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
-                                starts=starts, cumulative=bool(cumulative), instrument=instrument,
-                                from_last=direction == "toward_first",
-                                boundary_temperature=boundary, boundary_emissivity=emissivity)
-
-    def _sweep_runs(self, request, passes, remove_pedestal, range_policy, sweeper,
-                    level_blocks=1, reductions=None, whole_paths=False):
-        """{quantity: array [levels or paths, columns or bands]}: the "total" block of a run of
-        levels at a time, queued like _compute_levels queues it, then the path kernels on it --
-        for each of `passes` (_Pass: its order, and the quantities it returns per level and per
-        path) in turn, every pass over all levels.
-        sweeper(engine, take, run) returns sweep(index, beta, a, b, outputs), which queues the
-        path kernels of pass `index` on the levels [a, b) and their block `beta`, with `outputs`
-        {quantity of any pass: DeviceSpectra}; take(rows, n=n) hands it blocks of its own for the
-        call (carries, scratch).  level_blocks: blocks of [run, n] counted against
-        device_output_limit.  A pass that starts on the run the previous pass ended on finds
-        that run's block still in HBM and does not compute it again: sweeps of a call with
-        several passes must leave beta as they found it.
-        reductions: with request.instrument, [(result, quantity of a pass, transmittance)]: the
-        sweeps write their quantities on the grid into blocks of their own, and
-        lbl_instrument_apply reduces those rows into [rows, channels] blocks (of exp(-value)
-        with `transmittance`), which alone go to the host as `result`.  Each per-level grid
-        block counts against device_output_limit.
-        whole_paths: every run is a whole number of paths (_cut_runs), for sweeps that carry
-        nothing from run to run."""
-        temperature = self.atmosphere.temperature.ravel()
-        pressure = self.atmosphere.pressure.ravel()
-        mole_fractions = {name: x.ravel() for name, x in self.atmosphere.gases.items()}
-        levels = temperature.size
-        per_path, paths = _path_layout(request.shape)
-        v0, vn, n_per_v = grid_arguments(self.grid)
-        n = (vn - v0)*n_per_v
-        columns = self.grid.size
-        instrument = getattr(request, "instrument", None)
-        level_quantities = [q for step in passes for q in step.level_quantities]
-        path_quantities = [q for step in passes for q in step.path_quantities]
-        if instrument is not None:
-            level_blocks += len(level_quantities)
-        # Runs of consecutive levels when the blocks would not fit: the sweep carries over in HBM.
-        run, runs = _cut_runs(levels, per_path, level_blocks*n*8, self.device_output_limit,
-                              whole_paths)
-        starts = request.starts
-        width = columns if starts is None else starts.size - 1
-        if instrument is not None:
-            width = len(instrument)
-
-        engine, present, heavy = self._present_gases(temperature, pressure, mole_fractions)
-        if engine is None:
-            from .engine import default_engine
-            engine = default_engine(self.device)
-        if heavy is not None:
-            present = [heavy] + present[:-1]
-        if instrument is None:
-            results = {q: engine.host_array((levels, width)) for q in level_quantities}
-            results.update({q: engine.host_array((paths, width)) for q in path_quantities})
-        else:
-            from .instrument import resident_instrument
-            handle = resident_instrument(engine, instrument, self.grid)
-            level_reductions = [r for r in reductions if r[1] in level_quantities]
-            path_reductions = [r for r in reductions if r[1] in path_quantities]
-            results = {r[0]: engine.host_array((levels, width)) for r in level_reductions}
-            results.update({r[0]: engine.host_array((paths, width)) for r in path_reductions})
-        # One block of `run` levels for beta (and for each per-level output) serves every run;
-        # the shorter last run uses its leading rows.  Together with the sweeper's blocks and the
-        # per-path outputs that is all this call holds in HBM.
-        band_width = width if starts is not None else n
-        taken = []
-
-        def take(rows, columns=n):
-            block = engine.blocks.take(rows, columns)
-            taken.append(block)
-            return block
-        with engine.pipeline:
-            try:
-                sweep = sweeper(engine, take, run)
-                beta = take(run, n)
-                outputs = {q: take(run, band_width) for q in level_quantities}
-                outputs.update({q: take(paths, band_width) for q in path_quantities})
-                if instrument is not None:
-                    channels = {r[0]: take(run, width) for r in level_reductions}
-                    channels.update({r[0]: take(paths, width) for r in path_reductions})
-                resident = None
-                for index, step in enumerate(passes):
-                    for a, b in (runs[::-1] if step.from_last else runs):
-                        kept = (a, b) == resident
-                        if resident is not None and not kept:
-                            # The previous run's block and outputs are written again below: what
-                            # still reads them -- its sweep, its copies to the host -- is done
-                            # first.
-                            engine.synchronize()
-                        rows = beta if b - a == run else beta.rows(b - a)
-                        if not kept:
-                            queue = _Queue(self, temperature[a:b], pressure[a:b],
-                                           {k: v[a:b] for k, v in mole_fractions.items()},
-                                           remove_pedestal, range_policy, self.delivery_pieces)
-                            total = _Sum(engine, b - a, n, buffer=rows)
-                            if present:
-                                self._queue_total(queue, engine, present, heavy, total, None)
-                            else:
-                                engine.fill_zero(total.buffer, asynchronous=True)
-                        resident = (a, b)
-                        run_outputs = {q: outputs[q] if b - a == run else outputs[q].rows(b - a)
-                                       for q in level_quantities}
-                        run_outputs.update({q: outputs[q] for q in path_quantities})
-                        sweep(index, rows, a, b, run_outputs)
-                        if instrument is not None:
-                            for q, source, transmittance in level_reductions:
-                                if source not in step.level_quantities:
-                                    continue
-                                engine.instrument_apply(run_outputs[source], b - a, handle,
-                                                        channels[q], transmittance=transmittance,
-                                                        asynchronous=True)
-                                channels[q].rows(b - a).to_host_into(results[q][a:b], width,
-                                                                     asynchronous=True)
-                            continue
-                        for q in step.level_quantities:
-                            run_outputs[q].to_host_into(results[q][a:b], width, asynchronous=True)
-                if instrument is not None:
-                    for q, source, transmittance in path_reductions:
-                        engine.instrument_apply(outputs[source], paths, handle, channels[q],
-                                                transmittance=transmittance, asynchronous=True)
-                        channels[q].to_host_into(results[q], width, asynchronous=True)
-                for q in path_quantities if instrument is None else ():
-                    outputs[q].to_host_into(results[q], width, asynchronous=True)
-                engine.synchronize()
-            except BaseException:
-                try:
-                    engine.cancel_deferred()
-                    engine.synchronize()
-                except Exception:       # the first error is the one to report
-                    pass
-                raise
-            finally:
-                for block in taken:
-                    engine.blocks.give(block)
-        return results
-
-    def _create_path_dataset(self, values, request):
-        """compute_path's, compute_radiance's and compute_jacobian's result from {quantity:
-        [paths or levels, columns or bands]}, in the conventions of _create_output_dataset:
-        per level when cumulative and for the per-level Jacobians."""
-        axis = _spectral_axis(request)
-        variables = {}
-        for q in request.quantities:
-            dims, shape = list(self.atmosphere.dims), list(request.shape)
-            if not (request.cumulative or q in JACOBIAN_LEVEL_QUANTITIES):
-                dims, shape = dims[:-1], shape[:-1]
-            variables[q] = (dims + [axis], np.asarray(values[q]).reshape(shape + [-1]),
-                            _PATH_UNITS[q])
-        return self._path_variables(variables, request)
-
-    def _create_flux_dataset(self, values, request):
-        """compute_flux's result from {quantity: [..., interfaces or levels, columns or bands]}:
-        fluxes on the "interface" dim in place of the atmosphere's last, heating rates on it."""
-        dims = list(self.atmosphere.dims)
-        axis = "wavenumber" if request.edges is None else "band"
-        variables = {}
-        for q in request.quantities:
-            here = dims + [axis] if q == "heating_rate" else dims[:-1] + ["interface", axis]
-            variables[q] = (here, values[q], _FLUX_UNITS[q][request.edges is not None])
-        return self._path_variables(variables, request)
-
-    def _path_variables(self, variables, request):
-        """{name: (dims, values, units)} with the grid's, the bands' or the channels'
-        coordinates, in the conventions of _create_output_dataset."""
-        instrument = getattr(request, "instrument", None)
-        if instrument is not None:
-            lower, upper = instrument.window()
-            start, end = instrument.columns(self.grid)
-            coords = {"channel_center": (instrument.centers, {"units": "cm-1"}),
-                      "channel_lower": (lower, {"units": "cm-1"}),
-                      "channel_upper": (upper, {"units": "cm-1"}),
-                      "channel_points": (end - start, {})}
-        elif request.edges is None:
-            coords = {"wavenumber": (self.grid, {"units": "cm-1"})}
-        else:
-            coords = {"band_lower": (request.edges[:-1], {"units": "cm-1"}),
-                      "band_upper": (request.edges[1:], {"units": "cm-1"}),
-                      "band_points": (np.diff(request.starts), {})}
-        xarray = _optional_xarray()
-        if xarray is None:
-            out = {name: value for name, (value, _) in coords.items()}
-            out.update({q: v for q, (_, v, _) in variables.items()})
-            return out
-        DataArray, Dataset = xarray.DataArray, xarray.Dataset
-        axis = _spectral_axis(request)
-        return Dataset(
-            data_vars={q: DataArray(v, dims=dims, attrs={"units": units})
-                       for q, (dims, v, units) in variables.items()},
-            coords={name: DataArray(value, dims=(axis,), attrs=attrs)
-                    for name, (value, attrs) in coords.items()})
-
-    def _present_gases(self, temperature, pressure, mole_fractions):
+    def _present_gases(self, temperature, pressure, mole_fractions, total=False):
         """(engine, gases, heaviest): the gases of the atmosphere that some mechanism computes, as
-        (name, Gas or None, continua, cross-section or None), lightest lines table first; the
-        last entry when it has lines; the engine they share (None without any)."""
+        (name, Gas or None, continua, cross-section or None), lightest lines table first (with
+        `total`: in "total" order, the heaviest first and the others behind it as they were);
+        the heaviest, when it has lines; the engine they share (None without any)."""
         engine = None
         present = []
         for name in self.atmosphere.gases:
@@ -1220,6 +700,8 @@ class Spectroscopy(object):
         # (profiles/r03_ab_api.txt).
         present.sort(key=lambda entry: entry[1].num_lines if entry[1] is not None else -1)
         heavy = present[-1] if present and present[-1][1] is not None else None
+        if total and heavy is not None:
+            present = [heavy] + present[:-1]
         return engine, present, heavy
 
     def _queue_total(self, queue, engine, present, heavy, total, deliver):
@@ -1280,10 +762,37 @@ class Spectroscopy(object):
         # queues behind everything is the one that counts.)
         return True
 
-    def _compute_levels(self, temperature, pressure, mole_fractions, mode, remove_pedestal,
-                        range_policy):
-        """The three mechanism slots for a flat list of levels: {variable name: array with the
-        levels as leading dimension} ("total" under mode "total")."""
+    def total_into(self, block, a, b, remove_pedestal, range_policy="reference", deliver=None,
+                   gases=None):
+        """Queues the "total" absorption of the flat levels [a, b) of the atmosphere into `block`
+        (DeviceSpectra [b - a, >= padded grid]) the way compute_absorption("total") does: the
+        heaviest gas first in line and last to add (_queue_total), or zeros where no mechanism
+        computes any gas.  The block is complete behind what is queued (Engine.synchronize).
+        deliver: as for _queue_total, whose value is returned (True: `deliver` was not handed the
+        finished block).  gases: what _present_gases(..., total=True) returned, for callers that
+        queue several ranges in one call."""
+        temperature = self.atmosphere.temperature.ravel()[a:b]
+        pressure = self.atmosphere.pressure.ravel()[a:b]
+        mole_fractions = {name: x.ravel()[a:b] for name, x in self.atmosphere.gases.items()}
+        if gases is None:
+            gases = self._present_gases(temperature, pressure, mole_fractions, total=True)
+        _, present, heavy = gases
+        engine = block.engine
+        if not present:
+            engine.fill_zero(block, asynchronous=True)
+            return True
+        queue = _Queue(self, temperature, pressure, mole_fractions, remove_pedestal, range_policy,
+                       self.delivery_pieces)
+        return self._queue_total(queue, engine, present, heavy,
+                                 _Sum(engine, b - a, block.shape[1], buffer=block), deliver)
+
+    def _compute_levels(self, a, b, mode, remove_pedestal, range_policy):
+        """The three mechanism slots for the flat levels [a, b) of the atmosphere: {variable
+        name: array with the levels as leading dimension} ("total" under mode "total")."""
+        temperature = self.atmosphere.temperature.ravel()[a:b]
+        pressure = self.atmosphere.pressure.ravel()[a:b]
+        # Every gas at every level, the dictionary the continua read (spectroscopy.py:173).
+        mole_fractions = {name: x.ravel()[a:b] for name, x in self.atmosphere.gases.items()}
         levels = temperature.size
         v0, vn, n_per_v = grid_arguments(self.grid)
         n = (vn - v0)*n_per_v
@@ -1308,19 +817,13 @@ class Spectroscopy(object):
         zero_fills = []         # row views of results that no mechanism writes
         results = {}            # gas -> its finished array, being filled by queued copies
         in_flight = []          # blocks in HBM to release once everything has arrived
-        total = None
-        engine, present, heavy = self._present_gases(temperature, pressure, mole_fractions)
-        if heavy is not None and mode == "total":
-            present = [heavy] + present[:-1]
+        gases = self._present_gases(temperature, pressure, mole_fractions, total=mode == "total")
+        engine, present, heavy = gases
 
         # ("all" is bound by the link -- four 40 MB blocks per level for H2O + CO2 -- and its
         # copies are queued back to back as they are: cutting the last one into pieces only
         # puts gaps into that queue, 3.6 -> 4.1 ms per call.)
         pieces = 1 if mode == "all" else self.delivery_pieces
-
-        queue = _Queue(self, temperature, pressure, mole_fractions, remove_pedestal, range_policy,
-                       pieces)
-        lines_into, slots_into = queue.lines_into, queue.slots_into
 
         # Everything from the first queued call to the final wait is one pipeline on the engine:
         # calls add into shared blocks in a fixed order and one of them may be kept back, so
@@ -1352,11 +855,15 @@ class Spectroscopy(object):
                 elif mode == "total" and present:
                     total = _Sum(engine, levels, n)
                     results["total"] = engine.host_array((levels, columns))
-                    if self._queue_total(queue, engine, present, heavy, total, results["total"]):
+                    if self.total_into(total.buffer, a, b, remove_pedestal, range_policy,
+                                       deliver=results["total"], gases=gases):
                         in_flight.append(total.into(results["total"]))
                     else:
                         in_flight.append(total)
                 else:
+                    queue = _Queue(self, temperature, pressure, mole_fractions, remove_pedestal,
+                                   range_policy, pieces)
+                    lines_into, slots_into = queue.lines_into, queue.slots_into
                     for index, (name, gas, continua_here, cross) in enumerate(present):
                         last = index + 1 == len(present)
                         if mode == "gas":

@@ -14,37 +14,21 @@ Reports
     python scripts/flux_timing.py [--out FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/flux_timing.py
 """
-import argparse
-import json
-import os
-from pathlib import Path
-import sys
 import time
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT))
-os.environ.setdefault("PYLBL_MT_CKD", str(ROOT / "tests" / "golden" / "mt_ckd_bands.npz"))
+from timing_common import SURFACE, median_wall, parser, resident_total, setup, \
+    write_report
 
-from pylbl_amd import MemoryDatabase, Spectroscopy, synthetic  # noqa: E402
-from pylbl_amd import spectroscopy  # noqa: E402
-from pylbl_amd.mt_ckd import resident_grid  # noqa: E402
-
-
-def wall(call):
-    call()
-    walls = []
-    for _ in range(3):
-        start = time.perf_counter()
-        call()
-        walls.append(time.perf_counter() - start)
-    return float(np.median(walls))*1e3
+from pylbl_amd import synthetic
+from pylbl_amd.mt_ckd import resident_grid
+from pylbl_amd.spectroscopy import flux_angles
 
 
 def emulate(spec, thickness, surface, edges, angles):
     """compute_flux's band fluxes (surface at level 0, eps = 1) from 2K compute_radiance calls."""
-    mu, weight = spectroscopy.flux_angles(angles)
+    mu, weight = flux_angles(angles)
     down = up = 0.
     for k in range(mu.size):
         s = thickness/mu[k]
@@ -58,46 +42,16 @@ def emulate(spec, thickness, surface, edges, angles):
 
 
 def main():
-    parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    parser.add_argument("--out", default=None, help="also write the report (JSON) here")
-    parser.add_argument("--levels", type=int, default=64)
-    parser.add_argument("--angles", type=int, default=3)
-    args = parser.parse_args()
-
-    gases = ("H2O", "CO2", "O3")
-    tables = [synthetic.line_table(name, 1., 3000.) for name in gases]
-    full = synthetic.standard_atmosphere(args.levels)
-    atmos = synthetic.Atmos(p=full.p, t=full.t, vmr={k: full.vmr[k] for k in gases})
-    grid = np.arange(1., 3000., 0.001)
-    spec = Spectroscopy(atmos, grid, MemoryDatabase(tables))
-    # The layer thicknesses of the scale-height altitudes [m]; level 0 at the surface.
-    z = -7000.*np.log(full.p/101325.)
-    thickness = np.gradient(z)
-    temperature = np.ascontiguousarray(full.t, dtype=np.float64)
-    surface = 290.
-    edges = np.arange(1., 3000.5, 1.)
-    starts = np.searchsorted(grid, edges)
-    mu, weight = spectroscopy.flux_angles(args.angles)
+    arguments = parser(__doc__)
+    arguments.add_argument("--angles", type=int, default=3)
+    args = arguments.parse_args()
+    spec, grid, thickness, temperature, edges, starts, report = setup(args.levels)
+    surface = SURFACE
+    mu, weight = flux_angles(args.angles)
     lengths = thickness[:, None]/mu
-    report = {"levels": args.levels, "points": int(grid.size), "angles": args.angles,
-              "lines": [int(t.num_lines) for t in tables]}
+    report["angles"] = args.angles
 
-    # The "total" block of all levels in HBM, queued as compute_flux queues it.
-    temperature_flat = spec.atmosphere.temperature.ravel()
-    pressure = spec.atmosphere.pressure.ravel()
-    fractions = {k: v.ravel() for k, v in spec.atmosphere.gases.items()}
-    engine, present, heavy = spec._present_gases(temperature_flat, pressure, fractions)
-    if heavy is not None:
-        present = [heavy] + present[:-1]
-    v0, vn, n_per_v = synthetic.grid_arguments(grid)
-    n = (vn - v0)*n_per_v
-    beta = engine.blocks.take(args.levels, n)
-    with engine.pipeline:
-        queue = spectroscopy._Queue(spec, temperature_flat, pressure, fractions, True,
-                                    "reference", spec.delivery_pieces)
-        spec._queue_total(queue, engine, present, heavy,
-                          spectroscopy._Sum(engine, args.levels, n, buffer=beta), None)
-        engine.synchronize()
+    engine, beta, n = resident_total(spec)
     handle = resident_grid(engine, spec.grid)
     carry = engine.blocks.take(mu.size, n)
     reflection = engine.blocks.take(1, n)
@@ -112,11 +66,12 @@ def main():
             reflection, level, surface_temperature=[surface], surface_emissivity=[1.],
             flux=band_flux if bands else None, surface_flux=band_surface if bands and up else None,
             band_start=starts if bands else None, up=up, from_last=not up)
+    down_sweep = flux(False, False)
     sweeps = {
         "radiance": lambda: engine.path_radiance(
             beta, grid.size, handle, 1, args.levels, 0, thickness, temperature, rad,
             boundary_temperature=[surface], radiance=rad),
-        "flux_down": flux(False, False),
+        "flux_down": down_sweep,
         "flux_up": flux(True, False),
         "flux_down_bands": flux(False, True),
         "flux_up_bands": flux(True, True),
@@ -125,7 +80,7 @@ def main():
         times = []
         for _ in range(11):
             if label.startswith("flux_up"):
-                flux(False, False)()            # R for the up sweep, outside the timing
+                down_sweep()                    # R for the up sweep, outside the timing
             start = time.perf_counter()
             sweep()
             times.append(time.perf_counter() - start)
@@ -134,11 +89,11 @@ def main():
         engine.blocks.give(block)
 
     # End to end with 1 cm-1 bands.
-    report["compute_flux_bands_ms"] = wall(lambda: spec.compute_flux(
+    report["compute_flux_bands_ms"] = 1e3*median_wall(lambda: spec.compute_flux(
         thickness, surface, angles=args.angles, band_edges=edges))
-    report["compute_radiance_bands_ms"] = wall(lambda: spec.compute_radiance(
+    report["compute_radiance_bands_ms"] = 1e3*median_wall(lambda: spec.compute_radiance(
         thickness, boundary_temperature=surface, band_edges=edges))
-    report["emulation_2K_compute_radiance_ms"] = wall(lambda: emulate(
+    report["emulation_2K_compute_radiance_ms"] = 1e3*median_wall(lambda: emulate(
         spec, thickness, surface, edges, args.angles))
     report["compute_flux_over_compute_radiance"] = \
         report["compute_flux_bands_ms"]/report["compute_radiance_bands_ms"]
@@ -147,6 +102,7 @@ def main():
 
     out = spec.compute_flux(thickness, surface, angles=args.angles, band_edges=edges)
     up, down = emulate(spec, thickness, surface, edges, args.angles)
+    _, _, n_per_v = synthetic.grid_arguments(grid)
     width = np.diff(starts)/float(n_per_v)
     worst = 0.
     for got, levels in ((out["upward_flux"][1:], up), (out["downward_flux"][:-1], down)):
@@ -154,10 +110,7 @@ def main():
         ok = np.isfinite(expect) & (expect != 0.)
         worst = max(worst, float(np.max(np.abs(got[ok] - expect[ok])/np.abs(expect[ok]))))
     report["emulation_max_relative_difference"] = worst
-    print(json.dumps(report, indent=1))
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(json.dumps(report, indent=1) + "\n")
+    write_report(report, args.out)
 
 
 if __name__ == "__main__":

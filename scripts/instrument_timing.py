@@ -15,63 +15,22 @@ The kernel times come from a run under rocprofv3:
     python scripts/instrument_timing.py [--out FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/instrument_timing.py
 """
-import argparse
-import json
-import os
-from pathlib import Path
-import sys
-import time
-
 import numpy as np
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT))
-os.environ.setdefault("PYLBL_MT_CKD", str(ROOT / "tests" / "golden" / "mt_ckd_bands.npz"))
+from timing_common import PEAK, SURFACE, best_of, iasi_like, median_wall, parser, \
+    resident_total, setup, write_report
 
-from pylbl_amd import Instrument, MemoryDatabase, Spectroscopy, synthetic  # noqa: E402
-from pylbl_amd import spectroscopy  # noqa: E402
-from pylbl_amd.instrument import resident_instrument  # noqa: E402
-
-PEAK = 6.3e12       # bytes/s: in-order HBM sweeps on the MI355X
+from pylbl_amd import Instrument
+from pylbl_amd.instrument import resident_instrument
 
 
 def main():
-    parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    parser.add_argument("--out", default=None, help="also write the report (JSON) here")
-    parser.add_argument("--levels", type=int, default=64)
-    args = parser.parse_args()
+    args = parser(__doc__).parse_args()
+    spec, grid, lengths, _, edges, _, report = setup(args.levels)
+    surface = SURFACE
+    instrument = iasi_like()
 
-    gases = ("H2O", "CO2", "O3")
-    tables = [synthetic.line_table(name, 1., 3000.) for name in gases]
-    full = synthetic.standard_atmosphere(args.levels)
-    atmos = synthetic.Atmos(p=full.p, t=full.t, vmr={k: full.vmr[k] for k in gases})
-    grid = np.arange(1., 3000., 0.001)
-    spec = Spectroscopy(atmos, grid, MemoryDatabase(tables))
-    # A nadir path: the layer thicknesses of the scale-height altitudes [m].
-    z = -7000.*np.log(full.p/101325.)
-    lengths = np.gradient(z)
-    surface = 290.
-    edges = np.arange(1., 3000.5, 1.)
-    instrument = Instrument.gaussian(645. + 0.25*np.arange(8461), 0.5, half_width=1.5)
-    report = {"levels": args.levels, "points": int(grid.size),
-              "lines": [int(t.num_lines) for t in tables]}
-
-    # The "total" block of all levels in HBM, queued as compute_radiance queues it.
-    temperature_flat = spec.atmosphere.temperature.ravel()
-    pressure = spec.atmosphere.pressure.ravel()
-    fractions = {k: v.ravel() for k, v in spec.atmosphere.gases.items()}
-    engine, present, heavy = spec._present_gases(temperature_flat, pressure, fractions)
-    if heavy is not None:
-        present = [heavy] + present[:-1]
-    v0, vn, n_per_v = synthetic.grid_arguments(grid)
-    n = (vn - v0)*n_per_v
-    beta = engine.blocks.take(args.levels, n)
-    with engine.pipeline:
-        queue = spectroscopy._Queue(spec, temperature_flat, pressure, fractions, True,
-                                    "reference", spec.delivery_pieces)
-        spec._queue_total(queue, engine, present, heavy,
-                          spectroscopy._Sum(engine, args.levels, n, buffer=beta), None)
-        engine.synchronize()
+    engine, beta, n = resident_total(spec)
     handle = resident_instrument(engine, instrument, spec.grid)
     out = engine.blocks.take(args.levels, len(instrument))
     start, end = instrument.columns(grid)
@@ -79,12 +38,7 @@ def main():
     read = args.levels*covered*8
     report["channels"] = len(instrument)
     report["apply_bytes_read"] = read
-    times = []
-    for _ in range(11):
-        begin = time.perf_counter()
-        engine.instrument_apply(beta, args.levels, handle, out)
-        times.append(time.perf_counter() - begin)
-    best = min(times[1:])
+    best = best_of(lambda: engine.instrument_apply(beta, args.levels, handle, out))
     report["apply_ms"] = best*1e3
     report["apply_fraction_of_6.3TBps"] = read/best/PEAK
 
@@ -104,23 +58,13 @@ def main():
     for block in (beta, out):
         engine.blocks.give(block)
 
-    for label, call in (("compute_radiance_instrument_ms", lambda: spec.compute_radiance(
-                             lengths, boundary_temperature=surface, instrument=instrument)),
-                        ("compute_radiance_bands_ms", lambda: spec.compute_radiance(
-                             lengths, boundary_temperature=surface, band_edges=edges))):
-        call()
-        walls = []
-        for _ in range(3):
-            begin = time.perf_counter()
-            call()
-            walls.append(time.perf_counter() - begin)
-        report[label] = float(np.median(walls))*1e3
+    report["compute_radiance_instrument_ms"] = 1e3*median_wall(lambda: spec.compute_radiance(
+        lengths, boundary_temperature=surface, instrument=instrument))
+    report["compute_radiance_bands_ms"] = 1e3*median_wall(lambda: spec.compute_radiance(
+        lengths, boundary_temperature=surface, band_edges=edges))
     report["instrument_over_bands"] = report["compute_radiance_instrument_ms"] / \
         report["compute_radiance_bands_ms"]
-    print(json.dumps(report, indent=1))
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(json.dumps(report, indent=1) + "\n")
+    write_report(report, args.out)
 
 
 if __name__ == "__main__":

@@ -21,83 +21,26 @@ Reports
     python scripts/jacobian_timing.py [--out FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/jacobian_timing.py --kernels-only
 """
-import argparse
-import json
-import os
-from pathlib import Path
-import sys
 import time
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT))
-os.environ.setdefault("PYLBL_MT_CKD", str(ROOT / "tests" / "golden" / "mt_ckd_bands.npz"))
+from timing_common import PEAK, SURFACE, best_of, iasi_like, median_wall, parser, \
+    resident_total, setup, write_report
 
-from pylbl_amd import MemoryDatabase, Spectroscopy, synthetic  # noqa: E402
-from pylbl_amd import spectroscopy  # noqa: E402
-from pylbl_amd.instrument import Instrument  # noqa: E402
-from pylbl_amd.mt_ckd import resident_grid  # noqa: E402
-
-PEAK = 6.3e12       # bytes/s: in-order HBM sweeps on the MI355X
-
-
-def best_of(call, count=10):
-    times = []
-    for _ in range(count + 1):
-        start = time.perf_counter()
-        call()
-        times.append(time.perf_counter() - start)
-    return min(times[1:])
-
-
-def median_wall(call, count=3):
-    call()
-    walls = []
-    for _ in range(count):
-        start = time.perf_counter()
-        call()
-        walls.append(time.perf_counter() - start)
-    return float(np.median(walls))
+from pylbl_amd.mt_ckd import resident_grid
 
 
 def main():
-    parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    parser.add_argument("--out", default=None, help="also write the report (JSON) here")
-    parser.add_argument("--levels", type=int, default=64)
-    parser.add_argument("--kernels-only", action="store_true",
-                        help="the sweeps on the resident block alone (for a kernel trace)")
-    args = parser.parse_args()
-
-    gases = ("H2O", "CO2", "O3")
-    tables = [synthetic.line_table(name, 1., 3000.) for name in gases]
-    full = synthetic.standard_atmosphere(args.levels)
-    atmos = synthetic.Atmos(p=full.p, t=full.t, vmr={k: full.vmr[k] for k in gases})
-    grid = np.arange(1., 3000., 0.001)
-    spec = Spectroscopy(atmos, grid, MemoryDatabase(tables))
-    z = -7000.*np.log(full.p/101325.)
-    lengths = np.gradient(z)
-    temperature = np.ascontiguousarray(full.t, dtype=np.float64)
-    surface = 290.
+    arguments = parser(__doc__)
+    arguments.add_argument("--kernels-only", action="store_true",
+                           help="the sweeps on the resident block alone (for a kernel trace)")
+    args = arguments.parse_args()
+    spec, grid, lengths, temperature, _, _, report = setup(args.levels)
+    surface = SURFACE
     levels = args.levels
-    report = {"levels": levels, "points": int(grid.size),
-              "lines": [int(t.num_lines) for t in tables]}
 
-    # The "total" block of all levels in HBM, queued as compute_jacobian queues it.
-    pressure = spec.atmosphere.pressure.ravel()
-    fractions = {k: v.ravel() for k, v in spec.atmosphere.gases.items()}
-    engine, present, heavy = spec._present_gases(temperature, pressure, fractions)
-    if heavy is not None:
-        present = [heavy] + present[:-1]
-    v0, vn, n_per_v = synthetic.grid_arguments(grid)
-    n = (vn - v0)*n_per_v
-    beta = engine.blocks.take(levels, n)
-    with engine.pipeline:
-        queue = spectroscopy._Queue(spec, temperature, pressure, fractions, True, "reference",
-                                    spec.delivery_pieces)
-        spec._queue_total(queue, engine, present, heavy,
-                          spectroscopy._Sum(engine, levels, n, buffer=beta), None)
-        engine.synchronize()
+    engine, beta, n = resident_total(spec)
     handle = resident_grid(engine, spec.grid)
     carry, rad = engine.blocks.take(1, n), engine.blocks.take(1, n)
     work, depth, dtemp = (engine.blocks.take(levels, n) for _ in range(3))
@@ -126,7 +69,7 @@ def main():
         report[f"sweep_{label}_bytes"] = streams*block_bytes
         report[f"sweep_{label}_fraction_of_6.3TBps"] = streams*block_bytes/best/PEAK
     if args.kernels_only:
-        print(json.dumps(report, indent=1))
+        write_report(report)
         return
 
     # The GPU against the float64 numpy mirror, on every 16th column.
@@ -148,7 +91,7 @@ def main():
         engine.blocks.give(block)
 
     # End to end with the IASI-like instrument.
-    instrument = Instrument.gaussian(645. + 0.25*np.arange(8461), 0.5, half_width=1.5)
+    instrument = iasi_like()
     report["channels"] = len(instrument)
     quantities = ("radiance", "optical_depth_jacobian", "temperature_jacobian")
     report["compute_jacobian_instrument_ms"] = 1e3*median_wall(lambda: spec.compute_jacobian(
@@ -181,10 +124,7 @@ def main():
     scale = np.nanmax(np.abs(analytic), axis=0)
     report["finite_difference_max_difference_of_channel_max"] = float(
         np.nanmax(np.abs(differences - analytic)/scale))
-    print(json.dumps(report, indent=1))
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(json.dumps(report, indent=1) + "\n")
+    write_report(report, args.out)
 
 
 if __name__ == "__main__":
