@@ -41,7 +41,7 @@ def api_leg(engine, tables, atmos, v_lo, v_hi, dv, device_step_ms, repeats=9):
                        f"continua, host arrays returned", "formats": {},
            "d2h_pinned_gbs_measured": link_gbs}
     # Arrays that cross the link per format; in "all" a mechanism slot no back end fills is zeroed
-    # on the host (spectroscopy._zero_in_background) and never travels.
+    # on the host (absorption._Results.wait) and never travels.
     filled = 0
     for f in formulas:
         data = spec._molecule(f)

@@ -3,12 +3,14 @@ compute_jacobian -- on the host: their quantities and units, the checks of their
 request per call, made before anything touches the GPU), the run loop that sweeps the "total"
 absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
 cuts (_level_bytes) and the assembly of the results.  The sweeps themselves are the kernels of
-csrc/path.h behind Engine.path_*; the "total" block is queued by Spectroscopy.total_into.
+csrc/path.h behind Engine.path_*; the "total" block is queued by Spectroscopy.total_into
+(absorption.py, whose pipeline guard the run loop shares).
 """
 from collections import namedtuple
 
 import numpy as np
 
+from .absorption import _Levels, pipeline, present_gases
 from .synthetic import grid_arguments
 
 # Levels of one run at most: what one call of the continuum group kernels takes
@@ -357,10 +359,8 @@ def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, l
     paths (_cut_runs), for sweeps that carry nothing from run to run."""
     if remove_pedestal is None:
         remove_pedestal = spec.continua_backend == "mt_ckd"
-    temperature = spec.atmosphere.temperature.ravel()
-    pressure = spec.atmosphere.pressure.ravel()
-    mole_fractions = {name: x.ravel() for name, x in spec.atmosphere.gases.items()}
-    levels = temperature.size
+    whole = _Levels(spec, 0, spec.atmosphere.temperature.size, remove_pedestal, range_policy)
+    temperature, levels = whole.temperature, whole.count
     per_path, paths = _path_layout(request.shape)
     v0, vn, n_per_v = grid_arguments(spec.grid)
     n = (vn - v0)*n_per_v
@@ -379,8 +379,8 @@ def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, l
     band_width = n if starts is None else starts.size - 1
     width = spec.grid.size if starts is None else starts.size - 1
 
-    gases = spec._present_gases(temperature, pressure, mole_fractions, total=True)
-    engine = gases[0]
+    gases = present_gases(spec, whole, total=True)
+    engine = gases.engine
     if engine is None:
         from .engine import default_engine
         engine = default_engine(spec.device)
@@ -413,48 +413,38 @@ def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, l
                                     transmittance=product.transmittance, asynchronous=True)
             block = _first_rows(channels[product.name], rows)
         block.to_host_into(target, width, asynchronous=True)
-    with engine.pipeline:
-        try:
-            sweep = sweeper(_Call(engine, take, paths, per_path, spec.grid.size, temperature,
-                                  grid_handle), run)
-            beta = take(run, n)
-            outputs = {q: take(run, band_width) for q in level_quantities}
-            outputs.update({q: take(paths, band_width) for q in path_quantities})
-            channels = {} if instrument is None else {
-                product.name: take(run if product.per_level else paths, width)
-                for product in products}
-            resident = None
-            for index, step in enumerate(passes):
-                for a, b in (runs[::-1] if step.from_last else runs):
-                    kept = (a, b) == resident
-                    if resident is not None and not kept:
-                        # The previous run's block and outputs are written again below: what
-                        # still reads them -- its sweep, its copies to the host -- is done first.
-                        engine.synchronize()
-                    rows = _first_rows(beta, b - a)
-                    if not kept:
-                        spec.total_into(rows, a, b, remove_pedestal, range_policy, gases=gases)
-                    resident = (a, b)
-                    sweep(index, rows, a, b,
-                          {q: _first_rows(block, b - a) if q in level_quantities else block
-                           for q, block in outputs.items()})
-                    for product in products:
-                        if product.per_level and product.source in step.level_quantities:
-                            send_home(product, b - a, results[product.name][a:b])
-            for product in products:
-                if not product.per_level:
-                    send_home(product, paths, results[product.name])
-            engine.synchronize()
-        except BaseException:
-            try:
-                engine.cancel_deferred()
-                engine.synchronize()
-            except Exception:       # the first error is the one to report
-                pass
-            raise
-        finally:
-            for block in taken:
-                engine.blocks.give(block)
+    # The pooled blocks go back whether the call failed or not: behind the guard's cancel-and-wait.
+    with pipeline(engine, give_back=taken):
+        sweep = sweeper(_Call(engine, take, paths, per_path, spec.grid.size, temperature,
+                              grid_handle), run)
+        beta = take(run, n)
+        outputs = {q: take(run, band_width) for q in level_quantities}
+        outputs.update({q: take(paths, band_width) for q in path_quantities})
+        channels = {} if instrument is None else {
+            product.name: take(run if product.per_level else paths, width)
+            for product in products}
+        resident = None
+        for index, step in enumerate(passes):
+            for a, b in (runs[::-1] if step.from_last else runs):
+                kept = (a, b) == resident
+                if resident is not None and not kept:
+                    # The previous run's block and outputs are written again below: what
+                    # still reads them -- its sweep, its copies to the host -- is done first.
+                    engine.synchronize()
+                rows = _first_rows(beta, b - a)
+                if not kept:
+                    spec.total_into(rows, a, b, remove_pedestal, range_policy, gases=gases)
+                resident = (a, b)
+                sweep(index, rows, a, b,
+                      {q: _first_rows(block, b - a) if q in level_quantities else block
+                       for q, block in outputs.items()})
+                for product in products:
+                    if product.per_level and product.source in step.level_quantities:
+                        send_home(product, b - a, results[product.name][a:b])
+        for product in products:
+            if not product.per_level:
+                send_home(product, paths, results[product.name])
+        engine.synchronize()
     return results
 
 

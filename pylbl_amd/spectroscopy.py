@@ -13,22 +13,20 @@ number-density scaling happens in the kernel epilogue; xarray is optional (not i
 this image) -- without it the atmosphere is a plain (p, t, vmr) tuple and the result a dict
 of numpy arrays with the same variable names.
 
-What is in this module: Atmosphere, MoleculeCache, the queueing of the kernels of one (molecule,
-mechanism) into blocks in HBM (_Sum, _Queue) and Spectroscopy -- compute_absorption with
-_compute_levels, the "total" block of a range of levels (total_into, _present_gases,
-_queue_total), and the four path products compute_path, compute_radiance, compute_jacobian and
-compute_flux: their documentation and their sweeps.  Everything else of the path products
-(argument checks, the run loop, HBM accounting, results) is in paths.py, whose public names
-stay importable from here and whose request, run-loop and result functions are also Spectroscopy's
-private methods of the same names.
+What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
+four path products compute_path, compute_radiance, compute_jacobian and compute_flux: their
+documentation and their sweeps.  The host side of compute_absorption (the gases present, the
+queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
+else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
+whose public names stay importable from here; their functions take the Spectroscopy first, and
+total_into, _compute_levels and paths.py's request, run-loop and result functions are its methods.
 """
 from collections import namedtuple
-import contextlib
 import os
 
 import numpy as np
 
-from . import errors, paths
+from . import absorption, errors, paths
 from .paths import (CP_DRY, FLUX_QUANTITIES, FLUX_SURFACES, JACOBIAN_LEVEL_QUANTITIES,  # noqa: F401
                     JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
                     PATH_CUMULATIVE, PATH_QUANTITIES, PLANCK_C1, PLANCK_C2, R_DRY,
@@ -36,7 +34,6 @@ from .paths import (CP_DRY, FLUX_QUANTITIES, FLUX_SURFACES, JACOBIAN_LEVEL_QUANT
                     heating_rate, _MAX_RUN_LEVELS, _PATH_UNITS, _Pass, _Product, _cut_runs,
                     _path_layout, _sweep_pass)
 from .plugins import continua, cross_sections, molecular_lines
-from .synthetic import grid_arguments
 
 kb = 1.38064852e-23  # Boltzmann constant [J K-1] (pyLBL/spectroscopy.py:15).
 
@@ -149,89 +146,6 @@ class MoleculeCache(object):
                 self.cross_section = None
 
 
-class _Sum(object):
-    """A [levels, n] block in HBM that kernels write first and add into afterwards (`buffer`: one
-    the caller holds, else one taken from the engine's pool)."""
-    def __init__(self, engine, levels, n, buffer=None):
-        self.engine = engine
-        # recycled (engine.DevicePool)
-        self.buffer = engine.blocks.take(levels, n) if buffer is None else buffer
-        self.written = False
-
-    def take(self):
-        """True if the next kernel must add to what is there."""
-        written, self.written = self.written, True
-        return written
-
-    def into(self, target):
-        """Queues the copy of the first target.shape[1] columns of every level straight into
-        `target` (a [levels, columns] view with contiguous rows, page-locked); it runs behind
-        the kernels queued so far and beside those queued later."""
-        self.buffer.to_host_into(target, target.shape[1], asynchronous=True)
-        return self
-
-
-class _Queue(object):
-    """Queues the kernels of one (molecule, mechanism) into a block in HBM, for a flat list of
-    levels: what Spectroscopy._compute_levels and compute_path share."""
-    def __init__(self, spec, temperature, pressure, mole_fractions, remove_pedestal, range_policy,
-                 pieces):
-        self.spec = spec
-        self.temperature, self.pressure, self.mole_fractions = temperature, pressure, mole_fractions
-        self.remove_pedestal, self.range_policy, self.pieces = remove_pedestal, range_policy, pieces
-
-    def lines_into(self, name, gas, block, deliver=None, defer=False):
-        gas.absorption_coefficients(
-            self.temperature, self.pressure, self.mole_fractions[name], self.spec.grid,
-            remove_pedestal=self.remove_pedestal, range_policy=self.range_policy,
-            scale_density=True, out=block.buffer, accumulate=block.take(),
-            asynchronous=True, farfield=self.spec.farfield, deliver=deliver,
-            pieces=self.pieces, defer_finish=defer)
-
-    def continua_into(self, continua_list, continuum_sum):
-        # All of them in one pass over the grid where they are this package's (one launch that
-        # writes the block once instead of a read-modify-write pass per continuum; the same
-        # bits: csrc/continuum.h, group kernels); anything else one by one.
-        if not continua_list:
-            return
-        from .mt_ckd import BandedContinuum, spectra_levels_many
-        if all(isinstance(c, BandedContinuum) for c in continua_list):
-            spectra_levels_many(continua_list, self.temperature, self.pressure,
-                                self.mole_fractions, self.spec.grid, continuum_sum.buffer,
-                                accumulate=continuum_sum.take(), asynchronous=True)
-            return
-        for continuum in continua_list:
-            continuum.spectra_levels(self.temperature, self.pressure, self.mole_fractions,
-                                     self.spec.grid, out=continuum_sum.buffer,
-                                     accumulate=continuum_sum.take(), asynchronous=True)
-
-    def slots_into(self, name, continua_here, cross, continuum_sum, cross_sum):
-        self.continua_into(continua_here, continuum_sum)
-        if cross is not None:
-            cross.absorption_coefficients(self.spec.grid, self.temperature, self.pressure,
-                                          volume_mixing_ratio=self.mole_fractions[name],
-                                          out=cross_sum.buffer, accumulate=cross_sum.take(),
-                                          asynchronous=True)
-
-
-def _zero_in_background(views):
-    """Zeroes float64 [rows, columns] views with contiguous rows on a helper thread (ctypes
-    releases the interpreter lock during memset); returns the started thread, or None."""
-    if not views:
-        return None
-    import ctypes
-    import threading
-
-    def fill():
-        for view in views:
-            row_bytes = view.shape[1]*8
-            for row in range(view.shape[0]):
-                ctypes.memset(view[row].ctypes.data, 0, row_bytes)
-    thread = threading.Thread(target=fill)
-    thread.start()
-    return thread
-
-
 class Spectroscopy(object):
     """Line-by-line gas optics (lines, MT-CKD continua, ARTS-crossfit cross-sections) on an
     MI355X.
@@ -275,7 +189,7 @@ class Spectroscopy(object):
         self.farfield = bool(farfield)
         self.device_output_limit = 8 << 30     # bytes of spectra kept in HBM per block
         self.delivery_pieces = 4               # runs of tiles of the call that delivers its result
-        # "total": in which order the gases add into the one block (see _compute_levels).
+        # "total": in which order the gases add into the one block (absorption.queue_total).
         self.total_order = "heavy_last"
         # "gas": "each" -- every gas's lines call delivers its block piece by piece; "last" -- only
         # the last gas does, the others' blocks travel in one copy each.
@@ -655,298 +569,14 @@ class Spectroscopy(object):
                                    level_blocks=2)
         return self._create_flux_dataset(self._flux_interfaces(values, request), request)
 
-    # The host side of the path products is paths.py, whose functions take the Spectroscopy first.
+    # The host side of the path products is paths.py and that of compute_absorption is
+    # absorption.py: their functions take the Spectroscopy first.
+    _compute_levels, total_into = absorption.compute_levels, absorption.total_into
     _path_request, _radiance_request = paths._path_request, paths._radiance_request
     _flux_request, _sweep_runs = paths._flux_request, paths._sweep_runs
     _flux_interfaces = paths._flux_interfaces
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
-
-    def _present_gases(self, temperature, pressure, mole_fractions, total=False):
-        """(engine, gases, heaviest): the gases of the atmosphere that some mechanism computes, as
-        (name, Gas or None, continua, cross-section or None), lightest lines table first (with
-        `total`: in "total" order, the heaviest first and the others behind it as they were);
-        the heaviest, when it has lines; the engine they share (None without any)."""
-        engine = None
-        present = []
-        for name in self.atmosphere.gases:
-            data = self._molecule(name)
-            gas = data.gas
-            if gas is not None and gas.molecule is None:
-                # Deferred errors (unknown alias) surface here like in the reference.
-                gas.absorption_coefficients(temperature[:1], pressure[:1],
-                                            mole_fractions[name][:1], self.grid)
-                gas = None
-            continua_here = data.gas_continua or []
-            cross = data.cross_section
-            if gas is None and not continua_here and cross is None:
-                continue
-            if engine is None:
-                engine = gas.engine if gas is not None else \
-                    (continua_here[0].engine if continua_here else cross.engine)
-            present.append((name, gas, continua_here, cross))
-        # "total" (one block for everything): the gas with the most transitions is queued FIRST and
-        # finished LAST.  Its lines call is the longest (with the pedestal removed it ends in a
-        # serial chain), so everything it does in buffers of its own -- prologue, far-field series,
-        # accumulate, pedestal pre-pass -- starts at once and runs beside the other gases' calls,
-        # while the kernels that touch its block, and the copies that hand that block to the host
-        # piece by piece, are kept back (LBL_DEFER_FINISH) until the others have been queued: it
-        # stays the last to add into a shared block, and its copies queue up behind the other gases'
-        # copies, not in front of them.  (Units are independent, spectroscopy.py:166,179; results
-        # are reported in the atmosphere's order.) Per-gas blocks ("gas", "all") are the other way
-        # round: the link to the host is the bottleneck there (one block per gas to copy), so the
-        # lightest gas goes first -- its block is complete early and travels beside the kernels of
-        # the others -- and the heaviest last, delivering its block piece by piece while it computes
-        # (profiles/r03_ab_api.txt).
-        present.sort(key=lambda entry: entry[1].num_lines if entry[1] is not None else -1)
-        heavy = present[-1] if present and present[-1][1] is not None else None
-        if total and heavy is not None:
-            present = [heavy] + present[:-1]
-        return engine, present, heavy
-
-    def _queue_total(self, queue, engine, present, heavy, total, deliver):
-        """Queues every gas's kernels into the one block `total` (a _Sum; `present` in "total"
-        order: the heavy gas first).  deliver: the page-locked [levels, columns] view the last
-        lines call hands the finished block to, piece by piece -- or None: the block stays in
-        HBM, complete behind what is queued.  Returns True when `deliver` was not handed the
-        finished block (the caller copies it behind everything)."""
-        lines_into, slots_into = queue.lines_into, queue.slots_into
-        # Every gas adds into one block.  The heavy gas's slot kernels go first (the first of them
-        # writes the block -- or the engine clears it), then its lines call, kept back; the other
-        # gases' lines with their short continuum and cross-section kernels behind them; then the
-        # heavy gas's last kernels and the delivery of the finished block.
-        kept_back = False
-        if heavy is not None and self.total_order == "heavy_last":
-            # The short continuum and cross-section kernels of every gas first, the lighter gases'
-            # lines behind them, the heaviest gas last: each run of tiles it finishes completes
-            # that part of the block, which goes to the host while the next run computes (its
-            # pedestal pass is short since round 4, so the first copy starts a third of the way
-            # into the call instead of behind everything).  (Lines first and the slot kernels
-            # behind them was tried: the slot kernels then wait for the first gas's pedestal to be
-            # applied and the heaviest gas is queued later, 1.58 -> 1.70 ms.)
-            # (every continuum of every gas in ONE pass -- the block is written once -- then the
-            # cross-sections.  The additions into the block therefore run c(g1), c(g2), ..., x(g1),
-            # x(g2), ..., lines -- not the reference's gas-by-gas order, spectroscopy.py:225-234:
-            # the continua are bit-identical to the one-by-one sum among themselves, the total may
-            # differ from the reference's order of additions in its last bits, within the parity
-            # bar: tests/test_gpu_api.py::test_total_with_continuum_and_cross_section_of_two_gases)
-            queue.continua_into([c for _, _, continua_here, _ in present
-                                 for c in continua_here], total)
-            for name, gas, continua_here, cross in present:
-                slots_into(name, [], cross, total, total)
-            if not total.written:
-                engine.fill_zero(total.buffer, asynchronous=True)
-                total.take()
-            for name, gas, continua_here, cross in present[1:]:
-                if gas is not None:
-                    lines_into(name, gas, total)
-            lines_into(heavy[0], heavy[1], total, deliver=deliver)
-            return False
-        for index, (name, gas, continua_here, cross) in enumerate(present):
-            if heavy is not None and index == 0:
-                slots_into(name, continua_here, cross, total, total)
-                if not total.written:
-                    engine.fill_zero(total.buffer, asynchronous=True)
-                    total.take()
-                lines_into(name, gas, total, deliver=deliver, defer=deliver is not None)
-                kept_back = deliver is not None and engine.deferred()
-                continue
-            if gas is not None:
-                lines_into(name, gas, total)
-            slots_into(name, continua_here, cross, total, total)
-        if kept_back:
-            engine.finish_deferred()
-            return False
-        # (No gas with lines -- or a call the engine could not keep back, e.g. without a pedestal
-        # pass: it added at once and delivered a block that was not complete; the copy the caller
-        # queues behind everything is the one that counts.)
-        return True
-
-    def total_into(self, block, a, b, remove_pedestal, range_policy="reference", deliver=None,
-                   gases=None):
-        """Queues the "total" absorption of the flat levels [a, b) of the atmosphere into `block`
-        (DeviceSpectra [b - a, >= padded grid]) the way compute_absorption("total") does: the
-        heaviest gas first in line and last to add (_queue_total), or zeros where no mechanism
-        computes any gas.  The block is complete behind what is queued (Engine.synchronize).
-        deliver: as for _queue_total, whose value is returned (True: `deliver` was not handed the
-        finished block).  gases: what _present_gases(..., total=True) returned, for callers that
-        queue several ranges in one call."""
-        temperature = self.atmosphere.temperature.ravel()[a:b]
-        pressure = self.atmosphere.pressure.ravel()[a:b]
-        mole_fractions = {name: x.ravel()[a:b] for name, x in self.atmosphere.gases.items()}
-        if gases is None:
-            gases = self._present_gases(temperature, pressure, mole_fractions, total=True)
-        _, present, heavy = gases
-        engine = block.engine
-        if not present:
-            engine.fill_zero(block, asynchronous=True)
-            return True
-        queue = _Queue(self, temperature, pressure, mole_fractions, remove_pedestal, range_policy,
-                       self.delivery_pieces)
-        return self._queue_total(queue, engine, present, heavy,
-                                 _Sum(engine, b - a, block.shape[1], buffer=block), deliver)
-
-    def _compute_levels(self, a, b, mode, remove_pedestal, range_policy):
-        """The three mechanism slots for the flat levels [a, b) of the atmosphere: {variable
-        name: array with the levels as leading dimension} ("total" under mode "total")."""
-        temperature = self.atmosphere.temperature.ravel()[a:b]
-        pressure = self.atmosphere.pressure.ravel()[a:b]
-        # Every gas at every level, the dictionary the continua read (spectroscopy.py:173).
-        mole_fractions = {name: x.ravel()[a:b] for name, x in self.atmosphere.gases.items()}
-        levels = temperature.size
-        v0, vn, n_per_v = grid_arguments(self.grid)
-        n = (vn - v0)*n_per_v
-        columns = self.grid.size
-        if levels == 0:
-            # A rank without levels (fewer levels than GPUs): empty blocks of the right shape.
-            if mode == "total":
-                return {"total": np.zeros((0, columns))}
-            tail = (len(MECHANISMS), columns) if mode == "all" else (columns,)
-            return {"{}_absorption".format(name): np.zeros((0,) + tail)
-                    for name in self.atmosphere.gases}
-        in_hbm = levels*n*8 <= self.device_output_limit
-
-        # Queue every kernel before waiting: one batched call per (molecule, mechanism) for
-        # all levels, n*k applied in the kernel epilogue, spectra left in HBM until the end;
-        # the sums over mechanisms ("gas") and over gases ("total") happen on the device.
-        # Within a block the short continuum and cross-section kernels go first and the lines
-        # last: the lines call that completes the LAST block of the whole call hands its result
-        # to the host itself, piece by piece while it computes (lbl_compute_streamed), so no
-        # copy is left standing behind the last kernel.
-        blocks = {}             # (gas, mechanism) -> host array (only when too large for HBM)
-        zero_fills = []         # row views of results that no mechanism writes
-        results = {}            # gas -> its finished array, being filled by queued copies
-        in_flight = []          # blocks in HBM to release once everything has arrived
-        gases = self._present_gases(temperature, pressure, mole_fractions, total=mode == "total")
-        engine, present, heavy = gases
-
-        # ("all" is bound by the link -- four 40 MB blocks per level for H2O + CO2 -- and its
-        # copies are queued back to back as they are: cutting the last one into pieces only
-        # puts gaps into that queue, 3.6 -> 4.1 ms per call.)
-        pieces = 1 if mode == "all" else self.delivery_pieces
-
-        # Everything from the first queued call to the final wait is one pipeline on the engine:
-        # calls add into shared blocks in a fixed order and one of them may be kept back, so
-        # another thread's calls must not come in between (Engine.pipeline; single calls from
-        # other threads -- Gas.absorption_coefficient -- only wait for their turn).  If anything
-        # fails on the way, what the engine still holds for this call is dropped and waited for
-        # BEFORE the blocks and page-locked arrays go back to their pools: a call kept back
-        # (LBL_DEFER_FINISH) would otherwise apply itself, and copy, into recycled memory the next
-        # time the engine is synchronized.
-        with (engine.pipeline if engine is not None else contextlib.nullcontext()):
-            try:
-                if not in_hbm:
-                    for name, gas, continua_here, cross in present:
-                        # Too large to keep: one host block per mechanism, summed by numpy below.
-                        if gas is not None:
-                            blocks[(name, 0)] = gas.absorption_coefficients(
-                                temperature, pressure, mole_fractions[name], self.grid,
-                                remove_pedestal=remove_pedestal, range_policy=range_policy,
-                                scale_density=True, farfield=self.farfield)[:, :columns]
-                        for continuum in continua_here:
-                            values = continuum.spectra_levels(temperature, pressure, mole_fractions,
-                                                              self.grid)
-                            blocks[(name, 1)] = blocks[(name, 1)] + values if (name, 1) in blocks \
-                                else values
-                        if cross is not None:
-                            blocks[(name, 2)] = cross.absorption_coefficients(
-                                self.grid, temperature, pressure,
-                                volume_mixing_ratio=mole_fractions[name])
-                elif mode == "total" and present:
-                    total = _Sum(engine, levels, n)
-                    results["total"] = engine.host_array((levels, columns))
-                    if self.total_into(total.buffer, a, b, remove_pedestal, range_policy,
-                                       deliver=results["total"], gases=gases):
-                        in_flight.append(total.into(results["total"]))
-                    else:
-                        in_flight.append(total)
-                else:
-                    queue = _Queue(self, temperature, pressure, mole_fractions, remove_pedestal,
-                                   range_policy, pieces)
-                    lines_into, slots_into = queue.lines_into, queue.slots_into
-                    for index, (name, gas, continua_here, cross) in enumerate(present):
-                        last = index + 1 == len(present)
-                        if mode == "gas":
-                            block = _Sum(engine, levels, n)
-                            results[name] = engine.host_array((levels, columns))
-                            if gas is not None and (last or self.gas_delivery == "each"):
-                                slots_into(name, continua_here, cross, block, block)
-                                lines_into(name, gas, block, deliver=results[name])
-                                in_flight.append(block)
-                            else:
-                                if gas is not None:
-                                    lines_into(name, gas, block)
-                                slots_into(name, continua_here, cross, block, block)
-                                # This gas's block goes home while the next gas computes: one copy,
-                                # from HBM straight into its place in a page-locked result.
-                                in_flight.append(block.into(results[name]))
-                            continue
-                        values = engine.host_array([levels, len(MECHANISMS), columns])
-                        results[name] = values
-                        continuum_sum = _Sum(engine, levels, n) if continua_here else None
-                        cross_sum = _Sum(engine, levels, n) if cross is not None else None
-                        if continua_here or cross is not None:
-                            slots_into(name, continua_here, cross, continuum_sum, cross_sum)
-                        for slot, block in ((1, continuum_sum), (2, cross_sum)):
-                            if block is None:
-                                # An empty mechanism slot reads zero (40 MB per level at 5 M
-                                # points): filled by a helper thread beside the queueing and the
-                                # kernels.
-                                zero_fills.append(values[:, slot, :])
-                            else:
-                                in_flight.append(block.into(values[:, slot, :]))
-                        if gas is None:
-                            zero_fills.append(values[:, 0, :])
-                        else:
-                            lines_sum = _Sum(engine, levels, n)
-                            if last:
-                                lines_into(name, gas, lines_sum, deliver=values[:, 0, :])
-                                in_flight.append(lines_sum)
-                            else:
-                                lines_into(name, gas, lines_sum)
-                                in_flight.append(lines_sum.into(values[:, 0, :]))
-                filler = _zero_in_background(zero_fills)
-                if engine is not None:
-                    engine.synchronize()
-                if filler is not None:
-                    filler.join()
-                for block in in_flight:
-                    engine.blocks.give(block.buffer)
-            except BaseException:
-                if engine is not None:
-                    try:
-                        engine.cancel_deferred()
-                        engine.synchronize()
-                    except Exception:       # the first error is the one to report
-                        pass
-                raise
-
-        if mode == "total":
-            values = results.get("total")
-            if values is None:
-                values = np.zeros((levels, columns))
-            for block in blocks.values():           # host blocks of the too-large case
-                values += block
-            return {"total": values}
-        beta = {}
-        for name in self.atmosphere.gases:
-            varname = "{}_absorption".format(name)
-            values = results.get(name)
-            if mode == "all":
-                if values is None:
-                    values = np.zeros([levels, len(MECHANISMS), columns])
-                    for slot in range(len(MECHANISMS)):
-                        if (name, slot) in blocks:
-                            values[:, slot, :] = blocks[(name, slot)]
-                beta[varname] = values
-            else:
-                if values is None:
-                    values = np.zeros((levels, columns))
-                    for slot in range(len(MECHANISMS)):
-                        if (name, slot) in blocks:
-                            values += blocks[(name, slot)]
-                beta[varname] = values
-        return beta
 
     def _create_output_dataset(self, absorption, output_format):
         dims = list(self.output.dims)
