@@ -24,6 +24,8 @@ ncclGroup of send/recv over xGMI, no padding and no concatenation copy), or one 
 the cross-rank total.  Backend "nccl" is RCCL on ROCm (tensors stay in HBM); with "gloo" (CPU
 tests, or rehearsing several ranks on one GPU) the blocks travel through host memory.
 """
+from collections import namedtuple
+
 import numpy as np
 
 
@@ -199,6 +201,23 @@ class Pending(object):
             f"{list(self.peers)} not complete after {timeout:g} s "
             f"({self.bytes_sent} B to send, {self.bytes_received} B to receive)")
 
+    def order_stream(self):
+        """Device tensors: orders torch's current stream of the exchange's device behind the
+        exchange, without stopping the host, and returns that stream.  An nccl work object only
+        orders the *current torch stream of its device* behind the transfer: name the device (the
+        caller's current device may be another one).  The `issued` event covers what the issuing
+        stream did around the exchange, should the caller have changed torch streams since.
+        (Also with nothing to send or receive: the rank's own blocks were copied into the
+        collected array on that stream, and the engine overwrites them two calls later.)"""
+        import torch
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            if self.issued is not None:
+                stream.wait_event(self.issued)
+            for request in self.requests:
+                request.wait()              # nccl: orders torch's current stream, not the host
+        return stream
+
     def wait(self, timeout=None):
         """Blocks until the exchange has finished and its result may be read.
 
@@ -226,19 +245,10 @@ class Pending(object):
                     raise self._late(timeout)
         else:
             import torch
-            # An nccl work object only orders the *current torch stream of its device* behind
-            # the transfer: name the device (the caller's current device may be another one)
-            # and settle that stream with an event that can be polled against the deadline.
-            # (Also with nothing to send or receive: the rank's own blocks were copied into the
-            # collected array on that stream, and the engine overwrites them two calls later.)
-            stream = torch.cuda.current_stream(self.device)
-            with torch.cuda.device(self.device):
-                if self.issued is not None:
-                    stream.wait_event(self.issued)
-                for request in self.requests:
-                    request.wait()
-                marker = torch.cuda.Event()
-                marker.record(stream)
+            # Settle the ordered stream with an event that can be polled against the deadline.
+            stream = self.order_stream()
+            marker = torch.cuda.Event()
+            marker.record(stream)
             spins = 0
             while not marker.query():
                 spins += 1
@@ -250,6 +260,69 @@ class Pending(object):
         self.seconds = time.perf_counter() - self.started
         self.done = True
         return self.result
+
+
+Transfer = namedtuple("Transfer", "kind key levels peer")
+Transfer.__doc__ = """One step of the grouped gather on one rank.  kind: "copy" (this rank's own
+block into the collected array), "send" or "recv"; key: None ("total") or the molecule index;
+levels: the block's levels, ascending and contiguous; peer: group-local rank."""
+
+
+def gather_plan(plan, output, rank, receivers, to_self=False):
+    """What `rank` does in the grouped gather of `plan`'s blocks onto `receivers`: the Transfers
+    in the order their operations are issued (both sides of a grouped send/recv rely on matching
+    order: a receiver takes the senders in rank order and each sender's blocks in key order,
+    which is the order the sender posts them in).  Ranks and blocks without levels do not appear.
+
+    Args:
+        to_self: a receiver's own blocks travel as a send/recv pair to itself inside the same
+                 group of operations instead of being copied (always_exchange over RCCL: the
+                 code and the library a block from another GPU goes through).
+    """
+    def pieces(r):
+        found = [(None, plan.levels_of(r))] if output == "total" else \
+            sorted(plan.by_molecule(r).items())
+        return [(key, levels) for key, levels in found if levels]
+    transfers = []
+    for receiver in receivers:
+        if receiver != rank:
+            transfers += [Transfer("send", key, levels, receiver) for key, levels in pieces(rank)]
+            continue
+        for sender in range(len(plan.units)):
+            for key, levels in pieces(sender):
+                if sender == rank and not to_self:
+                    transfers.append(Transfer("copy", key, levels, rank))
+                    continue
+                if sender == rank:
+                    transfers.append(Transfer("send", key, levels, rank))
+                transfers.append(Transfer("recv", key, levels, sender))
+    return transfers
+
+
+class _Call(object):
+    """What one run() knows about itself; every stage reads it.
+
+    Attributes:
+        plan, my_levels: the partition and the sorted levels this rank touches.
+        on_device: the per-rank blocks are in HBM; through_host: ... and travel through host
+                   memory (gloo on a GPU).
+        where: where the exchange's tensors are ("cpu" or the device); wait_on: the device a
+               Pending of this call settles on (None: its requests complete on the host).
+        receivers, i_receive: group-local ranks that get the result; whether this one does.
+        used: keys of the kept buffers this call's exchange reads or writes (_buffer adds them).
+    """
+    def __init__(self, lines, n_levels, dst, output):
+        self.rank, self.world, self.backend = _group_info(lines.group)
+        self.dst, self.output = dst, output
+        self.plan = partition(n_levels, lines.weights, self.world)
+        self.my_levels = self.plan.levels_of(self.rank)
+        self.on_device = str(lines.device) != "cpu"
+        self.through_host = self.on_device and self.world > 1 and self.backend != "nccl"
+        self.where = "cpu" if (self.through_host or not self.on_device) else lines.device
+        self.wait_on = None if self.where == "cpu" else lines.device
+        self.receivers = range(self.world) if dst is None else (dst,)
+        self.i_receive = self.rank in self.receivers
+        self.used = []
 
 
 class ShardedLines(object):
@@ -295,7 +368,15 @@ class ShardedLines(object):
     and whoever writes it next is ordered behind that exchange first -- on the device (the
     writer's stream waits; RCCL) or by waiting for it (host tensors; gloo).  Calls may therefore
     be queued back to back with async_op without waiting for their Pendings; what is lost by not
-    waiting is only a result that a later call has overwritten.
+    waiting is only a result that a later call has overwritten.  In the code: `_buffer` hands out
+    a kept buffer only after `_settle` has ordered its writer behind the buffer's last user, and
+    enters it in the call's record (`_Call.used`); `_started`, the one tail of both kinds of
+    exchange, makes the new Pending the last user of everything entered there.
+
+    A call, run(): compute (`_compute_total` / `_compute_gas`), then either `_one_rank_result` or
+    `_order_or_flush` and one exchange -- `_exchange_by_reduce` ("total" when the molecules of a
+    level sit on several ranks) or `_exchange_by_gather`, which executes what the torch-free
+    `gather_plan` lists.
     """
     def __init__(self, compute, molecules, n, weights=None, group=None, device="cpu",
                  flush=None, order=None, zero=None, order_on_device=None, order_compute=None,
@@ -373,13 +454,14 @@ class ShardedLines(object):
                    order_on_device=order_on_device, order_compute=order_compute,
                    always_exchange=always_exchange)
 
-    # -- buffers -----------------------------------------------------------------------------
-    def _buffer(self, name, shape, zero=False, sets=2, writer="compute"):
+    # -- buffers ---------------------------------------------------------------------------------
+    def _buffer(self, call, name, shape, sets=2, writer="compute"):
         """Per-rank blocks are kept between calls, two of each so that an exchange still in
         flight (async_op) is not overwritten by the next call (sets=1: one, for a collected
         array too large to keep twice).  Whoever is about to write the buffer -- `compute`
         (the engine's streams) or the exchange library's stream ("exchange") -- is first ordered
-        behind the exchange that last used it (_settle)."""
+        behind the exchange that last used it (_settle), and the buffer is entered in
+        `call.used`, so that this call's exchange becomes the one its next writer waits for."""
         import torch
         key = (name, self._turn % sets, tuple(shape))
         tensor = self._buffers.get(key)
@@ -387,9 +469,7 @@ class ShardedLines(object):
             tensor = torch.empty(shape, dtype=torch.float64, device=self.device)
             self._buffers[key] = tensor
         self._settle(key, writer)
-        self._last_key = key
-        if zero:
-            self._zero(tensor)
+        call.used.append(key)
         return tensor
 
     def _settle(self, key, writer):
@@ -397,31 +477,20 @@ class ShardedLines(object):
         (if that is still in flight).  Host tensors: the host waits for the exchange (gloo's
         requests complete inside wait() only: this may block for up to PYLBL_AMD_EXCHANGE_TIMEOUT
         seconds and raise ExchangeTimeout).  Device tensors: the exchange library's current
-        stream waits for the exchange's work objects -- no host wait -- and, when the writer is
-        `compute`, the engine's streams are then ordered behind that stream."""
+        stream waits for the exchange (Pending.order_stream) -- no host wait -- and, when the
+        writer is `compute`, the engine's streams are then ordered behind that stream."""
         pending = self._users.pop(key, None)
         if pending is None or pending.done:
             return
         if pending.device is None:
             pending.wait()
             return
-        import torch
-        with torch.cuda.device(pending.device):
-            if pending.issued is not None:
-                # (what the issuing stream did around the exchange, should the caller have changed
-                # torch streams since)
-                torch.cuda.current_stream(pending.device).wait_event(pending.issued)
-            for request in pending.requests:
-                request.wait()              # nccl: orders torch's current stream, not the host
+        stream = pending.order_stream()
         if writer == "compute":
             if self.order_compute is not None:
                 self.order_compute()
             else:
-                torch.cuda.current_stream(pending.device).synchronize()
-
-    def _used_by(self, pending, keys):
-        for key in keys:
-            self._users[key] = pending
+                stream.synchronize()
 
     def _zero(self, tensor):
         """With the engine's own fill the zeroes are ordered like a compute call.  Otherwise
@@ -435,6 +504,156 @@ class ShardedLines(object):
         if tensor.is_cuda:
             import torch
             torch.cuda.current_stream(tensor.device).synchronize()
+
+    # -- the stages of a call ---------------------------------------------------------------------
+    def _compute_total(self, call, temperature, pressure, x):
+        """One [levels touched, n] block; every molecule adds to the rows of its levels."""
+        my_levels = call.my_levels
+        row = {level: i for i, level in enumerate(my_levels)}
+        block = self._buffer(call, "total", (len(my_levels), self.n))
+        first = True
+        for m, levels in sorted(call.plan.by_molecule(call.rank).items()):
+            formula = self.molecules[m]
+            rows = [row[level] for level in levels]
+            lo, hi = rows[0], rows[-1] + 1      # contiguous: units are level-major runs
+            assert rows == list(range(lo, hi))
+            if lo > 0 or hi < len(my_levels):
+                # This molecule covers only part of the block (unit mode): make sure the
+                # rows it skips are defined before anything adds to them.
+                if first:
+                    self._zero(block)
+                self.compute(formula, temperature[levels], pressure[levels], x[formula][levels],
+                             block[lo:hi], True)
+            else:
+                self.compute(formula, temperature[levels], pressure[levels], x[formula][levels],
+                             block, not first)
+            first = False
+        if first and len(my_levels):
+            self._zero(block)
+        return {None: block}
+
+    def _compute_gas(self, call, temperature, pressure, x):
+        """One contiguous [levels of this molecule, n] block per molecule."""
+        blocks = {}
+        for m, levels in sorted(call.plan.by_molecule(call.rank).items()):
+            formula = self.molecules[m]
+            blocks[m] = self._buffer(call, ("gas", m), (len(levels), self.n))
+            self.compute(formula, temperature[levels], pressure[levels], x[formula][levels],
+                         blocks[m], False)
+        return blocks
+
+    def _one_rank_result(self, call, blocks, async_op):
+        """One rank and no exchange asked for: the rank's own blocks are the result (with
+        async_op the kernels stay queued until wait())."""
+        if call.output == "total":
+            result = blocks[None]
+        else:
+            result = {f: blocks[m] for m, f in enumerate(self.molecules)}
+        if async_op:
+            return Pending([], lambda: result, flush=self.flush)
+        if self.flush is not None:
+            self.flush()
+        return result
+
+    def _order_or_flush(self, call, blocks):
+        """Puts the exchange behind the kernels and returns the blocks as they travel."""
+        if call.on_device and self.order is not None and \
+                (not call.through_host or self.order_on_device):
+            # RCCL: the exchange is queued behind the kernels on the device; the host goes on
+            # (to the next call's kernels: compute k+1 runs beside exchange k).  (Rehearsed with
+            # gloo under order_on_device: the staging copies below wait on torch's stream.)
+            self.order()
+        elif self.flush is not None:
+            self.flush()
+        if call.through_host:
+            blocks = {key: value.cpu() for key, value in blocks.items()}
+            del call.used[:]    # the exchange reads host copies made just now, not the kept blocks
+        return blocks
+
+    def _collected(self, call, shape, name="final"):
+        """The array an exchange collects into on this rank.  In HBM it is kept between calls --
+        two of it, used in turn, unless it is too large for that: "gas" output of BASELINE
+        config 5 is 164 GB on the receiving rank, two would not fit its 288 GB (then ONE: its
+        next writer is ordered behind the exchange still using it, _settle; see run()'s
+        Returns)."""
+        if call.where == "cpu":
+            import torch
+            return torch.empty(shape, dtype=torch.float64)
+        nbytes = 8*int(np.prod(shape))
+        return self._buffer(call, name, shape, writer="exchange",
+                            sets=2 if 2*nbytes <= self.collect_limit else 1)
+
+    def _started(self, call, requests, finish, async_op, **about):
+        """The tail of every exchange: its Pending, entered as the last user of the kept buffers
+        the exchange reads or writes; waited for here unless async_op."""
+        pending = Pending(requests, finish, device=call.wait_on, rank=call.rank, **about)
+        for key in call.used:
+            self._users[key] = pending
+        self.last_exchange = pending
+        return pending if async_op else pending.wait()
+
+    def _exchange_by_reduce(self, call, block, async_op):
+        """"total" in unit mode: the molecules of one level sit on several ranks -- a real sum
+        over ranks of [all levels, n] arrays that hold this rank's rows and zeroes."""
+        import torch.distributed as dist
+        partial = self._collected(call, (call.plan.n_levels, self.n), name="reduce")
+        partial.zero_()
+        for i, level in enumerate(call.my_levels):
+            partial[level] = block[i]
+        if call.dst is None:
+            work = dist.all_reduce(partial, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+        else:
+            work = dist.reduce(partial, dst=_global_rank(self.group, call.dst),
+                               op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+        return self._started(
+            call, [work], (lambda: partial) if call.i_receive else (lambda: None), async_op,
+            describe="sum over ranks of the per-level totals "
+                     f"({'all_reduce' if call.dst is None else 'reduce'})",
+            peers=[r for r in range(call.world) if r != call.rank],
+            bytes_sent=partial.numel()*8,
+            bytes_received=partial.numel()*8 if call.i_receive else 0)
+
+    def _exchange_by_gather(self, call, blocks, async_op):
+        """Grouped point-to-point gather (gather_plan): every block goes straight into its final
+        place in the collected array, [L, n] for "total", [molecules, L, n] for "gas"."""
+        import torch.distributed as dist
+        output, molecules = call.output, self.molecules
+        final = None
+        if call.i_receive:
+            final = self._collected(call, (call.plan.n_levels, self.n) if output == "total" else
+                                    (len(molecules), call.plan.n_levels, self.n))
+
+        def place(key, levels):
+            rows = slice(levels[0], levels[-1] + 1)
+            return final[rows] if key is None else final[key, rows]
+        ops, peers, sent, received = [], set(), 0, 0
+        for kind, key, levels, peer in gather_plan(
+                call.plan, output, call.rank, call.receivers,
+                to_self=self.always_exchange and call.backend == "nccl"):
+            if kind == "copy":
+                place(key, levels).copy_(blocks[key])
+                continue
+            if kind == "send":
+                tensor, how = blocks[key], dist.isend
+                sent += tensor.numel()*8
+            else:
+                tensor, how = place(key, levels), dist.irecv
+                received += tensor.numel()*8
+            ops.append(dist.P2POp(how, tensor, _global_rank(self.group, peer), self.group))
+            peers.add(peer)
+        requests = dist.batch_isend_irecv(ops) if ops else []
+
+        def finish():
+            if not call.i_receive:
+                return None if output == "total" else {f: None for f in molecules}
+            if output == "total":
+                return final
+            return {f: final[m] for m, f in enumerate(molecules)}
+        return self._started(
+            call, requests, finish, async_op,
+            describe=f"grouped send/recv of the {output!r} blocks to "
+                     f"{'every rank' if call.dst is None else f'rank {call.dst}'}",
+            peers=sorted(peers), bytes_sent=sent, bytes_received=received)
 
     # -- the call ----------------------------------------------------------------------------
     def run(self, temperature, pressure, vmr, dst=0, output="gas", async_op=False):
@@ -459,179 +678,19 @@ class ShardedLines(object):
             result: a buffer's next writer is ordered behind the exchange that last used it
             (see the class docstring).
         """
-        import torch
-        import torch.distributed as dist
-        rank, world, backend = _group_info(self.group)
         temperature = np.ascontiguousarray(temperature, dtype=np.float64)
         pressure = np.ascontiguousarray(pressure, dtype=np.float64)
         x = {f: np.ascontiguousarray(vmr[f], dtype=np.float64) for f in self.molecules}
-        n_levels, n, m_count = temperature.size, self.n, len(self.molecules)
-        plan = partition(n_levels, self.weights, world)
-        mine = plan.by_molecule(rank)
-        my_levels = plan.levels_of(rank)
-        row = {level: i for i, level in enumerate(my_levels)}
+        call = _Call(self, temperature.size, dst, output)
         self._turn += 1
-        on_device = str(self.device) != "cpu"
-        through_host = on_device and world > 1 and backend != "nccl"
-
-        # 1. compute this rank's units into its blocks
-        used = []               # keys of the kept buffers this call's exchange reads or writes
-        if output == "total":
-            # One [levels touched, n] block; every molecule adds to the rows of its levels.
-            block = self._buffer("total", (len(my_levels), n))
-            used.append(self._last_key)
-            first = True
-            for m, levels in sorted(mine.items()):
-                rows = [row[level] for level in levels]
-                lo, hi = rows[0], rows[-1] + 1      # contiguous: units are level-major runs
-                assert rows == list(range(lo, hi))
-                if lo > 0 or hi < len(my_levels):
-                    # This molecule covers only part of the block (unit mode): make sure the
-                    # rows it skips are defined before anything adds to them.
-                    if first:
-                        self._zero(block)
-                    self.compute(self.molecules[m], temperature[levels], pressure[levels],
-                                 x[self.molecules[m]][levels], block[lo:hi], True)
-                else:
-                    self.compute(self.molecules[m], temperature[levels], pressure[levels],
-                                 x[self.molecules[m]][levels], block, not first)
-                first = False
-            if first and len(my_levels):
-                self._zero(block)
-            blocks = {None: block}
-        else:
-            # One contiguous [levels of this molecule, n] block per molecule.
-            blocks = {}
-            for m, levels in sorted(mine.items()):
-                blocks[m] = self._buffer(("gas", m), (len(levels), n))
-                used.append(self._last_key)
-                self.compute(self.molecules[m], temperature[levels], pressure[levels],
-                             x[self.molecules[m]][levels], blocks[m], False)
-        # 2. one rank: done (with async_op the kernels stay queued until wait())
-        if world == 1 and not (self.always_exchange and backend is not None):
-            if output == "total":
-                result = blocks[None]
-            else:
-                result = {f: blocks[m] for m, f in enumerate(self.molecules)}
-            if async_op:
-                return Pending([], lambda: result, flush=self.flush)
-            if self.flush is not None:
-                self.flush()
-            return result
-        if on_device and self.order is not None and \
-                (not through_host or self.order_on_device):
-            # RCCL: the exchange is queued behind the kernels on the device; the host goes on
-            # (to the next call's kernels: compute k+1 runs beside exchange k).  (Rehearsed with
-            # gloo under order_on_device: the staging copies below wait on torch's stream.)
-            self.order()
-        elif self.flush is not None:
-            self.flush()
-
-        if through_host:
-            blocks = {key: value.cpu() for key, value in blocks.items()}
-            used = []           # the exchange reads host copies made just now, not the kept blocks
-        where = "cpu" if (through_host or not on_device) else self.device
-        wait_on = None if where == "cpu" else self.device
-        sizes = {key: value.numel()*8 for key, value in blocks.items()}
-
-        # 3. exchange
-        receivers = range(world) if dst is None else (dst,)
-        i_receive = rank in receivers
-        if output == "total" and plan.mode == "units":
-            # The molecules of one level sit on several ranks: a real sum over ranks.
-            if where != "cpu":
-                partial = self._buffer("reduce", (n_levels, n), writer="exchange",
-                                       sets=2 if 16*n_levels*n <= self.collect_limit else 1)
-                used.append(self._last_key)
-            else:
-                partial = torch.empty((n_levels, n), dtype=torch.float64)
-            partial.zero_()
-            for i, level in enumerate(my_levels):
-                partial[level] = blocks[None][i]
-            if dst is None:
-                work = dist.all_reduce(partial, op=dist.ReduceOp.SUM, group=self.group,
-                                       async_op=True)
-            else:
-                work = dist.reduce(partial, dst=_global_rank(self.group, dst),
-                                   op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-            finish = (lambda: partial) if i_receive else (lambda: None)
-            pending = Pending([work], finish, device=wait_on, rank=rank,
-                              describe="sum over ranks of the per-level totals "
-                                       f"({'all_reduce' if dst is None else 'reduce'})",
-                              peers=[r for r in range(world) if r != rank],
-                              bytes_sent=partial.numel()*8,
-                              bytes_received=partial.numel()*8 if i_receive else 0)
-            self._used_by(pending, used)
-            self.last_exchange = pending
-            return pending if async_op else pending.wait()
-
-        # Grouped point-to-point gather: every block goes straight into its final place.
-        # The collected array is kept between calls -- two of it, used in turn, unless it is too
-        # large for that: "gas" output of BASELINE config 5 is 164 GB on the receiving rank, two
-        # would not fit its 288 GB (then ONE: its next writer is ordered behind the exchange still
-        # using it, _settle; see run()'s Returns).
-        def collected(shape):
-            if not i_receive:
-                return None
-            if where == "cpu":
-                return torch.empty(shape, dtype=torch.float64)
-            nbytes = 8*int(np.prod(shape))
-            tensor = self._buffer("final", shape, writer="exchange",
-                                  sets=2 if 2*nbytes <= self.collect_limit else 1)
-            used.append(self._last_key)
-            return tensor
-        if output == "total":
-            final = collected((n_levels, n))
-            pieces = lambda r: [(None, plan.levels_of(r))]                      # noqa: E731
-            place = lambda key, levels: final[levels[0]:levels[-1] + 1]          # noqa: E731
-        else:
-            final = collected((m_count, n_levels, n))
-            pieces = lambda r: sorted(plan.by_molecule(r).items())              # noqa: E731
-            place = lambda key, levels: final[key, levels[0]:levels[-1] + 1]     # noqa: E731
-        ops, peers, sent, received = [], set(), 0, 0
-        for receiver in receivers:
-            if receiver == rank:
-                for sender in range(world):
-                    for key, levels in pieces(sender):
-                        if not levels:
-                            continue
-                        if sender == rank and not (self.always_exchange and backend == "nccl"):
-                            place(key, levels).copy_(blocks[key])
-                        else:
-                            if sender == rank:
-                                # (always_exchange over RCCL: this rank's own blocks travel by
-                                # a send to itself inside the same group of operations -- the
-                                # code and the library a block from another GPU goes through)
-                                ops.append(dist.P2POp(dist.isend, blocks[key],
-                                                      _global_rank(self.group, rank), self.group))
-                                sent += sizes[key]
-                            target = place(key, levels)
-                            ops.append(dist.P2POp(dist.irecv, target,
-                                                  _global_rank(self.group, sender), self.group))
-                            peers.add(sender)
-                            received += target.numel()*8
-            else:
-                for key, levels in pieces(rank):
-                    if levels:
-                        ops.append(dist.P2POp(dist.isend, blocks[key],
-                                              _global_rank(self.group, receiver), self.group))
-                        peers.add(receiver)
-                        sent += sizes[key]
-        requests = dist.batch_isend_irecv(ops) if ops else []
-
-        def finish():
-            if not i_receive:
-                return None if output == "total" else {f: None for f in self.molecules}
-            if output == "total":
-                return final
-            return {f: final[m] for m, f in enumerate(self.molecules)}
-        pending = Pending(requests, finish, device=wait_on, rank=rank,
-                          describe=f"grouped send/recv of the {output!r} blocks to "
-                                   f"{'every rank' if dst is None else f'rank {dst}'}",
-                          peers=sorted(peers), bytes_sent=sent, bytes_received=received)
-        self._used_by(pending, used)
-        self.last_exchange = pending
-        return pending if async_op else pending.wait()
+        compute = self._compute_total if output == "total" else self._compute_gas
+        blocks = compute(call, temperature, pressure, x)
+        if call.world == 1 and not (self.always_exchange and call.backend is not None):
+            return self._one_rank_result(call, blocks, async_op)
+        blocks = self._order_or_flush(call, blocks)
+        if output == "total" and call.plan.mode == "units":
+            return self._exchange_by_reduce(call, blocks[None], async_op)
+        return self._exchange_by_gather(call, blocks, async_op)
 
 
 def gather_arrays(local, n_levels, dst=0, group=None, device=None):

@@ -61,6 +61,25 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _spawn_ranks(world, target, arguments, patience, exit_codes=True):
+    """Starts `world` spawned ranks of target(rank, *arguments(port, queue)), collects one result
+    from each through the queue (waiting `patience` seconds for each), joins them and, unless
+    exit_codes is False, wants every exit code 0.  Returns the results as they arrived."""
+    import torch.multiprocessing as mp
+    context = mp.get_context("spawn")
+    queue = context.Queue()
+    port = _free_port()
+    procs = [context.Process(target=target, args=(r,) + tuple(arguments(port, queue)))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    results = [queue.get(timeout=patience) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+        assert not exit_codes or p.exitcode == 0
+    return results
+
+
 FORMULAS = ("H2O", "CO2", "O3")
 EIGHT = ("H2O", "CO2", "O3", "N2O", "CO", "CH4", "O2", "N2")
 GRID = (1, 41, 10)
@@ -142,27 +161,12 @@ def _worker(rank, world, port, n_levels, dst, output, queue, FORMULAS=FORMULAS, 
     (3, 2, 0, "gas"), (3, 2, 0, "total"), (3, 1, None, "gas"),
 ])
 def test_ranks_shard_units_and_collect(world, n_levels, dst, output):
-    import torch.multiprocessing as mp
-    context = mp.get_context("spawn")
-    queue = context.Queue()
-    port = _free_port()
     _run_ranks(world, n_levels, dst, output)
 
 
 def _run_ranks(world, n_levels, dst, output, formulas=FORMULAS, members=None):
-    import torch.multiprocessing as mp
-    context = mp.get_context("spawn")
-    queue = context.Queue()
-    port = _free_port()
-    procs = [context.Process(target=_worker, args=(r, world, port, n_levels, dst, output, queue,
-                                                   formulas, members))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [queue.get(timeout=240) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    results = _spawn_ranks(world, _worker, lambda port, queue: (
+        world, port, n_levels, dst, output, queue, formulas, members), patience=240)
     assert sorted(r[:2] for r in results) == [(r, True) for r in range(world)]
     assert sum(r[2] for r in results) == 2*n_levels*len(formulas)
 
@@ -214,16 +218,8 @@ def _late_worker(rank, port, queue):
 
 
 def test_exchange_timeout_names_the_rank_and_its_peers():
-    import torch.multiprocessing as mp
-    context = mp.get_context("spawn")
-    queue = context.Queue()
-    port = _free_port()
-    procs = [context.Process(target=_late_worker, args=(r, port, queue)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = dict((r[0], r[1:]) for r in (queue.get(timeout=120) for _ in procs))
-    for p in procs:
-        p.join(timeout=60)
+    results = dict((r[0], r[1:]) for r in _spawn_ranks(
+        2, _late_worker, lambda port, queue: (port, queue), patience=120, exit_codes=False))
     message, seconds = results[0]
     assert "rank 0" in message and "[1]" in message and "not complete after 1 s" in message
     assert "B to receive" in message and seconds < 3.5
@@ -276,16 +272,6 @@ def test_calls_queued_back_to_back_without_waiting(n_levels, output, dst):
     """four asynchronous calls in a row, none waited for until all are queued -- every
     one of them must still deliver its own result (a buffer's next writer is ordered behind the
     exchange that last used it)."""
-    import torch.multiprocessing as mp
-    context = mp.get_context("spawn")
-    queue = context.Queue()
-    port = _free_port()
-    procs = [context.Process(target=_back_to_back_worker,
-                             args=(r, port, n_levels, output, dst, queue)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = sorted(queue.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    results = sorted(_spawn_ranks(2, _back_to_back_worker, lambda port, queue: (
+        port, n_levels, output, dst, queue), patience=120))
     assert results == [(0, True), (1, True)]

@@ -49,26 +49,38 @@ def test_for_engine_single_rank_against_oracle(oracle, output):
     engine.close()
 
 
-def _run_ranks(n_levels, output, backend, world=2, order_on_device=False):
+def _run_children(world, script, arguments, settings, patience, says="rank {} ok", tail=3000):
+    """Starts `world` fresh interpreters of tests/<script> as the ranks of one rendezvous (RANK,
+    WORLD_SIZE, LOCAL_RANK, MASTER_ADDR and a free MASTER_PORT, plus `settings`), gives each
+    `patience` seconds -- all are killed when one runs out of them -- and wants exit code 0 and
+    the line `says` (with the rank) from every one.  Returns what rank 0 printed."""
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     procs = []
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), LOCAL_RANK=str(rank), DIST_BACKEND=backend,
-                   PYLBL_AMD_ORDER_ON_DEVICE="1" if order_on_device else "0")
+                   MASTER_PORT=str(port), LOCAL_RANK=str(rank), **settings)
         procs.append(subprocess.Popen(
-            [sys.executable, os.path.join(ROOT, "tests", "dist_gpu_worker.py"), str(n_levels),
-             output], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+            [sys.executable, os.path.join(ROOT, "tests", script)] + list(arguments),
+            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    printed = []
     for rank, proc in enumerate(procs):
         try:
-            out, err = proc.communicate(timeout=300)
+            out, err = proc.communicate(timeout=patience)
         except subprocess.TimeoutExpired:
             for other in procs:
                 other.kill()
             raise
-        assert proc.returncode == 0 and f"rank {rank} ok" in out, out + err[-3000:]
+        assert proc.returncode == 0 and says.format(rank) in out, out + err[-tail:]
+        printed.append(out)
+    return printed[0]
+
+
+def _run_ranks(n_levels, output, backend, world=2, order_on_device=False):
+    _run_children(world, "dist_gpu_worker.py", [str(n_levels), output],
+                  {"DIST_BACKEND": backend,
+                   "PYLBL_AMD_ORDER_ON_DEVICE": "1" if order_on_device else "0"}, patience=300)
 
 
 @pytest.mark.parametrize("ordering", ["host", "device"])
@@ -91,25 +103,8 @@ def test_config3_shape_over_the_ranks_the_card_allows():
     in tests/test_gpu_baseline_configs.py): 1-101 cm-1 at 0.001
     cm-1, gloo, kernels and exchange ordered on the device.  Rank 0 compares two levels of every
     rank's block with the oracle (tests/dist_config3_worker.py)."""
-    world = 5
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), LOCAL_RANK=str(rank), PYLBL_AMD_ORDER_ON_DEVICE="1")
-        procs.append(subprocess.Popen(
-            [sys.executable, os.path.join(ROOT, "tests", "dist_config3_worker.py"), "64"],
-            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    for rank, proc in enumerate(procs):
-        try:
-            out, err = proc.communicate(timeout=600)
-        except subprocess.TimeoutExpired:
-            for other in procs:
-                other.kill()
-            raise
-        assert proc.returncode == 0 and f"rank {rank} ok" in out, out + err[-3000:]
+    _run_children(5, "dist_config3_worker.py", ["64"], {"PYLBL_AMD_ORDER_ON_DEVICE": "1"},
+                  patience=600)
 
 
 def _visible_gpus():
@@ -177,18 +172,7 @@ def test_rccl_at_world_size_one():
     views of the collected array), calls queued back to back without waiting, all_reduce / reduce
     on an engine-written block ordered by lbl_order_stream_after_engine, Pending.wait's device
     branch -- all oracle-checked (tests/rccl_one_rank_worker.py)."""
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-               MASTER_PORT=str(port))
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    proc = subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "rccl_one_rank_worker.py")],
-                            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    try:
-        out, err = proc.communicate(timeout=300)
-    except subprocess.TimeoutExpired:
-        proc.kill()
-        raise
-    assert proc.returncode == 0 and "rccl one rank ok" in out, out + err[-4000:]
+    legacy = os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")          # (kept where it is set)
+    out = _run_children(1, "rccl_one_rank_worker.py", [], {"HSA_ENABLE_IPC_MODE_LEGACY": legacy},
+                        patience=300, says="rccl one rank ok", tail=4000)
     assert "librccl" in out
