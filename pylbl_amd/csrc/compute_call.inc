@@ -10,7 +10,7 @@ namespace {
 // wait_for: where a blocking call (no LBL_ASYNC) leaves an event behind its last operation instead
 // of waiting for it -- the caller waits after it has released the engine's mutex, so that other
 // threads queue their calls meanwhile.  nullptr: wait here.
-int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_for = nullptr)
+int compute(lbl_engine * engine, const ComputeRequest & rq, Event * wait_for = nullptr)
 {
     CallShape shape;
     const int checked = shape_of(engine, rq, shape);
@@ -67,7 +67,7 @@ int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_fo
             }
             else if (pass.finish_stream != stream)
             {
-                HIP_TRY(hipEventRecord(lane.piece_summed[piece], stream));
+                lane.piece_summed[piece].record(stream);
             }
         }
         if (with_pedestal) finish_with_pedestal(call, pass);
@@ -80,13 +80,13 @@ int compute(lbl_engine * engine, const ComputeRequest & rq, hipEvent_t * wait_fo
 // the one thing entry() alone would not give.
 int locked_compute(lbl_engine * engine, const ComputeRequest & rq)
 {
-    hipEvent_t last = nullptr;
+    Event last;
     int status = entry(engine, [&] { return compute(engine, rq, &last); });
     if (last != nullptr)
     {
         const hipError_t waited = hipEventSynchronize(last);
         EngineLock lock(engine->mutex);
-        engine->event_pool.push_back(last);
+        engine->event_pool.push_back(std::move(last));
         if (waited != hipSuccess && status == LBL_OK)
         {
             status = fail(engine, LBL_ERROR, hipGetErrorString(waited));

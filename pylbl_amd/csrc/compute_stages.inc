@@ -256,12 +256,7 @@ void reserve_for_call(const LinesCall & c)
     const CallTraits & t = c.traits;
     Lane & lane = c.lane;
     const long long n_lines = s.m->n_lines, n_tiles = s.tiling.n_tiles, chunk = c.chunk;
-    if (lane.levels_in_flight)
-    {
-        HIP_TRY(hipEventSynchronize(lane.levels_copied));
-        lane.levels_in_flight = false;
-    }
-    lane.reserve_pinned((size_t)chunk);
+    lane.level_feed.refill((size_t)chunk);
     lane.levels.reserve((size_t)chunk);
     lane.wing.reserve((size_t)(chunk*std::max(n_lines, 1ll)));
     lane.core.reserve((size_t)(chunk*std::max(n_lines, 1ll)));
@@ -352,7 +347,7 @@ int stage_levels(const LinesCall & c, long long base, int count)
     for (int l = 0; l < count; ++l)
     {
         std::string why;
-        LevelScalars & lv = lane.pinned_levels[l];
+        LevelScalars & lv = lane.level_feed.block[l];
         if (!fill_level(*c.shape.m, rq.temperature[base + l], rq.pressure[base + l],
                         rq.vmr[base + l], lv, why))
         {
@@ -363,10 +358,7 @@ int stage_levels(const LinesCall & c, long long base, int count)
     }
     if (!levels_inline(c.engine, count))
     {
-        HIP_TRY(hipMemcpyAsync(lane.levels.data, lane.pinned_levels, count*sizeof(LevelScalars),
-                               hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(hipEventRecord(lane.levels_copied, c.stream));
-        lane.levels_in_flight = true;
+        lane.level_feed.upload(lane.levels.data, (size_t)count, c.stream);
     }
     return LBL_OK;
 }
@@ -421,7 +413,7 @@ void prepare_on_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
                                                                : nullptr;
                 LineWing & w = hp.wing[(size_t)(l*n_lines + j)];
                 const int status = prepare_line(
-                    lane.pinned_levels[l], s.g, m.column[0][j], m.column[1][j], m.column[2][j],
+                    lane.level_feed.block[l], s.g, m.column[0][j], m.column[1][j], m.column[2][j],
                     m.column[3][j], m.column[4][j], m.column[5][j], m.column[6][j],
                     std::max(m.iso_slot[j], 0), ok, w, hp.core[(size_t)(l*n_lines + j)], d);
                 if (status == 1 && w.last >= w.first) total += w.last - w.first + 1;
@@ -477,7 +469,7 @@ void launch_prologue(const LinesCall & c, int count, HostPrep & hp)
     InlineLevels packed;
     if (inline_levels)
     {
-        std::memcpy(packed.level, lane.pinned_levels, count*sizeof(LevelScalars));
+        std::memcpy(packed.level, lane.level_feed.block, count*sizeof(LevelScalars));
     }
     const int prepare_blocks = (int)((s.m->n_lines + 255)/256);
     const int schedule_blocks = c.traits.want_k ? (int)((8ll*s.tiling.n_tiles + 255)/256) : 0;
@@ -531,7 +523,7 @@ void start_pedestal_search(const LinesCall & c, const Lane::Pass & p)
     Lane & lane = c.lane;
     if (engine->overlap_pedestal)
     {
-        HIP_TRY(hipEventRecord(lane.prepared, c.stream));
+        lane.prepared.record(c.stream);
         HIP_TRY(hipStreamWaitEvent(lane.side, lane.prepared, 0));
     }
     engine->timed(kTimePedestal, p.ped_stream, [&] {
@@ -541,7 +533,7 @@ void start_pedestal_search(const LinesCall & c, const Lane::Pass & p)
     }, 0);
     if (engine->overlap_pedestal)
     {
-        HIP_TRY(hipEventRecord(lane.runs_found, lane.side));
+        lane.runs_found.record(lane.side);
     }
 }
 
@@ -576,7 +568,7 @@ AccumulateArgs accumulate_args(const LinesCall & c, const Lane::Pass & p)
     // With a pedestal the kernel stores plain sums; pedestal_apply_kernel finishes.
     args.scale_density = (!c.with_pedestal && (rq.flags & LBL_SCALE_DENSITY)) ? 1 : 0;
     args.accumulate = (!c.with_pedestal && add_into) ? 1 : 0;
-    args.inner_everywhere = inner_points_everywhere(lane.pinned_levels, p.count, rq, s);
+    args.inner_everywhere = inner_points_everywhere(lane.level_feed.block, p.count, rq, s);
 #ifdef LBL_ABLATE
     args.ablate = c.engine->ablate;
 #endif
@@ -740,7 +732,7 @@ void derived_to_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
 
 // The end of a call: the block's write record, what goes back by value, and the wait of a call
 // without LBL_ASYNC -- here, or left to the caller as an event (compute()'s wait_for).
-int end_call(const LinesCall & c, const HostPrep & hp, hipEvent_t * wait_for)
+int end_call(const LinesCall & c, const HostPrep & hp, Event * wait_for)
 {
     lbl_engine * engine = c.engine;
     const ComputeRequest & rq = c.rq;
@@ -767,7 +759,7 @@ int end_call(const LinesCall & c, const HostPrep & hp, hipEvent_t * wait_for)
         if (wait_for != nullptr)
         {
             *wait_for = engine->take_event();
-            HIP_TRY(hipEventRecord(*wait_for, stream));
+            wait_for->record(stream);
         }
         else
         {

@@ -89,13 +89,7 @@ int lbl_continuum_load(lbl_engine * engine, int32_t n_bands, const lbl_band * ba
 
 int lbl_continuum_free(lbl_engine * engine, int32_t continuum)
 {
-    return entry(engine, [&] {
-        if (find_slot(engine->continua, continuum) == nullptr)
-        {
-            return fail(engine, LBL_BAD_ARGUMENT, "unknown continuum handle.");
-        }
-        (void)hipSetDevice(engine->device);
-        engine->drain_lanes();
+    return free_slot(engine, &lbl_engine::continua, continuum, "unknown continuum handle.", [&] {
         // (groups that hold the continuum's table go with it)
         for (auto & group : engine->groups)
         {
@@ -105,8 +99,6 @@ int lbl_continuum_free(lbl_engine * engine, int32_t continuum)
                 group.reset();
             }
         }
-        engine->continua[continuum].reset();
-        return LBL_OK;
     });
 }
 
@@ -146,16 +138,7 @@ int lbl_grid_load(lbl_engine * engine, int64_t n, const double * wavenumber, int
 
 int lbl_grid_free(lbl_engine * engine, int32_t grid)
 {
-    return entry(engine, [&] {
-        if (find_slot(engine->grids, grid) == nullptr)
-        {
-            return fail(engine, LBL_BAD_ARGUMENT, "unknown grid handle.");
-        }
-        (void)hipSetDevice(engine->device);
-        engine->drain_lanes();
-        engine->grids[grid].reset();
-        return LBL_OK;
-    });
+    return free_slot(engine, &lbl_engine::grids, grid, "unknown grid handle.");
 }
 
 int lbl_continuum_compute(lbl_engine * engine, int32_t continuum, int32_t grid,
@@ -276,8 +259,8 @@ int lbl_continuum_compute_many(lbl_engine * engine, int32_t n_continua,
             engine->groups.push_back(std::move(fresh));
             group = engine->groups.back().get();
         }
-        group->wait();      // the previous call's copy may still read the pinned level block
-        group->reserve_pinned((size_t)n_continua*n_levels);
+        // (waits first: the previous call's copy may still read the pinned level block)
+        ContinuumLevel * staged = group->pinned.refill((size_t)n_continua*n_levels);
         group->levels.reserve((size_t)n_continua*n_levels);
         group->coarse.reserve((size_t)n_levels*group->level_points);
         group->slopes.reserve((size_t)n_levels*group->level_points);
@@ -286,15 +269,12 @@ int lbl_continuum_compute_many(lbl_engine * engine, int32_t n_continua,
             for (int l = 0; l < n_levels; ++l)
             {
                 // vmr: [continuum][level][LBL_VMR_COUNT] -- LBL_VMR_SELF differs between them
-                group->pinned[(size_t)m*n_levels + l] = continuum_level(
+                staged[(size_t)m*n_levels + l] = continuum_level(
                     temperature[l], pressure[l]*0.01,
                     vmr + ((size_t)m*n_levels + l)*LBL_VMR_COUNT);      // utils.py:13,172
             }
         }
-        HIP_TRY(hipMemcpyAsync(group->levels.data, group->pinned,
-                               (size_t)n_continua*n_levels*sizeof(ContinuumLevel),
-                               hipMemcpyHostToDevice, stream));
-        group->copied_on(stream);
+        group->pinned.upload(group->levels.data, (size_t)n_continua*n_levels, stream);
         engine->timed(kTimeBandSpectra, stream, [&] {
             dim3 blocks((unsigned)((group->widest + 255)/256), (unsigned)group->n_bands,
                         (unsigned)n_levels);
@@ -340,7 +320,7 @@ int lbl_continuum_bands(lbl_engine * engine, int32_t continuum, double temperatu
         HIP_TRY(hipSetDevice(engine->device));
         for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
         hipStream_t stream = engine->stream;
-        c->wait();
+        c->pinned.wait();
         const ContinuumLevel level = continuum_level(temperature, pressure_mb, vmr);
         c->levels.reserve(1);
         c->coarse.reserve((size_t)c->set.coarse_points);

@@ -20,18 +20,9 @@ __global__ void touch_kernel() {}
 // stream, and if that only gets through when the lane is done, the two are one queue.
 void calibrate_delivery_lanes(lbl_engine * e)
 {
-    // (Events that leave with the function, also when a HIP call fails on the way.)
-    struct Events
-    {
-        hipEvent_t lane_done = nullptr, through = nullptr;
-        ~Events()
-        {
-            if (lane_done != nullptr) (void)hipEventDestroy(lane_done);
-            if (through != nullptr) (void)hipEventDestroy(through);
-        }
-    } ev;
-    HIP_TRY(hipEventCreate(&ev.lane_done));
-    HIP_TRY(hipEventCreate(&ev.through));
+    Event lane_done(true), through(true);
+    lane_done.create();
+    through.create();
     // The runtime creates a stream's hardware queue at its first submission: every stream gets
     // an empty kernel first, so that no probe below times a queue being set up.
     hipLaunchKernelGGL(touch_kernel, dim3(1), dim3(64), 0, e->copy_stream);
@@ -51,14 +42,14 @@ void calibrate_delivery_lanes(lbl_engine * e)
         {
             hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, e->lanes[l].main, ticks,
                                (int *)nullptr);
-            HIP_TRY(hipEventRecord(ev.lane_done, e->lanes[l].main));
+            lane_done.record(e->lanes[l].main);
             hipLaunchKernelGGL(touch_kernel, dim3(1), dim3(64), 0, e->copy_stream);
-            HIP_TRY(hipEventRecord(ev.through, e->copy_stream));
+            through.record(e->copy_stream);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventSynchronize(ev.lane_done));
-            HIP_TRY(hipEventSynchronize(ev.through));
+            lane_done.synchronize();
+            through.synchronize();
             float ahead = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ahead, ev.through, ev.lane_done));
+            HIP_TRY(hipEventElapsedTime(&ahead, through, lane_done));
             if (!(ahead > 0.01f)) shared += 1;
         }
         e->delivers_badly[l] = 2*shared > probes;
@@ -91,10 +82,10 @@ int lbl_order_stream_after_engine(lbl_engine * engine, void * stream)
         // the main streams and the copy stream stand for everything the engine has queued.
         for (auto & lane : engine->lanes)
         {
-            HIP_TRY(hipEventRecord(lane.handed_over, lane.main));
+            lane.handed_over.record(lane.main);
             HIP_TRY(hipStreamWaitEvent(theirs, lane.handed_over, 0));
         }
-        HIP_TRY(hipEventRecord(engine->copies_handed_over, engine->copy_stream));
+        engine->copies_handed_over.record(engine->copy_stream);
         HIP_TRY(hipStreamWaitEvent(theirs, engine->copies_handed_over, 0));
         return LBL_OK;
     });
@@ -104,7 +95,7 @@ int lbl_order_engine_after_stream(lbl_engine * engine, void * stream)
 {
     return entry(engine, [&] {
         HIP_TRY(hipSetDevice(engine->device));
-        HIP_TRY(hipEventRecord(engine->taken_over, reinterpret_cast<hipStream_t>(stream)));
+        engine->taken_over.record(reinterpret_cast<hipStream_t>(stream));
         for (auto & lane : engine->lanes)
         {
             HIP_TRY(hipStreamWaitEvent(lane.main, engine->taken_over, 0));
@@ -227,7 +218,7 @@ int lbl_copy_rows_to_host(lbl_engine * engine, void * host, int64_t host_pitch,
         // them holds now, then copies beside whatever is queued afterwards.
         for (auto & lane : engine->lanes)
         {
-            HIP_TRY(hipEventRecord(lane.queued, lane.main));
+            lane.queued.record(lane.main);
             HIP_TRY(hipStreamWaitEvent(engine->copy_stream, lane.queued, 0));
         }
         HIP_TRY(hipMemcpy2DAsync(host, (size_t)host_pitch, device, (size_t)device_pitch,
@@ -264,7 +255,7 @@ int lbl_host_free(lbl_engine * engine, void * pointer)
             try { engine->finish_deferred(); } catch (const HipFailure &) { engine->cancel_deferred(); }
             engine->drain_lanes();
         }
-        if (engine->copy_stream != nullptr) (void)hipStreamSynchronize(engine->copy_stream);
+        engine->copy_stream.drain();
         hipError_t status = hipHostFree(pointer);
         if (status != hipSuccess) return fail(engine, LBL_ERROR, hipGetErrorString(status));
         return LBL_OK;

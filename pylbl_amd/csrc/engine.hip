@@ -11,12 +11,15 @@
 // workspace); calls that can share the GPU rotate over them and are ordered against each other
 // only through the memory they write (Lane::note_write, lbl_engine::order_after_writers).
 // There is no CPU compute path in this file: without a HIP device every entry point fails.
+// An engine that fails half-way through lbl_engine_create, and one that is destroyed, release
+// their streams, events and memory the same way: through ~lbl_engine (engine_core.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -45,6 +48,8 @@
 
 // (calibrate_delivery_lanes, used by lbl_engine_create)
 #include "delivery.inc"
+// (find_slot, store_slot, free_slot: the handle tables)
+#include "slot_entry.inc"
 
 extern "C" {
 
@@ -81,15 +86,25 @@ int lbl_engine_create(int device, lbl_engine ** engine)
         e->device = device;
         for (int i = 0; i < kAllLanes; ++i) e->lanes[i].create(i == kSlotLane);
         e->stream = e->lanes[0].main;
-        HIP_TRY(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+        e->copy_stream.create();
         calibrate_delivery_lanes(e.get());
-        HIP_TRY(hipEventCreateWithFlags(&e->copies_handed_over, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->taken_over, hipEventDisableTiming));
+        e->copies_handed_over.create();
+        e->taken_over.create();
         *engine = e.release();
     }
+    // (What entry() catches.  An engine made in part leaves through ~lbl_engine, with its device
+    // still current.)
     catch (const HipFailure & f)
     {
         return fail(nullptr, LBL_NO_DEVICE, f.message);
+    }
+    catch (const std::bad_alloc &)
+    {
+        return fail(nullptr, LBL_NO_DEVICE, "host allocation failed.");
+    }
+    catch (const std::exception & e)
+    {
+        return fail(nullptr, LBL_NO_DEVICE, e.what());
     }
     return LBL_OK;
 }
@@ -104,24 +119,6 @@ int lbl_engine_destroy(lbl_engine * engine)
         engine->cancel_deferred();
     }
     (void)hipSetDevice(engine->device);
-    engine->drain_lanes();
-    for (auto & s : engine->spans)
-    {
-        (void)hipEventDestroy(s.begin);
-        (void)hipEventDestroy(s.end);
-    }
-    for (auto & e : engine->event_pool) (void)hipEventDestroy(e);
-    if (engine->epoch != nullptr) (void)hipEventDestroy(engine->epoch);
-    engine->molecules.clear();
-    engine->groups.clear();
-    engine->continua.clear();
-    engine->xsecs.clear();
-    engine->grids.clear();
-    engine->instruments.clear();
-    for (auto & lane : engine->lanes) lane.destroy();
-    if (engine->copy_stream != nullptr) (void)hipStreamDestroy(engine->copy_stream);
-    if (engine->copies_handed_over != nullptr) (void)hipEventDestroy(engine->copies_handed_over);
-    if (engine->taken_over != nullptr) (void)hipEventDestroy(engine->taken_over);
     delete engine;
     return LBL_OK;
 }
@@ -248,31 +245,14 @@ int lbl_molecule_load(lbl_engine * engine, int64_t n_lines,
             }
         }
         HIP_TRY(hipStreamSynchronize(stream));
-        // Reuse a freed slot if there is one.
-        size_t slot = engine->molecules.size();
-        for (size_t i = 0; i < engine->molecules.size(); ++i)
-        {
-            if (!engine->molecules[i]) { slot = i; break; }
-        }
-        if (slot == engine->molecules.size()) engine->molecules.emplace_back();
-        engine->molecules[slot] = std::move(m);
-        *molecule = (int32_t)slot;
+        *molecule = store_slot(engine->molecules, std::move(m));
         return LBL_OK;
     });
 }
 
 int lbl_molecule_free(lbl_engine * engine, int32_t molecule)
 {
-    return entry(engine, [&] {
-        if (find_molecule(engine, molecule) == nullptr)
-        {
-            return fail(engine, LBL_BAD_ARGUMENT, "unknown molecule handle.");
-        }
-        (void)hipSetDevice(engine->device);
-        engine->drain_lanes();
-        engine->molecules[molecule].reset();
-        return LBL_OK;
-    });
+    return free_slot(engine, &lbl_engine::molecules, molecule, "unknown molecule handle.");
 }
 
 int lbl_compute(lbl_engine * engine, int32_t molecule, int32_t n_levels,
@@ -509,7 +489,6 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 
 }  // extern "C"
 
-#include "slot_entry.inc"
 #include "continuum_entry.inc"
 #include "path_entry.inc"
 #include "radiance_entry.inc"

@@ -1,8 +1,13 @@
-// State of the engine: device buffers, a molecule's resident line table and work-item plans,
-// the lanes (stream pair + workspace) asynchronous calls rotate over, and struct lbl_engine
-// itself -- options, timing spans, the write records calls are ordered by and the part of a
-// call that LBL_DEFER_FINISH keeps back.  Included by engine.hip only (one translation unit).
+// State of the engine: a molecule's resident line table and work-item plans, the lanes (stream
+// pair + workspace) asynchronous calls rotate over, and struct lbl_engine itself -- options,
+// timing spans, the write records calls are ordered by and the part of a call that
+// LBL_DEFER_FINISH keeps back.  Every stream, event, device buffer and page-locked block in here
+// is held by an owner type of hip_owners.h: nothing is released by hand, and ~lbl_engine and the
+// order of its members decide what leaves when.  Included by engine.hip only (one translation
+// unit).
 #pragma once
+
+#include "hip_owners.h"
 
 namespace {
 
@@ -13,56 +18,6 @@ thread_local std::string g_create_error;
 // lbl_last_error returns, so that a thread never reads a message another thread is writing.
 thread_local std::string g_thread_error;
 thread_local const void * g_thread_error_engine = nullptr;
-
-struct HipFailure
-{
-    std::string message;
-};
-
-#define HIP_TRY(call)                                                                     \
-    do {                                                                                  \
-        hipError_t status_ = (call);                                                      \
-        if (status_ != hipSuccess)                                                        \
-        {                                                                                 \
-            throw HipFailure{std::string(#call) + ": " + hipGetErrorString(status_)};     \
-        }                                                                                 \
-    } while (0)
-
-template <typename T>
-struct DeviceBuffer
-{
-    T * data = nullptr;
-    size_t capacity = 0;   // elements
-
-    void reserve(size_t count)
-    {
-        if (count <= capacity) return;
-        release();
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&data), count*sizeof(T)));
-        capacity = count;
-    }
-    void release()
-    {
-        if (data != nullptr)
-        {
-            (void)hipFree(data);
-            data = nullptr;
-            capacity = 0;
-        }
-    }
-    void upload(const T * host, size_t count, hipStream_t stream)
-    {
-        reserve(count);
-        if (count > 0)
-        {
-            HIP_TRY(hipMemcpyAsync(data, host, count*sizeof(T), hipMemcpyHostToDevice, stream));
-        }
-    }
-    ~DeviceBuffer() { release(); }
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer & operator=(const DeviceBuffer &) = delete;
-};
 
 struct Molecule
 {
@@ -146,14 +101,15 @@ enum { kTimePrepare = 0, kTimeSchedule = 1, kTimeAccumulate = 2, kTimePedestal =
 // overlaps the accumulate kernels of the others, and its own).
 struct Lane
 {
-    hipStream_t main = nullptr;     // prepare, schedule, accumulate, apply, copies
-    hipStream_t side = nullptr;     // the pedestal pre-pass
-    hipEvent_t prepared = nullptr, pedestal_done = nullptr, levels_copied = nullptr;
-    hipEvent_t runs_found = nullptr;
-    hipEvent_t queued = nullptr;    // what the copy stream waits for (lbl_copy_rows_to_host)
-    hipEvent_t handed_over = nullptr;   // what a caller's stream waits for (lbl_order_stream_after_engine)
-    hipEvent_t piece_done[8] = {};      // behind the last kernel of each piece of a streamed call
-    hipEvent_t piece_summed[8] = {};    // behind a piece's accumulate launch (pedestal: applied elsewhere)
+    // (The streams first: members leave in reverse order, so every event and buffer below is
+    // gone before the streams are.)
+    Stream main;                    // prepare, schedule, accumulate, apply, copies
+    Stream side;                    // the pedestal pre-pass
+    Event prepared, pedestal_done, runs_found;
+    Event queued;                   // what the copy stream waits for (lbl_copy_rows_to_host)
+    Event handed_over;              // what a caller's stream waits for (lbl_order_stream_after_engine)
+    Event piece_done[8];            // behind the last kernel of each piece of a streamed call
+    Event piece_summed[8];          // behind a piece's accumulate launch (pedestal: applied elsewhere)
     // One pass of a lines call (levels [base, base + count) of the request): where its spectra end
     // up, where the accumulate kernel writes, and the streams its later stages run on.
     struct Pass
@@ -189,13 +145,12 @@ struct Lane
     } finish;
     // The last few writes of device output queued on this lane: where, and an event behind the
     // kernel that wrote.  A call on another lane that touches the same memory waits for it.
-    struct Write { const char * begin = nullptr; const char * end = nullptr; hipEvent_t done = nullptr; };
+    struct Write { const char * begin = nullptr; const char * end = nullptr; Event done; };
     static constexpr int kWrites = 4;
     Write writes[kWrites];
     int next_write = 0;
     bool writes_wrapped = false;
     bool used = false;              // something was queued here since lane 0 last joined it
-    bool levels_in_flight = false;
     DeviceBuffer<LineWing> wing;
     DeviceBuffer<LineCore> core;
     DeviceBuffer<TileSchedule> schedule;
@@ -208,73 +163,38 @@ struct Lane
     DeviceBuffer<unsigned long long> evals;
     DeviceBuffer<int> wing_bounds;  // [levels][kWingBounds] of the pass (line_prep.h)
     PedestalWorkspace pedestal;
-    LevelScalars * pinned_levels = nullptr;
-    size_t pinned_capacity = 0;
+    PinnedFeed<LevelScalars> level_feed;    // the level scalars of a pass on their way to `levels`
 
+    // The events are made here, not at first use: no call pays for one.
     void create(bool urgent = false)
     {
         // The pre-pass is short and latency-bound (a serial chain): its queue goes first
         // whenever the accumulate grid frees a slot.
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        if (urgent)
+        main.create(urgent);
+        side.create(true);
+        for (Event * e : {&prepared, &pedestal_done, &runs_found, &queued, &handed_over,
+                          &level_feed.copied})
         {
-            HIP_TRY(hipStreamCreateWithPriority(&main, hipStreamNonBlocking, greatest));
+            e->create();
         }
-        else
-        {
-            HIP_TRY(hipStreamCreateWithFlags(&main, hipStreamNonBlocking));
-        }
-        HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, greatest));
-        HIP_TRY(hipEventCreateWithFlags(&prepared, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&runs_found, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&queued, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&handed_over, hipEventDisableTiming));
-        for (auto & e : piece_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto & e : piece_summed) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto & w : writes) HIP_TRY(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&pedestal_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&levels_copied, hipEventDisableTiming));
+        for (auto & e : piece_done) e.create();
+        for (auto & e : piece_summed) e.create();
+        for (auto & w : writes) w.done.create();
     }
     void drain()
     {
-        if (main != nullptr) (void)hipStreamSynchronize(main);
-        if (side != nullptr) (void)hipStreamSynchronize(side);
+        main.drain();
+        side.drain();
     }
-    void destroy()
-    {
-        drain();
-        if (pinned_levels != nullptr) (void)hipHostFree(pinned_levels);
-        pinned_levels = nullptr;
-        if (prepared != nullptr) (void)hipEventDestroy(prepared);
-        if (pedestal_done != nullptr) (void)hipEventDestroy(pedestal_done);
-        if (runs_found != nullptr) (void)hipEventDestroy(runs_found);
-        if (queued != nullptr) (void)hipEventDestroy(queued);
-        if (handed_over != nullptr) (void)hipEventDestroy(handed_over);
-        for (auto & e : piece_done) { if (e != nullptr) (void)hipEventDestroy(e); e = nullptr; }
-        for (auto & e : piece_summed) { if (e != nullptr) (void)hipEventDestroy(e); e = nullptr; }
-        for (auto & w : writes) { if (w.done != nullptr) (void)hipEventDestroy(w.done); w.done = nullptr; }
-        if (levels_copied != nullptr) (void)hipEventDestroy(levels_copied);
-        if (main != nullptr) (void)hipStreamDestroy(main);
-        if (side != nullptr) (void)hipStreamDestroy(side);
-        main = side = nullptr;
-    }
-    void reserve_pinned(size_t count)
-    {
-        if (count <= pinned_capacity) return;
-        if (pinned_levels != nullptr) (void)hipHostFree(pinned_levels);
-        pinned_levels = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&pinned_levels),
-                              count*sizeof(LevelScalars), hipHostMallocDefault));
-        pinned_capacity = count;
-    }
+    // Nothing a lane owns is released while its streams still run.
+    ~Lane() { drain(); }
     // Everything queued on `stream` (this lane's) so far has written [begin, end).
     void note_write(const void * begin, long long bytes, hipStream_t stream)
     {
         Write & w = writes[next_write];
         w.begin = reinterpret_cast<const char *>(begin);
         w.end = w.begin + bytes;
-        HIP_TRY(hipEventRecord(w.done, stream));
+        w.done.record(stream);
         next_write = (next_write + 1) % kWrites;
         if (next_write == 0) writes_wrapped = true;
     }
@@ -295,48 +215,11 @@ template <typename Level>
 struct LevelFeed
 {
     DeviceBuffer<Level> levels;
-    Level * pinned = nullptr;
-    size_t pinned_capacity = 0;
-    hipEvent_t done = nullptr;      // last kernel of the last call (the destructor waits for it)
-    hipEvent_t copied = nullptr;    // last copy out of the pinned block
-    bool in_flight = false;
+    PinnedFeed<Level> pinned;
+    Event done;                     // last kernel of the last call (the destructor waits for it)
 
-    // The host may refill the pinned block once the copy that read it has run; everything on the
-    // device side is ordered by the stream.
-    void wait()
-    {
-        if (in_flight) HIP_TRY(hipEventSynchronize(copied));
-        in_flight = false;
-    }
-    void copied_on(hipStream_t stream)
-    {
-        if (copied == nullptr) HIP_TRY(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(copied, stream));
-        in_flight = true;
-    }
-    void mark(hipStream_t stream)
-    {
-        if (done == nullptr) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(done, stream));
-    }
-    void reserve_pinned(size_t count)
-    {
-        if (count <= pinned_capacity) return;
-        if (pinned != nullptr) (void)hipHostFree(pinned);
-        pinned = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&pinned), count*sizeof(Level),
-                              hipHostMallocDefault));
-        pinned_capacity = count;
-    }
-    ~LevelFeed()
-    {
-        if (done != nullptr) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
-        if (copied != nullptr) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-        if (pinned != nullptr) (void)hipHostFree(pinned);
-    }
-    LevelFeed() = default;
-    LevelFeed(const LevelFeed &) = delete;
-    LevelFeed & operator=(const LevelFeed &) = delete;
+    void mark(hipStream_t stream) { done.record(stream); }
+    ~LevelFeed() { if (done != nullptr) (void)hipEventSynchronize(done); }
 };
 
 // One continuum (continuum.h): its bands, their coefficient table and the per-level
@@ -412,44 +295,7 @@ struct PathWorkspace
 {
     DeviceBuffer<double> tables;
     DeviceBuffer<double> partial;       // [rows][segments]
-    double * pinned = nullptr;
-    size_t pinned_capacity = 0;
-    hipEvent_t copied = nullptr;        // behind the last upload out of `pinned`
-    bool in_flight = false;
-
-    // The host may refill the pinned block once the copy that read it has run.
-    double * stage(size_t count)
-    {
-        if (in_flight) HIP_TRY(hipEventSynchronize(copied));
-        in_flight = false;
-        if (count > pinned_capacity)
-        {
-            if (pinned != nullptr) (void)hipHostFree(pinned);
-            pinned = nullptr;
-            pinned_capacity = 0;
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&pinned), count*sizeof(double),
-                                  hipHostMallocDefault));
-            pinned_capacity = count;
-        }
-        return pinned;
-    }
-    void upload(size_t count, hipStream_t stream)
-    {
-        tables.reserve(count);
-        HIP_TRY(hipMemcpyAsync(tables.data, pinned, count*sizeof(double), hipMemcpyHostToDevice,
-                               stream));
-        if (copied == nullptr) HIP_TRY(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(copied, stream));
-        in_flight = true;
-    }
-    ~PathWorkspace()
-    {
-        if (copied != nullptr) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-        if (pinned != nullptr) (void)hipHostFree(pinned);
-    }
-    PathWorkspace() = default;
-    PathWorkspace(const PathWorkspace &) = delete;
-    PathWorkspace & operator=(const PathWorkspace &) = delete;
+    PinnedFeed<double> staged;
 };
 
 }  // namespace
@@ -465,7 +311,6 @@ struct lbl_engine
     std::recursive_mutex mutex;
     int device = 0;
     hipStream_t stream = nullptr;   // == lanes[0].main: uploads, and what lbl_stream() returns
-    hipStream_t copy_stream = nullptr;  // results on their way to host memory
     // The runtime multiplexes its streams onto a handful of hardware queues (GPU_MAX_HW_QUEUES, 4
     // by default) in an order of its own, and a queue runs its packets one after the other: a copy
     // that shares its queue with the main stream of the lane that is computing waits for that
@@ -477,7 +322,11 @@ struct lbl_engine
     // each chosen to run beside it, was tried first: slower than the best single one -- every
     // further stream in use is one more queue for the hardware to take turns on.)
     bool delivers_badly[kLanes] = {};
-    hipEvent_t copies_handed_over = nullptr, taken_over = nullptr;  // lbl_order_*_after_*
+    // Members leave in reverse order, after the destructor's body has drained every stream and
+    // dropped the handle tables: the timing events and `path` first, then the lanes, then the
+    // copy stream, then these two.  Nothing waits on a stream that is gone.
+    Event copies_handed_over, taken_over;   // lbl_order_*_after_*
+    Stream copy_stream;             // results on their way to host memory
     std::string error;
     std::vector<std::unique_ptr<Molecule>> molecules;
     std::vector<std::unique_ptr<ContinuumSet>> continua;
@@ -508,26 +357,37 @@ struct lbl_engine
     int skip_delivery_lanes = 1;    // delivering calls avoid lanes that share the copy stream's queue
 
     // Timing.
-    struct Span { hipEvent_t begin, end; int kind, counts; };
+    struct Span { Event begin, end; int kind, counts; };
     std::vector<Span> spans;
-    std::vector<hipEvent_t> event_pool;
+    std::vector<Event> event_pool;      // timing events between uses
     double time_ms[kTimeKinds] = {};
     double busy_ms[kTimeKinds] = {};    // time during which AT LEAST ONE timed span of the kind ran
     double busy_reach[kTimeKinds] = {}; // where the union of the kind's spans ends so far [ms from epoch]
-    hipEvent_t epoch = nullptr;         // origin of the spans' positions (reset_epoch)
+    Event epoch;                        // origin of the spans' positions (reset_epoch)
     long long launches[kTimeKinds] = {};
 
-    hipEvent_t take_event()
+    Event take_event()
     {
+        Event e(true);
         if (!event_pool.empty())
         {
-            hipEvent_t e = event_pool.back();
+            e = std::move(event_pool.back());
             event_pool.pop_back();
-            return e;
         }
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
+        e.create();
         return e;
+    }
+
+    // Every stream drained, then whatever the handles stand for; the members follow (see above).
+    ~lbl_engine()
+    {
+        drain_lanes();
+        molecules.clear();
+        groups.clear();
+        continua.clear();
+        xsecs.clear();
+        grids.clear();
+        instruments.clear();
     }
 
     template <typename F>
@@ -539,10 +399,10 @@ struct lbl_engine
             return;
         }
         Span s{take_event(), take_event(), kind, counts};
-        HIP_TRY(hipEventRecord(s.begin, on));
+        s.begin.record(on);
         launch();
-        HIP_TRY(hipEventRecord(s.end, on));
-        spans.push_back(s);
+        s.end.record(on);
+        spans.push_back(std::move(s));
         if (spans.size() >= 4096) drain_spans();
     }
 
@@ -558,8 +418,8 @@ struct lbl_engine
     {
         if (spans.empty()) return;
         std::vector<std::pair<double, double>> placed[kTimeKinds];
-        for (auto & s : spans) HIP_TRY(hipEventSynchronize(s.end));
-        if (epoch != nullptr) HIP_TRY(hipEventSynchronize(epoch));
+        for (auto & s : spans) s.end.synchronize();
+        epoch.synchronize();
         for (auto & s : spans)
         {
             float ms = 0.f, from = 0.f;
@@ -595,8 +455,8 @@ struct lbl_engine
         }
         for (auto & s : spans)
         {
-            event_pool.push_back(s.begin);
-            event_pool.push_back(s.end);
+            event_pool.push_back(std::move(s.begin));
+            event_pool.push_back(std::move(s.end));
         }
         spans.clear();
     }
@@ -605,14 +465,14 @@ struct lbl_engine
     void reset_epoch()
     {
         if (epoch == nullptr) epoch = take_event();
-        HIP_TRY(hipEventRecord(epoch, stream));
+        epoch.record(stream);
         for (int kind = 0; kind < kTimeKinds; ++kind) busy_reach[kind] = 0.;
     }
 
     void drain_lanes()
     {
         for (auto & lane : lanes) lane.drain();
-        if (copy_stream != nullptr) (void)hipStreamSynchronize(copy_stream);
+        copy_stream.drain();
     }
 
     // Orders `stream` (a stream of lane `self`) behind every write of [begin, begin + bytes) queued
@@ -692,7 +552,7 @@ struct lbl_engine
         const long long q0 = f.point_begin[piece], q1 = f.point_begin[piece + 1];
         if (!f.streamed || q1 <= q0 || q0 >= f.columns) return;
         const long long c1 = std::min<long long>(q1, f.columns);
-        HIP_TRY(hipEventRecord(lane.piece_done[piece], after));
+        lane.piece_done[piece].record(after);
         HIP_TRY(hipStreamWaitEvent(copy_stream, lane.piece_done[piece], 0));
         HIP_TRY(hipMemcpy2DAsync(f.host + p.base*f.host_pitch + q0*8, (size_t)f.host_pitch,
                                  p.target + q0, (size_t)p.target_stride*8, (size_t)(c1 - q0)*8,
@@ -740,7 +600,7 @@ struct lbl_engine
         if (p.finish_stream != stream)
         {
             // Later users of the lane's main stream (and of the block) come after the last apply.
-            HIP_TRY(hipEventRecord(lane.pedestal_done, p.finish_stream));
+            lane.pedestal_done.record(p.finish_stream);
             HIP_TRY(hipStreamWaitEvent(stream, lane.pedestal_done, 0));
         }
         if (f.k != nullptr)
@@ -777,7 +637,7 @@ struct lbl_engine
         for (int i = 1; i < kAllLanes; ++i)
         {
             if (!lanes[i].used) continue;
-            HIP_TRY(hipEventRecord(lanes[i].queued, lanes[i].main));
+            lanes[i].queued.record(lanes[i].main);
             HIP_TRY(hipStreamWaitEvent(stream, lanes[i].queued, 0));
             lanes[i].used = false;
         }

@@ -212,17 +212,8 @@ int lbl_instrument_create(lbl_engine * engine, int32_t grid, int32_t shape, int3
 
 int lbl_instrument_free(lbl_engine * engine, int32_t handle)
 {
-    return entry(engine, [&] {
-        if (find_slot(engine->instruments, handle) == nullptr)
-        {
-            return fail(engine, LBL_BAD_ARGUMENT,
-                        "lbl_instrument_free: unknown instrument handle.");
-        }
-        (void)hipSetDevice(engine->device);
-        engine->drain_lanes();
-        engine->instruments[handle].reset();
-        return LBL_OK;
-    });
+    return free_slot(engine, &lbl_engine::instruments, handle,
+                     "lbl_instrument_free: unknown instrument handle.");
 }
 
 int lbl_instrument_apply(lbl_engine * engine, const double * values, int64_t row_stride,

@@ -262,7 +262,7 @@ struct PathCall
         HIP_TRY(hipSetDevice(engine->device));
         PathWorkspace & w = engine->path;
         const size_t words = tables.words.size();
-        std::memcpy(w.stage(words), tables.words.data(), words*8);
+        std::memcpy(w.staged.refill(words), tables.words.data(), words*8);
         engine->finish_deferred();
         if (flags & LBL_ASYNC)
         {
@@ -272,7 +272,8 @@ struct PathCall
         {
             for (int i = 1; i < kAllLanes; ++i) engine->lanes[i].drain();
         }
-        w.upload(words, engine->stream);
+        w.tables.reserve(words);
+        w.staged.upload(w.tables.data, words, engine->stream);
         return w.tables.data;
     }
 

@@ -39,6 +39,7 @@
 #include <string>
 #include <vector>
 
+#include "hip_owners.h"
 #include "line_prep.h"
 #include "tile_schedule.h"
 #include "wave_ops.h"
@@ -72,58 +73,28 @@ struct alignas(16) RunLink
 };
 static_assert(sizeof(RunLink) == 48, "RunLink");
 
-template <typename T>
-struct RawBuffer
-{
-    T * data = nullptr;
-    size_t capacity = 0;
-    void reserve(size_t count)
-    {
-        if (count <= capacity) return;
-        if (data != nullptr) (void)hipFree(data);
-        data = nullptr;
-        capacity = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&data), count*sizeof(T)) != hipSuccess)
-        {
-            throw std::runtime_error("hipMalloc failed in the pedestal workspace.");
-        }
-        capacity = count;
-    }
-    ~RawBuffer() { if (data != nullptr) (void)hipFree(data); }
-    RawBuffer() = default;
-    RawBuffer(const RawBuffer &) = delete;
-    RawBuffer & operator=(const RawBuffer &) = delete;
-};
-
 struct PedestalWorkspace
 {
-    RawBuffer<unsigned long long> scan[2];  // [levels][blocks of kScanThreads rows]: run_find_kernel's descriptors, used in turn
+    // [levels][blocks of kScanThreads rows]: run_find_kernel's descriptors, used in turn
+    DeviceBuffer<unsigned long long> scan[2];
     int scan_turn = 0;
-    RawBuffer<int> run_start;       // [levels][n_lines]
-    RawBuffer<int> prefix_bin;      // [levels][n_lines]: running maximum of the runs' bins
-    RawBuffer<int> run_count;       // [levels]
-    RawBuffer<RunMeta> runs;        // [levels][max_runs]
-    RawBuffer<double> slot_sums;    // [levels][max_runs][slot_stride]
-    RawBuffer<RunLink> links;       // [levels][max_runs]
-    RawBuffer<double> pedestals;    // [sweeps][levels][max_runs]: every sweep's values
-    RawBuffer<int> progress;        // [levels][chunks of 64 runs]: sweeps completed
-    RawBuffer<int2> run_slots;      // [levels][max_runs]: the runs' end slots, packed for the relaxation
-    RawBuffer<int> run_bin;         // [levels][max_runs]
-    RawBuffer<int> bin_end;         // [levels][bins]: 1 + the last run of every bin
-    RawBuffer<int> bin_first;       // [levels][bins]: the first run of every bin
-    RawBuffer<int> state;           // [levels][kChainState], see pedestal_chain.h
-    RawBuffer<double> slots;        // [levels][cells+1]: the serial chain's slots of the spectrum
-    RawBuffer<double> bin_sum;      // [levels][cells+2*cut+3]: total pedestal of every window
+    DeviceBuffer<int> run_start;    // [levels][n_lines]
+    DeviceBuffer<int> prefix_bin;   // [levels][n_lines]: running maximum of the runs' bins
+    DeviceBuffer<int> run_count;    // [levels]
+    DeviceBuffer<RunMeta> runs;     // [levels][max_runs]
+    DeviceBuffer<double> slot_sums; // [levels][max_runs][slot_stride]
+    DeviceBuffer<RunLink> links;    // [levels][max_runs]
+    DeviceBuffer<double> pedestals; // [sweeps][levels][max_runs]: every sweep's values
+    DeviceBuffer<int> progress;     // [levels][chunks of 64 runs]: sweeps completed
+    DeviceBuffer<int2> run_slots;   // [levels][max_runs]: the runs' end slots, packed for the relaxation
+    DeviceBuffer<int> run_bin;      // [levels][max_runs]
+    DeviceBuffer<int> bin_end;      // [levels][bins]: 1 + the last run of every bin
+    DeviceBuffer<int> bin_first;    // [levels][bins]: the first run of every bin
+    DeviceBuffer<int> state;        // [levels][kChainState], see pedestal_chain.h
+    DeviceBuffer<double> slots;     // [levels][cells+1]: the serial chain's slots of the spectrum
+    DeviceBuffer<double> bin_sum;   // [levels][cells+2*cut+3]: total pedestal of every window
     std::vector<int> host_counts;
 };
-
-inline void pedestal_check(hipError_t status, const char * what)
-{
-    if (status != hipSuccess)
-    {
-        throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(status));
-    }
-}
 
 constexpr int kRunCut = 1024;     // see opens_run
 constexpr int kPedestalSweepBuffers = 7;    // kMaxRelaxLaunches (pedestal_chain.h)
@@ -168,8 +139,8 @@ constexpr int pedestal_cut_off_limit()
 inline void pedestal_lds_opt_in(const void * kernel, size_t bytes)
 {
     if (bytes <= kLdsWithoutOptIn) return;
-    pedestal_check(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
-                   "LDS opt-in");
+    hip_check(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
+              "LDS opt-in");
 }
 
 }  // namespace lbl
@@ -284,7 +255,7 @@ inline void pedestal_poison(hipStream_t stream, double * data, size_t capacity)
 {
     if (data != nullptr)
     {
-        pedestal_check(hipMemsetAsync(data, 0xFF, capacity*sizeof(double), stream), "workspace poison");
+        hip_check(hipMemsetAsync(data, 0xFF, capacity*sizeof(double), stream), "workspace poison");
     }
 }
 
@@ -295,7 +266,6 @@ inline void pedestal_find_runs(PedestalWorkspace & ws, hipStream_t stream, const
                                const LineWing * wing, const GridSpec & g, int count, int n_cells,
                                bool parallel_chain, bool poison = false)
 {
-    auto check = pedestal_check;
     const long long n_lines = t.n_lines;
     const int n_blocks = (int)((n_lines + kScanThreads - 1)/kScanThreads);
     const int n_bins = n_cells + 2*g.cut_off + 3;
@@ -307,7 +277,7 @@ inline void pedestal_find_runs(PedestalWorkspace & ws, hipStream_t stream, const
         for (auto & array : ws.scan)
         {
             array.reserve(descriptors);
-            check(hipMemsetAsync(array.data, 0, array.capacity*sizeof(unsigned long long), stream),
+            hip_check(hipMemsetAsync(array.data, 0, array.capacity*sizeof(unsigned long long), stream),
                   "descriptor clear");
         }
     }
@@ -333,9 +303,9 @@ inline void pedestal_find_runs(PedestalWorkspace & ws, hipStream_t stream, const
                        (long long)ws.scan[0].capacity, ws.run_start.data, ws.prefix_bin.data,
                        ws.run_count.data, n_bins, ws.bin_end.data, ws.bin_first.data,
                        ws.bin_sum.data, ws.state.data, parallel_chain ? 1 : 0);
-    check(hipGetLastError(), "run_find_kernel");
+    hip_check(hipGetLastError(), "run_find_kernel");
     ws.host_counts.resize((size_t)count);
-    check(hipMemcpyAsync(ws.host_counts.data(), ws.run_count.data, count*sizeof(int),
+    hip_check(hipMemcpyAsync(ws.host_counts.data(), ws.run_count.data, count*sizeof(int),
                          hipMemcpyDeviceToHost, stream), "run count copy");
 }
 
@@ -347,7 +317,6 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
                             int count, int n_cells, bool parallel_chain = true, int relax_launches = 0,
                             bool poison = false)
 {
-    auto check = pedestal_check;
     const long long n_lines = t.n_lines;
     const int slot_stride = 2*g.cut_off + 3;
     const int n_bins = n_cells + 2*g.cut_off + 3;
@@ -357,7 +326,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
     // counts back into page-locked instead of pageable memory, so that the copy in
     // pedestal_find_runs does not hold the host either: 0 ... -4 % on the same legs,
     // profiles/r04_ab_pinned_counts.txt.)
-    check(hipStreamSynchronize(stream), "run count sync");
+    hip_check(hipStreamSynchronize(stream), "run count sync");
     int max_runs = 1;
     for (int c : ws.host_counts)
     {
@@ -391,7 +360,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
                        stream, wing, core, t.sorted_of_row, n_lines, g, n_cells,
                        ws.run_start.data, ws.run_count.data, max_runs, slot_stride,
                        ws.runs.data, ws.slot_sums.data);
-    check(hipGetLastError(), "run_sums_kernel");
+    hip_check(hipGetLastError(), "run_sums_kernel");
     // The serial chain in its small-LDS form (slots of the spectrum in HBM, the active ones in
     // registers and a ring in LDS): 15.5 KB, less than one accumulate workgroup holds.
     const size_t staged_bytes = (size_t)2*kChainChunk*slot_stride*sizeof(double);
@@ -408,7 +377,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
                            ws.slot_sums.data, ws.prefix_bin.data, n_lines, ws.bin_end.data,
                            ws.bin_first.data, ws.progress.data, max_chunks, ws.links.data,
                            ws.run_slots.data, ws.run_bin.data, ws.state.data);
-        check(hipGetLastError(), "run_links_kernel");
+        hip_check(hipGetLastError(), "run_links_kernel");
         // Windows of at most 64 slots (cut_off <= 30) keep the active slots in registers.
         auto solve = slot_stride <= 64 ? run_solve_kernel<true> : run_solve_kernel<false>;
         pedestal_lds_opt_in(reinterpret_cast<const void *>(solve), staged_bytes + ring_bytes);
@@ -418,7 +387,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
                            ws.bin_first.data, ws.pedestals.data, (long long)count*max_runs,
                            ws.progress.data, ws.state.data, ws.bin_sum.data, slot_stride, g,
                            n_cells, ws.runs.data, ws.slot_sums.data, ws.slots.data);
-        check(hipGetLastError(), "run_solve_kernel");
+        hip_check(hipGetLastError(), "run_solve_kernel");
         return;
     }
     // The serial chain alone (engine option scan_chain = 0): slots and bin totals in LDS where they
@@ -428,10 +397,10 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
     {
         if (lds_bytes > 64*1024)
         {
-            check(hipFuncSetAttribute(reinterpret_cast<const void *>(run_chain_kernel<true, true>),
+            hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(run_chain_kernel<true, true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds_bytes), "LDS opt-in");
-            check(hipFuncSetAttribute(reinterpret_cast<const void *>(run_chain_kernel<true, false>),
+            hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(run_chain_kernel<true, false>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds_bytes), "LDS opt-in");
         }
@@ -449,7 +418,7 @@ inline void pedestal_finish(PedestalWorkspace & ws, hipStream_t stream, const Li
                            ws.run_count.data, max_runs, slot_stride, g, n_cells, n_bins,
                            ws.runs.data, ws.slot_sums.data, ws.slots.data, ws.bin_sum.data);
     }
-    check(hipGetLastError(), "run_chain_kernel");
+    hip_check(hipGetLastError(), "run_chain_kernel");
 }
 
 }  // namespace lbl

@@ -1,7 +1,8 @@
-// What the slot entries share (lbl_continuum_compute and lbl_continuum_compute_many in
-// continuum_entry.inc, lbl_xsec_compute in xsec_entry.inc): the handle tables, the grid and
-// stride checks, the lane a call runs on and its ordering, and the chunked run over the levels
-// with its copy back to a host output.  Included by engine.hip before both entry files.
+// The handle tables (find_slot, store_slot, free_slot: every load and free entry), and what the
+// slot entries share (lbl_continuum_compute and lbl_continuum_compute_many in
+// continuum_entry.inc, lbl_xsec_compute in xsec_entry.inc): the grid and stride checks, the lane a
+// call runs on and its ordering, and the chunked run over the levels with its copy back to a host
+// output.  Included by engine.hip before its entries.
 namespace {
 
 template <typename T>
@@ -22,6 +23,24 @@ int32_t store_slot(std::vector<std::unique_ptr<T>> & slots, std::unique_ptr<T> v
     if (slot == slots.size()) slots.emplace_back();
     slots[slot] = std::move(value);
     return (int32_t)slot;
+}
+
+// A free entry: drops what `handle` stands for in `table` once everything queued has run (a
+// kernel on any lane may still read it).  `unknown`: the message for a handle that is not in
+// use; `before`: what else goes with the object, dropped first.
+template <typename T>
+int free_slot(lbl_engine * engine, std::vector<std::unique_ptr<T>> lbl_engine::* table,
+              int32_t handle, const char * unknown, const std::function<void()> & before = {})
+{
+    return entry(engine, [&] {
+        auto & slots = engine->*table;
+        if (find_slot(slots, handle) == nullptr) return fail(engine, LBL_BAD_ARGUMENT, unknown);
+        (void)hipSetDevice(engine->device);
+        engine->drain_lanes();
+        if (before) before();
+        slots[handle].reset();
+        return LBL_OK;
+    });
 }
 
 // One slot call: n_levels rows of the grid's n points, `stride` apart, written or (LBL_ACCUMULATE)
@@ -90,10 +109,10 @@ struct SlotCall
             Stage stage, Model model, Interp interp)
     {
         open();
-        feed.wait();      // the previous call's copy may still read the pinned level block
         long long chunk = std::min<long long>(n_levels, 65535);
         if (!out_device) chunk = std::max(1ll, std::min(chunk, engine->workspace_bytes/(n*8)));
-        feed.reserve_pinned((size_t)chunk);
+        // (waits first: the previous call's copy may still read the pinned level block)
+        auto * staged = feed.pinned.refill((size_t)chunk);
         feed.levels.reserve((size_t)chunk);
         values.reserve((size_t)(chunk*points));
         feed.slopes.reserve((size_t)(chunk*points));
@@ -101,10 +120,8 @@ struct SlotCall
         for (long long base = 0; base < n_levels; base += chunk)
         {
             const int count = (int)std::min<long long>(chunk, n_levels - base);
-            for (int l = 0; l < count; ++l) feed.pinned[l] = stage(base + l);
-            HIP_TRY(hipMemcpyAsync(feed.levels.data, feed.pinned, count*sizeof(*feed.pinned),
-                                   hipMemcpyHostToDevice, stream));
-            feed.copied_on(stream);
+            for (int l = 0; l < count; ++l) staged[l] = stage(base + l);
+            feed.pinned.upload(feed.levels.data, (size_t)count, stream);
             model(count);
             double * target = out_device ? out + base*stride : feed.staging.data;
             const long long target_stride = out_device ? stride : n;
@@ -115,7 +132,7 @@ struct SlotCall
             feed.mark(stream);
             if (out_device)
             {
-                if (base + count < n_levels) feed.wait();
+                if (base + count < n_levels) feed.pinned.wait();
                 continue;
             }
             std::vector<double> row;

@@ -63,16 +63,7 @@ int lbl_xsec_load(lbl_engine * engine, int32_t n_bands, const int32_t * sizes,
 
 int lbl_xsec_free(lbl_engine * engine, int32_t xsec)
 {
-    return entry(engine, [&] {
-        if (find_slot(engine->xsecs, xsec) == nullptr)
-        {
-            return fail(engine, LBL_BAD_ARGUMENT, "unknown cross-section handle.");
-        }
-        (void)hipSetDevice(engine->device);
-        engine->drain_lanes();
-        engine->xsecs[xsec].reset();
-        return LBL_OK;
-    });
+    return free_slot(engine, &lbl_engine::xsecs, xsec, "unknown cross-section handle.");
 }
 
 int lbl_xsec_compute(lbl_engine * engine, int32_t xsec, int32_t grid, int32_t n_levels,
@@ -134,13 +125,13 @@ int lbl_xsec_bands(lbl_engine * engine, int32_t xsec, double temperature, double
         }
         HIP_TRY(hipSetDevice(engine->device));
         hipStream_t stream = engine->stream;
-        x->wait();
-        x->reserve_pinned(1);
-        x->pinned[0] = XsecLevel{temperature, pressure, 1.};
+        XsecLevel * staged = x->pinned.refill(1);
+        staged[0] = XsecLevel{temperature, pressure, 1.};
         x->levels.reserve(1);
         x->values.reserve((size_t)x->set.total);
         x->slopes.reserve((size_t)x->set.total);
-        HIP_TRY(hipMemcpyAsync(x->levels.data, x->pinned, sizeof(XsecLevel),
+        // (no event behind this copy: the call waits for the stream below)
+        HIP_TRY(hipMemcpyAsync(x->levels.data, staged, sizeof(XsecLevel),
                                hipMemcpyHostToDevice, stream));
         launch_xsec_model(engine, *x, 1, stream);
         HIP_TRY(hipMemcpyAsync(values, x->values.data, (size_t)x->set.total*8,
