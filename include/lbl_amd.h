@@ -295,6 +295,51 @@ int lbl_path_flux(lbl_engine *engine, double *beta, int64_t row_stride, int64_t 
                   int32_t n_bands, const int64_t *band_start, double *carry, double *reflection,
                   double *level_flux, double *flux, double *surface_flux, int32_t flags);
 
+/* lbl_path_radiance and lbl_path_flux with a source that is linear in optical depth inside each
+ * level (Spectroscopy.compute_radiance / compute_flux with source="linear_in_tau").  Every argument
+ * as for lbl_path_radiance / lbl_path_flux, and
+ *   edge_temperature (host, [level_count][2] values [K], finite and > 0, or NULL): [r][0] is the
+ *   temperature of the interface of level level_begin + r on the side of its path's first level,
+ *   [r][1] of the interface on the side of its path's last level.  Inside a path of the run the
+ *   table must be continuous, [r][1] == [r + 1][0]: the kernels evaluate Planck once per level, at
+ *   the interface the sweep leaves it through, and keep it as the next level's entry value.
+ * NULL: the isothermal source, exactly lbl_path_radiance / lbl_path_flux (which are these calls
+ * with NULL).  Otherwise `temperature` is still checked but not used for the source, and for a
+ * level in sweep order, with B_in = B(nu, T_edge) at the interface the sweep enters it through
+ * ([r][0] upward, [r][1] with LBL_PATH_FROM_LAST) and B_out at the one it leaves through:
+ *   x = s*beta, t = exp(-x), a = -expm1(-x)
+ *   w = 1 - a/x  (x/2 - x^2/6 + x^3/24 - ...; 0 at x = 0),  u_in = a - w
+ *   I = I*t + (B_in*u_in + B_out*w)
+ * each product and sum rounded as written, with w formed as
+ *   |x| <  1/16:  x*(1./2. - x*(1./6. - x*(1./24. - x*(1./120. - x*(1./720. - x*(1./5040.
+ *                 - x*(1./40320. - x*(1./362880.))))))))   (8 terms, Horner)
+ *   otherwise:    1. - a/x
+ * (1 - a/x alone is 0/0 at x = 0 and wrong by 4e-4 relative at x = 1e-12; this form is within
+ * 6.2e-15 relative of long double for x from -3 to 1e3).  x = 0 leaves I unchanged bit for bit;
+ * negative x gives finite results.  In lbl_path_flux_source B_in and B_out are shared by the
+ * angles.  The boundary and surface terms, carry and reflection rows, band means, cumulative rows
+ * and LBL_PATH_CONTINUE are those of lbl_path_radiance / lbl_path_flux: a run that continues a
+ * path takes B_in of its first level from its own table.
+ * LBL_BAD_ARGUMENT as for lbl_path_radiance / lbl_path_flux, and for an edge temperature that is
+ * not finite and > 0 or a table that is not continuous within a path; the engine stays usable. */
+int lbl_path_radiance_source(lbl_engine *engine, double *beta, int64_t row_stride, int64_t columns,
+                             int32_t grid, int32_t n_paths, int32_t levels_per_path,
+                             int32_t level_begin, int32_t level_count, const double *path_length,
+                             const double *temperature, const double *edge_temperature,
+                             const double *boundary_temperature,
+                             const double *boundary_emissivity, int32_t n_bands,
+                             const int64_t *band_start, double *carry, double *radiance,
+                             double *brightness_temperature, int32_t flags);
+int lbl_path_flux_source(lbl_engine *engine, double *beta, int64_t row_stride, int64_t columns,
+                         int32_t grid, int32_t n_paths, int32_t levels_per_path,
+                         int32_t level_begin, int32_t level_count, int32_t n_angles,
+                         const double *path_length, const double *weight,
+                         const double *temperature, const double *edge_temperature,
+                         const double *surface_temperature, const double *surface_emissivity,
+                         int32_t n_bands, const int64_t *band_start, double *carry,
+                         double *reflection, double *level_flux, double *flux,
+                         double *surface_flux, int32_t flags);
+
 /* Analytic radiance Jacobians (Spectroscopy.compute_jacobian): the derivatives of
  * lbl_path_radiance's radiance with respect to the state of every level and of the boundary, for
  * a run of whole paths.  beta (read only), row_stride, columns, grid, n_paths, levels_per_path,

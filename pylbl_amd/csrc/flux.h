@@ -6,6 +6,9 @@
 //   I_k = I_k*exp(-x) + B(nu, T_l)*(-expm1(-x))     (radiance.h's update, path length s_{l,k})
 //   down: I_k = 0 at space; up: I_k = eps*B(nu, T_s) + (1 - eps)*R, R = sum_k w_k*I_k of the
 //   down sweep at the surface; F = pi*(sum_k w_k*I_k), sums from k = 0 upward.
+// kLinear (lbl_path_flux_source with edge temperatures): radiance.h's linear-in-tau update,
+//   I_k = I_k*exp(-x) + (B_in*u_in + B_out*w), w = 1 - a/x in radiance.h's two-branch form,
+//   with B_in and B_out shared by the K angles; each angle adds its division and its weight.
 // The TU builds with -ffp-contract=off: every product and sum is rounded as written, and with
 // K = 1 and w_0 = 1 the radiances are bit for bit path_radiance_kernel's.
 //
@@ -46,6 +49,8 @@ struct PathFlux : PathLevels
     double * reflection;        // [paths][stride]: R (down sweep writes, up sweep reads), then
                                 // the up sweep's flux at the surface interface
     double * level_flux;        // F after each level
+    const double * edge;        // [count][2]: interface temperatures as PathRadiance's (kLinear),
+                                // or null
 };
 
 // sum_k w_k*I_k from k = 0, for every column of the lane.
@@ -99,8 +104,32 @@ __device__ __forceinline__ void flux_level(const double * length, double t,
     }
 }
 
-// grid and kVector as for path_sweep_kernel.
-template <bool kVector, int K>
+// One level of every angle with the linear-in-tau source: B at the exit interface once per
+// column, which becomes b_in of the next level.
+template <int K>
+__device__ __forceinline__ void flux_level_linear(const double * length, double t_out,
+                                                  const double (&b)[kPathWidth],
+                                                  const double (&nu)[kPathWidth],
+                                                  const double (&c1nu3)[kPathWidth],
+                                                  const double (&c2nu)[kPathWidth],
+                                                  double (&b_in)[kPathWidth],
+                                                  double (&rad)[K][kPathWidth])
+{
+#pragma unroll
+    for (int i = 0; i < kPathWidth; ++i)
+    {
+        const double b_out = planck(nu[i], c1nu3[i], c2nu[i], t_out);
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+        {
+            rad[k][i] = linear_update(rad[k][i], length[k]*b[i], b_in[i], b_out);
+        }
+        b_in[i] = b_out;
+    }
+}
+
+// grid and kVector as for path_sweep_kernel.  kLinear: the linear-in-tau source of a.edge.
+template <bool kVector, int K, bool kLinear = false>
 __global__ __launch_bounds__(kPathThreads) void path_flux_kernel(PathFlux a)
 {
     const PathLane l = path_lane(a);
@@ -151,10 +180,29 @@ __global__ __launch_bounds__(kPathThreads) void path_flux_kernel(PathFlux a)
 #pragma unroll
         for (int k = 0; k < K; ++k) path_load<kVector>(carry + (long long)k*a.stride, width, rad[k]);
     }
+    // kLinear: B at the interface the lane's next level is entered through.
+    const int side = entry_side(l.direction);
+    const double * edge = kLinear ? a.edge + 2*(long long)l.index0 : nullptr;
+    double b_in[kPathWidth];
+    if (kLinear)
+    {
+        const double t = edge[side];
+#pragma unroll
+        for (int i = 0; i < kPathWidth; ++i) b_in[i] = planck(nu[i], c1nu3[i], c2nu[i], t);
+    }
     path_levels<kFluxAhead<K>, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
                                                   long long at) {
-        flux_level<K>(length + (long long)k*l.direction*K, temperature[k*l.direction], b, nu,
-                      c1nu3, c2nu, rad);
+        if (kLinear)
+        {
+            flux_level_linear<K>(length + (long long)k*l.direction*K,
+                                 edge[2*(long long)(k*l.direction) + (1 - side)], b, nu, c1nu3,
+                                 c2nu, b_in, rad);
+        }
+        else
+        {
+            flux_level<K>(length + (long long)k*l.direction*K, temperature[k*l.direction], b, nu,
+                          c1nu3, c2nu, rad);
+        }
         flux_store<kVector, K>(a.level_flux, at, width, a.weight, rad);
     });
 

@@ -1,12 +1,21 @@
-// lbl_path_flux: one sweep (down from space or up from the surface) of K angles through a block
-// of absorption coefficients in HBM (kernel: flux.h; band means: path.h).  Included by engine.hip
+// lbl_path_flux_source: one sweep (down from space or up from the surface) of K angles through a
+// block of absorption coefficients in HBM (kernel: flux.h; band means: path.h), and
+// lbl_path_flux, the same call without edge temperatures.  Included by engine.hip
 // after radiance_entry.inc; shares path_entry.inc's PathCall, PathTables and PathBands.
 namespace {
 
 template <bool kVector, int K>
 void launch_flux(const PathFlux & a, const dim3 & grid, hipStream_t stream)
 {
-    hipLaunchKernelGGL((path_flux_kernel<kVector, K>), grid, dim3(kPathThreads), 0, stream, a);
+    if (a.edge != nullptr)
+    {
+        hipLaunchKernelGGL((path_flux_kernel<kVector, K, true>), grid, dim3(kPathThreads), 0,
+                           stream, a);
+    }
+    else
+    {
+        hipLaunchKernelGGL((path_flux_kernel<kVector, K>), grid, dim3(kPathThreads), 0, stream, a);
+    }
 }
 
 template <bool kVector>
@@ -29,17 +38,18 @@ void launch_flux(int angles, const PathFlux & a, const dim3 & grid, hipStream_t 
 
 extern "C" {
 
-int lbl_path_flux(lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns,
-                  int32_t grid, int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
-                  int32_t level_count, int32_t n_angles, const double * path_length,
-                  const double * weight, const double * temperature,
-                  const double * surface_temperature, const double * surface_emissivity,
-                  int32_t n_bands, const int64_t * band_start, double * carry,
-                  double * reflection, double * level_flux, double * flux, double * surface_flux,
-                  int32_t flags)
+int lbl_path_flux_source(lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns,
+                         int32_t grid, int32_t n_paths, int32_t levels_per_path,
+                         int32_t level_begin, int32_t level_count, int32_t n_angles,
+                         const double * path_length, const double * weight,
+                         const double * temperature, const double * edge_temperature,
+                         const double * surface_temperature, const double * surface_emissivity,
+                         int32_t n_bands, const int64_t * band_start, double * carry,
+                         double * reflection, double * level_flux, double * flux,
+                         double * surface_flux, int32_t flags)
 {
     return path_entry(engine, flags, [&] {
-        PathCall call{engine, "lbl_path_flux", row_stride, columns, n_paths, levels_per_path,
+        PathCall call{engine, "lbl_path_flux_source", row_stride, columns, n_paths, levels_per_path,
                       level_begin, level_count, flags};
         const bool up = (flags & LBL_PATH_FLUX_UP) != 0;
         if (beta == nullptr || path_length == nullptr || weight == nullptr ||
@@ -67,6 +77,14 @@ int lbl_path_flux(lbl_engine * engine, double * beta, int64_t row_stride, int64_
         if (!finite_at_least_zero(temperature, level_count, true))
         {
             return call.bad("temperatures must be finite and > 0.");
+        }
+        if (edge_temperature != nullptr)
+        {
+            if (const char * problem = check_edge_temperatures(edge_temperature, level_begin,
+                                                               level_count, levels_per_path))
+            {
+                return call.bad(problem);
+            }
         }
         if (up)
         {
@@ -106,6 +124,9 @@ int lbl_path_flux(lbl_engine * engine, double * beta, int64_t row_stride, int64_
             surface[run.paths + i] = surface_emissivity[run.first_path + i];
         }
         const size_t band_at = tables.add(bands, band_start);
+        // After the tables every call has, so that theirs lie where they always lay.
+        const bool linear = edge_temperature != nullptr;
+        const size_t edge_at = linear ? tables.add(2*(size_t)level_count, edge_temperature) : 0;
         const double * d_tables = call.begin(tables);
 
         PathFlux a;
@@ -118,6 +139,7 @@ int lbl_path_flux(lbl_engine * engine, double * beta, int64_t row_stride, int64_
         a.temperature = d_tables + temperature_at;
         a.surface_t = d_tables + surface_at;
         a.surface_e = a.surface_t + run.paths;
+        a.edge = linear ? d_tables + edge_at : nullptr;
         a.first = level_begin;
         a.count = level_count;
         a.row_base = level_begin;
@@ -163,6 +185,22 @@ int lbl_path_flux(lbl_engine * engine, double * beta, int64_t row_stride, int64_
         }
         return LBL_OK;
     });
+}
+
+int lbl_path_flux(lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns,
+                  int32_t grid, int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                  int32_t level_count, int32_t n_angles, const double * path_length,
+                  const double * weight, const double * temperature,
+                  const double * surface_temperature, const double * surface_emissivity,
+                  int32_t n_bands, const int64_t * band_start, double * carry,
+                  double * reflection, double * level_flux, double * flux, double * surface_flux,
+                  int32_t flags)
+{
+    return lbl_path_flux_source(engine, beta, row_stride, columns, grid, n_paths, levels_per_path,
+                                level_begin, level_count, n_angles, path_length, weight,
+                                temperature, nullptr, surface_temperature, surface_emissivity,
+                                n_bands, band_start, carry, reflection, level_flux, flux,
+                                surface_flux, flags);
 }
 
 }  // extern "C"

@@ -49,6 +49,28 @@ bool finite_at_least_zero(const double * values, long long count, bool positive)
     return true;
 }
 
+// nullptr, or what is wrong with the interface temperatures [level_count][2] of a run that starts
+// at flat level `level_begin` (lbl_path_radiance_source, lbl_path_flux_source): every value finite
+// and > 0, and inside a path the far side of a level equal to the near side of the next -- the
+// kernels carry B at a level's exit interface into the next level as its entry value.
+const char * check_edge_temperatures(const double * edge, int level_begin, int level_count,
+                                     int levels_per_path)
+{
+    if (!finite_at_least_zero(edge, 2*(long long)level_count, true))
+    {
+        return "edge temperatures must be finite and > 0.";
+    }
+    for (int r = 0; r + 1 < level_count; ++r)
+    {
+        const bool same_path = (level_begin + r + 1) % levels_per_path != 0;
+        if (same_path && edge[2*r + 1] != edge[2*(r + 1)])
+        {
+            return "edge temperatures must be continuous within a path: [r][1] == [r + 1][0].";
+        }
+    }
+    return nullptr;
+}
+
 // Every row starts 16-byte aligned: an even stride and aligned bases (null: not used).
 bool path_vector(int64_t row_stride, std::initializer_list<const void *> bases)
 {

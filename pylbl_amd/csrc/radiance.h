@@ -1,10 +1,21 @@
 // Thermal emission along paths (Spectroscopy.compute_radiance, lbl_path_radiance): the
-// Schwarzschild sweep over the "total" absorption block in HBM, with isothermal layers.
+// Schwarzschild sweep over the "total" absorption block in HBM, with isothermal layers or, in
+// the kLinear instantiations (lbl_path_radiance_source with edge temperatures), a source that is
+// linear in optical depth between the Planck values at a layer's two interfaces.
 //
 //   B(nu, T) = (((C1*nu)*nu)*nu) / expm1((C2*nu)/T), 0 for nu <= 0  [W m-2 sr-1 (cm-1)-1]
 //   layer of level l, x = s_l*beta_l:  t = exp(-x),  a = -expm1(-x),  source B(nu, T_l)
 //   I = eps*B(nu, T_boundary) (or 0), then I = I*t + B_l*a level by level in sweep order.
 //   brightness temperature = (C2*nu) / log1p((((C1*nu)*nu)*nu) / I), 0 where I <= 0 or nu <= 0.
+// Linear-in-tau source (kLinear), B_in / B_out = B(nu, T) at the interface the sweep enters the
+// level through / leaves it through:
+//   w = 1 - a/x, u_in = a - w, I = I*t + (B_in*u_in + B_out*w)
+//   w is formed as 1. - a/x for |x| >= 1/16 and below that as the 8-term Horner series
+//     x*(1./2. - x*(1./6. - x*(1./24. - x*(1./120. - x*(1./720. - x*(1./5040. - x*(1./40320.
+//       - x*(1./362880.))))))))
+//   (1 - a/x is 0/0 at x = 0 and loses x's leading digits below it: 4e-4 relative at x = 1e-12;
+//   the two-branch form stays within 6.2e-15 relative of long double from x = -3 to 1e3).
+//   x = 0 gives w = u_in = 0 and t = 1: I is unchanged bit for bit.
 // The TU builds with -ffp-contract=off: every product and sum is rounded as written.
 //
 // path_radiance_kernel runs on path.h's sweep skeleton with kPathAhead rows in flight: a lane
@@ -12,6 +23,10 @@
 // the whole wavefront.  Per element: two divisions (Planck's argument and Planck itself), one
 // expm1 for Planck, one exp and one expm1 for the layer, the update -- fp64 VALU work of the same
 // order as the HBM time of reading the row.  Band means go through path.h's band kernels.
+// kLinear: the lane evaluates Planck at the entry interface of the first level it handles in the
+// launch and then once per level at the exit interface, which it keeps in registers as the next
+// level's B_in (the table is continuous within a path: the entry checks it) -- one Planck per
+// element and level as before, plus one division and the weight.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,7 +49,34 @@ struct PathRadiance : PathLevels
     double * final_rad;         // [paths][stride]: I of a finished path, or null
     double * final_bt;          // [paths][stride]: its brightness temperature, or null
     int keep_final;             // a finished path's I stays in its carry row (band means)
+    const double * edge;        // [count][2]: interface temperatures of flat level first + i on
+                                // its first-level / last-level side [K] (kLinear), or null
 };
+
+constexpr double kLinearSeriesBelow = 1./16.;   // |x| below which w comes from its series
+
+// w = 1 - a/x for a = -expm1(-x): the weight of B_out in a layer of optical depth x.
+__device__ __forceinline__ double linear_weight(double x, double a)
+{
+    const double series =
+        x*(1./2. - x*(1./6. - x*(1./24. - x*(1./120. - x*(1./720. - x*(1./5040. - x*(1./40320. -
+        x*(1./362880.))))))));
+    return fabs(x) < kLinearSeriesBelow ? series : 1. - a/x;
+}
+
+// One level with the linear-in-tau source: I*t + (B_in*u_in + B_out*w).
+__device__ __forceinline__ double linear_update(double i, double x, double b_in, double b_out)
+{
+    const double a = -expm1(-x);
+    const double w = linear_weight(x, a);
+    return i*exp(-x) + (b_in*(a - w) + b_out*w);
+}
+
+// The side ([.][0] or [.][1] of the edge table) a sweep in `direction` enters a level through.
+__device__ __forceinline__ int entry_side(int direction)
+{
+    return direction > 0 ? 0 : 1;
+}
 
 __device__ __forceinline__ double planck(double nu, double c1nu3, double c2nu, double t)
 {
@@ -64,8 +106,8 @@ __device__ __forceinline__ void radiance_store(double * rad, double * bt, long l
     }
 }
 
-// grid and kVector as for path_sweep_kernel.
-template <bool kVector>
+// grid and kVector as for path_sweep_kernel.  kLinear: the linear-in-tau source of a.edge.
+template <bool kVector, bool kLinear = false>
 __global__ __launch_bounds__(kPathThreads) void path_radiance_kernel(PathRadiance a)
 {
     const PathLane l = path_lane(a);
@@ -99,15 +141,39 @@ __global__ __launch_bounds__(kPathThreads) void path_radiance_kernel(PathRadianc
         path_load<kVector>(a.carry + (long long)l.p*a.stride + l.j, width, rad);
     }
     const bool per_level = a.level_rad != nullptr || a.level_bt != nullptr;
+    // kLinear: B at the interface the lane's next level is entered through.
+    const int side = entry_side(l.direction);
+    const double * edge = kLinear ? a.edge + 2*(long long)l.index0 : nullptr;
+    double b_in[kPathWidth];
+    if (kLinear)
+    {
+        const double t = edge[side];
+#pragma unroll
+        for (int i = 0; i < kPathWidth; ++i) b_in[i] = planck(nu[i], c1nu3[i], c2nu[i], t);
+    }
     path_levels<kPathAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth], long long at)
                                                  {
         const double s = length[k*l.direction];
-        const double t = temperature[k*l.direction];
-#pragma unroll
-        for (int i = 0; i < kPathWidth; ++i)
+        if (kLinear)
         {
-            const double x = s*b[i];
-            rad[i] = rad[i]*exp(-x) + planck(nu[i], c1nu3[i], c2nu[i], t)*(-expm1(-x));
+            const double t = edge[2*(long long)(k*l.direction) + (1 - side)];
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                const double b_out = planck(nu[i], c1nu3[i], c2nu[i], t);
+                rad[i] = linear_update(rad[i], s*b[i], b_in[i], b_out);
+                b_in[i] = b_out;
+            }
+        }
+        else
+        {
+            const double t = temperature[k*l.direction];
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                const double x = s*b[i];
+                rad[i] = rad[i]*exp(-x) + planck(nu[i], c1nu3[i], c2nu[i], t)*(-expm1(-x));
+            }
         }
         if (per_level)
         {

@@ -1,17 +1,21 @@
-// lbl_path_radiance: thermal emission along paths through a block of absorption coefficients in
-// HBM (kernel: radiance.h; band means: path.h).  Included by engine.hip after path_entry.inc,
+// lbl_path_radiance_source: thermal emission along paths through a block of absorption
+// coefficients in HBM (kernel: radiance.h; band means: path.h), and lbl_path_radiance, the same
+// call without edge temperatures.  Included by engine.hip after path_entry.inc,
 // whose PathCall, PathTables and PathBands it shares.
 extern "C" {
 
-int lbl_path_radiance(lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns,
-                      int32_t grid, int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
-                      int32_t level_count, const double * path_length, const double * temperature,
-                      const double * boundary_temperature, const double * boundary_emissivity,
-                      int32_t n_bands, const int64_t * band_start, double * carry,
-                      double * radiance, double * brightness_temperature, int32_t flags)
+int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_stride,
+                             int64_t columns, int32_t grid, int32_t n_paths,
+                             int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+                             const double * path_length, const double * temperature,
+                             const double * edge_temperature,
+                             const double * boundary_temperature,
+                             const double * boundary_emissivity, int32_t n_bands,
+                             const int64_t * band_start, double * carry, double * radiance,
+                             double * brightness_temperature, int32_t flags)
 {
     return path_entry(engine, flags, [&] {
-        PathCall call{engine, "lbl_path_radiance", row_stride, columns, n_paths, levels_per_path,
+        PathCall call{engine, "lbl_path_radiance_source", row_stride, columns, n_paths, levels_per_path,
                       level_begin, level_count, flags};
         const bool want_rad = (flags & LBL_PATH_RADIANCE) != 0;
         const bool want_bt = (flags & LBL_PATH_BRIGHTNESS) != 0;
@@ -32,6 +36,14 @@ int lbl_path_radiance(lbl_engine * engine, double * beta, int64_t row_stride, in
         if (!finite_at_least_zero(temperature, level_count, true))
         {
             return call.bad("temperatures must be finite and > 0.");
+        }
+        if (edge_temperature != nullptr)
+        {
+            if (const char * problem = check_edge_temperatures(edge_temperature, level_begin,
+                                                               level_count, levels_per_path))
+            {
+                return call.bad(problem);
+            }
         }
         for (int p = 0; p < n_paths; ++p)
         {
@@ -63,6 +75,9 @@ int lbl_path_radiance(lbl_engine * engine, double * beta, int64_t row_stride, in
             boundary[run.paths + i] = boundary_emissivity != nullptr ? boundary_emissivity[p] : 1.;
         }
         const size_t band_at = tables.add(bands, band_start);
+        // After the tables every call has, so that theirs lie where they always lay.
+        const bool linear = edge_temperature != nullptr;
+        const size_t edge_at = linear ? tables.add(2*(size_t)level_count, edge_temperature) : 0;
         const double * d_tables = call.begin(tables);
 
         PathRadiance a;
@@ -74,6 +89,7 @@ int lbl_path_radiance(lbl_engine * engine, double * beta, int64_t row_stride, in
         a.temperature = d_tables + temperature_at;
         a.boundary_t = d_tables + boundary_at;
         a.boundary_e = a.boundary_t + run.paths;
+        a.edge = linear ? d_tables + edge_at : nullptr;
         a.first = level_begin;
         a.count = level_count;
         a.row_base = level_begin;
@@ -105,7 +121,17 @@ int lbl_path_radiance(lbl_engine * engine, double * beta, int64_t row_stride, in
                                                      a.final_rad, a.final_bt});
         call.launch([&](const dim3 & launch, int first_path) {
             a.first_path = first_path;
-            if (vector)
+            if (vector && linear)
+            {
+                hipLaunchKernelGGL((path_radiance_kernel<true, true>), launch,
+                                   dim3(kPathThreads), 0, engine->stream, a);
+            }
+            else if (linear)
+            {
+                hipLaunchKernelGGL((path_radiance_kernel<false, true>), launch,
+                                   dim3(kPathThreads), 0, engine->stream, a);
+            }
+            else if (vector)
             {
                 hipLaunchKernelGGL(path_radiance_kernel<true>, launch, dim3(kPathThreads), 0,
                                    engine->stream, a);
@@ -138,6 +164,20 @@ int lbl_path_radiance(lbl_engine * engine, double * beta, int64_t row_stride, in
         }
         return LBL_OK;
     });
+}
+
+int lbl_path_radiance(lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns,
+                      int32_t grid, int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                      int32_t level_count, const double * path_length, const double * temperature,
+                      const double * boundary_temperature, const double * boundary_emissivity,
+                      int32_t n_bands, const int64_t * band_start, double * carry,
+                      double * radiance, double * brightness_temperature, int32_t flags)
+{
+    return lbl_path_radiance_source(engine, beta, row_stride, columns, grid, n_paths,
+                                    levels_per_path, level_begin, level_count, path_length,
+                                    temperature, nullptr, boundary_temperature,
+                                    boundary_emissivity, n_bands, band_start, carry, radiance,
+                                    brightness_temperature, flags);
 }
 
 }  // extern "C"

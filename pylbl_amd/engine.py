@@ -59,7 +59,7 @@ EXPORTED_SYMBOLS = (
     "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
     "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
-    "lbl_path_jacobian",
+    "lbl_path_jacobian", "lbl_path_radiance_source", "lbl_path_flux_source",
     "lbl_instrument_create", "lbl_instrument_free", "lbl_instrument_apply",
 )
 
@@ -204,6 +204,11 @@ def library():
                                   c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_int32]
+    # The two entries with a linear-in-tau source: edge_temperature after temperature.
+    lib.lbl_path_radiance_source.argtypes = lib.lbl_path_radiance.argtypes[:11] + [c_void_p] + \
+        lib.lbl_path_radiance.argtypes[11:]
+    lib.lbl_path_flux_source.argtypes = lib.lbl_path_flux.argtypes[:13] + [c_void_p] + \
+        lib.lbl_path_flux.argtypes[13:]
     lib.lbl_instrument_create.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                           c_void_p, c_int32, c_void_p, c_void_p, c_int32, i32p]
     lib.lbl_instrument_free.argtypes = [c_void_p, c_int32]
@@ -256,6 +261,16 @@ def _per_path(n_paths, message, *values):
     if any(x is not None and x.shape != (int(n_paths),) for x in arrays):
         raise ValueError(message)
     return arrays
+
+
+def _edge_rows(edge_temperature, rows):
+    """None, or the interface temperatures of a path call as a float64 array [rows, 2]."""
+    if edge_temperature is None:
+        return None
+    edges = _f64(edge_temperature)
+    if edges.shape != (rows, 2):
+        raise ValueError(f"edge_temperature has shape {edges.shape}, need {rows} x 2.")
+    return edges
 
 
 def _check_outputs(outputs, rows, width):
@@ -752,17 +767,22 @@ class Engine(object):
     def path_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                       temperature, carry, boundary_temperature=None, boundary_emissivity=None,
                       radiance=None, brightness_temperature=None, band_start=None,
-                      cumulative=False, from_last=False, asynchronous=False):
+                      cumulative=False, from_last=False, asynchronous=False,
+                      edge_temperature=None):
         """Thermal emission along paths through the DeviceSpectra `beta` -- lbl_path_radiance.
         Rows, lengths, carry, band_start, cumulative, from_last and asynchronous as for
         path_compute; grid: handle of load_grid (the wavenumbers of the columns); temperature
         [K] one per row; boundary_temperature [K] (0: none) / boundary_emissivity one per path
         (None: no boundary / 1).  radiance / brightness_temperature: DeviceSpectra outputs (None:
-        not wanted), shaped as path_compute's."""
+        not wanted), shaped as path_compute's.  edge_temperature: None (isothermal layers), or
+        [rows, 2] interface temperatures [K] -- [r, 0] on the first-level side of row r, [r, 1]
+        on the last-level side, continuous within a path -- for the linear-in-tau source
+        (lbl_path_radiance_source)."""
         rows, stride, lengths, temperature = _per_row(
             beta, "one path length and one temperature per row of beta.", lengths, temperature)
         if tuple(carry.shape) != (int(n_paths), stride):
             raise ValueError("carry must be [n_paths, row length of beta].")
+        edge_temperature = _edge_rows(edge_temperature, rows)
         boundary = _per_path(n_paths, "one boundary value per path.", boundary_temperature,
                              boundary_emissivity)
         starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
@@ -772,11 +792,12 @@ class Engine(object):
                  (PATH_CUMULATIVE if cumulative else 0)
         _check_outputs((radiance, brightness_temperature),
                        rows if cumulative else int(n_paths), n_bands if n_bands > 0 else stride)
-        self._check(self.lib.lbl_path_radiance(
+        self._check(self.lib.lbl_path_radiance_source(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, lengths.ctypes.data,
-            temperature.ctypes.data, *map(_address, boundary), n_bands, _address(starts),
-            carry.pointer, _address(radiance), _address(brightness_temperature), flags))
+            temperature.ctypes.data, _address(edge_temperature), *map(_address, boundary),
+            n_bands, _address(starts), carry.pointer, _address(radiance),
+            _address(brightness_temperature), flags))
 
     def path_jacobian(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                       temperature, work, boundary_temperature=None, boundary_emissivity=None,
@@ -870,13 +891,14 @@ class Engine(object):
     def path_flux(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                   weight, temperature, carry, reflection, level_flux, surface_temperature=None,
                   surface_emissivity=None, flux=None, surface_flux=None, band_start=None,
-                  up=False, from_last=False, asynchronous=False):
+                  up=False, from_last=False, asynchronous=False, edge_temperature=None):
         """One sweep of K angles through the DeviceSpectra `beta` -- lbl_path_flux.  Rows,
         columns, grid, temperature, band_start, from_last and asynchronous as for path_radiance;
         lengths [rows, K]: s_l/mu_k [m]; weight [K]; carry [n_paths*K, row length];
         reflection [n_paths, row length]; level_flux [>= rows, row length] (F after each level);
         surface_temperature / surface_emissivity one per path (up sweep); flux [>= rows, bands]
-        and, up, surface_flux [n_paths, bands]: the band means (with band_start only)."""
+        and, up, surface_flux [n_paths, bands]: the band means (with band_start only).
+        edge_temperature: as for path_radiance (lbl_path_flux_source)."""
         lengths = _f64(lengths)
         weight = _f64(np.atleast_1d(weight))
         temperature = _f64(np.atleast_1d(temperature))
@@ -898,12 +920,14 @@ class Engine(object):
             if out is not None and (out.shape[1] != n_bands or out.shape[0] < count):
                 raise ValueError(f"a band output has shape {out.shape}, need {count} x {n_bands}.")
         flags |= PATH_FLUX_UP if up else 0
-        self._check(self.lib.lbl_path_flux(
+        edge_temperature = _edge_rows(edge_temperature, rows)
+        self._check(self.lib.lbl_path_flux_source(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, angles, lengths.ctypes.data,
-            weight.ctypes.data, temperature.ctypes.data, *map(_address, surface), n_bands,
-            _address(starts), carry.pointer, reflection.pointer, level_flux.pointer,
-            _address(flux), _address(surface_flux), flags))
+            weight.ctypes.data, temperature.ctypes.data, _address(edge_temperature),
+            *map(_address, surface), n_bands, _address(starts), carry.pointer,
+            reflection.pointer, level_flux.pointer, _address(flux), _address(surface_flux),
+            flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):

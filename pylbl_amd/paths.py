@@ -39,6 +39,10 @@ JACOBIAN_PATH_QUANTITIES = ("radiance", "boundary_temperature_jacobian",
                             "boundary_emissivity_jacobian")
 JACOBIAN_QUANTITIES = ("radiance",) + JACOBIAN_LEVEL_QUANTITIES + JACOBIAN_PATH_QUANTITIES[1:]
 
+# The source inside a level of compute_radiance and compute_flux: B(T_level) throughout, or
+# linear in optical depth between the Planck values at the level's two interfaces.
+SOURCES = ("isothermal", "linear_in_tau")
+
 FLUX_QUANTITIES = ("upward_flux", "downward_flux", "heating_rate")
 FLUX_SURFACES = ("first", "last")
 MAX_FLUX_ANGLES = 8
@@ -60,12 +64,16 @@ _FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
 # None), and whether the result is per level (compute_path: None, "from_first" or "from_last").
 _COMMON = ("lengths", "shape", "quantities", "edges", "starts", "instrument", "cumulative")
 _PathRequest = namedtuple("_PathRequest", _COMMON)
-# compute_radiance's and compute_jacobian's: the sweep order and one boundary value per path.
+# compute_radiance's and compute_jacobian's: the sweep order and one boundary value per path;
+# edge_temperature: None (isothermal levels) or the interface temperatures per flat level,
+# [levels, 2] (_edge_temperatures), of the linear-in-tau source.
 _RadianceRequest = namedtuple("_RadianceRequest", _COMMON + (
-    "from_last", "boundary_temperature", "boundary_emissivity"))
-# compute_flux's: the angles and the surface of every path.
+    "from_last", "boundary_temperature", "boundary_emissivity", "edge_temperature"),
+    defaults=(None,))
+# compute_flux's: the angles and the surface of every path; edge_temperature as above.
 _FluxRequest = namedtuple("_FluxRequest", _COMMON + (
-    "surface", "mu", "weight", "surface_temperature", "surface_emissivity"))
+    "surface", "mu", "weight", "surface_temperature", "surface_emissivity", "edge_temperature"),
+    defaults=(None,))
 
 # One pass of _sweep_runs over the levels: its order, and what it writes per level and per path.
 _Pass = namedtuple("_Pass", ["from_last", "level_quantities", "path_quantities"])
@@ -216,6 +224,41 @@ def _emitter(temperature, emissivity, what, shape, optional=False):
     return temperatures, emissivities
 
 
+def _edge_temperatures(source, interface_temperature, shape):
+    """None for source "isothermal"; for "linear_in_tau" the interface temperatures as the path
+    entries take them, float64 [levels, 2]: row i = p*L + l holds interface l (between levels
+    l - 1 and l, the first-level side) and interface l + 1 (the last-level side) of path p.
+    interface_temperature: the atmosphere's shape with L + 1 in place of L, finite and > 0."""
+    if not (isinstance(source, str) and source in SOURCES):
+        raise ValueError(f"source must be one of {SOURCES}, not {source!r}.")
+    if source == "isothermal":
+        if interface_temperature is not None:
+            raise ValueError('interface_temperature is only used with source="linear_in_tau".')
+        return None
+    if interface_temperature is None:
+        raise ValueError('source="linear_in_tau" needs interface_temperature.')
+    per_path, paths = _path_layout(shape)
+    expected = tuple(shape[:-1]) + (per_path + 1,)
+    interfaces = np.asarray(interface_temperature, dtype=np.float64)
+    if interfaces.shape != expected:
+        raise ValueError(f"interface_temperature has shape {interfaces.shape}, need {expected}: "
+                         "the atmosphere's with one more value along the last axis.")
+    if not np.all(np.isfinite(interfaces)) or np.any(interfaces <= 0.):
+        raise ValueError("interface temperatures must be finite and > 0.")
+    interfaces = interfaces.reshape(paths, per_path + 1)
+    edges = np.stack([interfaces[:, :-1], interfaces[:, 1:]], axis=-1)
+    return np.ascontiguousarray(edges.reshape(paths*per_path, 2))
+
+
+def _run_edges(request, a, b):
+    """What a sweep of the flat levels [a, b) passes on to Engine.path_radiance / path_flux
+    beside its other tables: nothing for isothermal levels, edge_temperature [b - a, 2] for the
+    linear-in-tau source."""
+    if request.edge_temperature is None:
+        return {}
+    return {"edge_temperature": request.edge_temperature[a:b]}
+
+
 def _path_bands(spec, band_edges, instrument=None):
     """(edges, column starts) of band_edges, or (None, None); checks `instrument` too."""
     if instrument is not None:
@@ -250,10 +293,12 @@ def _path_request(spec, path_length, quantities, band_edges, cumulative, range_p
 
 def _radiance_request(spec, path_length, boundary_temperature, boundary_emissivity, direction,
                       quantities, band_edges, cumulative, range_policy, instrument=None,
-                      names=RADIANCE_QUANTITIES, caller="compute_radiance"):
+                      names=RADIANCE_QUANTITIES, caller="compute_radiance", source="isothermal",
+                      interface_temperature=None):
     """Checks every argument of compute_radiance; compute_jacobian's too, with its `names`."""
     lengths, shape = _path_geometry(spec, path_length, caller)
     _check_level_temperatures(spec)
+    edge_temperature = _edge_temperatures(source, interface_temperature, shape)
     boundary, emissivity = _emitter(boundary_temperature, boundary_emissivity, "boundary", shape,
                                     optional=True)
     if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
@@ -269,15 +314,18 @@ def _radiance_request(spec, path_length, boundary_temperature, boundary_emissivi
     return _RadianceRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
                             starts=starts, instrument=instrument, cumulative=bool(cumulative),
                             from_last=direction == "toward_first",
-                            boundary_temperature=boundary, boundary_emissivity=emissivity)
+                            boundary_temperature=boundary, boundary_emissivity=emissivity,
+                            edge_temperature=edge_temperature)
 
 
 def _flux_request(spec, layer_thickness, surface_temperature, surface_emissivity, surface,
-                  angles, quantities, band_edges, range_policy):
+                  angles, quantities, band_edges, range_policy, source="isothermal",
+                  interface_temperature=None):
     """Checks every argument of compute_flux."""
     lengths, shape = _path_geometry(spec, layer_thickness, "compute_flux", "layer_thickness",
                                     "layer thicknesses")
     _check_level_temperatures(spec)
+    edge_temperature = _edge_temperatures(source, interface_temperature, shape)
     if "heating_rate" in (quantities if not isinstance(quantities, str) else (quantities,)):
         pressure = spec.atmosphere.pressure
         if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
@@ -291,7 +339,8 @@ def _flux_request(spec, layer_thickness, surface_temperature, surface_emissivity
     edges, starts = _path_bands(spec, band_edges)
     return _FluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
                         starts=starts, instrument=None, cumulative=False, surface=surface, mu=mu,
-                        weight=weight, surface_temperature=ts, surface_emissivity=es)
+                        weight=weight, surface_temperature=ts, surface_emissivity=es,
+                        edge_temperature=edge_temperature)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -543,14 +592,19 @@ def _path_variables(spec, variables, request):
         coords = {"band_lower": (request.edges[:-1], {"units": "cm-1"}),
                   "band_upper": (request.edges[1:], {"units": "cm-1"}),
                   "band_points": (np.diff(request.starts), {})}
+    # Only a result formed with the linear-in-tau source says so: the others are as they were.
+    linear = getattr(request, "edge_temperature", None) is not None
     xarray = _optional_xarray()
     if xarray is None:
         out = {name: value for name, (value, _) in coords.items()}
         out.update({q: v for q, (_, v, _) in variables.items()})
+        if linear:
+            out["source"] = "linear_in_tau"
         return out
     DataArray, Dataset = xarray.DataArray, xarray.Dataset
     return Dataset(
         data_vars={q: DataArray(v, dims=dims, attrs={"units": units})
                    for q, (dims, v, units) in variables.items()},
         coords={name: DataArray(value, dims=(axis,), attrs=attrs)
-                for name, (value, attrs) in coords.items()})
+                for name, (value, attrs) in coords.items()},
+        **({"attrs": {"source": "linear_in_tau"}} if linear else {}))

@@ -30,9 +30,9 @@ from . import absorption, errors, paths
 from .paths import (CP_DRY, FLUX_QUANTITIES, FLUX_SURFACES, JACOBIAN_LEVEL_QUANTITIES,  # noqa: F401
                     JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
                     PATH_CUMULATIVE, PATH_QUANTITIES, PLANCK_C1, PLANCK_C2, R_DRY,
-                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, band_columns, flux_angles,
+                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOURCES, band_columns, flux_angles,
                     heating_rate, _MAX_RUN_LEVELS, _PATH_UNITS, _Pass, _Product, _cut_runs,
-                    _path_layout, _sweep_pass)
+                    _path_layout, _run_edges, _sweep_pass)
 from .plugins import continua, cross_sections, molecular_lines
 
 kb = 1.38064852e-23  # Boltzmann constant [J K-1] (pyLBL/spectroscopy.py:15).
@@ -315,10 +315,12 @@ class Spectroscopy(object):
     def compute_radiance(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
                          direction="toward_last", quantities=("radiance",), band_edges=None,
                          cumulative=False, remove_pedestal=None, range_policy="reference",
-                         instrument=None):
+                         instrument=None, source="isothermal", interface_temperature=None):
         """Thermal emission along the paths of the atmosphere: the radiance that leaves each
         path, formed on the GPU from the "total" absorption block like compute_path's optical
-        depth.  Every level is an isothermal layer at its own temperature.
+        depth.  Every level is an isothermal layer at its own temperature, or with
+        source="linear_in_tau" a layer whose source varies linearly in optical depth between
+        the Planck values at its two interfaces.
 
         Paths as in compute_path: the last dimension of the atmosphere, flat level i = p*L + l.
         With beta the absorption coefficient [m-1] of compute_absorption("total",
@@ -331,6 +333,17 @@ class Spectroscopy(object):
             each level in sweep order;
             brightness temperature = (C2*nu) / log1p((((C1*nu)*nu)*nu) / I), 0 where I <= 0 or
             nu <= 0.
+        source="linear_in_tau": the level's own temperature still sets beta, but not the
+        source.  With T_i the interface temperatures, B_in = B(nu, T) at the interface the
+        sweep enters level l through (l toward_last, l + 1 toward_first) and B_out at the one
+        it leaves through, the update is
+            w = 1 - a/x (x/2 - x^2/6 + ...; 0 at x = 0), u_in = a - w,
+            I = I*t + (B_in*u_in + B_out*w),
+        with w formed as 1. - a/x for |x| >= 1/16 and below that as the 8-term Horner series
+            x*(1./2. - x*(1./6. - x*(1./24. - x*(1./120. - x*(1./720. - x*(1./5040.
+              - x*(1./40320. - x*(1./362880.)))))))).
+        An optically thick layer then radiates at the temperature of the interface the
+        radiation leaves through, a thin one at the mean of the two Planck values.
         For an atmosphere whose paths start at the surface, "toward_last" with the surface as
         the boundary is the upwelling radiance at the top, "toward_first" the downwelling
         radiance at the surface.
@@ -352,16 +365,22 @@ class Spectroscopy(object):
                         inside the grid); "brightness_temperature" is then that of R_c at the
                         channel centre, (C2*nu_c)/log1p((((C1*nu_c)*nu_c)*nu_c)/R_c), 0 where
                         R_c <= 0.  Not with band_edges.
+            source: "isothermal" or "linear_in_tau".
+            interface_temperature: [K], the atmosphere's shape with L + 1 in place of L on the
+                        last axis, finite and > 0: interface i lies between levels i-1 and i.
+                        Needed with "linear_in_tau", refused without it.
 
         Returns:
             Like compute_path: an xarray Dataset when xarray is installed, else a dict --
             "radiance" ("W m-2 sr-1 (cm-1)-1") / "brightness_temperature" ("K") with the
             atmosphere's dims (without the last unless cumulative) and "wavenumber", "band" or
-            "channel".
+            "channel".  With "linear_in_tau" the result carries source = "linear_in_tau" (a
+            Dataset attribute, a key of the dict).
         """
         request = self._radiance_request(path_length, boundary_temperature,
                                           boundary_emissivity, direction, quantities, band_edges,
-                                          cumulative, range_policy, instrument)
+                                          cumulative, range_policy, instrument, source=source,
+                                          interface_temperature=interface_temperature)
 
         def sweeper(call, run):
             grid = call.grid()
@@ -376,7 +395,8 @@ class Spectroscopy(object):
                     radiance=outputs.get("radiance"),
                     brightness_temperature=outputs.get("brightness_temperature"),
                     band_start=request.starts, cumulative=request.cumulative,
-                    from_last=request.from_last, asynchronous=True)
+                    from_last=request.from_last, asynchronous=True,
+                    **_run_edges(request, a, b))
             return sweep
         if request.instrument is None:
             quantities, products = request.quantities, None
@@ -484,7 +504,8 @@ class Spectroscopy(object):
 
     def compute_flux(self, layer_thickness, surface_temperature, surface_emissivity=1.,
                      surface="first", angles=3, quantities=("upward_flux", "downward_flux"),
-                     band_edges=None, remove_pedestal=None, range_policy="reference"):
+                     band_edges=None, remove_pedestal=None, range_policy="reference",
+                     source="isothermal", interface_temperature=None):
         """Upward and downward longwave fluxes at every layer interface, and heating rates,
         formed on the GPU from the "total" absorption block: the radiance of K angles swept
         down from space and back up from a Lambertian surface, in two passes over the block.
@@ -507,6 +528,10 @@ class Spectroscopy(object):
                   from the returned fluxes, Fnet = F_up - F_down, i_lower the interface of level
                   l nearer the surface, rho_l = p_l/(R_DRY*T_l), c_p = CP_DRY; NaN where s_l = 0
                   (see heating_rate).
+        source="linear_in_tau" replaces the update of both sweeps by compute_radiance's linear
+        one, I_k = I_k*exp(-x) + (B_in*u_in + B_out*w) with B at the interfaces of
+        interface_temperature (shared by the angles; w per angle); the surface and the
+        heating rates are formed as above.
         When the absorption of every level fits device_output_limit (two blocks of it per level:
         beta and the fluxes of a level) it is computed once and both sweeps read it.  Otherwise
         each pass computes its runs again, save the one the down pass ends on: beyond that limit
@@ -524,6 +549,8 @@ class Spectroscopy(object):
             quantities: any of "upward_flux", "downward_flux", "heating_rate" (net flux is
                         up - down).
             band_edges: as in compute_path.
+            source, interface_temperature: as in compute_radiance; interface i is index i of
+                        the result's "interface" dim.
 
         Returns:
             Like compute_path: an xarray Dataset when xarray is installed, else a dict -- the
@@ -533,7 +560,8 @@ class Spectroscopy(object):
         """
         request = self._flux_request(layer_thickness, surface_temperature,
                                       surface_emissivity, surface, angles, quantities, band_edges,
-                                      range_policy)
+                                      range_policy, source=source,
+                                      interface_temperature=interface_temperature)
         angles = request.mu.size
         lengths = request.lengths[:, None]/request.mu[None, :]
         bands = request.starts is not None
@@ -562,7 +590,7 @@ class Spectroscopy(object):
                     flux=out if bands else None,
                     surface_flux=outputs["surface_flux"] if bands and up else None,
                     band_start=request.starts, up=up, from_last=passes[index].from_last,
-                    asynchronous=True)
+                    asynchronous=True, **_run_edges(request, a, b))
             return sweep
         # Two blocks per level: beta and the fluxes of a level.
         values = self._sweep_runs(request, passes, remove_pedestal, range_policy, sweeper,
