@@ -340,6 +340,56 @@ int lbl_path_flux_source(lbl_engine *engine, double *beta, int64_t row_stride, i
                          double *reflection, double *level_flux, double *flux,
                          double *surface_flux, int32_t flags);
 
+/* The lower boundary of Spectroscopy.compute_radiance: a surface with a spectral emissivity that
+ * may also reflect the radiance the atmosphere sends down to it.
+ *
+ * lbl_surface_emissivity fills rows[p][j] = E_p(nu_j) for the paths p in [path_begin, path_begin +
+ * path_count) of n_paths, nu_j the points of `grid` (a handle of lbl_grid_load, ascending or not):
+ *   knot_wavenumber (host, n_knots values k_0 < ... < k_{M-1} [cm-1], finite, 2 <= M <= 1024);
+ *   knot_emissivity (host, [path_count][n_knots], every value in [0, 1]): e_0 .. e_{M-1} of each
+ *   path of the call;
+ *   for k_j <= nu < k_{j+1}:  E = e_j + (nu - k_j)*((e_{j+1} - e_j)/(k_{j+1} - k_j)),
+ *   E = e_0 for nu <= k_0,  E = e_{M-1} for nu >= k_{M-1}
+ * -- numpy.interp: constant outside the knots, linear inside; each operation rounded as written,
+ * so a flat table e_j = c gives E = c exactly.
+ *   rows (device, [n_paths][row_stride], row_stride >= the grid's points): row p receives the
+ *   grid's points, the padding is left alone.  flags: LBL_ASYNC or 0.
+ * LBL_BAD_ARGUMENT (message in lbl_last_error) for knots that are not finite and strictly
+ * ascending, emissivities outside [0, 1], n_knots outside 2..1024, an unknown grid, a row_stride
+ * below the grid's points or paths outside n_paths; nothing is launched and the engine stays usable.
+ *
+ * lbl_path_radiance_surface is lbl_path_radiance_source with two more device pointers, read where
+ * a path starts in the run (a run under LBL_PATH_CONTINUE takes its carry row as always):
+ *   emissivity_rows ([n_paths][row_stride], e.g. lbl_surface_emissivity's rows, or NULL: E is the
+ *   path's scalar boundary_emissivity);
+ *   reflection ([n_paths][row_stride]: D, the radiance that arrives at the boundary of each path,
+ *   or NULL: nothing is reflected).
+ * A path behind a boundary (boundary temperature T_b > 0) starts from
+ *   I = E*B(nu, T_b) + (1. - E)*D        (I = E*B(nu, T_b) with reflection == NULL)
+ * each product and sum rounded as written, and goes on level by level as in
+ * lbl_path_radiance_source; a path without a boundary starts from 0.  With both pointers NULL the
+ * call is lbl_path_radiance_source bit for bit (the same kernels).  D is what a sweep against the
+ * direction leaves at the boundary: lbl_path_radiance_source with boundary_temperature NULL, the
+ * opposite LBL_PATH_FROM_LAST, the lengths of the reflected path (the same lengths: specular
+ * reflection in a plane-parallel atmosphere; 1.66 times the layer thickness: the diffusivity
+ * approximation of a Lambertian surface) and `reflection` as its per-path radiance output.
+ * LBL_BAD_ARGUMENT as for lbl_path_radiance_source, and when reflection is given and a path of the
+ * run has boundary temperature 0 (or boundary_temperature is NULL); the engine stays usable. */
+int lbl_surface_emissivity(lbl_engine *engine, int32_t grid, int32_t n_paths, int32_t path_begin,
+                           int32_t path_count, int32_t n_knots, const double *knot_wavenumber,
+                           const double *knot_emissivity, double *rows, int64_t row_stride,
+                           int32_t flags);
+int lbl_path_radiance_surface(lbl_engine *engine, double *beta, int64_t row_stride,
+                              int64_t columns, int32_t grid, int32_t n_paths,
+                              int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+                              const double *path_length, const double *temperature,
+                              const double *edge_temperature,
+                              const double *boundary_temperature,
+                              const double *boundary_emissivity, int32_t n_bands,
+                              const int64_t *band_start, double *carry, double *radiance,
+                              double *brightness_temperature, int32_t flags,
+                              const double *emissivity_rows, const double *reflection);
+
 /* Analytic radiance Jacobians (Spectroscopy.compute_jacobian): the derivatives of
  * lbl_path_radiance's radiance with respect to the state of every level and of the boundary, for
  * a run of whole paths.  beta (read only), row_stride, columns, grid, n_paths, levels_per_path,

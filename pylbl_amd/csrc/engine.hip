@@ -39,6 +39,7 @@
 #include "path.h"
 #include "pedestal.h"
 #include "radiance.h"
+#include "surface.h"
 #include "tile_schedule.h"
 
 #include "engine_core.h"

@@ -16,6 +16,12 @@
 //   (1 - a/x is 0/0 at x = 0 and loses x's leading digits below it: 4e-4 relative at x = 1e-12;
 //   the two-branch form stays within 6.2e-15 relative of long double from x = -3 to 1e3).
 //   x = 0 gives w = u_in = 0 and t = 1: I is unchanged bit for bit.
+// Reflecting surface and spectral emissivity (path_radiance_surface_kernel, lbl_path_radiance_surface;
+// the table and its interpolation are surface.h's): a path that starts behind a boundary starts from
+//   I = E*B(nu, T_boundary) + (1. - E)*D
+// with E the path's emissivity at nu (or the scalar eps) and D the radiance that arrives at the
+// boundary (or E*B alone where nothing is reflected).  Only the start differs: both kernels run the
+// same radiance_sweep, and path_radiance_kernel's instantiations are what they were.
 // The TU builds with -ffp-contract=off: every product and sum is rounded as written.
 //
 // path_radiance_kernel runs on path.h's sweep skeleton with kPathAhead rows in flight: a lane
@@ -106,9 +112,20 @@ __device__ __forceinline__ void radiance_store(double * rad, double * bt, long l
     }
 }
 
-// grid and kVector as for path_sweep_kernel.  kLinear: the linear-in-tau source of a.edge.
-template <bool kVector, bool kLinear = false>
-__global__ __launch_bounds__(kPathThreads) void path_radiance_kernel(PathRadiance a)
+// What lbl_path_radiance_surface adds to the arguments (the kSurface kernels): device rows
+// [paths][stride] like the carry rows, read where a path starts.
+struct PathSurface : PathRadiance
+{
+    const double * emissivity_rows; // E per path and column, or null: boundary_e of the path
+    const double * reflection;      // D per path and column, or null: nothing is reflected
+};
+
+// The sweep of one lane.  kLinear: the linear-in-tau source of a.edge.  kSurface (Args =
+// PathSurface): a path that starts in the launch behind a boundary starts from
+// E*B(nu, T_boundary) + (1. - E)*D with E and D read from a.emissivity_rows and a.reflection
+// (E = eps without the rows; E*B alone without D); nothing else differs.
+template <bool kVector, bool kLinear, bool kSurface, typename Args>
+__device__ __forceinline__ void radiance_sweep(const Args & a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
@@ -130,10 +147,34 @@ __global__ __launch_bounds__(kPathThreads) void path_radiance_kernel(PathRadianc
     {
         const double tb = a.boundary_t[l.p - a.table_path];
         const double eb = a.boundary_e[l.p - a.table_path];
-#pragma unroll
-        for (int i = 0; i < kPathWidth; ++i)
+        if constexpr (kSurface)
         {
-            rad[i] = tb > 0. ? eb*planck(nu[i], c1nu3[i], c2nu[i], tb) : 0.;
+            const long long row = (long long)l.p*a.stride + l.j;
+            double e[kPathWidth], d[kPathWidth];
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                e[i] = eb;
+                d[i] = 0.;
+            }
+            if (a.emissivity_rows != nullptr) path_load<kVector>(a.emissivity_rows + row, width, e);
+            if (a.reflection != nullptr) path_load<kVector>(a.reflection + row, width, d);
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                const double b = planck(nu[i], c1nu3[i], c2nu[i], tb);
+                const double emitted = e[i]*b;
+                rad[i] = !(tb > 0.) ? 0. : a.reflection != nullptr ? emitted + (1. - e[i])*d[i]
+                                                                   : emitted;
+            }
+        }
+        else
+        {
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                rad[i] = tb > 0. ? eb*planck(nu[i], c1nu3[i], c2nu[i], tb) : 0.;
+            }
         }
     }
     else
@@ -187,6 +228,21 @@ __global__ __launch_bounds__(kPathThreads) void path_radiance_kernel(PathRadianc
     {
         radiance_store<kVector>(a.final_rad, a.final_bt, row, width, rad, nu, c1nu3, c2nu);
     }
+}
+
+// grid and kVector as for path_sweep_kernel.  kLinear: the linear-in-tau source of a.edge.
+template <bool kVector, bool kLinear = false>
+__global__ __launch_bounds__(kPathThreads) void path_radiance_kernel(PathRadiance a)
+{
+    radiance_sweep<kVector, kLinear, false>(a);
+}
+
+// The kSurface instantiations: path_radiance_kernel with the start value of a surface that has
+// a spectral emissivity and/or reflects (lbl_path_radiance_surface).
+template <bool kVector, bool kLinear>
+__global__ __launch_bounds__(kPathThreads) void path_radiance_surface_kernel(PathSurface a)
+{
+    radiance_sweep<kVector, kLinear, true>(a);
 }
 
 }  // namespace lbl

@@ -1,21 +1,24 @@
 // lbl_path_radiance_source: thermal emission along paths through a block of absorption
 // coefficients in HBM (kernel: radiance.h; band means: path.h), and lbl_path_radiance, the same
-// call without edge temperatures.  Included by engine.hip after path_entry.inc,
-// whose PathCall, PathTables and PathBands it shares.
-extern "C" {
+// call without edge temperatures.  lbl_path_radiance_surface: the same call with the start value
+// of a surface that has a spectral emissivity and/or reflects, and lbl_surface_emissivity, which
+// fills the emissivity rows it reads (kernel: surface.h).  Included by engine.hip after
+// path_entry.inc, whose PathCall, PathTables and PathBands it shares.
+namespace {
 
-int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_stride,
-                             int64_t columns, int32_t grid, int32_t n_paths,
-                             int32_t levels_per_path, int32_t level_begin, int32_t level_count,
-                             const double * path_length, const double * temperature,
-                             const double * edge_temperature,
-                             const double * boundary_temperature,
-                             const double * boundary_emissivity, int32_t n_bands,
-                             const int64_t * band_start, double * carry, double * radiance,
-                             double * brightness_temperature, int32_t flags)
+// The three radiance entries: `name` is the entry's, emissivity_rows / reflection are
+// lbl_path_radiance_surface's (device, both null for the others: their kernels and their bits).
+int path_radiance_call(const char * name, lbl_engine * engine, double * beta, int64_t row_stride,
+                       int64_t columns, int32_t grid, int32_t n_paths, int32_t levels_per_path,
+                       int32_t level_begin, int32_t level_count, const double * path_length,
+                       const double * temperature, const double * edge_temperature,
+                       const double * boundary_temperature, const double * boundary_emissivity,
+                       int32_t n_bands, const int64_t * band_start, double * carry,
+                       double * radiance, double * brightness_temperature, int32_t flags,
+                       const double * emissivity_rows, const double * reflection)
 {
     return path_entry(engine, flags, [&] {
-        PathCall call{engine, "lbl_path_radiance_source", row_stride, columns, n_paths, levels_per_path,
+        PathCall call{engine, name, row_stride, columns, n_paths, levels_per_path,
                       level_begin, level_count, flags};
         const bool want_rad = (flags & LBL_PATH_RADIANCE) != 0;
         const bool want_bt = (flags & LBL_PATH_BRIGHTNESS) != 0;
@@ -60,6 +63,16 @@ int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_str
         {
             return call.bad(problem);
         }
+        const bool surface = emissivity_rows != nullptr || reflection != nullptr;
+        for (int i = 0; reflection != nullptr && i < call.run.paths; ++i)
+        {
+            const int p = call.run.first_path + i;
+            if (boundary_temperature == nullptr || !(boundary_temperature[p] > 0.))
+            {
+                return call.bad("a reflecting surface needs a boundary temperature > 0 for "
+                                "every path of the run.");
+            }
+        }
 
         // The boundary temperatures and emissivities of the run's paths.
         const PathRun & run = call.run;
@@ -95,6 +108,7 @@ int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_str
         a.row_base = level_begin;
         a.levels_per_path = levels_per_path;
         a.table_path = run.first_path;
+        a.first_path = run.first_path;     // (every launch sets its own)
         a.from_last = call.from_last() ? 1 : 0;
         a.carry = carry;
         a.level_rad = a.level_bt = a.final_rad = a.final_bt = nullptr;
@@ -118,10 +132,39 @@ int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_str
             a.final_bt = want_bt ? brightness_temperature : nullptr;
         }
         const bool vector = path_vector(row_stride, {beta, carry, a.nu, a.level_rad, a.level_bt,
-                                                     a.final_rad, a.final_bt});
+                                                     a.final_rad, a.final_bt, emissivity_rows,
+                                                     reflection});
+        PathSurface s;
+        static_cast<PathRadiance &>(s) = a;
+        s.emissivity_rows = emissivity_rows;
+        s.reflection = reflection;
         call.launch([&](const dim3 & launch, int first_path) {
-            a.first_path = first_path;
-            if (vector && linear)
+            a.first_path = s.first_path = first_path;
+            if (surface)
+            {
+                const dim3 block(kPathThreads);
+                if (vector && linear)
+                {
+                    hipLaunchKernelGGL((path_radiance_surface_kernel<true, true>), launch, block,
+                                       0, engine->stream, s);
+                }
+                else if (linear)
+                {
+                    hipLaunchKernelGGL((path_radiance_surface_kernel<false, true>), launch, block,
+                                       0, engine->stream, s);
+                }
+                else if (vector)
+                {
+                    hipLaunchKernelGGL((path_radiance_surface_kernel<true, false>), launch, block,
+                                       0, engine->stream, s);
+                }
+                else
+                {
+                    hipLaunchKernelGGL((path_radiance_surface_kernel<false, false>), launch,
+                                       block, 0, engine->stream, s);
+                }
+            }
+            else if (vector && linear)
             {
                 hipLaunchKernelGGL((path_radiance_kernel<true, true>), launch,
                                    dim3(kPathThreads), 0, engine->stream, a);
@@ -148,6 +191,8 @@ int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_str
         call.note_rows(carry, n_paths);
         call.note_rows(a.final_rad, n_paths);
         call.note_rows(a.final_bt, n_paths);
+        call.note_rows(emissivity_rows, n_paths);
+        call.note_rows(reflection, n_paths);
 
         if (n_bands > 0)
         {
@@ -162,6 +207,123 @@ int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_str
             bands.means(engine, reinterpret_cast<const long long *>(d_tables + band_at), values,
                         (long long)row_stride, rows.count, false, out);
         }
+        return LBL_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int lbl_path_radiance_source(lbl_engine * engine, double * beta, int64_t row_stride,
+                             int64_t columns, int32_t grid, int32_t n_paths,
+                             int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+                             const double * path_length, const double * temperature,
+                             const double * edge_temperature,
+                             const double * boundary_temperature,
+                             const double * boundary_emissivity, int32_t n_bands,
+                             const int64_t * band_start, double * carry, double * radiance,
+                             double * brightness_temperature, int32_t flags)
+{
+    return path_radiance_call("lbl_path_radiance_source", engine, beta, row_stride, columns, grid,
+                              n_paths, levels_per_path, level_begin, level_count, path_length,
+                              temperature, edge_temperature, boundary_temperature,
+                              boundary_emissivity, n_bands, band_start, carry, radiance,
+                              brightness_temperature, flags, nullptr, nullptr);
+}
+
+int lbl_path_radiance_surface(lbl_engine * engine, double * beta, int64_t row_stride,
+                              int64_t columns, int32_t grid, int32_t n_paths,
+                              int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+                              const double * path_length, const double * temperature,
+                              const double * edge_temperature,
+                              const double * boundary_temperature,
+                              const double * boundary_emissivity, int32_t n_bands,
+                              const int64_t * band_start, double * carry, double * radiance,
+                              double * brightness_temperature, int32_t flags,
+                              const double * emissivity_rows, const double * reflection)
+{
+    return path_radiance_call("lbl_path_radiance_surface", engine, beta, row_stride, columns,
+                              grid, n_paths, levels_per_path, level_begin, level_count,
+                              path_length, temperature, edge_temperature, boundary_temperature,
+                              boundary_emissivity, n_bands, band_start, carry, radiance,
+                              brightness_temperature, flags, emissivity_rows, reflection);
+}
+
+int lbl_surface_emissivity(lbl_engine * engine, int32_t grid, int32_t n_paths, int32_t path_begin,
+                           int32_t path_count, int32_t n_knots, const double * knot_wavenumber,
+                           const double * knot_emissivity, double * rows, int64_t row_stride,
+                           int32_t flags)
+{
+    return path_entry(engine, flags, [&] {
+        // Paths stand where a sweep has its levels: one row per path, [path_begin, + path_count).
+        PathCall call{engine, "lbl_surface_emissivity", row_stride, 0, n_paths, 1, path_begin,
+                      path_count, flags};
+        if (knot_wavenumber == nullptr || knot_emissivity == nullptr || rows == nullptr)
+        {
+            return call.bad("knot_wavenumber, knot_emissivity and rows must not be NULL.");
+        }
+        if (const char * problem = call.find_grid(grid)) return call.bad(problem);
+        call.columns = call.grid->n;
+        if (call.columns < 1 || row_stride < call.columns)
+        {
+            return call.bad("row_stride is less than the grid's points.");
+        }
+        if (n_paths < 1 || path_begin < 0 || path_count < 1 || path_count > n_paths - path_begin)
+        {
+            return call.bad("the paths [path_begin, path_begin + path_count) are not inside "
+                            "n_paths.");
+        }
+        if (n_knots < 2 || n_knots > kSurfaceMaxKnots)
+        {
+            return call.bad("n_knots must lie in 2..1024.");
+        }
+        for (int j = 0; j < n_knots; ++j)
+        {
+            if (!std::isfinite(knot_wavenumber[j]) ||
+                (j > 0 && !(knot_wavenumber[j] > knot_wavenumber[j - 1])))
+            {
+                return call.bad("knots must be finite and strictly ascending.");
+            }
+        }
+        const long long values = (long long)path_count*n_knots;
+        for (long long i = 0; i < values; ++i)
+        {
+            if (!(knot_emissivity[i] >= 0. && knot_emissivity[i] <= 1.))
+            {
+                return call.bad("emissivities must lie in [0, 1].");
+            }
+        }
+        call.run = PathRun{path_begin, path_count, false};
+
+        PathTables tables;
+        const size_t knot_at = tables.add(n_knots, knot_wavenumber);
+        const size_t value_at = tables.add((size_t)values, knot_emissivity);
+        const double * d_tables = call.begin(tables);
+
+        SurfaceEmissivity a;
+        a.nu = call.grid->wavenumber.data;
+        a.columns = call.columns;
+        a.stride = row_stride;
+        a.knot = d_tables + knot_at;
+        a.n_knots = n_knots;
+        a.ascending = call.grid->ascending ? 1 : 0;
+        const bool vector = path_vector(row_stride, {rows, a.nu});
+        call.launch([&](const dim3 & launch, int first_path) {
+            a.value = d_tables + value_at + (long long)(first_path - path_begin)*n_knots;
+            a.rows = rows + (long long)first_path*row_stride;
+            if (vector)
+            {
+                hipLaunchKernelGGL(surface_emissivity_kernel<true>, launch, dim3(kPathThreads),
+                                   0, engine->stream, a);
+            }
+            else
+            {
+                hipLaunchKernelGGL(surface_emissivity_kernel<false>, launch, dim3(kPathThreads),
+                                   0, engine->stream, a);
+            }
+        });
+        call.note_rows(rows + (long long)path_begin*row_stride, path_count);
         return LBL_OK;
     });
 }

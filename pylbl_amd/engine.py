@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
     "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
     "lbl_path_jacobian", "lbl_path_radiance_source", "lbl_path_flux_source",
+    "lbl_surface_emissivity", "lbl_path_radiance_surface",
     "lbl_instrument_create", "lbl_instrument_free", "lbl_instrument_apply",
 )
 
@@ -209,6 +210,11 @@ def library():
         lib.lbl_path_radiance.argtypes[11:]
     lib.lbl_path_flux_source.argtypes = lib.lbl_path_flux.argtypes[:13] + [c_void_p] + \
         lib.lbl_path_flux.argtypes[13:]
+    # The surface entries: emissivity_rows and reflection after lbl_path_radiance_source's flags.
+    lib.lbl_path_radiance_surface.argtypes = lib.lbl_path_radiance_source.argtypes + \
+        [c_void_p, c_void_p]
+    lib.lbl_surface_emissivity.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_void_p, c_void_p, c_int64, c_int32]
     lib.lbl_instrument_create.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                           c_void_p, c_int32, c_void_p, c_void_p, c_int32, i32p]
     lib.lbl_instrument_free.argtypes = [c_void_p, c_int32]
@@ -768,7 +774,7 @@ class Engine(object):
                       temperature, carry, boundary_temperature=None, boundary_emissivity=None,
                       radiance=None, brightness_temperature=None, band_start=None,
                       cumulative=False, from_last=False, asynchronous=False,
-                      edge_temperature=None):
+                      edge_temperature=None, emissivity_rows=None, reflection=None):
         """Thermal emission along paths through the DeviceSpectra `beta` -- lbl_path_radiance.
         Rows, lengths, carry, band_start, cumulative, from_last and asynchronous as for
         path_compute; grid: handle of load_grid (the wavenumbers of the columns); temperature
@@ -777,11 +783,18 @@ class Engine(object):
         not wanted), shaped as path_compute's.  edge_temperature: None (isothermal layers), or
         [rows, 2] interface temperatures [K] -- [r, 0] on the first-level side of row r, [r, 1]
         on the last-level side, continuous within a path -- for the linear-in-tau source
-        (lbl_path_radiance_source)."""
+        (lbl_path_radiance_source).  emissivity_rows / reflection: None, or DeviceSpectra
+        [n_paths, row length of beta] read where a path starts behind a boundary -- E per column
+        (surface_emissivity's rows) in place of boundary_emissivity, and D, the radiance that
+        arrives at the boundary: the path starts from E*B(nu, T_b) + (1. - E)*D
+        (lbl_path_radiance_surface; with both None the call is lbl_path_radiance_source's)."""
         rows, stride, lengths, temperature = _per_row(
             beta, "one path length and one temperature per row of beta.", lengths, temperature)
         if tuple(carry.shape) != (int(n_paths), stride):
             raise ValueError("carry must be [n_paths, row length of beta].")
+        for name, block in (("emissivity_rows", emissivity_rows), ("reflection", reflection)):
+            if block is not None and tuple(block.shape) != (int(n_paths), stride):
+                raise ValueError(f"{name} must be [n_paths, row length of beta].")
         edge_temperature = _edge_rows(edge_temperature, rows)
         boundary = _per_path(n_paths, "one boundary value per path.", boundary_temperature,
                              boundary_emissivity)
@@ -792,12 +805,35 @@ class Engine(object):
                  (PATH_CUMULATIVE if cumulative else 0)
         _check_outputs((radiance, brightness_temperature),
                        rows if cumulative else int(n_paths), n_bands if n_bands > 0 else stride)
-        self._check(self.lib.lbl_path_radiance_source(
+        arguments = (
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, lengths.ctypes.data,
             temperature.ctypes.data, _address(edge_temperature), *map(_address, boundary),
             n_bands, _address(starts), carry.pointer, _address(radiance),
-            _address(brightness_temperature), flags))
+            _address(brightness_temperature), flags)
+        if emissivity_rows is None and reflection is None:
+            self._check(self.lib.lbl_path_radiance_source(*arguments))
+        else:
+            self._check(self.lib.lbl_path_radiance_surface(
+                *arguments, _address(emissivity_rows), _address(reflection)))
+
+    def surface_emissivity(self, grid, rows, knot_wavenumber, knot_emissivity, path_begin=0,
+                           asynchronous=False):
+        """Fills rows path_begin, path_begin + 1, ... of the DeviceSpectra `rows` [n_paths, row
+        length] with the emissivity of each path on the grid (handle of load_grid) --
+        lbl_surface_emissivity: knot_emissivity [paths of the call, M] at the knots
+        knot_wavenumber [M] (strictly ascending, 2 <= M <= 1024), interpolated like numpy.interp:
+        for k_j <= nu < k_{j+1}, E = e_j + (nu - k_j)*((e_{j+1} - e_j)/(k_{j+1} - k_j)); E = e_0
+        for nu <= k_0 and E = e_{M-1} for nu >= k_{M-1}."""
+        knots = _f64(knot_wavenumber)
+        values = _f64(knot_emissivity)
+        if knots.ndim != 1 or values.ndim != 2 or values.shape[1] != knots.size or \
+                values.shape[0] < 1:
+            raise ValueError("knot_wavenumber must be [M] and knot_emissivity [paths, M].")
+        self._check(self.lib.lbl_surface_emissivity(
+            self.handle, int(grid), int(rows.shape[0]), int(path_begin), values.shape[0],
+            knots.size, knots.ctypes.data, values.ctypes.data, rows.pointer, int(rows.shape[1]),
+            ASYNC if asynchronous else 0))
 
     def path_jacobian(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                       temperature, work, boundary_temperature=None, boundary_emissivity=None,

@@ -21,6 +21,10 @@ PATH_QUANTITIES = ("optical_depth", "transmittance")
 PATH_CUMULATIVE = (None, "from_first", "from_last")
 RADIANCE_QUANTITIES = ("radiance", "brightness_temperature")
 RADIANCE_DIRECTIONS = ("toward_last", "toward_first")
+# compute_radiance with reflection_path_length: D, the radiance that arrives at the boundary.
+DOWNWELLING = "boundary_downwelling_radiance"
+SURFACE_RADIANCE_QUANTITIES = RADIANCE_QUANTITIES + (DOWNWELLING,)
+MAX_EMISSIVITY_KNOTS = 1024             # kSurfaceMaxKnots of csrc/surface.h
 
 # Planck's function per wavenumber, B(nu, T) = C1 nu^3 / expm1(C2 nu / T) [W m-2 sr-1 (cm-1)-1]
 # for nu in cm-1: from the exact CODATA 2018 h, c and k (the same literals as LBL_PLANCK_C1 and
@@ -49,6 +53,7 @@ MAX_FLUX_ANGLES = 8
 
 _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
                "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K",
+               DOWNWELLING: "W m-2 sr-1 (cm-1)-1",
                "optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
                "log_optical_depth_jacobian": "W m-2 sr-1 (cm-1)-1",
                "temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
@@ -66,10 +71,14 @@ _COMMON = ("lengths", "shape", "quantities", "edges", "starts", "instrument", "c
 _PathRequest = namedtuple("_PathRequest", _COMMON)
 # compute_radiance's and compute_jacobian's: the sweep order and one boundary value per path;
 # edge_temperature: None (isothermal levels) or the interface temperatures per flat level,
-# [levels, 2] (_edge_temperatures), of the linear-in-tau source.
+# [levels, 2] (_edge_temperatures), of the linear-in-tau source.  The surface of compute_radiance:
+# emissivity_knots [M] with boundary_emissivity [paths, M] (a spectral emissivity) and
+# reflection_lengths, the flat lengths of the down pass (a reflecting surface), each None where
+# the call does not ask for it.
 _RadianceRequest = namedtuple("_RadianceRequest", _COMMON + (
-    "from_last", "boundary_temperature", "boundary_emissivity", "edge_temperature"),
-    defaults=(None,))
+    "from_last", "boundary_temperature", "boundary_emissivity", "edge_temperature",
+    "emissivity_knots", "reflection_lengths"),
+    defaults=(None, None, None))
 # compute_flux's: the angles and the surface of every path; edge_temperature as above.
 _FluxRequest = namedtuple("_FluxRequest", _COMMON + (
     "surface", "mu", "weight", "surface_temperature", "surface_emissivity", "edge_temperature"),
@@ -224,6 +233,43 @@ def _emitter(temperature, emissivity, what, shape, optional=False):
     return temperatures, emissivities
 
 
+def _spectral_emissivity(emissivity_wavenumber, boundary_emissivity, shape):
+    """(knots [M], emissivities [paths, M]) of compute_radiance's emissivity_wavenumber: M knots
+    [cm-1], finite and strictly ascending, 2 <= M <= 1024; boundary_emissivity [..., M] (the
+    atmosphere's shape without its last axis, then M) or [M] for every path, in [0, 1]."""
+    knots = np.asarray(emissivity_wavenumber, dtype=np.float64)
+    if knots.ndim != 1 or not 2 <= knots.size <= MAX_EMISSIVITY_KNOTS:
+        raise ValueError(f"emissivity_wavenumber must be a 1-d array of 2..{MAX_EMISSIVITY_KNOTS} "
+                         f"knots, not of shape {knots.shape}.")
+    if not np.all(np.isfinite(knots)) or not np.all(np.diff(knots) > 0.):
+        raise ValueError("emissivity_wavenumber must be finite and strictly ascending.")
+    _, paths = _path_layout(shape)
+    per_path_shape = tuple(shape[:-1]) + (knots.size,)
+    values = np.asarray(boundary_emissivity, dtype=np.float64)
+    if values.shape not in ((knots.size,), per_path_shape):
+        raise ValueError(f"boundary_emissivity has shape {values.shape}: with "
+                         f"emissivity_wavenumber give [{knots.size}] or one table per path, "
+                         f"shaped {per_path_shape}.")
+    if not np.all((values >= 0.) & (values <= 1.)):
+        raise ValueError("boundary emissivities must lie in [0, 1].")
+    values = np.broadcast_to(values, per_path_shape).reshape(paths, knots.size)
+    return np.ascontiguousarray(knots), np.ascontiguousarray(values)
+
+
+def interpolate_emissivity(knots, values, grid):
+    """E on the grid as lbl_surface_emissivity forms it, in the float type of the arguments:
+    for k_j <= nu < k_{j+1}, E = e_j + (nu - k_j)*((e_{j+1} - e_j)/(k_{j+1} - k_j)); E = e_0 for
+    nu <= k_0 and E = e_{M-1} for nu >= k_{M-1}.  values [..., M] -> [..., grid.size]."""
+    knots, values, grid = np.asarray(knots), np.asarray(values), np.asarray(grid)
+    last = knots.size - 1
+    j = np.clip(np.searchsorted(knots, grid, side="right") - 1, 0, last - 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        slope = (values[..., j + 1] - values[..., j])/(knots[j + 1] - knots[j])
+        inside = values[..., j] + (grid - knots[j])*slope
+    return np.where(grid >= knots[last], values[..., last:],
+                    np.where(grid > knots[0], inside, values[..., :1]))
+
+
 def _edge_temperatures(source, interface_temperature, shape):
     """None for source "isothermal"; for "linear_in_tau" the interface temperatures as the path
     entries take them, float64 [levels, 2]: row i = p*L + l holds interface l (between levels
@@ -294,13 +340,27 @@ def _path_request(spec, path_length, quantities, band_edges, cumulative, range_p
 def _radiance_request(spec, path_length, boundary_temperature, boundary_emissivity, direction,
                       quantities, band_edges, cumulative, range_policy, instrument=None,
                       names=RADIANCE_QUANTITIES, caller="compute_radiance", source="isothermal",
-                      interface_temperature=None):
+                      interface_temperature=None, emissivity_wavenumber=None,
+                      reflection_path_length=None):
     """Checks every argument of compute_radiance; compute_jacobian's too, with its `names`."""
     lengths, shape = _path_geometry(spec, path_length, caller)
     _check_level_temperatures(spec)
     edge_temperature = _edge_temperatures(source, interface_temperature, shape)
-    boundary, emissivity = _emitter(boundary_temperature, boundary_emissivity, "boundary", shape,
-                                    optional=True)
+    knots = reflection_lengths = None
+    if emissivity_wavenumber is None:
+        boundary, emissivity = _emitter(boundary_temperature, boundary_emissivity, "boundary",
+                                        shape, optional=True)
+    else:
+        boundary, _ = _emitter(boundary_temperature, 1., "boundary", shape, optional=True)
+        knots, emissivity = _spectral_emissivity(emissivity_wavenumber, boundary_emissivity,
+                                                 shape)
+    if reflection_path_length is not None:
+        reflection_lengths, _ = _path_geometry(spec, reflection_path_length, caller,
+                                               "reflection_path_length",
+                                               "reflection path lengths")
+        if boundary is None:
+            raise ValueError("reflection_path_length needs a boundary_temperature: the surface "
+                             "that reflects.")
     if not (isinstance(direction, str) and direction in RADIANCE_DIRECTIONS):
         raise ValueError(f"direction must be one of {RADIANCE_DIRECTIONS}, not {direction!r}.")
     quantities = _selection(quantities, names)
@@ -310,12 +370,18 @@ def _radiance_request(spec, path_length, boundary_temperature, boundary_emissivi
     if band_edges is not None and "brightness_temperature" in quantities:
         raise ValueError("brightness_temperature is only available on the grid: band means "
                          "are formed of the radiance alone.")
+    if DOWNWELLING in quantities:
+        if reflection_lengths is None:
+            raise ValueError(f'"{DOWNWELLING}" is only formed with reflection_path_length.')
+        if cumulative:
+            raise ValueError(f'"{DOWNWELLING}" is one result per path: not with cumulative=True.')
     edges, starts = _path_bands(spec, band_edges, instrument)
     return _RadianceRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
                             starts=starts, instrument=instrument, cumulative=bool(cumulative),
                             from_last=direction == "toward_first",
                             boundary_temperature=boundary, boundary_emissivity=emissivity,
-                            edge_temperature=edge_temperature)
+                            edge_temperature=edge_temperature, emissivity_knots=knots,
+                            reflection_lengths=reflection_lengths)
 
 
 def _flux_request(spec, layer_thickness, surface_temperature, surface_emissivity, surface,
@@ -554,7 +620,7 @@ def _create_path_dataset(spec, values, request):
     variables = {}
     for q in request.quantities:
         dims, shape = list(spec.atmosphere.dims), list(request.shape)
-        if not (request.cumulative or q in JACOBIAN_LEVEL_QUANTITIES):
+        if not (request.cumulative or q in JACOBIAN_LEVEL_QUANTITIES) or q == DOWNWELLING:
             dims, shape = dims[:-1], shape[:-1]
         variables[q] = (dims + [axis], np.asarray(values[q]).reshape(shape + [-1]),
                         _PATH_UNITS[q])
@@ -594,12 +660,17 @@ def _path_variables(spec, variables, request):
                   "band_points": (np.diff(request.starts), {})}
     # Only a result formed with the linear-in-tau source says so: the others are as they were.
     linear = getattr(request, "edge_temperature", None) is not None
+    marks = {"source": "linear_in_tau"} if linear else {}
+    # Likewise the surface of compute_radiance.
+    if getattr(request, "reflection_lengths", None) is not None:
+        marks["surface"] = "reflecting"
+    if getattr(request, "emissivity_knots", None) is not None:
+        marks["emissivity"] = "spectral"
     xarray = _optional_xarray()
     if xarray is None:
         out = {name: value for name, (value, _) in coords.items()}
         out.update({q: v for q, (_, v, _) in variables.items()})
-        if linear:
-            out["source"] = "linear_in_tau"
+        out.update(marks)
         return out
     DataArray, Dataset = xarray.DataArray, xarray.Dataset
     return Dataset(
@@ -607,4 +678,4 @@ def _path_variables(spec, variables, request):
                    for q, (dims, v, units) in variables.items()},
         coords={name: DataArray(value, dims=(axis,), attrs=attrs)
                 for name, (value, attrs) in coords.items()},
-        **({"attrs": {"source": "linear_in_tau"}} if linear else {}))
+        **({"attrs": marks} if marks else {}))

@@ -27,10 +27,11 @@ import os
 import numpy as np
 
 from . import absorption, errors, paths
-from .paths import (CP_DRY, FLUX_QUANTITIES, FLUX_SURFACES, JACOBIAN_LEVEL_QUANTITIES,  # noqa: F401
-                    JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
+from .paths import (CP_DRY, DOWNWELLING, FLUX_QUANTITIES, FLUX_SURFACES,  # noqa: F401
+                    JACOBIAN_LEVEL_QUANTITIES, JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
                     PATH_CUMULATIVE, PATH_QUANTITIES, PLANCK_C1, PLANCK_C2, R_DRY,
-                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOURCES, band_columns, flux_angles,
+                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOURCES,
+                    SURFACE_RADIANCE_QUANTITIES, band_columns, flux_angles,
                     heating_rate, _MAX_RUN_LEVELS, _PATH_UNITS, _Pass, _Product, _cut_runs,
                     _path_layout, _run_edges, _sweep_pass)
 from .plugins import continua, cross_sections, molecular_lines
@@ -315,7 +316,8 @@ class Spectroscopy(object):
     def compute_radiance(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
                          direction="toward_last", quantities=("radiance",), band_edges=None,
                          cumulative=False, remove_pedestal=None, range_policy="reference",
-                         instrument=None, source="isothermal", interface_temperature=None):
+                         instrument=None, source="isothermal", interface_temperature=None,
+                         emissivity_wavenumber=None, reflection_path_length=None):
         """Thermal emission along the paths of the atmosphere: the radiance that leaves each
         path, formed on the GPU from the "total" absorption block like compute_path's optical
         depth.  Every level is an isothermal layer at its own temperature, or with
@@ -347,13 +349,32 @@ class Spectroscopy(object):
         For an atmosphere whose paths start at the surface, "toward_last" with the surface as
         the boundary is the upwelling radiance at the top, "toward_first" the downwelling
         radiance at the surface.
+        The boundary as a surface.  emissivity_wavenumber gives it a spectral emissivity: with
+        knots k_0 < ... < k_{M-1} and the values e_0 .. e_{M-1} of a path, numpy.interp's
+            for k_j <= nu < k_{j+1}:  E = e_j + (nu - k_j)*((e_{j+1} - e_j)/(k_{j+1} - k_j)),
+            E = e_0 for nu <= k_0,  E = e_{M-1} for nu >= k_{M-1}
+        (constant outside the knots, linear inside; each operation rounded as written, so a flat
+        table e_j = c gives E = c exactly).  reflection_path_length makes it reflect: a down
+        pass first sweeps the radiance against `direction`, from the far end of every path
+        toward the boundary, starting from 0, with reflection_path_length as its lengths and the
+        call's source model (with "linear_in_tau" the same interface temperatures, entered from
+        the other side); what it leaves at the boundary is D.  The up pass is the sweep above,
+        except that it starts from
+            I = E*B(nu, T_boundary) + (1. - E)*D,
+        E the spectral value or the scalar eps.  reflection_path_length = path_length is
+        specular reflection in a plane-parallel atmosphere; 1.66 times the layer thickness is
+        the diffusivity approximation of a Lambertian surface.  When the absorption of every
+        level fits device_output_limit it is computed once and both passes read it; otherwise
+        the up pass computes its runs again, save the one the down pass ends on.
 
         Args:
             path_length: [m], shaped like the atmosphere's temperature, finite and >= 0.
             boundary_temperature: None (no source behind the paths), a scalar or one per path
                          (shaped like the atmosphere without its last dimension) [K], finite and
                          > 0: the source the radiation starts from.
-            boundary_emissivity: a scalar or one per path, in [0, 1].
+            boundary_emissivity: a scalar or one per path, in [0, 1]; with emissivity_wavenumber
+                         [..., M] (the atmosphere's shape without its last axis, then M) or [M]
+                         for every path.
             direction: "toward_last" (levels 0 .. L-1: the radiation leaves after level L-1) or
                        "toward_first" (levels L-1 .. 0).
             quantities: any of "radiance", "brightness_temperature".
@@ -369,18 +390,31 @@ class Spectroscopy(object):
             interface_temperature: [K], the atmosphere's shape with L + 1 in place of L on the
                         last axis, finite and > 0: interface i lies between levels i-1 and i.
                         Needed with "linear_in_tau", refused without it.
+            emissivity_wavenumber: None, or [M] knots [cm-1], finite and strictly ascending,
+                        2 <= M <= 1024.
+            reflection_path_length: None, or [m], shaped like the atmosphere's temperature,
+                        finite and >= 0: the lengths of the down pass.  Needs
+                        boundary_temperature.  With it "boundary_downwelling_radiance" (D per
+                        path, reduced by band_edges / instrument like the radiance; not with
+                        cumulative=True) may be among the quantities.
 
         Returns:
             Like compute_path: an xarray Dataset when xarray is installed, else a dict --
             "radiance" ("W m-2 sr-1 (cm-1)-1") / "brightness_temperature" ("K") with the
             atmosphere's dims (without the last unless cumulative) and "wavenumber", "band" or
             "channel".  With "linear_in_tau" the result carries source = "linear_in_tau" (a
-            Dataset attribute, a key of the dict).
+            Dataset attribute, a key of the dict); likewise surface = "reflecting" with
+            reflection_path_length and emissivity = "spectral" with emissivity_wavenumber.
         """
-        request = self._radiance_request(path_length, boundary_temperature,
-                                          boundary_emissivity, direction, quantities, band_edges,
-                                          cumulative, range_policy, instrument, source=source,
-                                          interface_temperature=interface_temperature)
+        surface = emissivity_wavenumber is not None or reflection_path_length is not None
+        request = self._radiance_request(
+            path_length, boundary_temperature, boundary_emissivity, direction, quantities,
+            band_edges, cumulative, range_policy, instrument, names=SURFACE_RADIANCE_QUANTITIES,
+            source=source, interface_temperature=interface_temperature,
+            emissivity_wavenumber=emissivity_wavenumber,
+            reflection_path_length=reflection_path_length)
+        if surface:
+            return self._surface_radiance(request, remove_pedestal, range_policy)
 
         def sweeper(call, run):
             grid = call.grid()
@@ -406,6 +440,71 @@ class Spectroscopy(object):
             products = [_Product("radiance", "radiance", request.cumulative)]
         step = _sweep_pass(quantities, request.cumulative, request.from_last)
         values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                   products=products)
+        if request.instrument is not None and "brightness_temperature" in request.quantities:
+            from .instrument import brightness_temperature
+            values["brightness_temperature"] = brightness_temperature(
+                values["radiance"], request.instrument.centers)
+        return self._create_path_dataset(values, request)
+
+    def _surface_radiance(self, request, remove_pedestal, range_policy):
+        """compute_radiance behind a surface with a spectral emissivity and/or one that reflects:
+        the down pass (D into the reflection rows), the emissivity rows, then the up pass."""
+        reflecting = request.reflection_lengths is not None
+        spectral = request.emissivity_knots is not None
+        wanted = DOWNWELLING in request.quantities
+        banded = request.starts is not None
+        up_quantities = tuple(q for q in request.quantities if q != DOWNWELLING)
+        if request.instrument is not None and up_quantities:
+            up_quantities = ("radiance",)
+        down = _Pass(not request.from_last, (), (DOWNWELLING,) if wanted else ())
+        up = _sweep_pass(up_quantities, request.cumulative, request.from_last)
+        passes = ([down] if reflecting else []) + ([up] if up_quantities else [])
+
+        def sweeper(call, run):
+            grid = call.grid()
+            carry = call.take(call.paths)
+            # D on the grid: the returned rows themselves where they are on the grid; else a
+            # block of its own, which with bands is the down pass's carry (D stays in it).
+            reflection = call.take(call.paths) if reflecting and (banded or not wanted) else None
+            emissivity = call.take(call.paths) if spectral else None
+            filled = []
+
+            def sweep(index, beta, a, b, outputs):
+                rows = None
+                if reflecting:
+                    rows = reflection if reflection is not None else outputs[DOWNWELLING]
+                if passes[index] is down:
+                    means = banded and wanted
+                    call.engine.path_radiance(
+                        beta, call.columns, grid, call.paths, call.per_path, a,
+                        request.reflection_lengths[a:b], call.temperature[a:b],
+                        rows if means else carry,
+                        radiance=outputs[DOWNWELLING] if means else rows,
+                        band_start=request.starts if means else None, cumulative=False,
+                        from_last=down.from_last, asynchronous=True, **_run_edges(request, a, b))
+                    return
+                if spectral and not filled:
+                    call.engine.surface_emissivity(grid, emissivity, request.emissivity_knots,
+                                                   request.boundary_emissivity,
+                                                   asynchronous=True)
+                    filled.append(True)
+                call.engine.path_radiance(
+                    beta, call.columns, grid, call.paths, call.per_path, a, request.lengths[a:b],
+                    call.temperature[a:b], carry,
+                    boundary_temperature=request.boundary_temperature,
+                    boundary_emissivity=None if spectral else request.boundary_emissivity,
+                    radiance=outputs.get("radiance"),
+                    brightness_temperature=outputs.get("brightness_temperature"),
+                    band_start=request.starts, cumulative=request.cumulative,
+                    from_last=request.from_last, asynchronous=True,
+                    emissivity_rows=emissivity, reflection=rows, **_run_edges(request, a, b))
+            return sweep
+        products = None
+        if request.instrument is not None:
+            products = [_Product(q, q, request.cumulative) for q in up_quantities] + \
+                ([_Product(DOWNWELLING, DOWNWELLING, False)] if wanted else [])
+        values = self._sweep_runs(request, passes, remove_pedestal, range_policy, sweeper,
                                    products=products)
         if request.instrument is not None and "brightness_temperature" in request.quantities:
             from .instrument import brightness_temperature
