@@ -768,6 +768,83 @@ const char *lbl_version(void);
  * no line contributed to.  Exposed for tests. */
 int lbl_wing_batches(const int32_t *bounds);
 
+/* Sunlight without scattering (Spectroscopy.compute_solar): the direct beam at every interface
+ * of the paths and the sunlight a Lambertian surface reflects to a viewer, both pure absorption
+ * along slant paths through the block of absorption coefficients in HBM.
+ *
+ * lbl_solar_spectrum fills row[j] = S(nu_j) [W m-2 (cm-1)-1] for the first `columns` points nu_j
+ * of `grid` (a handle of lbl_grid_load, ascending or not):
+ *   n_knots == 0: the blackbody  S = scale*B(nu, temperature), B as in lbl_path_radiance (0 for
+ *   nu <= 0); for the Sun scale = LBL_SOLAR_SOLID_ANGLE times the distance factor and temperature =
+ *   LBL_SOLAR_TEMPERATURE;
+ *   knot_wavenumber == NULL and n_knots == columns: S = scale*knot_irradiance[j], the values on
+ *   the grid as they are (host, finite and >= 0);
+ *   otherwise a table: knot_wavenumber (host, k_0 < ... < k_{M-1} [cm-1], finite, 2 <= M <= 2^22)
+ *   and knot_irradiance (host, e_0 .. e_{M-1}, finite and >= 0), interpolated exactly as
+ *   lbl_surface_emissivity interpolates:
+ *   for k_j <= nu < k_{j+1}:  E = e_j + (nu - k_j)*((e_{j+1} - e_j)/(k_{j+1} - k_j)),
+ *   E = e_0 for nu <= k_0,  E = e_{M-1} for nu >= k_{M-1},  S = scale*E;
+ *   scale finite and > 0 (1.: the table's own bits); row (device, >= columns values).
+ *   flags: LBL_ASYNC or 0.
+ * LBL_BAD_ARGUMENT (message in lbl_last_error) for an unknown grid, columns outside the grid, a
+ * scale or temperature that is not finite and > 0, knots that are not finite and strictly
+ * ascending, irradiances that are negative or not finite, or n_knots outside what its mode allows;
+ * nothing is launched and the engine stays usable.
+ *
+ * lbl_path_solar sweeps the levels of a run from space to the surface.  beta (read only),
+ * row_stride, columns, n_paths, levels_per_path, level_begin, level_count, n_bands, band_start and
+ * the flags LBL_PATH_FROM_LAST, LBL_PATH_CONTINUE and LBL_ASYNC as for lbl_path_flux: the Sun
+ * shines in from the end of each path the sweep starts at (its last level with
+ * LBL_PATH_FROM_LAST, else its first), and the surface lies behind the other end.
+ *   solar_length (host, [level_count], finite and >= 0): a_l, the solar slant length of level
+ *   level_begin + l [m];
+ *   view_length (host, [level_count], finite and >= 0, or NULL: no viewer): v_l, the length of the
+ *   path from the surface to the viewer in that level [m];
+ *   solar_zenith_cosine (host, [n_paths]): mu0 of each path, in (0, 1];
+ *   solar_row (device, >= columns values): S, e.g. lbl_solar_spectrum's row;
+ *   albedo_rows (device, [n_paths][row_stride], e.g. lbl_surface_emissivity's rows) or albedo
+ *   (host, [n_paths], in [0, 1]): the Lambertian albedo A; exactly one of them with view_length,
+ *   neither without;
+ *   carry (device, [n_paths][2][row_stride]): tau and tv of each path, left there by every call
+ *   and read under LBL_PATH_CONTINUE.
+ * Per path and column, each product and sum rounded as written (no fused multiply-add):
+ *   F0 = mu0*S;  tau = 0, tv = 0;  F at the interface that faces space = F0
+ *   for each level in order from space to the surface:
+ *     tau = tau + a_l*beta_l;  tv = tv + v_l*beta_l
+ *     F at the interface below the level = F0*exp(-tau)
+ *   reflected radiance = ((A*F0)/pi)*exp(-(tau + tv)),  pi = 3.141592653589793, tau and tv at the
+ *   surface.
+ * Both optical depths are added in the Sun's order, space to surface.  Outputs (device, NULL: not
+ * wanted; at least one is), all on the grid:
+ *   interface_rows ([level_count][row_stride], not beta): F at the interface below each level;
+ *   space_rows ([n_paths][row_stride]): F0, written for the paths the run starts;
+ *   surface_rows ([n_paths][row_stride]): F at the surface, written for the paths the run finishes
+ *   (the same bits as the last interface row of the path);
+ *   reflected_rows ([n_paths][row_stride]): the reflected radiance [W m-2 sr-1 (cm-1)-1] of the paths
+ *   the run finishes; given if and only if view_length is.
+ * With n_bands > 0, interface_mean ([level_count][n_bands]), space_mean, surface_mean and
+ * reflected_mean ([n_paths][n_bands]) receive lbl_path_compute's ordered band means of the rows
+ * of the same name, which must be given too (NULL: not wanted); NaN for a band without points.
+ * LBL_BAD_ARGUMENT for bad shapes, a run whose LBL_PATH_CONTINUE does not match, lengths that are
+ * negative or not finite, a cosine outside (0, 1], an albedo outside [0, 1], a view without an
+ * albedo or an albedo without a view, reflected_rows without a view, interface_rows == beta, no
+ * output at all, or a band mean without its rows or without bands; nothing is launched and the
+ * engine stays usable. */
+#define LBL_SOLAR_TEMPERATURE  5772.                    /* effective temperature of the Sun [K]   */
+#define LBL_SOLAR_SOLID_ANGLE  6.794273971369406e-05    /* pi (6.957e8/1.495978707e11)^2 [sr]     */
+int lbl_solar_spectrum(lbl_engine *engine, int32_t grid, int64_t columns, int32_t n_knots,
+                       const double *knot_wavenumber, const double *knot_irradiance,
+                       double temperature, double scale, double *row, int32_t flags);
+int lbl_path_solar(lbl_engine *engine, double *beta, int64_t row_stride, int64_t columns,
+                   int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                   int32_t level_count, const double *solar_length, const double *view_length,
+                   const double *solar_zenith_cosine, const double *solar_row,
+                   const double *albedo_rows, const double *albedo, int32_t n_bands,
+                   const int64_t *band_start, double *carry, double *interface_rows,
+                   double *space_rows, double *surface_rows, double *reflected_rows,
+                   double *interface_mean, double *space_mean, double *surface_mean,
+                   double *reflected_mean, int32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

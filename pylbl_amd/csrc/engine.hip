@@ -39,6 +39,7 @@
 #include "path.h"
 #include "pedestal.h"
 #include "radiance.h"
+#include "solar.h"
 #include "surface.h"
 #include "tile_schedule.h"
 
@@ -495,6 +496,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "radiance_entry.inc"
 #include "jacobian_entry.inc"
 #include "flux_entry.inc"
+#include "solar_entry.inc"
 #include "instrument_entry.inc"
 #include "xsec_entry.inc"
 #include "sqlite_entry.inc"

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
     "lbl_path_jacobian", "lbl_path_radiance_source", "lbl_path_flux_source",
     "lbl_surface_emissivity", "lbl_path_radiance_surface",
+    "lbl_solar_spectrum", "lbl_path_solar",
     "lbl_instrument_create", "lbl_instrument_free", "lbl_instrument_apply",
 )
 
@@ -215,6 +216,10 @@ def library():
         [c_void_p, c_void_p]
     lib.lbl_surface_emissivity.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                            c_void_p, c_void_p, c_void_p, c_int64, c_int32]
+    lib.lbl_solar_spectrum.argtypes = [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                       c_double, c_double, c_void_p, c_int32]
+    lib.lbl_path_solar.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                   c_int32] + [c_void_p]*6 + [c_int32] + [c_void_p]*10 + [c_int32]
     lib.lbl_instrument_create.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                           c_void_p, c_int32, c_void_p, c_void_p, c_int32, i32p]
     lib.lbl_instrument_free.argtypes = [c_void_p, c_int32]
@@ -964,6 +969,69 @@ class Engine(object):
             *map(_address, surface), n_bands, _address(starts), carry.pointer,
             reflection.pointer, level_flux.pointer, _address(flux), _address(surface_flux),
             flags))
+
+    def solar_spectrum(self, grid, row, columns, irradiance=None, wavenumber=None,
+                       temperature=0., scale=1., asynchronous=False):
+        """Fills the first `columns` values of the DeviceSpectra `row` (its first row) with the
+        solar irradiance S on the grid (handle of load_grid) -- lbl_solar_spectrum: with
+        irradiance None scale*B(nu, temperature); with irradiance [columns] and wavenumber None
+        scale*irradiance; with wavenumber [M] (strictly ascending, 2 <= M <= 2**22) and
+        irradiance [M] scale times the table interpolated as surface_emissivity does."""
+        knots = None if wavenumber is None else _f64(wavenumber)
+        values = None if irradiance is None else _f64(irradiance)
+        if values is None and knots is not None:
+            raise ValueError("wavenumber without irradiance.")
+        if values is not None and (values.ndim != 1 or
+                                   (knots is not None and knots.shape != values.shape)):
+            raise ValueError("irradiance must be [columns], or [M] with wavenumber [M].")
+        if not 0 < int(columns) <= int(row.shape[1]):
+            raise ValueError(f"{columns} columns into a row of {row.shape[1]}.")
+        self._check(self.lib.lbl_solar_spectrum(
+            self.handle, int(grid), int(columns), 0 if values is None else values.size,
+            _address(knots), _address(values), float(temperature), float(scale), row.pointer,
+            ASYNC if asynchronous else 0))
+
+    def path_solar(self, beta, columns, n_paths, levels_per_path, level_begin, solar_lengths,
+                   solar_zenith_cosine, solar_row, carry, view_lengths=None, albedo=None,
+                   albedo_rows=None, interface_rows=None, space_rows=None, surface_rows=None,
+                   reflected_rows=None, interface_mean=None, space_mean=None, surface_mean=None,
+                   reflected_mean=None, band_start=None, from_last=False, asynchronous=False):
+        """The direct solar beam and the reflected sunlight along paths through the DeviceSpectra
+        `beta` -- lbl_path_solar.  Rows, columns, band_start, from_last and asynchronous as for
+        path_compute: the sweep runs from space to the surface.  solar_lengths / view_lengths [m]
+        one per row (view_lengths None: no viewer); solar_zenith_cosine one per path; solar_row:
+        DeviceSpectra whose first row holds S (solar_spectrum's); carry [2*n_paths, row length]:
+        tau and tv of each path; albedo one per path or albedo_rows [n_paths, row length] (with
+        view_lengths, one of them).  Outputs (DeviceSpectra, None: not wanted): interface_rows
+        [>= rows, row length], space_rows, surface_rows and reflected_rows [n_paths, row length];
+        with band_start their band means interface_mean [>= rows, bands], space_mean,
+        surface_mean and reflected_mean [n_paths, bands]."""
+        rows, stride, solar_lengths = _per_row(beta, "one solar length per row of beta.",
+                                               solar_lengths)
+        if view_lengths is not None:
+            _, _, view_lengths = _per_row(beta, "one view length per row of beta.", view_lengths)
+        if tuple(carry.shape) != (2*int(n_paths), stride):
+            raise ValueError("carry must be [2*n_paths, row length of beta].")
+        if solar_row.shape[1] < int(columns):
+            raise ValueError(f"solar_row has {solar_row.shape[1]} values, need {columns}.")
+        mu0, albedo = _per_path(n_paths, "one cosine and one albedo per path.",
+                                solar_zenith_cosine, albedo)
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path,
+                                           from_last, asynchronous)
+        per_path = (albedo_rows, space_rows, surface_rows, reflected_rows)
+        if any(x is not None and tuple(x.shape) != (int(n_paths), stride) for x in per_path):
+            raise ValueError("albedo_rows, space_rows, surface_rows and reflected_rows must be "
+                             "[n_paths, row length of beta].")
+        _check_outputs((interface_rows,), rows, stride)
+        _check_outputs((interface_mean,), rows, n_bands)
+        _check_outputs((space_mean, surface_mean, reflected_mean), int(n_paths), n_bands)
+        self._check(self.lib.lbl_path_solar(
+            self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
+            int(level_begin), rows, solar_lengths.ctypes.data, _address(view_lengths),
+            _address(mu0), solar_row.pointer, _address(albedo_rows), _address(albedo), n_bands,
+            _address(starts), carry.pointer, _address(interface_rows), _address(space_rows),
+            _address(surface_rows), _address(reflected_rows), _address(interface_mean),
+            _address(space_mean), _address(surface_mean), _address(reflected_mean), flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):

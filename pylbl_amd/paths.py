@@ -1,6 +1,6 @@
-"""The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux and
-compute_jacobian -- on the host: their quantities and units, the checks of their arguments (one
-request per call, made before anything touches the GPU), the run loop that sweeps the "total"
+"""The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux,
+compute_jacobian and compute_solar -- on the host: their quantities and units, the checks of
+their arguments (one request per call, made before anything touches the GPU), the run loop that sweeps the "total"
 absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
 cuts (_level_bytes) and the assembly of the results.  The sweeps themselves are the kernels of
 csrc/path.h behind Engine.path_*; the "total" block is queued by Spectroscopy.total_into
@@ -51,6 +51,19 @@ FLUX_QUANTITIES = ("upward_flux", "downward_flux", "heating_rate")
 FLUX_SURFACES = ("first", "last")
 MAX_FLUX_ANGLES = 8
 
+# compute_solar: the Sun as a blackbody of SOLAR_TEMPERATURE that fills SOLAR_SOLID_ANGLE =
+# pi*(6.957e8/1.495978707e11)**2 sr at 1 au (the IAU 2015 nominal solar radius and the au),
+# evaluated once in fp64: the same literals as LBL_SOLAR_TEMPERATURE and LBL_SOLAR_SOLID_ANGLE in
+# include/lbl_amd.h.
+SOLAR_TEMPERATURE = 5772.               # [K]
+SOLAR_SOLID_ANGLE = 6.794273971369406e-05   # [sr]
+MAX_SOLAR_KNOTS = 1 << 22               # kSolarMaxKnots of csrc/solar.h
+SOLAR_QUANTITIES = ("direct_irradiance", "surface_irradiance", "reflected_radiance",
+                    "heating_rate")
+SOLAR_PATH_QUANTITIES = ("surface_irradiance", "reflected_radiance")
+# What the sweep writes for the paths it starts beside the interface rows: F0 at the space end.
+_SPACE = "space_irradiance"
+
 _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
                "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K",
                DOWNWELLING: "W m-2 sr-1 (cm-1)-1",
@@ -63,6 +76,12 @@ _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
 _FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
                "downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
                "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
+
+# compute_solar: on the grid (and per channel), per band.
+_SOLAR_UNITS = {"direct_irradiance": ("W m-2 (cm-1)-1", "W m-2"),
+                "surface_irradiance": ("W m-2 (cm-1)-1", "W m-2"),
+                "reflected_radiance": ("W m-2 sr-1 (cm-1)-1", "W m-2 sr-1 (cm-1)-1"),
+                "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
 
 # What every product checked and derived from its arguments: flat lengths, the atmosphere's shape,
 # the quantities asked for, band edges and their column starts (or None), the Instrument (or
@@ -83,6 +102,14 @@ _RadianceRequest = namedtuple("_RadianceRequest", _COMMON + (
 _FluxRequest = namedtuple("_FluxRequest", _COMMON + (
     "surface", "mu", "weight", "surface_temperature", "surface_emissivity", "edge_temperature"),
     defaults=(None,))
+
+# compute_solar's: mu0 per path, the flat solar and view lengths (view_lengths None: no viewer),
+# the albedo per path -- [paths], or [paths, M] at albedo_knots [M] -- and the Sun: solar_values
+# None (a blackbody of SOLAR_TEMPERATURE), [V] on the grid, or [M] at solar_knots [M]; scale: what
+# multiplies it (the distance factor, for the blackbody times SOLAR_SOLID_ANGLE).
+_SolarRequest = namedtuple("_SolarRequest", _COMMON + (
+    "surface", "mu0", "solar_lengths", "view_lengths", "albedo", "albedo_knots", "solar_knots",
+    "solar_values", "scale"))
 
 # One pass of _sweep_runs over the levels: its order, and what it writes per level and per path.
 _Pass = namedtuple("_Pass", ["from_last", "level_quantities", "path_quantities"])
@@ -233,25 +260,29 @@ def _emitter(temperature, emissivity, what, shape, optional=False):
     return temperatures, emissivities
 
 
-def _spectral_emissivity(emissivity_wavenumber, boundary_emissivity, shape):
+def _spectral_emissivity(emissivity_wavenumber, boundary_emissivity, shape,
+                         names=("emissivity_wavenumber", "boundary_emissivity",
+                                "boundary emissivities")):
     """(knots [M], emissivities [paths, M]) of compute_radiance's emissivity_wavenumber: M knots
     [cm-1], finite and strictly ascending, 2 <= M <= 1024; boundary_emissivity [..., M] (the
-    atmosphere's shape without its last axis, then M) or [M] for every path, in [0, 1]."""
+    atmosphere's shape without its last axis, then M) or [M] for every path, in [0, 1].
+    names: what the messages call the two arguments and the values (compute_solar's albedo)."""
+    knot_name, value_name, what = names
     knots = np.asarray(emissivity_wavenumber, dtype=np.float64)
     if knots.ndim != 1 or not 2 <= knots.size <= MAX_EMISSIVITY_KNOTS:
-        raise ValueError(f"emissivity_wavenumber must be a 1-d array of 2..{MAX_EMISSIVITY_KNOTS} "
+        raise ValueError(f"{knot_name} must be a 1-d array of 2..{MAX_EMISSIVITY_KNOTS} "
                          f"knots, not of shape {knots.shape}.")
     if not np.all(np.isfinite(knots)) or not np.all(np.diff(knots) > 0.):
-        raise ValueError("emissivity_wavenumber must be finite and strictly ascending.")
+        raise ValueError(f"{knot_name} must be finite and strictly ascending.")
     _, paths = _path_layout(shape)
     per_path_shape = tuple(shape[:-1]) + (knots.size,)
     values = np.asarray(boundary_emissivity, dtype=np.float64)
     if values.shape not in ((knots.size,), per_path_shape):
-        raise ValueError(f"boundary_emissivity has shape {values.shape}: with "
-                         f"emissivity_wavenumber give [{knots.size}] or one table per path, "
+        raise ValueError(f"{value_name} has shape {values.shape}: with "
+                         f"{knot_name} give [{knots.size}] or one table per path, "
                          f"shaped {per_path_shape}.")
     if not np.all((values >= 0.) & (values <= 1.)):
-        raise ValueError("boundary emissivities must lie in [0, 1].")
+        raise ValueError(f"{what} must lie in [0, 1].")
     values = np.broadcast_to(values, per_path_shape).reshape(paths, knots.size)
     return np.ascontiguousarray(knots), np.ascontiguousarray(values)
 
@@ -407,6 +438,96 @@ def _flux_request(spec, layer_thickness, surface_temperature, surface_emissivity
                         starts=starts, instrument=None, cumulative=False, surface=surface, mu=mu,
                         weight=weight, surface_temperature=ts, surface_emissivity=es,
                         edge_temperature=edge_temperature)
+
+
+def _solar_spectrum(spec, solar_irradiance, solar_wavenumber, distance_factor):
+    """(knots or None, values or None, scale) of compute_solar's Sun, checked."""
+    factor = np.asarray(distance_factor, dtype=np.float64)
+    if factor.shape != () or not np.isfinite(factor) or not factor > 0.:
+        raise ValueError("distance_factor must be one finite number > 0.")
+    factor = float(factor)
+    if solar_irradiance is None:
+        if solar_wavenumber is not None:
+            raise ValueError("solar_wavenumber needs solar_irradiance at its knots.")
+        return None, None, SOLAR_SOLID_ANGLE*factor
+    values = np.asarray(solar_irradiance, dtype=np.float64)
+    if solar_wavenumber is None:
+        if values.shape != (spec.grid.size,):
+            raise ValueError(f"solar_irradiance has shape {values.shape}: without "
+                             f"solar_wavenumber give one value per grid point, "
+                             f"[{spec.grid.size}].")
+        knots = None
+    else:
+        knots = np.asarray(solar_wavenumber, dtype=np.float64)
+        if knots.ndim != 1 or not 2 <= knots.size <= MAX_SOLAR_KNOTS:
+            raise ValueError(f"solar_wavenumber must be a 1-d array of 2..{MAX_SOLAR_KNOTS} "
+                             f"knots, not of shape {knots.shape}.")
+        if not np.all(np.isfinite(knots)) or not np.all(np.diff(knots) > 0.):
+            raise ValueError("solar_wavenumber must be finite and strictly ascending.")
+        if values.shape != knots.shape:
+            raise ValueError(f"solar_irradiance has shape {values.shape}: with solar_wavenumber "
+                             f"give one value per knot, [{knots.size}].")
+        knots = np.ascontiguousarray(knots)
+    if not np.all(np.isfinite(values)) or np.any(values < 0.):
+        raise ValueError("solar irradiances must be finite and >= 0.")
+    return knots, np.ascontiguousarray(values), factor
+
+
+def _solar_request(spec, layer_thickness, solar_zenith_cosine, solar_irradiance,
+                   solar_wavenumber, distance_factor, solar_path_length, surface, surface_albedo,
+                   albedo_wavenumber, view_path_length, quantities, band_edges, instrument,
+                   range_policy):
+    """Checks every argument of compute_solar."""
+    lengths, shape = _path_geometry(spec, layer_thickness, "compute_solar", "layer_thickness",
+                                    "layer thicknesses")
+    per_path, _ = _path_layout(shape)
+    if not (isinstance(surface, str) and surface in FLUX_SURFACES):
+        raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
+    mu0 = _per_path(solar_zenith_cosine, "solar_zenith_cosine", shape)
+    if not np.all((mu0 > 0.) & (mu0 <= 1.)):
+        raise ValueError("solar_zenith_cosine must lie in (0, 1].")
+    if solar_path_length is None:
+        solar_lengths = np.ascontiguousarray(lengths/np.repeat(mu0, per_path))
+    else:
+        solar_lengths, _ = _path_geometry(spec, solar_path_length, "compute_solar",
+                                          "solar_path_length", "solar path lengths")
+    solar_knots, solar_values, scale = _solar_spectrum(spec, solar_irradiance, solar_wavenumber,
+                                                       distance_factor)
+    quantities = _selection(quantities, SOLAR_QUANTITIES)
+    reflected = "reflected_radiance" in quantities
+    if reflected and (view_path_length is None or surface_albedo is None):
+        raise ValueError('"reflected_radiance" needs view_path_length and surface_albedo.')
+    if not reflected and not (view_path_length is None and surface_albedo is None and
+                              albedo_wavenumber is None):
+        raise ValueError('view_path_length, surface_albedo and albedo_wavenumber are only used '
+                         'by "reflected_radiance", which is not among the quantities.')
+    view_lengths = albedo = albedo_knots = None
+    if reflected:
+        view_lengths, _ = _path_geometry(spec, view_path_length, "compute_solar",
+                                         "view_path_length", "view path lengths")
+        if albedo_wavenumber is None:
+            albedo = _per_path(surface_albedo, "surface_albedo", shape)
+            if not np.all((albedo >= 0.) & (albedo <= 1.)):
+                raise ValueError("surface albedos must lie in [0, 1].")
+        else:
+            albedo_knots, albedo = _spectral_emissivity(
+                albedo_wavenumber, surface_albedo, shape,
+                ("albedo_wavenumber", "surface_albedo", "surface albedos"))
+    if "heating_rate" in quantities:
+        _check_level_temperatures(spec)
+        pressure = spec.atmosphere.pressure
+        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
+            raise ValueError("heating rates need pressures that are finite and > 0.")
+    _check_range_policy(range_policy)
+    edges, starts = _path_bands(spec, band_edges, instrument)
+    if instrument is not None and any(q not in SOLAR_PATH_QUANTITIES for q in quantities):
+        raise ValueError(f"instrument reduces the quantities per path, {SOLAR_PATH_QUANTITIES}, "
+                         f"not {quantities}.")
+    return _SolarRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                         starts=starts, instrument=instrument, cumulative=False, surface=surface,
+                         mu0=mu0, solar_lengths=solar_lengths, view_lengths=view_lengths,
+                         albedo=albedo, albedo_knots=albedo_knots, solar_knots=solar_knots,
+                         solar_values=solar_values, scale=scale)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -610,6 +731,54 @@ def _flux_interfaces(spec, values, request):
             request.lengths.reshape(paths, per_path),
             request.surface).reshape(shape + [width])
     return out
+
+
+def _solar_interfaces(spec, values, request):
+    """{quantity: array} of compute_solar from the sweep's rows: the direct irradiance below each
+    level and at the space end of each path, the surface rows and the reflected rows."""
+    shape = list(request.shape)
+    per_path, paths = _path_layout(request.shape)
+    widths = 1.
+    if request.starts is not None:
+        _, _, n_per_v = grid_arguments(spec.grid)
+        widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
+    out = {}
+    if "direct_irradiance" in values:
+        width = values["direct_irradiance"].shape[-1]
+        below = np.asarray(values["direct_irradiance"]).reshape(paths, per_path, width)
+        space = np.asarray(values[_SPACE]).reshape(paths, 1, width)
+        # Sweeping toward level 0 the irradiance below level l is at interface l, toward level
+        # L-1 at interface l + 1.
+        direct = np.concatenate([below, space] if request.surface == "first" else [space, below],
+                                axis=1)*widths
+        if "direct_irradiance" in request.quantities:
+            out["direct_irradiance"] = direct.reshape(shape[:-1] + [per_path + 1, width])
+        if "heating_rate" in request.quantities:
+            out["heating_rate"] = heating_rate(
+                np.zeros_like(direct), direct, spec.atmosphere.pressure.reshape(paths, per_path),
+                spec.atmosphere.temperature.reshape(paths, per_path),
+                request.lengths.reshape(paths, per_path), request.surface).reshape(shape + [width])
+    if "surface_irradiance" in request.quantities:
+        scale = 1. if request.instrument is not None else widths
+        out["surface_irradiance"] = (np.asarray(values["surface_irradiance"])*scale).reshape(
+            shape[:-1] + [-1])
+    if "reflected_radiance" in request.quantities:
+        out["reflected_radiance"] = np.asarray(values["reflected_radiance"]).reshape(
+            shape[:-1] + [-1])
+    return out
+
+
+def _create_solar_dataset(spec, values, request):
+    """compute_solar's result, built like _create_flux_dataset's: the direct irradiance on the
+    "interface" dim in place of the atmosphere's last, heating rates on it, the others per path."""
+    dims = list(spec.atmosphere.dims)
+    axis = _spectral_axis(request)
+    variables = {}
+    for q in request.quantities:
+        here = {"direct_irradiance": dims[:-1] + ["interface", axis],
+                "heating_rate": dims + [axis]}.get(q, dims[:-1] + [axis])
+        variables[q] = (here, values[q], _SOLAR_UNITS[q][request.edges is not None])
+    return _path_variables(spec, variables, request)
 
 
 def _create_path_dataset(spec, values, request):

@@ -14,8 +14,8 @@ this image) -- without it the atmosphere is a plain (p, t, vmr) tuple and the re
 of numpy arrays with the same variable names.
 
 What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
-four path products compute_path, compute_radiance, compute_jacobian and compute_flux: their
-documentation and their sweeps.  The host side of compute_absorption (the gases present, the
+path products compute_path, compute_radiance, compute_jacobian, compute_flux and compute_solar:
+their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
 queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
 else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
 whose public names stay importable from here; their functions take the Spectroscopy first, and
@@ -30,7 +30,8 @@ from . import absorption, errors, paths
 from .paths import (CP_DRY, DOWNWELLING, FLUX_QUANTITIES, FLUX_SURFACES,  # noqa: F401
                     JACOBIAN_LEVEL_QUANTITIES, JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
                     PATH_CUMULATIVE, PATH_QUANTITIES, PLANCK_C1, PLANCK_C2, R_DRY,
-                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOURCES,
+                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOLAR_QUANTITIES,
+                    SOLAR_SOLID_ANGLE, SOLAR_TEMPERATURE, SOURCES,
                     SURFACE_RADIANCE_QUANTITIES, band_columns, flux_angles,
                     heating_rate, _MAX_RUN_LEVELS, _PATH_UNITS, _Pass, _Product, _cut_runs,
                     _path_layout, _run_edges, _sweep_pass)
@@ -696,12 +697,151 @@ class Spectroscopy(object):
                                    level_blocks=2)
         return self._create_flux_dataset(self._flux_interfaces(values, request), request)
 
+    def compute_solar(self, layer_thickness, solar_zenith_cosine, solar_irradiance=None,
+                      solar_wavenumber=None, distance_factor=1., solar_path_length=None,
+                      surface="first", surface_albedo=None, albedo_wavenumber=None,
+                      view_path_length=None, quantities=("direct_irradiance",), band_edges=None,
+                      instrument=None, remove_pedestal=None, range_policy="reference"):
+        """Sunlight in an atmosphere that does not scatter: the direct solar beam at every layer
+        interface, the heating by its absorption and the sunlight a Lambertian surface reflects
+        to a viewer, formed on the GPU in one sweep over the "total" absorption block.  Thermal
+        and solar radiation superpose without scattering: add compute_radiance's result where
+        both matter.
+
+        Paths, levels, `surface` and layer_thickness as in compute_flux: the Sun shines in from
+        the end that faces space, and interface i lies between levels i-1 and i.  With beta the
+        absorption coefficient [m-1] of compute_absorption("total", remove_pedestal,
+        range_policy), nu the grid [cm-1], a_l the solar slant length and v_l the view length of
+        level l, per path and grid point, each product and sum rounded as written:
+            S(nu) = d*S_table(nu) [W m-2 (cm-1)-1], d = distance_factor; without a table
+                  S = (SOLAR_SOLID_ANGLE*d)*B(nu, SOLAR_TEMPERATURE), B as in compute_radiance
+                  (0 for nu <= 0); a table with knots k_0 < ... < k_{M-1} and values e_j is
+                  interpolated like compute_radiance's emissivity,
+                  for k_j <= nu < k_{j+1}:  E = e_j + (nu - k_j)*((e_{j+1} - e_j)/(k_{j+1} - k_j)),
+                  E = e_0 for nu <= k_0,  E = e_{M-1} for nu >= k_{M-1};
+            F0 = mu0*S;  tau = 0, tv = 0;  F at the interface that faces space = F0;
+            for each level in order from space to the surface:
+                tau = tau + a_l*beta_l;  tv = tv + v_l*beta_l;
+                F at the interface below the level = F0*exp(-tau);
+            reflected radiance = ((A*F0)/pi)*exp(-(tau + tv)), pi = numpy.pi, tau and tv at
+                  the surface.
+        Both optical depths are added in the Sun's order, from space to the surface (also the
+        viewer's, whose light travels the other way): one read of beta serves both beams, and
+        this order is the definition.
+            band irradiance F_b = (band mean of F)*(n_b/n_per_v) as in compute_flux; band
+                  radiances are means, as in compute_radiance (NaN without points);
+            heating rate: paths.heating_rate of the returned irradiance as the downward flux and
+                  an upward flux of zero: the absorption of the direct beam alone.  The
+                  absorption of the reflected light is not included.
+
+        Args:
+            layer_thickness: [m], shaped like the atmosphere's temperature, finite and >= 0.
+            solar_zenith_cosine: mu0, a scalar or one per path, in (0, 1].
+            solar_irradiance: None (the blackbody above), [V] values on the grid as they are, or
+                         with solar_wavenumber [M]: S at 1 au and normal incidence
+                         [W m-2 (cm-1)-1], finite and >= 0.
+            solar_wavenumber: None, or [M] knots [cm-1], finite and strictly ascending,
+                         2 <= M <= 2**22.
+            distance_factor: d, finite and > 0: (1 au / distance)**2.
+            solar_path_length: None (layer_thickness/mu0, formed in fp64 on the host), or [m]
+                         shaped like the atmosphere's temperature, finite and >= 0: the slant
+                         lengths of the beam, e.g. spherical or refracted ones at low Sun.
+            surface: "first" (level 0 touches the surface) or "last".
+            surface_albedo: the Lambertian albedo A in [0, 1]: a scalar or one per path; with
+                         albedo_wavenumber [..., M] or [M], 2 <= M <= 1024.
+            albedo_wavenumber: None, or [M] knots [cm-1] as compute_radiance's
+                         emissivity_wavenumber.
+            view_path_length: [m], shaped like the atmosphere's temperature, finite and >= 0:
+                         the lengths of the path from the surface to the viewer.
+                         "reflected_radiance" needs it and surface_albedo; without that quantity
+                         both are refused.
+            quantities: any of "direct_irradiance" (at every interface), "surface_irradiance"
+                         (per path: the bits of the surface interface), "reflected_radiance" (per
+                         path) and "heating_rate" (per level).
+            band_edges: as in compute_flux.
+            instrument: None, or an Instrument: channel values of the quantities per path
+                         ("surface_irradiance", "reflected_radiance") as compute_radiance's
+                         radiance.  Not with band_edges or the other quantities.
+
+        Returns:
+            Like compute_flux: an xarray Dataset when xarray is installed, else a dict --
+            "direct_irradiance" with the atmosphere's dims, the last replaced by "interface"
+            (L + 1), then "wavenumber" ("W m-2 (cm-1)-1") or "band" ("W m-2");
+            "surface_irradiance" (the same units) and "reflected_radiance"
+            ("W m-2 sr-1 (cm-1)-1") without the last dim; "heating_rate" with the level dim
+            ("K day-1 (cm-1)-1" / "K day-1").
+        """
+        request = self._solar_request(layer_thickness, solar_zenith_cosine, solar_irradiance,
+                                       solar_wavenumber, distance_factor, solar_path_length,
+                                       surface, surface_albedo, albedo_wavenumber,
+                                       view_path_length, quantities, band_edges, instrument,
+                                       range_policy)
+        bands = request.starts is not None
+        levels = "direct_irradiance" in request.quantities or "heating_rate" in request.quantities
+        # From space to the surface: "first" has its surface at level 0.
+        step = _Pass(request.surface == "first", ("direct_irradiance",) if levels else (),
+                     ((paths._SPACE,) if levels else ()) +
+                     tuple(q for q in request.quantities if q in paths.SOLAR_PATH_QUANTITIES))
+        rows = {"direct_irradiance": "interface", paths._SPACE: "space",
+                "surface_irradiance": "surface", "reflected_radiance": "reflected"}
+
+        def sweeper(call, run):
+            grid = call.grid()
+            carry = call.take(2*call.paths)
+            solar = call.take(1)
+            spectral = request.albedo_knots is not None
+            albedo_rows = call.take(call.paths) if spectral else None
+            # With bands the sweep's rows on the grid are blocks of this call, and the outputs
+            # their means; without, the outputs themselves.
+            fine = {q: call.take(run if q in step.level_quantities else call.paths)
+                    for q in step.level_quantities + step.path_quantities} if bands else {}
+            filled = []
+
+            def sweep(index, beta, a, b, outputs):
+                if not filled:
+                    call.engine.solar_spectrum(
+                        grid, solar, call.columns, irradiance=request.solar_values,
+                        wavenumber=request.solar_knots, temperature=SOLAR_TEMPERATURE,
+                        scale=request.scale, asynchronous=True)
+                    if spectral:
+                        call.engine.surface_emissivity(grid, albedo_rows, request.albedo_knots,
+                                                       request.albedo, asynchronous=True)
+                    filled.append(True)
+                blocks = {}
+                for q, name in rows.items():
+                    if q not in outputs:
+                        continue
+                    if bands:
+                        block = fine[q]
+                        if q in step.level_quantities and b - a != run:
+                            block = block.rows(b - a)
+                        blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[q]
+                    else:
+                        blocks[name + "_rows"] = outputs[q]
+                call.engine.path_solar(
+                    beta, call.columns, call.paths, call.per_path, a,
+                    request.solar_lengths[a:b], request.mu0, solar, carry,
+                    view_lengths=None if request.view_lengths is None
+                    else request.view_lengths[a:b],
+                    albedo=None if spectral else request.albedo, albedo_rows=albedo_rows,
+                    band_start=request.starts, from_last=step.from_last, asynchronous=True,
+                    **blocks)
+            return sweep
+        products = None if request.instrument is None else \
+            [_Product(q, q, False) for q in request.quantities]
+        # Two blocks per level, as compute_flux counts them: beta and the interface rows.
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                   level_blocks=2, products=products)
+        return self._create_solar_dataset(self._solar_interfaces(values, request), request)
+
     # The host side of the path products is paths.py and that of compute_absorption is
     # absorption.py: their functions take the Spectroscopy first.
     _compute_levels, total_into = absorption.compute_levels, absorption.total_into
     _path_request, _radiance_request = paths._path_request, paths._radiance_request
     _flux_request, _sweep_runs = paths._flux_request, paths._sweep_runs
     _flux_interfaces = paths._flux_interfaces
+    _solar_request, _solar_interfaces = paths._solar_request, paths._solar_interfaces
+    _create_solar_dataset = paths._create_solar_dataset
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
 
