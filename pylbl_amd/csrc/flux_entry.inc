@@ -2,40 +2,6 @@
 // block of absorption coefficients in HBM (kernel: flux.h; band means: path.h), and
 // lbl_path_flux, the same call without edge temperatures.  Included by engine.hip
 // after radiance_entry.inc; shares path_entry.inc's PathCall, PathTables and PathBands.
-namespace {
-
-template <bool kVector, int K>
-void launch_flux(const PathFlux & a, const dim3 & grid, hipStream_t stream)
-{
-    if (a.edge != nullptr)
-    {
-        hipLaunchKernelGGL((path_flux_kernel<kVector, K, true>), grid, dim3(kPathThreads), 0,
-                           stream, a);
-    }
-    else
-    {
-        hipLaunchKernelGGL((path_flux_kernel<kVector, K>), grid, dim3(kPathThreads), 0, stream, a);
-    }
-}
-
-template <bool kVector>
-void launch_flux(int angles, const PathFlux & a, const dim3 & grid, hipStream_t stream)
-{
-    switch (angles)
-    {
-    case 1: launch_flux<kVector, 1>(a, grid, stream); break;
-    case 2: launch_flux<kVector, 2>(a, grid, stream); break;
-    case 3: launch_flux<kVector, 3>(a, grid, stream); break;
-    case 4: launch_flux<kVector, 4>(a, grid, stream); break;
-    case 5: launch_flux<kVector, 5>(a, grid, stream); break;
-    case 6: launch_flux<kVector, 6>(a, grid, stream); break;
-    case 7: launch_flux<kVector, 7>(a, grid, stream); break;
-    default: launch_flux<kVector, 8>(a, grid, stream); break;
-    }
-}
-
-}  // namespace
-
 extern "C" {
 
 int lbl_path_flux_source(lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns,
@@ -78,13 +44,10 @@ int lbl_path_flux_source(lbl_engine * engine, double * beta, int64_t row_stride,
         {
             return call.bad("temperatures must be finite and > 0.");
         }
-        if (edge_temperature != nullptr)
+        if (const char * problem = check_edge_temperatures(edge_temperature, level_begin,
+                                                           level_count, levels_per_path))
         {
-            if (const char * problem = check_edge_temperatures(edge_temperature, level_begin,
-                                                               level_count, levels_per_path))
-            {
-                return call.bad(problem);
-            }
+            return call.bad(problem);
         }
         if (up)
         {
@@ -116,23 +79,16 @@ int lbl_path_flux_source(lbl_engine * engine, double * beta, int64_t row_stride,
         const size_t length_at = tables.add((size_t)level_count*n_angles, path_length);
         const size_t weight_at = tables.add(n_angles, weight);
         const size_t temperature_at = tables.add(level_count, temperature);
-        const size_t surface_at = tables.add(2*(size_t)run.paths);
-        double * surface = tables.words.data() + surface_at;
-        for (int i = 0; i < run.paths && up; ++i)
-        {
-            surface[i] = surface_temperature[run.first_path + i];
-            surface[run.paths + i] = surface_emissivity[run.first_path + i];
-        }
-        const size_t band_at = tables.add(bands, band_start);
+        const size_t surface_at = tables.add_pair(run, up ? surface_temperature : nullptr, 0.,
+                                                  up ? surface_emissivity : nullptr, 0.);
+        tables.add(bands, band_start);
         // After the tables every call has, so that theirs lie where they always lay.
         const bool linear = edge_temperature != nullptr;
         const size_t edge_at = linear ? tables.add(2*(size_t)level_count, edge_temperature) : 0;
         const double * d_tables = call.begin(tables);
 
         PathFlux a;
-        a.beta = beta;
-        a.stride = row_stride;
-        a.columns = columns;
+        call.fill(a, beta, carry);
         a.nu = call.grid->wavenumber.data;
         a.length = d_tables + length_at;
         a.weight = d_tables + weight_at;
@@ -140,49 +96,26 @@ int lbl_path_flux_source(lbl_engine * engine, double * beta, int64_t row_stride,
         a.surface_t = d_tables + surface_at;
         a.surface_e = a.surface_t + run.paths;
         a.edge = linear ? d_tables + edge_at : nullptr;
-        a.first = level_begin;
-        a.count = level_count;
-        a.row_base = level_begin;
-        a.levels_per_path = levels_per_path;
         a.table_path = run.first_path;
-        a.from_last = call.from_last() ? 1 : 0;
         a.up = up ? 1 : 0;
-        a.carry = carry;
         a.reflection = reflection;
         a.level_flux = level_flux;
         const bool vector = path_vector(row_stride, {beta, carry, a.nu, reflection, level_flux});
-        call.launch([&](const dim3 & launch, int first_path) {
-            a.first_path = first_path;
-            if (vector)
-            {
-                launch_flux<true>(n_angles, a, launch, engine->stream);
-            }
-            else
-            {
-                launch_flux<false>(n_angles, a, launch, engine->stream);
-            }
+        call.launch(a, [&](const dim3 & launch) {
+            // (1 <= n_angles <= kFluxMaxAngles was checked above: one of them is launched)
+            dispatch_range<kFluxMaxAngles>([&](auto k, auto v, auto l) {
+                hipLaunchKernelGGL((path_flux_kernel<v.value, k.value, l.value>), launch,
+                                   dim3(kPathThreads), 0, engine->stream, a);
+            }, n_angles, vector, linear);
         });
         call.note_rows(beta, level_count);
         call.note_rows(level_flux, level_count);
         call.note_rows(carry, (long long)n_paths*n_angles);
         call.note_rows(reflection, n_paths);
 
-        if (n_bands > 0)
-        {
-            const long long * d_bands = reinterpret_cast<const long long *>(d_tables + band_at);
-            bands.means(engine, d_bands, level_flux, (long long)row_stride, level_count, false,
-                        flux);
-            if (up)
-            {
-                // The surface-interface rows of the paths this run starts in sweep order: upward
-                // those whose first level is in the run, downward those whose last level is.
-                const PathRows rows = path_rows(level_begin, call.level_end(), levels_per_path,
-                                                call.from_last());
-                bands.means(engine, d_bands, reflection + (long long)rows.first*row_stride,
-                            (long long)row_stride, rows.count, false,
-                            surface_flux + (long long)rows.first*n_bands);
-            }
-        }
+        // Every interface of the run, and the surface-interface rows of the paths it starts.
+        call.means(bands, PathMeanRows::kLevels, level_flux, flux);
+        call.means(bands, PathMeanRows::kStarted, reflection, up ? surface_flux : nullptr);
         return LBL_OK;
     });
 }

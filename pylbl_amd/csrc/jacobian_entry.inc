@@ -64,14 +64,12 @@ int lbl_path_jacobian(lbl_engine * engine, const double * beta, int64_t row_stri
         const PathRun & run = call.run;
         for (int p = 0; p < n_paths; ++p)
         {
-            const double t = boundary_temperature != nullptr ? boundary_temperature[p] : 0.;
-            const double e = boundary_emissivity != nullptr ? boundary_emissivity[p] : 1.;
-            if (!(t >= 0.) || !std::isfinite(t))
+            if (const char * problem = check_boundary(boundary_temperature, boundary_emissivity, p))
             {
-                return call.bad("boundary temperatures must be finite and >= 0 (0: no boundary).");
+                return call.bad(problem);
             }
-            if (!(e >= 0. && e <= 1.)) return call.bad("boundary emissivities must lie in [0, 1].");
-            if (t == 0. && (want[4] || want[5]) && p >= run.first_path &&
+            const bool none = boundary_temperature == nullptr || boundary_temperature[p] == 0.;
+            if (none && (want[4] || want[5]) && p >= run.first_path &&
                 p < run.first_path + run.paths)
             {
                 return call.bad("a boundary Jacobian is requested for a path without a boundary "
@@ -102,15 +100,9 @@ int lbl_path_jacobian(lbl_engine * engine, const double * beta, int64_t row_stri
         PathTables tables;
         const size_t length_at = tables.add(level_count, path_length);
         const size_t temperature_at = tables.add(level_count, temperature);
-        const size_t boundary_at = tables.add(2*(size_t)run.paths);
-        double * boundary = tables.words.data() + boundary_at;
-        for (int i = 0; i < run.paths; ++i)
-        {
-            const int p = run.first_path + i;
-            boundary[i] = boundary_temperature != nullptr ? boundary_temperature[p] : 0.;
-            boundary[run.paths + i] = boundary_emissivity != nullptr ? boundary_emissivity[p] : 1.;
-        }
-        const size_t band_at = tables.add(bands, band_start);
+        const size_t boundary_at =
+            tables.add_pair(run, boundary_temperature, 0., boundary_emissivity, 1.);
+        tables.add(bands, band_start);
         const double * d_tables = call.begin(tables);
 
         // Where the kernel writes quantity q: row 0 is flat level level_begin (per level) or
@@ -143,21 +135,13 @@ int lbl_path_jacobian(lbl_engine * engine, const double * beta, int64_t row_stri
         }
 
         PathJacobian a;
-        a.beta = beta;
-        a.stride = row_stride;
-        a.columns = columns;
+        call.fill(a, beta, nullptr);
         a.nu = call.grid->wavenumber.data;
         a.length = d_tables + length_at;
         a.temperature = d_tables + temperature_at;
         a.boundary_t = d_tables + boundary_at;
         a.boundary_e = a.boundary_t + run.paths;
-        a.first = level_begin;
-        a.count = level_count;
-        a.row_base = level_begin;
-        a.levels_per_path = levels_per_path;
         a.table_path = run.first_path;
-        a.from_last = call.from_last() ? 1 : 0;
-        a.carry = nullptr;
         a.work = work;
         a.d_depth = rows[0];
         a.d_log_depth = rows[1];
@@ -167,18 +151,11 @@ int lbl_path_jacobian(lbl_engine * engine, const double * beta, int64_t row_stri
         a.d_boundary_e = rows[5];
         const bool vector = path_vector(row_stride, {beta, a.nu, work, rows[0], rows[1], rows[2],
                                                      rows[3], rows[4], rows[5]});
-        call.launch([&](const dim3 & launch, int first_path) {
-            a.first_path = first_path;
-            if (vector)
-            {
-                hipLaunchKernelGGL(path_jacobian_kernel<true>, launch, dim3(kPathThreads), 0,
+        call.launch(a, [&](const dim3 & launch) {
+            dispatch([&](auto v) {
+                hipLaunchKernelGGL(path_jacobian_kernel<v.value>, launch, dim3(kPathThreads), 0,
                                    engine->stream, a);
-            }
-            else
-            {
-                hipLaunchKernelGGL(path_jacobian_kernel<false>, launch, dim3(kPathThreads), 0,
-                                   engine->stream, a);
-            }
+            }, vector);
         });
         call.note_rows(beta, level_count);
         call.note_rows(work, level_count);
@@ -198,24 +175,12 @@ int lbl_path_jacobian(lbl_engine * engine, const double * beta, int64_t row_stri
             }
         }
 
-        if (!fine)
+        // The fine rows' means: per level every level of the run, per path its (whole) paths.
+        for (int q = 0; q < kQuantities && !fine; ++q)
         {
-            const long long * d_bands = reinterpret_cast<const long long *>(d_tables + band_at);
-            for (int q = 0; q < kQuantities; ++q)
-            {
-                if (!want[q]) continue;
-                if (q < kPerLevel)
-                {
-                    bands.means(engine, d_bands, rows[q], (long long)row_stride, level_count,
-                                false, out[q]);
-                }
-                else
-                {
-                    bands.means(engine, d_bands, rows[q] + (long long)run.first_path*row_stride,
-                                (long long)row_stride, run.paths, false,
-                                out[q] + (long long)run.first_path*n_bands);
-                }
-            }
+            if (!want[q]) continue;
+            call.means(bands, q < kPerLevel ? PathMeanRows::kLevels : PathMeanRows::kFinished,
+                       rows[q], out[q]);
         }
         return LBL_OK;
     });

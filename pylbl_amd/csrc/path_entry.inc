@@ -1,7 +1,11 @@
 // What the path entries share (lbl_path_compute here, lbl_path_radiance, lbl_path_jacobian,
-// lbl_path_flux), and lbl_path_compute: optical depth and transmittance along paths through a
-// block of absorption coefficients in HBM (kernels: path.h).  Included by engine.hip after
+// lbl_path_flux, lbl_path_solar) -- the checks of a run, of its bands, boundaries and knots, the
+// staged tables, the PathLevels part of the kernel arguments, the launches, the choice of outputs
+// and the band means -- and lbl_path_compute: optical depth and transmittance along paths through
+// a block of absorption coefficients in HBM (kernels: path.h).  Included by engine.hip after
 // slot_entry.inc (grid handles).
+#include "dispatch.h"
+
 namespace {
 
 // Where a run of flat levels [begin, end) leaves the paths it touches: the first path, how many,
@@ -49,13 +53,14 @@ bool finite_at_least_zero(const double * values, long long count, bool positive)
     return true;
 }
 
-// nullptr, or what is wrong with the interface temperatures [level_count][2] of a run that starts
-// at flat level `level_begin` (lbl_path_radiance_source, lbl_path_flux_source): every value finite
+// nullptr, or what is wrong with the interface temperatures [level_count][2] (null: none) of a run
+// that starts at flat level `level_begin` (lbl_path_radiance_source, lbl_path_flux_source): finite
 // and > 0, and inside a path the far side of a level equal to the near side of the next -- the
 // kernels carry B at a level's exit interface into the next level as its entry value.
 const char * check_edge_temperatures(const double * edge, int level_begin, int level_count,
                                      int levels_per_path)
 {
+    if (edge == nullptr) return nullptr;
     if (!finite_at_least_zero(edge, 2*(long long)level_count, true))
     {
         return "edge temperatures must be finite and > 0.";
@@ -66,6 +71,33 @@ const char * check_edge_temperatures(const double * edge, int level_begin, int l
         if (same_path && edge[2*r + 1] != edge[2*(r + 1)])
         {
             return "edge temperatures must be continuous within a path: [r][1] == [r + 1][0].";
+        }
+    }
+    return nullptr;
+}
+
+// nullptr, or what is wrong with the boundary of path p (lbl_path_radiance_*, lbl_path_jacobian):
+// its temperature (null: 0, no boundary) and its emissivity (null: 1).
+const char * check_boundary(const double * temperature, const double * emissivity, int p)
+{
+    const double t = temperature != nullptr ? temperature[p] : 0.;
+    const double e = emissivity != nullptr ? emissivity[p] : 1.;
+    if (!(t >= 0.) || !std::isfinite(t))
+    {
+        return "boundary temperatures must be finite and >= 0 (0: no boundary).";
+    }
+    if (!(e >= 0. && e <= 1.)) return "boundary emissivities must lie in [0, 1].";
+    return nullptr;
+}
+
+// nullptr, or what is wrong with the knots of a table (lbl_surface_emissivity, lbl_solar_spectrum).
+const char * check_knots(const double * knot, int n_knots)
+{
+    for (int j = 0; j < n_knots; ++j)
+    {
+        if (!std::isfinite(knot[j]) || (j > 0 && !(knot[j] > knot[j - 1])))
+        {
+            return "knots must be finite and strictly ascending.";
         }
     }
     return nullptr;
@@ -90,6 +122,7 @@ struct PathBands
     int n_bands = 0;
     std::vector<long long> band_segment;
     long long n_segments = 0;
+    size_t at = 0;              // where PathTables::add staged them among the call's words
 
     // nullptr, or what is wrong with the bands.
     const char * check(int32_t bands, const int64_t * band_start, int64_t columns)
@@ -154,11 +187,12 @@ struct PathBands
 
     // Queues out[r][b] = the mean over band b of row r of `values` (of exp(-value) with
     // `transmittance`) for `rows` rows `row_stride` apart, and records the write of `out`.
-    // d_table: the staged words on the device.
-    void means(lbl_engine * engine, const long long * d_table, const double * values,
+    // d_tables: the call's tables on the device.
+    void means(lbl_engine * engine, const double * d_tables, const double * values,
                long long row_stride, int rows, bool transmittance, double * out) const
     {
         if (rows <= 0) return;
+        const long long * d_table = reinterpret_cast<const long long *>(d_tables + at);
         PathWorkspace & w = engine->path;
         hipStream_t stream = engine->stream;
         // Rows go in the grid's y dimension, at most kPathGridY per launch; the chunks run one
@@ -208,13 +242,64 @@ struct PathTables
         return at;
     }
 
-    size_t add(const PathBands & bands, const int64_t * band_start)
+    void add(PathBands & bands, const int64_t * band_start)
     {
-        const size_t at = add(bands.words());
-        bands.stage(reinterpret_cast<long long *>(words.data() + at), band_start);
+        bands.at = add(bands.words());
+        bands.stage(reinterpret_cast<long long *>(words.data() + bands.at), band_start);
+    }
+
+    // Two values per path of the run: [run.paths] of `first`, then [run.paths] of `second`, each
+    // its path's value or, where the pointer is null, the default.
+    size_t add_pair(const PathRun & run, const double * first, double first_default,
+                    const double * second, double second_default)
+    {
+        const size_t at = add(2*(size_t)run.paths);
+        double * pair = words.data() + at;
+        for (int i = 0; i < run.paths; ++i)
+        {
+            const int p = run.first_path + i;
+            pair[i] = first != nullptr ? first[p] : first_default;
+            pair[run.paths + i] = second != nullptr ? second[p] : second_default;
+        }
         return at;
     }
 };
+
+// Where a sweep writes its two quantities (null: not wanted): after every level (cumulative) or
+// where a path finishes, and with bands as fine rows for the means to read -- in place in beta
+// (cumulative) or left in the carry rows (keep_final).
+struct PathOutputs
+{
+    double * level[2] = {nullptr, nullptr};
+    double * final[2] = {nullptr, nullptr};
+    int keep_final = 0;
+
+    PathOutputs(bool cumulative, bool banded, double * beta, double * first, double * second)
+    {
+        if (cumulative && banded)
+        {
+            level[0] = beta;            // in place: the band means read the rows back
+        }
+        else if (cumulative)
+        {
+            level[0] = first;
+            level[1] = second;
+        }
+        else if (banded)
+        {
+            keep_final = 1;
+        }
+        else
+        {
+            final[0] = first;
+            final[1] = second;
+        }
+    }
+};
+
+// The rows a band mean is taken of: every level of the run, or one row per path the run starts
+// or finishes in sweep order.
+enum class PathMeanRows { kLevels, kStarted, kFinished };
 
 // One call of a path entry: its run, its checks and the steps every entry takes in order.
 struct PathCall
@@ -225,6 +310,7 @@ struct PathCall
     int32_t n_paths, levels_per_path, level_begin, level_count, flags;
     const SpectralGrid * grid = nullptr;
     PathRun run = {};
+    const double * d_tables = nullptr;      // begin()'s
 
     int bad(const char * what) const
     {
@@ -296,7 +382,32 @@ struct PathCall
         }
         w.tables.reserve(words);
         w.staged.upload(w.tables.data, words, engine->stream);
-        return w.tables.data;
+        return d_tables = w.tables.data;
+    }
+
+    // What every sweep's arguments share: the run and its rows in `beta` and `carry`.
+    void fill(PathLevels & a, const double * beta, double * carry) const
+    {
+        a.beta = beta;
+        a.stride = row_stride;
+        a.columns = columns;
+        a.first = level_begin;
+        a.count = level_count;
+        a.row_base = level_begin;
+        a.levels_per_path = levels_per_path;
+        a.first_path = run.first_path;      // (every launch sets its own)
+        a.from_last = from_last() ? 1 : 0;
+        a.carry = carry;
+    }
+
+    // The same with a sweep's arguments: sets a.first_path and queues launch(grid).
+    template <typename Launch>
+    void launch(PathLevels & a, Launch launch_one) const
+    {
+        launch([&](const dim3 & grid, int first_path) {
+            a.first_path = first_path;
+            launch_one(grid);
+        });
     }
 
     // Queues launch(grid, first path) for every kPathGridY paths of the run (the grid's y limit).
@@ -320,6 +431,36 @@ struct PathCall
     {
         if (p == nullptr) return;
         engine->lanes[0].note_write(p, ((rows - 1)*row_stride + columns)*8, engine->stream);
+    }
+
+    // What a sweep with PathOutputs touches.
+    void note_sweep(const double * beta, const double * carry, const PathOutputs & o) const
+    {
+        note_rows(beta, level_count);
+        note_rows(o.level[0] != beta ? o.level[0] : nullptr, level_count);
+        note_rows(o.level[1], level_count);
+        note_rows(carry, n_paths);
+        note_rows(o.final[0], n_paths);
+        note_rows(o.final[1], n_paths);
+    }
+
+    // Queues the means over `bands` of the rows `which` of `values` into the same rows of `out`
+    // (null, or no bands: nothing).  values: row 0 is flat level level_begin (kLevels) or path 0;
+    // out likewise, n_bands per row.  In sweep order a run starts the paths whose first level it
+    // holds and finishes those whose last level it holds; from_last() swaps the two.
+    void means(const PathBands & bands, PathMeanRows which, const double * values, double * out,
+               bool transmittance = false) const
+    {
+        if (out == nullptr || bands.n_bands == 0) return;
+        PathRows rows{0, level_count};
+        if (which != PathMeanRows::kLevels)
+        {
+            rows = path_rows(level_begin, level_end(), levels_per_path,
+                             (which == PathMeanRows::kStarted) == from_last());
+        }
+        bands.means(engine, d_tables, values + (long long)rows.first*row_stride,
+                    (long long)row_stride, rows.count, transmittance,
+                    out + (long long)rows.first*bands.n_bands);
     }
 };
 
@@ -373,80 +514,35 @@ int lbl_path_compute(lbl_engine * engine, double * beta, int64_t row_stride, int
 
         PathTables tables;
         const size_t length_at = tables.add(level_count, path_length);
-        const size_t band_at = tables.add(bands, band_start);
+        tables.add(bands, band_start);
         const double * d_tables = call.begin(tables);
 
         PathSweep a;
-        a.beta = beta;
-        a.stride = row_stride;
-        a.columns = columns;
+        call.fill(a, beta, carry);
         a.length = d_tables + length_at;
-        a.first = level_begin;
-        a.count = level_count;
-        a.row_base = level_begin;
-        a.levels_per_path = levels_per_path;
-        a.from_last = call.from_last() ? 1 : 0;
-        a.carry = carry;
-        a.level_tau = a.level_trans = a.final_tau = a.final_trans = nullptr;
-        a.keep_final = 0;
-        if (cumulative && n_bands > 0)
-        {
-            a.level_tau = beta;         // in place: the band means read the rows back
-        }
-        else if (cumulative)
-        {
-            a.level_tau = want_tau ? optical_depth : nullptr;
-            a.level_trans = want_trans ? transmittance : nullptr;
-        }
-        else if (n_bands > 0)
-        {
-            a.keep_final = 1;
-        }
-        else
-        {
-            a.final_tau = want_tau ? optical_depth : nullptr;
-            a.final_trans = want_trans ? transmittance : nullptr;
-        }
+        const PathOutputs o(cumulative, n_bands > 0, beta, want_tau ? optical_depth : nullptr,
+                            want_trans ? transmittance : nullptr);
+        a.level_tau = o.level[0];
+        a.level_trans = o.level[1];
+        a.final_tau = o.final[0];
+        a.final_trans = o.final[1];
+        a.keep_final = o.keep_final;
         const bool vector = path_vector(row_stride, {beta, carry, a.level_tau, a.level_trans,
                                                      a.final_tau, a.final_trans});
-        call.launch([&](const dim3 & grid, int first_path) {
-            a.first_path = first_path;
-            if (vector)
-            {
-                hipLaunchKernelGGL(path_sweep_kernel<true>, grid, dim3(kPathThreads), 0,
+        call.launch(a, [&](const dim3 & grid) {
+            dispatch([&](auto v) {
+                hipLaunchKernelGGL(path_sweep_kernel<v.value>, grid, dim3(kPathThreads), 0,
                                    engine->stream, a);
-            }
-            else
-            {
-                hipLaunchKernelGGL(path_sweep_kernel<false>, grid, dim3(kPathThreads), 0,
-                                   engine->stream, a);
-            }
+            }, vector);
         });
-        call.note_rows(beta, level_count);
-        call.note_rows(a.level_tau != beta ? a.level_tau : nullptr, level_count);
-        call.note_rows(a.level_trans, level_count);
-        call.note_rows(carry, n_paths);
-        call.note_rows(a.final_tau, n_paths);
-        call.note_rows(a.final_trans, n_paths);
+        call.note_sweep(beta, carry, o);
 
-        if (n_bands > 0)
-        {
-            // Rows: every level of the run (cumulative, in place in beta) or the paths the run
-            // finishes (upward: those whose last level is in the run), from their carry rows.
-            const PathRows rows = cumulative ? PathRows{0, level_count}
-                                             : path_rows(level_begin, call.level_end(),
-                                                         levels_per_path, true);
-            const double * values = cumulative ? beta : carry + (long long)rows.first*row_stride;
-            const long long * d_bands = reinterpret_cast<const long long *>(d_tables + band_at);
-            for (int q = 0; q < 2; ++q)
-            {
-                const bool trans = q == 1;
-                if (!(trans ? want_trans : want_tau)) continue;
-                double * out = (trans ? transmittance : optical_depth) +
-                               (cumulative ? 0 : (long long)rows.first*n_bands);
-                bands.means(engine, d_bands, values, (long long)row_stride, rows.count, trans, out);
-            }
-        }
+        // Rows: every level of the run (cumulative, in place in beta) or the paths the run
+        // finishes, from their carry rows.
+        const PathMeanRows rows = cumulative ? PathMeanRows::kLevels : PathMeanRows::kFinished;
+        const double * values = cumulative ? beta : carry;
+        call.means(bands, rows, values, want_tau ? optical_depth : nullptr);
+        call.means(bands, rows, values, want_trans ? transmittance : nullptr, true);
         return LBL_OK;
     });
 }

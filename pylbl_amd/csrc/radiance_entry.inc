@@ -40,23 +40,17 @@ int path_radiance_call(const char * name, lbl_engine * engine, double * beta, in
         {
             return call.bad("temperatures must be finite and > 0.");
         }
-        if (edge_temperature != nullptr)
+        if (const char * problem = check_edge_temperatures(edge_temperature, level_begin,
+                                                           level_count, levels_per_path))
         {
-            if (const char * problem = check_edge_temperatures(edge_temperature, level_begin,
-                                                               level_count, levels_per_path))
-            {
-                return call.bad(problem);
-            }
+            return call.bad(problem);
         }
         for (int p = 0; p < n_paths; ++p)
         {
-            const double t = boundary_temperature != nullptr ? boundary_temperature[p] : 0.;
-            const double e = boundary_emissivity != nullptr ? boundary_emissivity[p] : 1.;
-            if (!(t >= 0.) || !std::isfinite(t))
+            if (const char * problem = check_boundary(boundary_temperature, boundary_emissivity, p))
             {
-                return call.bad("boundary temperatures must be finite and >= 0 (0: no boundary).");
+                return call.bad(problem);
             }
-            if (!(e >= 0. && e <= 1.)) return call.bad("boundary emissivities must lie in [0, 1].");
         }
         PathBands bands;
         if (const char * problem = bands.check(n_bands, band_start, columns))
@@ -79,134 +73,59 @@ int path_radiance_call(const char * name, lbl_engine * engine, double * beta, in
         PathTables tables;
         const size_t length_at = tables.add(level_count, path_length);
         const size_t temperature_at = tables.add(level_count, temperature);
-        const size_t boundary_at = tables.add(2*(size_t)run.paths);
-        double * boundary = tables.words.data() + boundary_at;
-        for (int i = 0; i < run.paths; ++i)
-        {
-            const int p = run.first_path + i;
-            boundary[i] = boundary_temperature != nullptr ? boundary_temperature[p] : 0.;
-            boundary[run.paths + i] = boundary_emissivity != nullptr ? boundary_emissivity[p] : 1.;
-        }
-        const size_t band_at = tables.add(bands, band_start);
+        const size_t boundary_at =
+            tables.add_pair(run, boundary_temperature, 0., boundary_emissivity, 1.);
+        tables.add(bands, band_start);
         // After the tables every call has, so that theirs lie where they always lay.
         const bool linear = edge_temperature != nullptr;
         const size_t edge_at = linear ? tables.add(2*(size_t)level_count, edge_temperature) : 0;
         const double * d_tables = call.begin(tables);
 
-        PathRadiance a;
-        a.beta = beta;
-        a.stride = row_stride;
-        a.columns = columns;
+        // One set of arguments: the kernels without a surface take its PathRadiance part.
+        PathSurface a;
+        call.fill(a, beta, carry);
         a.nu = call.grid->wavenumber.data;
         a.length = d_tables + length_at;
         a.temperature = d_tables + temperature_at;
         a.boundary_t = d_tables + boundary_at;
         a.boundary_e = a.boundary_t + run.paths;
         a.edge = linear ? d_tables + edge_at : nullptr;
-        a.first = level_begin;
-        a.count = level_count;
-        a.row_base = level_begin;
-        a.levels_per_path = levels_per_path;
         a.table_path = run.first_path;
-        a.first_path = run.first_path;     // (every launch sets its own)
-        a.from_last = call.from_last() ? 1 : 0;
-        a.carry = carry;
-        a.level_rad = a.level_bt = a.final_rad = a.final_bt = nullptr;
-        a.keep_final = 0;
-        if (cumulative && n_bands > 0)
-        {
-            a.level_rad = beta;         // in place: the band means read the rows back
-        }
-        else if (cumulative)
-        {
-            a.level_rad = want_rad ? radiance : nullptr;
-            a.level_bt = want_bt ? brightness_temperature : nullptr;
-        }
-        else if (n_bands > 0)
-        {
-            a.keep_final = 1;
-        }
-        else
-        {
-            a.final_rad = want_rad ? radiance : nullptr;
-            a.final_bt = want_bt ? brightness_temperature : nullptr;
-        }
+        const PathOutputs o(cumulative, n_bands > 0, beta, want_rad ? radiance : nullptr,
+                            want_bt ? brightness_temperature : nullptr);
+        a.level_rad = o.level[0];
+        a.level_bt = o.level[1];
+        a.final_rad = o.final[0];
+        a.final_bt = o.final[1];
+        a.keep_final = o.keep_final;
+        a.emissivity_rows = emissivity_rows;
+        a.reflection = reflection;
         const bool vector = path_vector(row_stride, {beta, carry, a.nu, a.level_rad, a.level_bt,
                                                      a.final_rad, a.final_bt, emissivity_rows,
                                                      reflection});
-        PathSurface s;
-        static_cast<PathRadiance &>(s) = a;
-        s.emissivity_rows = emissivity_rows;
-        s.reflection = reflection;
-        call.launch([&](const dim3 & launch, int first_path) {
-            a.first_path = s.first_path = first_path;
-            if (surface)
-            {
+        call.launch(a, [&](const dim3 & launch) {
+            dispatch([&](auto v, auto l) {
                 const dim3 block(kPathThreads);
-                if (vector && linear)
+                if (surface)
                 {
-                    hipLaunchKernelGGL((path_radiance_surface_kernel<true, true>), launch, block,
-                                       0, engine->stream, s);
-                }
-                else if (linear)
-                {
-                    hipLaunchKernelGGL((path_radiance_surface_kernel<false, true>), launch, block,
-                                       0, engine->stream, s);
-                }
-                else if (vector)
-                {
-                    hipLaunchKernelGGL((path_radiance_surface_kernel<true, false>), launch, block,
-                                       0, engine->stream, s);
+                    hipLaunchKernelGGL((path_radiance_surface_kernel<v.value, l.value>), launch,
+                                       block, 0, engine->stream, a);
                 }
                 else
                 {
-                    hipLaunchKernelGGL((path_radiance_surface_kernel<false, false>), launch,
-                                       block, 0, engine->stream, s);
+                    hipLaunchKernelGGL((path_radiance_kernel<v.value, l.value>), launch, block, 0,
+                                       engine->stream, static_cast<const PathRadiance &>(a));
                 }
-            }
-            else if (vector && linear)
-            {
-                hipLaunchKernelGGL((path_radiance_kernel<true, true>), launch,
-                                   dim3(kPathThreads), 0, engine->stream, a);
-            }
-            else if (linear)
-            {
-                hipLaunchKernelGGL((path_radiance_kernel<false, true>), launch,
-                                   dim3(kPathThreads), 0, engine->stream, a);
-            }
-            else if (vector)
-            {
-                hipLaunchKernelGGL(path_radiance_kernel<true>, launch, dim3(kPathThreads), 0,
-                                   engine->stream, a);
-            }
-            else
-            {
-                hipLaunchKernelGGL(path_radiance_kernel<false>, launch, dim3(kPathThreads), 0,
-                                   engine->stream, a);
-            }
+            }, vector, linear);
         });
-        call.note_rows(beta, level_count);
-        call.note_rows(a.level_rad != beta ? a.level_rad : nullptr, level_count);
-        call.note_rows(a.level_bt, level_count);
-        call.note_rows(carry, n_paths);
-        call.note_rows(a.final_rad, n_paths);
-        call.note_rows(a.final_bt, n_paths);
+        call.note_sweep(beta, carry, o);
         call.note_rows(emissivity_rows, n_paths);
         call.note_rows(reflection, n_paths);
 
-        if (n_bands > 0)
-        {
-            // Rows: every level of the run (cumulative, in place in beta) or the paths the run
-            // finishes -- upward those whose last level is in the run, downward those whose
-            // first level is -- from their carry rows.
-            const PathRows rows = cumulative ? PathRows{0, level_count}
-                                             : path_rows(level_begin, call.level_end(),
-                                                         levels_per_path, !call.from_last());
-            const double * values = cumulative ? beta : carry + (long long)rows.first*row_stride;
-            double * out = radiance + (cumulative ? 0 : (long long)rows.first*n_bands);
-            bands.means(engine, reinterpret_cast<const long long *>(d_tables + band_at), values,
-                        (long long)row_stride, rows.count, false, out);
-        }
+        // Rows: every level of the run (cumulative, in place in beta) or the paths the run
+        // finishes, from their carry rows.
+        call.means(bands, cumulative ? PathMeanRows::kLevels : PathMeanRows::kFinished,
+                   cumulative ? beta : carry, radiance);
         return LBL_OK;
     });
 }
@@ -278,14 +197,7 @@ int lbl_surface_emissivity(lbl_engine * engine, int32_t grid, int32_t n_paths, i
         {
             return call.bad("n_knots must lie in 2..1024.");
         }
-        for (int j = 0; j < n_knots; ++j)
-        {
-            if (!std::isfinite(knot_wavenumber[j]) ||
-                (j > 0 && !(knot_wavenumber[j] > knot_wavenumber[j - 1])))
-            {
-                return call.bad("knots must be finite and strictly ascending.");
-            }
-        }
+        if (const char * problem = check_knots(knot_wavenumber, n_knots)) return call.bad(problem);
         const long long values = (long long)path_count*n_knots;
         for (long long i = 0; i < values; ++i)
         {
@@ -312,16 +224,10 @@ int lbl_surface_emissivity(lbl_engine * engine, int32_t grid, int32_t n_paths, i
         call.launch([&](const dim3 & launch, int first_path) {
             a.value = d_tables + value_at + (long long)(first_path - path_begin)*n_knots;
             a.rows = rows + (long long)first_path*row_stride;
-            if (vector)
-            {
-                hipLaunchKernelGGL(surface_emissivity_kernel<true>, launch, dim3(kPathThreads),
+            dispatch([&](auto v) {
+                hipLaunchKernelGGL(surface_emissivity_kernel<v.value>, launch, dim3(kPathThreads),
                                    0, engine->stream, a);
-            }
-            else
-            {
-                hipLaunchKernelGGL(surface_emissivity_kernel<false>, launch, dim3(kPathThreads),
-                                   0, engine->stream, a);
-            }
+            }, vector);
         });
         call.note_rows(rows + (long long)path_begin*row_stride, path_count);
         return LBL_OK;

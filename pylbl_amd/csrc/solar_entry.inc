@@ -3,25 +3,6 @@
 // Lambertian surface reflects to a viewer, one sweep through a block of absorption coefficients in
 // HBM (kernels: solar.h; band means: path.h).  Included by engine.hip after flux_entry.inc; shares
 // path_entry.inc's PathCall, PathTables and PathBands.
-namespace {
-
-template <bool kVector>
-void launch_solar(bool view, const PathSolar & a, const dim3 & grid, hipStream_t stream)
-{
-    if (view)
-    {
-        hipLaunchKernelGGL((path_solar_kernel<kVector, true>), grid, dim3(kPathThreads), 0, stream,
-                           a);
-    }
-    else
-    {
-        hipLaunchKernelGGL((path_solar_kernel<kVector, false>), grid, dim3(kPathThreads), 0,
-                           stream, a);
-    }
-}
-
-}  // namespace
-
 extern "C" {
 
 int lbl_solar_spectrum(lbl_engine * engine, int32_t grid, int64_t columns, int32_t n_knots,
@@ -57,13 +38,10 @@ int lbl_solar_spectrum(lbl_engine * engine, int32_t grid, int64_t columns, int32
             {
                 return call.bad("n_knots must lie in 2..4194304.");
             }
-            for (int j = 0; mode == kSolarTable && j < n_knots; ++j)
+            if (const char * problem =
+                    mode == kSolarTable ? check_knots(knot_wavenumber, n_knots) : nullptr)
             {
-                if (!std::isfinite(knot_wavenumber[j]) ||
-                    (j > 0 && !(knot_wavenumber[j] > knot_wavenumber[j - 1])))
-                {
-                    return call.bad("knots must be finite and strictly ascending.");
-                }
+                return call.bad(problem);
             }
             if (!finite_at_least_zero(knot_irradiance, n_knots, false))
             {
@@ -90,16 +68,10 @@ int lbl_solar_spectrum(lbl_engine * engine, int32_t grid, int64_t columns, int32
         a.row = row;
         const long long per_block = (long long)kPathThreads*kPathWidth;
         const dim3 launch((unsigned)((columns + per_block - 1)/per_block));
-        if (path_vector(0, {row, a.nu}))
-        {
-            hipLaunchKernelGGL(solar_spectrum_kernel<true>, launch, dim3(kPathThreads), 0,
+        dispatch([&](auto v) {
+            hipLaunchKernelGGL(solar_spectrum_kernel<v.value>, launch, dim3(kPathThreads), 0,
                                engine->stream, a);
-        }
-        else
-        {
-            hipLaunchKernelGGL(solar_spectrum_kernel<false>, launch, dim3(kPathThreads), 0,
-                               engine->stream, a);
-        }
+        }, path_vector(0, {row, a.nu}));
         HIP_TRY(hipGetLastError());
         call.note_rows(row, 1);
         return LBL_OK;
@@ -184,19 +156,11 @@ int lbl_path_solar(lbl_engine * engine, double * beta, int64_t row_stride, int64
         const size_t mu0_at = tables.add(run.paths, solar_zenith_cosine + run.first_path);
         const size_t albedo_at =
             tables.add(run.paths, albedo != nullptr ? albedo + run.first_path : nullptr);
-        const size_t band_at = tables.add(bands, band_start);
+        tables.add(bands, band_start);
         const double * d_tables = call.begin(tables);
 
         PathSolar a;
-        a.beta = beta;
-        a.stride = row_stride;
-        a.columns = columns;
-        a.first = level_begin;
-        a.count = level_count;
-        a.row_base = level_begin;
-        a.levels_per_path = levels_per_path;
-        a.from_last = call.from_last() ? 1 : 0;
-        a.carry = carry;
+        call.fill(a, beta, carry);
         a.length = d_tables + length_at;
         a.view = d_tables + view_at;
         a.mu0 = d_tables + mu0_at;
@@ -211,16 +175,11 @@ int lbl_path_solar(lbl_engine * engine, double * beta, int64_t row_stride, int64
         const bool vector = path_vector(row_stride, {beta, carry, solar_row, albedo_rows,
                                                      interface_rows, space_rows, surface_rows,
                                                      reflected_rows});
-        call.launch([&](const dim3 & launch, int first_path) {
-            a.first_path = first_path;
-            if (vector)
-            {
-                launch_solar<true>(view, a, launch, engine->stream);
-            }
-            else
-            {
-                launch_solar<false>(view, a, launch, engine->stream);
-            }
+        call.launch(a, [&](const dim3 & launch) {
+            dispatch([&](auto v, auto w) {
+                hipLaunchKernelGGL((path_solar_kernel<v.value, w.value>), launch,
+                                   dim3(kPathThreads), 0, engine->stream, a);
+            }, vector, view);
         });
         call.note_rows(beta, level_count);
         call.note_rows(interface_rows, level_count);
@@ -229,39 +188,12 @@ int lbl_path_solar(lbl_engine * engine, double * beta, int64_t row_stride, int64
         call.note_rows(surface_rows, n_paths);
         call.note_rows(reflected_rows, n_paths);
 
-        if (n_bands > 0)
-        {
-            const long long * d_bands = reinterpret_cast<const long long *>(d_tables + band_at);
-            const long long stride = (long long)row_stride;
-            if (interface_mean != nullptr)
-            {
-                bands.means(engine, d_bands, interface_rows, stride, level_count, false,
-                            interface_mean);
-            }
-            // The paths this run starts in sweep order (upward those whose first level is in the
-            // run, downward those whose last level is), and the paths it finishes.
-            const PathRows started = path_rows(level_begin, call.level_end(), levels_per_path,
-                                               call.from_last());
-            const PathRows finished = path_rows(level_begin, call.level_end(), levels_per_path,
-                                                !call.from_last());
-            if (space_mean != nullptr)
-            {
-                bands.means(engine, d_bands, space_rows + started.first*stride, stride,
-                            started.count, false, space_mean + (long long)started.first*n_bands);
-            }
-            if (surface_mean != nullptr)
-            {
-                bands.means(engine, d_bands, surface_rows + finished.first*stride, stride,
-                            finished.count, false,
-                            surface_mean + (long long)finished.first*n_bands);
-            }
-            if (reflected_mean != nullptr)
-            {
-                bands.means(engine, d_bands, reflected_rows + finished.first*stride, stride,
-                            finished.count, false,
-                            reflected_mean + (long long)finished.first*n_bands);
-            }
-        }
+        // Every interface of the run; the top rows of the paths the run starts; the surface rows
+        // of the paths it finishes.
+        call.means(bands, PathMeanRows::kLevels, interface_rows, interface_mean);
+        call.means(bands, PathMeanRows::kStarted, space_rows, space_mean);
+        call.means(bands, PathMeanRows::kFinished, surface_rows, surface_mean);
+        call.means(bands, PathMeanRows::kFinished, reflected_rows, reflected_mean);
         return LBL_OK;
     });
 }

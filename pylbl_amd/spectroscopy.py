@@ -407,56 +407,22 @@ class Spectroscopy(object):
             Dataset attribute, a key of the dict); likewise surface = "reflecting" with
             reflection_path_length and emissivity = "spectral" with emissivity_wavenumber.
         """
-        surface = emissivity_wavenumber is not None or reflection_path_length is not None
         request = self._radiance_request(
             path_length, boundary_temperature, boundary_emissivity, direction, quantities,
             band_edges, cumulative, range_policy, instrument, names=SURFACE_RADIANCE_QUANTITIES,
             source=source, interface_temperature=interface_temperature,
             emissivity_wavenumber=emissivity_wavenumber,
             reflection_path_length=reflection_path_length)
-        if surface:
-            return self._surface_radiance(request, remove_pedestal, range_policy)
-
-        def sweeper(call, run):
-            grid = call.grid()
-            carry = call.take(call.paths)
-
-            def sweep(index, beta, a, b, outputs):
-                call.engine.path_radiance(
-                    beta, call.columns, grid, call.paths, call.per_path, a, request.lengths[a:b],
-                    call.temperature[a:b], carry,
-                    boundary_temperature=request.boundary_temperature,
-                    boundary_emissivity=request.boundary_emissivity,
-                    radiance=outputs.get("radiance"),
-                    brightness_temperature=outputs.get("brightness_temperature"),
-                    band_start=request.starts, cumulative=request.cumulative,
-                    from_last=request.from_last, asynchronous=True,
-                    **_run_edges(request, a, b))
-            return sweep
-        if request.instrument is None:
-            quantities, products = request.quantities, None
-        else:
-            # Channel radiances on the GPU; their brightness temperatures at the centres here.
-            quantities = ("radiance",)
-            products = [_Product("radiance", "radiance", request.cumulative)]
-        step = _sweep_pass(quantities, request.cumulative, request.from_last)
-        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
-                                   products=products)
-        if request.instrument is not None and "brightness_temperature" in request.quantities:
-            from .instrument import brightness_temperature
-            values["brightness_temperature"] = brightness_temperature(
-                values["radiance"], request.instrument.centers)
-        return self._create_path_dataset(values, request)
-
-    def _surface_radiance(self, request, remove_pedestal, range_policy):
-        """compute_radiance behind a surface with a spectral emissivity and/or one that reflects:
-        the down pass (D into the reflection rows), the emissivity rows, then the up pass."""
+        # Behind a surface that reflects, the down pass (D into the reflection rows) comes first;
+        # behind one with a spectral emissivity, the emissivity rows are filled before the up
+        # pass.  With neither, the up pass alone is the plain sweep.
         reflecting = request.reflection_lengths is not None
         spectral = request.emissivity_knots is not None
         wanted = DOWNWELLING in request.quantities
         banded = request.starts is not None
         up_quantities = tuple(q for q in request.quantities if q != DOWNWELLING)
         if request.instrument is not None and up_quantities:
+            # Channel radiances on the GPU; their brightness temperatures at the centres here.
             up_quantities = ("radiance",)
         down = _Pass(not request.from_last, (), (DOWNWELLING,) if wanted else ())
         up = _sweep_pass(up_quantities, request.cumulative, request.from_last)
@@ -490,6 +456,9 @@ class Spectroscopy(object):
                                                    request.boundary_emissivity,
                                                    asynchronous=True)
                     filled.append(True)
+                # (a call that uses nothing of the surface passes neither keyword)
+                surface = {} if emissivity is None and rows is None else \
+                    dict(emissivity_rows=emissivity, reflection=rows)
                 call.engine.path_radiance(
                     beta, call.columns, grid, call.paths, call.per_path, a, request.lengths[a:b],
                     call.temperature[a:b], carry,
@@ -499,7 +468,7 @@ class Spectroscopy(object):
                     brightness_temperature=outputs.get("brightness_temperature"),
                     band_start=request.starts, cumulative=request.cumulative,
                     from_last=request.from_last, asynchronous=True,
-                    emissivity_rows=emissivity, reflection=rows, **_run_edges(request, a, b))
+                    **surface, **_run_edges(request, a, b))
             return sweep
         products = None
         if request.instrument is not None:
