@@ -845,6 +845,43 @@ int lbl_path_solar(lbl_engine *engine, double *beta, int64_t row_stride, int64_t
                    double *interface_mean, double *space_mean, double *surface_mean,
                    double *reflected_mean, int32_t flags);
 
+/* Band k-distributions: every (row, band) segment of a block sorted in place, and what a
+ * correlated-k table stores of it (kernels: pylbl_amd/csrc/band_sort.h).
+ *
+ * values (device, [n_rows][row_stride], the first `columns` of each row used; rows of any stride
+ * and alignment): band b is the columns band_start[b] <= j < band_start[b + 1] (host,
+ * [n_bands + 1], n_bands >= 1, not decreasing, inside [0, columns]; a band may be empty).  On return each band
+ * of each row holds its own values sorted ascending in this total order: with u the 64 bits of a
+ * value, key = u ^ 0x8000000000000000 for a clear sign bit and ~u for a set one, keys compared as
+ * unsigned integers: -inf < negatives < -0 < +0 < positives < +inf < NaN with the sign clear.
+ * The sorted values are the input's bits, permuted; columns in no band and the padding of the
+ * rows are not touched.  The result does not depend on how the work is cut: repeated calls, any
+ * layout and any split of the rows over calls give the same bits.
+ *   scratch (device, a block shaped like `values`, not overlapping it): work space, needed when a
+ *   band is longer than 4096 columns (else it may be NULL); its contents are undefined afterwards.
+ *   interval_start (host, [n_intervals + 1], not decreasing, inside [0, columns]) and means
+ *   (device, [n_rows][n_intervals]), or both NULL / 0: means[r][q] = the arithmetic mean of the
+ *   sorted row r over the columns interval_start[q] <= j < interval_start[q + 1], formed as
+ *   lbl_path_compute forms its band means (fixed order, no atomics); NaN for an interval without
+ *   columns.  The intervals are columns of the row, so sub-ranges of the sorted bands.
+ *   point_index (host, int64 [n_bands][n_points]), point_fraction (host, [n_bands][n_points]) and
+ *   quantiles (device, [n_rows][n_bands][n_points]), or all NULL / 0: with k the sorted band of N
+ *   values, i = point_index[b][p] and f = point_fraction[b][p],
+ *     quantiles[r][b][p] = k_i + f*(k_j - k_i),  j = min(i + 1, N - 1),
+ *   each operation rounded as written (no fused multiply-add); NaN where i < 0 or i >= N.
+ *   flags: LBL_ASYNC or 0.
+ * The call runs on the engine's stream like lbl_path_compute, behind whatever wrote `values`, and
+ * is recorded as a write of values, scratch, means and quantiles.
+ * LBL_BAD_ARGUMENT (message in lbl_last_error) for bad shapes, band or interval starts that
+ * decrease or leave [0, columns], a band longer than 4096 columns without scratch, scratch ==
+ * values, means without intervals or quantiles without their tables, or other flags; nothing is
+ * launched and the engine stays usable. */
+int lbl_band_distribution(lbl_engine *engine, double *values, int64_t row_stride, int64_t columns,
+                          int32_t n_rows, const int64_t *band_start, int32_t n_bands,
+                          double *scratch, const int64_t *interval_start, int32_t n_intervals,
+                          double *means, const int64_t *point_index, const double *point_fraction,
+                          int32_t n_points, double *quantiles, int32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

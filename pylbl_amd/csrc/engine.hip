@@ -29,6 +29,7 @@
 
 #include "../../include/lbl_amd.h"
 #include "accumulate.h"
+#include "band_sort.h"
 #include "continuum.h"
 #include "xsec.h"
 #include "farfield.h"
@@ -497,6 +498,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "jacobian_entry.inc"
 #include "flux_entry.inc"
 #include "solar_entry.inc"
+#include "band_sort_entry.inc"
 #include "instrument_entry.inc"
 #include "xsec_entry.inc"
 #include "sqlite_entry.inc"

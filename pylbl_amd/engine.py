@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = (
     "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
     "lbl_path_jacobian", "lbl_path_radiance_source", "lbl_path_flux_source",
     "lbl_surface_emissivity", "lbl_path_radiance_surface",
-    "lbl_solar_spectrum", "lbl_path_solar",
+    "lbl_solar_spectrum", "lbl_path_solar", "lbl_band_distribution",
     "lbl_instrument_create", "lbl_instrument_free", "lbl_instrument_apply",
 )
 
@@ -220,6 +220,9 @@ def library():
                                        c_double, c_double, c_void_p, c_int32]
     lib.lbl_path_solar.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                    c_int32] + [c_void_p]*6 + [c_int32] + [c_void_p]*10 + [c_int32]
+    lib.lbl_band_distribution.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
+                                          c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_int32]
     lib.lbl_instrument_create.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                           c_void_p, c_int32, c_void_p, c_void_p, c_int32, i32p]
     lib.lbl_instrument_free.argtypes = [c_void_p, c_int32]
@@ -774,6 +777,53 @@ class Engine(object):
             self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
             int(level_begin), rows, lengths.ctypes.data, n_bands, _address(starts), carry.pointer,
             _address(optical_depth), _address(transmittance), flags))
+
+    def band_distribution(self, values, columns, band_start, scratch=None, interval_start=None,
+                          means=None, point_index=None, point_fraction=None, quantiles=None,
+                          asynchronous=False):
+        """Sorts every band of every row of the DeviceSpectra `values` in place, ascending in the
+        total order of lbl_band_distribution (the fp64 bits as integer keys), and forms what a
+        k-distribution stores of the sorted rows.  band_start: int64 column starts of the bands
+        (n_bands + 1 values).  scratch: a DeviceSpectra shaped like `values` (None is enough while
+        no band is longer than 4096 columns).  interval_start (int64, n_intervals + 1 column
+        starts) with means (DeviceSpectra [rows, n_intervals]): the arithmetic mean of the sorted
+        row over each interval of columns.  point_index (int64) and point_fraction, both
+        [n_bands, n_points], with quantiles (DeviceSpectra [rows, n_bands*n_points]):
+        k_i + f*(k_min(i+1, N-1) - k_i) of each sorted band; NaN where i < 0."""
+        rows, stride = int(values.shape[0]), int(values.shape[1])
+        starts = np.ascontiguousarray(band_start, dtype=np.int64)
+        if starts.ndim != 1 or starts.size < 2:
+            raise ValueError("band_start must hold n_bands + 1 >= 2 column starts.")
+        n_bands = starts.size - 1
+        if scratch is not None and tuple(scratch.shape) != (rows, stride):
+            raise ValueError("scratch must be shaped like values.")
+        intervals, n_intervals = None, 0
+        if (interval_start is None) != (means is None):
+            raise ValueError("interval_start and means go together.")
+        if means is not None:
+            intervals = np.ascontiguousarray(interval_start, dtype=np.int64)
+            if intervals.ndim != 1 or intervals.size < 2:
+                raise ValueError("interval_start must hold n_intervals + 1 >= 2 column starts.")
+            n_intervals = intervals.size - 1
+            _check_outputs((means,), rows, n_intervals)
+        index = fraction = None
+        n_points = 0
+        if (point_index is None) != (quantiles is None) or \
+                (point_fraction is None) != (quantiles is None):
+            raise ValueError("point_index, point_fraction and quantiles go together.")
+        if quantiles is not None:
+            index = np.ascontiguousarray(point_index, dtype=np.int64)
+            fraction = _f64(point_fraction)
+            if index.ndim != 2 or index.shape[0] != n_bands or index.shape[1] < 1 or \
+                    fraction.shape != index.shape:
+                raise ValueError("point_index and point_fraction must be [n_bands, n_points].")
+            n_points = index.shape[1]
+            _check_outputs((quantiles,), rows, n_bands*n_points)
+        self._check(self.lib.lbl_band_distribution(
+            self.handle, values.pointer, stride, int(columns), rows, starts.ctypes.data, n_bands,
+            _address(scratch), _address(intervals), n_intervals, _address(means),
+            _address(index), _address(fraction), n_points, _address(quantiles),
+            ASYNC if asynchronous else 0))
 
     def path_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                       temperature, carry, boundary_temperature=None, boundary_emissivity=None,

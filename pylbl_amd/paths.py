@@ -1,5 +1,5 @@
 """The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux,
-compute_jacobian and compute_solar -- on the host: their quantities and units, the checks of
+compute_jacobian, compute_solar and the per-level compute_kdistribution -- on the host: their quantities and units, the checks of
 their arguments (one request per call, made before anything touches the GPU), the run loop that sweeps the "total"
 absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
 cuts (_level_bytes) and the assembly of the results.  The sweeps themselves are the kernels of
@@ -64,6 +64,12 @@ SOLAR_PATH_QUANTITIES = ("surface_irradiance", "reflected_radiance")
 # What the sweep writes for the paths it starts beside the interface rows: F0 at the space end.
 _SPACE = "space_irradiance"
 
+# compute_kdistribution: per band and g interval, per band and g point, and on the grid.
+KDISTRIBUTION_QUANTITIES = ("absorption_g_mean", "absorption_g_quantile", "sorted_absorption")
+MAX_G_INTERVALS = 64
+# _sweep_runs: the product source that stands for the run's block of beta itself.
+_BETA = "beta"
+
 _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
                "radiance": "W m-2 sr-1 (cm-1)-1", "brightness_temperature": "K",
                DOWNWELLING: "W m-2 sr-1 (cm-1)-1",
@@ -111,6 +117,12 @@ _SolarRequest = namedtuple("_SolarRequest", _COMMON + (
     "surface", "mu0", "solar_lengths", "view_lengths", "albedo", "albedo_knots", "solar_knots",
     "solar_values", "scale"))
 
+# compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
+# points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
+# quantile tables [B, P] (quantile_table).
+_KDistributionRequest = namedtuple("_KDistributionRequest", _COMMON + (
+    "g_edges", "g_points", "interval_starts", "point_index", "point_fraction"))
+
 # One pass of _sweep_runs over the levels: its order, and what it writes per level and per path.
 _Pass = namedtuple("_Pass", ["from_last", "level_quantities", "path_quantities"])
 # One returned array of _sweep_runs: host array `name` is filled from the sweeps' block `source`,
@@ -141,6 +153,69 @@ def band_columns(grid, band_edges):
     if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.):
         raise ValueError("band_edges must be finite and strictly increasing.")
     return np.searchsorted(np.asarray(grid, dtype=np.float64), edges, side="left").astype(np.int64)
+
+
+def g_intervals(g_edges=16):
+    """The g edges [Q + 1] of compute_kdistribution's `g_edges`, checked: an int Q in 1..64 gives
+    [0, cumsum(w/2)] of x, w = leggauss(Q) with the last edge set to exactly 1 (intervals of the
+    Gauss weights, narrow near g = 1); an array is taken as it is: Q + 1 strictly increasing
+    values from exactly 0 to exactly 1, Q <= 64."""
+    if isinstance(g_edges, (bool, np.bool_)):
+        raise ValueError("g_edges must be an int in 1..64 or an array of edges.")
+    if isinstance(g_edges, (int, np.integer)):
+        count = int(g_edges)
+        if not 1 <= count <= MAX_G_INTERVALS:
+            raise ValueError(f"g_edges must be an int in 1..{MAX_G_INTERVALS}, not {count}.")
+        _, w = np.polynomial.legendre.leggauss(count)
+        edges = np.concatenate([[0.], np.cumsum(w/2.)])
+        edges[-1] = 1.
+    else:
+        edges = np.array(g_edges, dtype=np.float64)
+        if edges.ndim != 1 or not 2 <= edges.size <= MAX_G_INTERVALS + 1:
+            raise ValueError(f"g_edges must be a 1-d array of 2..{MAX_G_INTERVALS + 1} edges.")
+    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.):
+        raise ValueError("g_edges must be finite and strictly increasing.")
+    if edges[0] != 0. or edges[-1] != 1.:
+        raise ValueError("g_edges must run from exactly 0 to exactly 1.")
+    return np.ascontiguousarray(edges)
+
+
+def g_quadrature_points(g_points, intervals):
+    """The g points [P] of compute_kdistribution's `g_points`, checked: None gives (x + 1)/2 of
+    x, w = leggauss(intervals); an array of values in [0, 1] is taken as it is."""
+    if g_points is None:
+        x, _ = np.polynomial.legendre.leggauss(int(intervals))
+        return np.ascontiguousarray((x + 1.)/2.)
+    points = np.array(g_points, dtype=np.float64)
+    if points.ndim != 1 or points.size < 1:
+        raise ValueError("g_points must be a non-empty 1-d array.")
+    if not np.all((points >= 0.) & (points <= 1.)):
+        raise ValueError("g_points must lie in [0, 1].")
+    return np.ascontiguousarray(points)
+
+
+def interval_columns(starts, g_edges):
+    """int64 [B, Q + 1]: the column starts of every band's g intervals.  Interval q of band b
+    (N = starts[b + 1] - starts[b] points) holds the sorted samples ceil(G_q N) <= i <
+    ceil(G_q+1 N), the products formed in fp64; its columns are starts[b] + i."""
+    starts = np.asarray(starts, dtype=np.int64)
+    counts = np.diff(starts).astype(np.float64)
+    first = np.ceil(np.asarray(g_edges, dtype=np.float64)[None, :]*counts[:, None])
+    return np.ascontiguousarray(starts[:-1, None] + first.astype(np.int64))
+
+
+def quantile_table(counts, g_points):
+    """(i int64 [B, P], f float64 [B, P]) of the quantile at every g point of bands of `counts`
+    points: x = min(max(g N - 0.5, 0), N - 1), i = floor(x), f = x - i, in fp64; i = -1 and
+    f = 0 for a band without points."""
+    n = np.asarray(counts, dtype=np.int64).astype(np.float64)[:, None]
+    g = np.asarray(g_points, dtype=np.float64)[None, :]
+    x = np.minimum(np.maximum(g*n - 0.5, 0.), np.maximum(n - 1., 0.))
+    index = np.floor(x)
+    fraction = x - index
+    empty = np.broadcast_to(n == 0., x.shape)
+    return (np.ascontiguousarray(np.where(empty, -1, index.astype(np.int64))),
+            np.ascontiguousarray(np.where(empty, 0., fraction)))
 
 
 def flux_angles(angles):
@@ -530,6 +605,28 @@ def _solar_request(spec, layer_thickness, solar_zenith_cosine, solar_irradiance,
                          solar_values=solar_values, scale=scale)
 
 
+def _kdistribution_request(spec, band_edges, g_edges, g_points, quantities, range_policy):
+    """Checks every argument of compute_kdistribution."""
+    if spec.group is not None:
+        raise NotImplementedError("compute_kdistribution does not split levels over processes "
+                                  "yet (group is set).")
+    shape = tuple(spec.atmosphere.temperature.shape)
+    if spec.atmosphere.temperature.size == 0:
+        raise ValueError("the atmosphere has no levels.")
+    if band_edges is None:
+        raise ValueError("compute_kdistribution needs band_edges.")
+    quantities = _selection(quantities, KDISTRIBUTION_QUANTITIES)
+    _check_range_policy(range_policy)
+    edges, starts = _path_bands(spec, band_edges)
+    g = g_intervals(g_edges)
+    points = g_quadrature_points(g_points, g.size - 1)
+    index, fraction = quantile_table(np.diff(starts), points)
+    return _KDistributionRequest(
+        lengths=None, shape=shape, quantities=quantities, edges=edges, starts=starts,
+        instrument=None, cumulative=False, g_edges=g, g_points=points,
+        interval_starts=interval_columns(starts, g), point_index=index, point_fraction=fraction)
+
+
 # ---------------------------------------------------------------------------------------------
 # The run loop.
 def _sweep_pass(quantities, cumulative, from_last):
@@ -579,7 +676,7 @@ def _first_rows(block, count):
 
 
 def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, level_blocks=1,
-                products=None, grid_outputs=False, whole_paths=False):
+                products=None, grid_outputs=False, whole_paths=False, widths=None):
     """{product: array [levels or paths, columns, bands or channels]}: the "total" block of a run
     of levels at a time (Spectroscopy.total_into), then the path kernels on it -- for each of
     `passes` (_Pass) in turn, every pass over all levels.
@@ -592,7 +689,11 @@ def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, l
     With request.instrument the sweeps write their quantities on the grid and only the products,
     reduced to [rows, channels] by lbl_instrument_apply, travel.
     level_blocks, grid_outputs: see _level_bytes.  whole_paths: every run is a whole number of
-    paths (_cut_runs), for sweeps that carry nothing from run to run."""
+    paths (_cut_runs), for sweeps that carry nothing from run to run.
+    widths: {quantity: columns} of the outputs whose rows are neither the grid nor the bands
+    (compute_kdistribution).  A product of source _BETA is the run's block itself as the sweep
+    leaves it, sent home after every run of the one pass."""
+    widths = widths or {}
     if remove_pedestal is None:
         remove_pedestal = spec.continua_backend == "mt_ckd"
     whole = _Levels(spec, 0, spec.atmosphere.temperature.size, remove_pedestal, range_policy)
@@ -624,7 +725,8 @@ def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, l
         from .instrument import resident_instrument
         handle = resident_instrument(engine, instrument, spec.grid)
         width = len(instrument)
-    results = {product.name: engine.host_array((levels if product.per_level else paths, width))
+    results = {product.name: engine.host_array((levels if product.per_level else paths,
+                                                widths.get(product.source, width)))
                for product in products}
     # One block of `run` levels for beta (and for each per-level output) serves every run; the
     # shorter last run uses its leading rows.  Together with the sweeper's blocks and the
@@ -643,18 +745,18 @@ def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, l
     def send_home(product, rows, target):
         """Queues the copy of the first `rows` rows of the product's source to `target`: reduced
         to channels first with an instrument."""
-        block = _first_rows(outputs[product.source], rows)
+        block = _first_rows(beta if product.source == _BETA else outputs[product.source], rows)
         if instrument is not None:
             engine.instrument_apply(block, rows, handle, channels[product.name],
                                     transmittance=product.transmittance, asynchronous=True)
             block = _first_rows(channels[product.name], rows)
-        block.to_host_into(target, width, asynchronous=True)
+        block.to_host_into(target, widths.get(product.source, width), asynchronous=True)
     # The pooled blocks go back whether the call failed or not: behind the guard's cancel-and-wait.
     with pipeline(engine, give_back=taken):
         sweep = sweeper(_Call(engine, take, paths, per_path, spec.grid.size, temperature,
                               grid_handle), run)
         beta = take(run, n)
-        outputs = {q: take(run, band_width) for q in level_quantities}
+        outputs = {q: take(run, widths.get(q, band_width)) for q in level_quantities}
         outputs.update({q: take(paths, band_width) for q in path_quantities})
         channels = {} if instrument is None else {
             product.name: take(run if product.per_level else paths, width)
@@ -675,7 +777,8 @@ def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, l
                       {q: _first_rows(block, b - a) if q in level_quantities else block
                        for q, block in outputs.items()})
                 for product in products:
-                    if product.per_level and product.source in step.level_quantities:
+                    if product.per_level and (product.source in step.level_quantities or
+                                              product.source == _BETA):
                         send_home(product, b - a, results[product.name][a:b])
         for product in products:
             if not product.per_level:
@@ -806,6 +909,63 @@ def _create_flux_dataset(spec, values, request):
         here = dims + [axis] if q == "heating_rate" else dims[:-1] + ["interface", axis]
         variables[q] = (here, values[q], _FLUX_UNITS[q][request.edges is not None])
     return _path_variables(spec, variables, request)
+
+
+def _create_kdistribution_dataset(spec, values, request):
+    """compute_kdistribution's result from the sweeps' rows: the means of the device's flat
+    interval list [levels, B (Q + 1) - 1] (the last of every band's Q + 1 is the gap to the next
+    band), the quantiles [levels, B P] and the sorted block [levels, grid]."""
+    from .spectroscopy import _optional_xarray
+    dims, shape = list(spec.atmosphere.dims), list(request.shape)
+    bands, q, p = request.starts.size - 1, request.g_edges.size - 1, request.g_points.size
+    levels = int(np.prod(shape, dtype=np.int64))
+    units = {"units": "m-1"}
+    variables = {}
+    if "absorption_g_mean" in request.quantities:
+        flat = np.full((levels, bands*(q + 1)), np.nan)
+        flat[:, :-1] = values["absorption_g_mean"]
+        variables["absorption_g_mean"] = (
+            dims + ["band", "g_interval"],
+            np.ascontiguousarray(flat.reshape(levels, bands, q + 1)[:, :, :q]).reshape(
+                shape + [bands, q]), units)
+    if "absorption_g_quantile" in request.quantities:
+        variables["absorption_g_quantile"] = (
+            dims + ["band", "g_point"],
+            np.array(values["absorption_g_quantile"]).reshape(shape + [bands, p]), units)
+    in_band = np.zeros(spec.grid.size, dtype=bool)
+    g = np.full(spec.grid.size, np.nan)
+    for b in range(bands):
+        a, e = int(request.starts[b]), int(request.starts[b + 1])
+        in_band[a:e] = True
+        g[a:e] = (np.arange(e - a) + 0.5)/max(e - a, 1)
+    if "sorted_absorption" in request.quantities:
+        block = np.array(values["sorted_absorption"])
+        block[:, ~in_band] = np.nan
+        variables["sorted_absorption"] = (dims + ["wavenumber"],
+                                          block.reshape(shape + [spec.grid.size]), units)
+    coords = {"band_lower": (("band",), request.edges[:-1], {"units": "cm-1"}),
+              "band_upper": (("band",), request.edges[1:], {"units": "cm-1"}),
+              "band_points": (("band",), np.diff(request.starts), {}),
+              "g_lower": (("g_interval",), request.g_edges[:-1], {}),
+              "g_upper": (("g_interval",), request.g_edges[1:], {}),
+              "g_weight": (("g_interval",), np.diff(request.g_edges), {}),
+              "g_interval_points": (("band", "g_interval"),
+                                    np.diff(request.interval_starts, axis=1), {}),
+              "g_point": (("g_point",), request.g_points, {})}
+    if "sorted_absorption" in request.quantities:
+        coords["wavenumber"] = (("wavenumber",), spec.grid, {"units": "cm-1"})
+        coords["g"] = (("wavenumber",), g, {})
+    xarray = _optional_xarray()
+    if xarray is None:
+        out = {name: value for name, (_, value, _) in coords.items()}
+        out.update({name: value for name, (_, value, _) in variables.items()})
+        return out
+    DataArray, Dataset = xarray.DataArray, xarray.Dataset
+    return Dataset(
+        data_vars={name: DataArray(value, dims=d, attrs=attrs)
+                   for name, (d, value, attrs) in variables.items()},
+        coords={name: DataArray(value, dims=d, attrs=attrs)
+                for name, (d, value, attrs) in coords.items()})
 
 
 def _path_variables(spec, variables, request):

@@ -14,8 +14,8 @@ this image) -- without it the atmosphere is a plain (p, t, vmr) tuple and the re
 of numpy arrays with the same variable names.
 
 What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
-path products compute_path, compute_radiance, compute_jacobian, compute_flux and compute_solar:
-their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
+path products compute_path, compute_radiance, compute_jacobian, compute_flux and compute_solar,
+and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
 queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
 else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
 whose public names stay importable from here; their functions take the Spectroscopy first, and
@@ -29,6 +29,8 @@ import numpy as np
 from . import absorption, errors, paths
 from .paths import (CP_DRY, DOWNWELLING, FLUX_QUANTITIES, FLUX_SURFACES,  # noqa: F401
                     JACOBIAN_LEVEL_QUANTITIES, JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
+                    KDISTRIBUTION_QUANTITIES, MAX_G_INTERVALS, g_intervals, g_quadrature_points,
+                    interval_columns, quantile_table,
                     PATH_CUMULATIVE, PATH_QUANTITIES, PLANCK_C1, PLANCK_C2, R_DRY,
                     RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOLAR_QUANTITIES,
                     SOLAR_SOLID_ANGLE, SOLAR_TEMPERATURE, SOURCES,
@@ -802,6 +804,79 @@ class Spectroscopy(object):
         values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
                                    level_blocks=2, products=products)
         return self._create_solar_dataset(self._solar_interfaces(values, request), request)
+
+    def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
+                              quantities=("absorption_g_mean",), remove_pedestal=None,
+                              range_policy="reference"):
+        """Band k-distributions, what a correlated-k table is built from: within every band and
+        at every level the absorption coefficient re-ordered by size and summarised on intervals
+        of the cumulative probability g, formed on the GPU from the "total" absorption block
+        without handing that block to the host.  A per-level product: no path lengths.
+
+        With beta the absorption coefficient [m-1] of compute_absorption("total",
+        remove_pedestal, range_policy), band b the N grid points e_b <= grid < e_b+1, and
+        k_0 <= ... <= k_N-1 the band's beta at one level sorted ascending -- in the total order
+        of the fp64 bits u read as keys, u ^ 2^63 for a clear sign bit and ~u for a set one,
+        compared unsigned (-inf < negatives < -0 < +0 < positives < +inf < NaN; numpy.sort
+        apart from +-0 ties and NaN payloads), which makes the result unique: repeated calls
+        and any device_output_limit give the same bits.
+
+        Args:
+            band_edges: strictly increasing finite edges e_0 < ... < e_B, as compute_path's.
+            g_edges: an int Q in 1..64 -- the edges [0, cumsum(w/2)] of x, w = leggauss(Q), the
+                     last set to exactly 1: intervals of the Gauss weights -- or Q + 1 strictly
+                     increasing edges from exactly 0 to exactly 1.  Interval q of a band holds
+                     the sorted samples ceil(G_q N) <= i < ceil(G_q+1 N) (products in fp64).
+            g_points: None -- (x + 1)/2 of the same Q -- or values in [0, 1].
+            quantities: any of
+                "absorption_g_mean" [..., band, g_interval]: the arithmetic mean of the
+                    interval's samples (NaN for an interval or band without points);
+                "absorption_g_quantile" [..., band, g_point]: with x = min(max(g N - 0.5, 0),
+                    N - 1), i = floor(x), f = x - i: k_i + f*(k_min(i+1, N-1) - k_i), each
+                    operation rounded as written (NaN for a band without points);
+                "sorted_absorption" [..., wavenumber]: every band's columns holding its sorted
+                    values, NaN in the columns of no band.
+
+        Returns:
+            Like compute_absorption: an xarray Dataset when xarray is installed, else a dict of
+            numpy arrays [m-1], with the coordinates "band_lower", "band_upper", "band_points",
+            "g_lower", "g_upper", "g_weight" (the interval widths), "g_interval_points"
+            [band, g_interval], "g_point", and with "sorted_absorption" also "wavenumber" and
+            "g" = (i + 0.5)/N on the wavenumber dim.
+        """
+        request = paths._kdistribution_request(self, band_edges, g_edges, g_points, quantities,
+                                               range_policy)
+        want_means = "absorption_g_mean" in request.quantities
+        want_quantiles = "absorption_g_quantile" in request.quantities
+        bands, points = request.starts.size - 1, request.g_points.size
+        # The device takes one flat list of intervals: every band's Q + 1 starts in a row, the
+        # last "interval" of a band being the gap to the next band (dropped on the host).
+        intervals = request.interval_starts.ravel()
+        level_quantities = tuple(q for q in ("absorption_g_mean", "absorption_g_quantile")
+                                 if q in request.quantities)
+
+        def sweeper(call, run):
+            scratch = call.take(run)
+
+            def sweep(index, beta, a, b, outputs):
+                call.engine.band_distribution(
+                    beta, call.columns, request.starts, scratch=scratch.rows(b - a),
+                    interval_start=intervals if want_means else None,
+                    means=outputs.get("absorption_g_mean"),
+                    point_index=request.point_index if want_quantiles else None,
+                    point_fraction=request.point_fraction if want_quantiles else None,
+                    quantiles=outputs.get("absorption_g_quantile"), asynchronous=True)
+            return sweep
+        products = [_Product(q, q, True) for q in level_quantities]
+        if "sorted_absorption" in request.quantities:
+            products.append(_Product("sorted_absorption", paths._BETA, True))
+        # Two blocks per level: beta, sorted in place, and the sort's scratch.
+        values = self._sweep_runs(
+            request, [_Pass(False, level_quantities, ())], remove_pedestal, range_policy, sweeper,
+            level_blocks=2, products=products,
+            widths={"absorption_g_mean": intervals.size - 1,
+                    "absorption_g_quantile": bands*points, paths._BETA: self.grid.size})
+        return paths._create_kdistribution_dataset(self, values, request)
 
     # The host side of the path products is paths.py and that of compute_absorption is
     # absorption.py: their functions take the Spectroscopy first.
