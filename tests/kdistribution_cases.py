@@ -163,3 +163,148 @@ def packed_starts(lengths):
         if i % 3 == 2:
             starts.append(at)           # an empty band
     return np.array(starts, dtype=np.int64), at + 7, real
+
+
+# ---------------------------------------------------------------------------------------------
+# Beyond the lengths above: the run arithmetic of the 4096 chunk and 2048 tile (band_sort.h) --
+# 4096 + 2047 / 2048 / 2049 (a partner run one short of, exactly and one over a tile), three full
+# runs, three runs with the last 7 short, 5 1/2 runs and a value (an unpaired run of 6145 that the
+# third pass merges) and two runs and a tile.
+EXTRA_LENGTHS = [6143, 6144, 6145, 12288, 12281, 22529, 2*4096 + 2048]
+# Inputs for merge path's splits (merge_values_of): the kinds the tuple above does not hold.
+MERGE_KINDS = ("interleaved", "plateau", "blocks")
+SORT_CHUNK, MERGE_TILE = 4096, 2048
+
+
+def merge_pass_tiles(n, chunk=SORT_CHUNK, tile=MERGE_TILE):
+    """[(run, [(na, nb, d0, count) per tile])] per merge pass of a segment of n values, from the
+    comment at the top of band_sort.h: pass p merges neighbouring runs of chunk*2^p values; the
+    tile of outputs [offset, offset + tile) lies in the pair of runs that starts at the multiple
+    of 2*run below offset, a = the pair's first na values, b its next nb (0: a run without a
+    partner, copied through), d0 the tile's offset in the pair and count its outputs."""
+    passes = []
+    for p in range(merge_passes(n, chunk)):
+        run, tiles = chunk << p, []
+        for offset in range(0, n, tile):
+            pair = offset//(2*run)*(2*run)
+            left = n - pair
+            na = min(left, run)
+            nb = min(left - na, run)
+            d0 = offset - pair
+            tiles.append((na, nb, d0, min(na + nb - d0, tile)))
+        passes.append((run, tiles))
+    return passes
+
+
+def merge_tiles(n, chunk=SORT_CHUNK, tile=MERGE_TILE):
+    """(na, nb, d0, count) of every tile of every merge pass of a segment of n values."""
+    for _, tiles in merge_pass_tiles(n, chunk, tile):
+        for one in tiles:
+            yield one
+
+
+def ascending(n, rng, low=1e-9):
+    """n strictly ascending positive values: no two share their bits."""
+    return low*np.cumsum(0.1 + rng.random(n))
+
+
+def plateau_bounds(n):
+    """[lo, hi) of the plateau in the sorted order of n values: [0.4 n, 0.6 n) in integers."""
+    return (2*n)//5, (3*n)//5
+
+
+def merge_values_of(kind, n, rng, signed_zeros=False, chunk=SORT_CHUNK):
+    """n float64 values of a kind of MERGE_KINDS, arranged by blocks of `chunk` values (the runs
+    after the chunk sort); the order inside a block is random.
+    "interleaved": every pair of blocks (2j, 2j + 1) holds a random share of n strictly ascending
+        values, dealt alternately: with lb the length of block 2j + 1, the pair's ranks 0, 2, ...,
+        2 lb - 2 and everything from 2 lb on go to block 2j, the ranks 1, 3, ..., 2 lb - 1 to
+        block 2j + 1 -- every split of the first pass lands inside both runs.
+    "plateau": ascending values with one plateau of equal bits at [0.4 n, 0.6 n) of the sorted
+        order (plateau_bounds), half of its copies in block 0 and half in block 1 (all in block 0
+        while n <= chunk), everything else anywhere.  signed_zeros: the plateau is zero -- below
+        it negatives, above it positives -- one half of its copies -0.0 and the other +0.0,
+        scattered at random over both blocks.
+    "blocks": block i holds the values that n strictly ascending ones have at the places of block
+        i counted from the end: every value of a block is greater than every value of each later
+        block, so every split of every pass lies at the end of a run."""
+    assert kind in MERGE_KINDS and n >= 1
+    bounds = list(range(0, n, chunk)) + [n]
+    out = np.empty(n, dtype=F64)
+    if kind == "interleaved":
+        values = ascending(n, rng)
+        order = rng.permutation(n)
+        for a in range(0, len(bounds) - 1, 2):
+            begin, middle = bounds[a], bounds[a + 1]
+            end = bounds[a + 2] if a + 2 < len(bounds) else middle
+            share = np.sort(values[order[begin:end]])
+            lb = end - middle
+            out[begin:middle] = rng.permutation(np.concatenate([share[0:2*lb:2], share[2*lb:]]))
+            out[middle:end] = rng.permutation(share[1:2*lb:2])
+        return out
+    if kind == "blocks":
+        values = ascending(n, rng)
+        for a in range(len(bounds) - 1):
+            out[bounds[a]:bounds[a + 1]] = rng.permutation(values[n - bounds[a + 1]:n - bounds[a]])
+        return out
+    lo, hi = plateau_bounds(n)
+    values = ascending(n, rng)
+    if signed_zeros and hi > lo:
+        values = values - values[lo]
+        zeros = np.zeros(hi - lo)
+        zeros[:(hi - lo)//2] = -0.
+        values[lo:hi] = rng.permutation(zeros)
+        assert np.all(values[:lo] < 0.) and np.all(values[hi:] > 0.)
+    elif hi > lo:
+        values[lo:hi] = values[lo]
+    plateau, others = values[lo:hi], rng.permutation(np.concatenate([values[:lo], values[hi:]]))
+    size0 = min(n, chunk)
+    size1 = min(n, 2*chunk) - size0
+    second = min(plateau.size - plateau.size//2, size1)      # the plateau's copies in block 1
+    first = plateau.size - second
+    assert first <= size0
+    cut0, cut1 = size0 - first, size0 - first + size1 - second
+    out[:size0] = rng.permutation(np.concatenate([plateau[:first], others[:cut0]]))
+    out[size0:size0 + size1] = rng.permutation(np.concatenate([plateau[first:],
+                                                               others[cut0:cut1]]))
+    out[size0 + size1:] = others[cut1:]
+    return out
+
+
+def sort_band_rows(rows, starts):
+    """sort_bands for many rows at once: numpy.sort of the keys along the rows of every band."""
+    out = np.array(rows, dtype=F64)
+    for b in range(len(starts) - 1):
+        a, e = int(starts[b]), int(starts[b + 1])
+        if e > a:
+            out[:, a:e] = from_keys(np.sort(keys(out[:, a:e]), axis=1))
+    return out
+
+
+def quantile_rows(sorted_rows, g_points):
+    """quantiles of one band of many rows [rows, N] at once: the same expression, elementwise."""
+    n = sorted_rows.shape[1]
+    out = np.full((sorted_rows.shape[0], len(g_points)), np.nan)
+    if n == 0:
+        return out
+    with np.errstate(invalid="ignore", over="ignore"):
+        for p, g in enumerate(g_points):
+            i, f = quantile_index(n, g)
+            k = sorted_rows[:, i]
+            out[:, p] = k + f*(sorted_rows[:, min(i + 1, n - 1)] - k)
+    return out
+
+
+def interval_mean_rows(sorted_rows, g_edges):
+    """interval_means of one band of many rows [rows, N] at once: (mean, mean of |k|), each
+    long double [rows, Q]."""
+    bounds = interval_bounds(sorted_rows.shape[1], g_edges)
+    shape = (sorted_rows.shape[0], len(g_edges) - 1)
+    mean, magnitude = np.full(shape, np.nan, dtype=LD), np.full(shape, np.nan, dtype=LD)
+    with np.errstate(invalid="ignore"):
+        for q in range(len(g_edges) - 1):
+            part = sorted_rows[:, bounds[q]:bounds[q + 1]].astype(LD)
+            if part.shape[1]:
+                mean[:, q] = np.sum(part, axis=1)/LD(part.shape[1])
+                magnitude[:, q] = np.sum(np.abs(part), axis=1)/LD(part.shape[1])
+    return mean, magnitude

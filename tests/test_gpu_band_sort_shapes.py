@@ -63,69 +63,106 @@ def plain(rows, width):
     return torch.full((rows, width), SENTINEL, dtype=torch.float64, device="cuda:0")
 
 
-def tables(starts):
+def tables(starts, g_edges=G_EDGES, g_points=G_POINTS):
     """(flat interval starts, point index, point fraction) of the bands, stated per band."""
     counts = np.diff(starts)
-    intervals = np.concatenate([starts[b] + cases.interval_bounds(n, G_EDGES)
+    intervals = np.concatenate([starts[b] + cases.interval_bounds(n, g_edges)
                                 for b, n in enumerate(counts)]).astype(np.int64)
-    index = np.full((counts.size, G_POINTS.size), -1, dtype=np.int64)
-    fraction = np.zeros((counts.size, G_POINTS.size))
+    index = np.full((counts.size, len(g_points)), -1, dtype=np.int64)
+    fraction = np.zeros((counts.size, len(g_points)))
     for b, n in enumerate(counts):
-        for p, g in enumerate(G_POINTS):
+        for p, g in enumerate(g_points):
             if n > 0:
                 index[b, p], fraction[b, p] = cases.quantile_index(n, g)
     return intervals, index, fraction
 
 
-def run(engine, values, starts, layout="aligned"):
-    """{sorted [rows, columns], means [rows, bands, Q], quantiles [rows, bands, P]} of one call;
-    the padding of the rows is checked to come back untouched."""
+WANT = ("scratch", "means", "quantiles")
+
+
+def queue(engine, values, starts, layout="aligned", g_edges=G_EDGES, g_points=G_POINTS, want=WANT,
+          asynchronous=False):
+    """Queues one call on `values` [rows, columns] and returns its blocks for collect(): `want`
+    names what the call is given beside the values -- scratch, means, quantiles."""
     import torch
     rows, columns = values.shape
-    bands, q = starts.size - 1, G_EDGES.size - 1
-    intervals, index, fraction = tables(starts)
-    data = block(values, rows, columns, layout, SENTINEL)
-    scratch = block(None, rows, columns, layout, np.nan)
-    means, quantiles = plain(rows, intervals.size - 1), plain(rows, bands*G_POINTS.size)
+    bands = starts.size - 1
+    intervals, index, fraction = tables(starts, g_edges, g_points)
+    call = {"columns": columns, "bands": bands, "q": len(g_edges) - 1, "p": len(g_points),
+            "data": block(values, rows, columns, layout, SENTINEL)}
+    keywords = {}
+    if "scratch" in want:
+        call["scratch"] = block(None, rows, columns, layout, np.nan)
+        keywords.update(scratch=Rows(call["scratch"]))
+    if "means" in want:
+        call["means"] = plain(rows, intervals.size - 1)
+        keywords.update(interval_start=intervals, means=Rows(call["means"]))
+    if "quantiles" in want:
+        call["quantiles"] = plain(rows, bands*len(g_points))
+        keywords.update(point_index=index, point_fraction=fraction,
+                        quantiles=Rows(call["quantiles"]))
     engine.order_after_stream(torch.cuda.current_stream("cuda:0").cuda_stream)
-    engine.band_distribution(Rows(data), columns, starts, scratch=Rows(scratch),
-                             interval_start=intervals, means=Rows(means), point_index=index,
-                             point_fraction=fraction, quantiles=Rows(quantiles))
-    engine.synchronize()
-    host = data.cpu().numpy()
+    engine.band_distribution(Rows(call["data"]), columns, starts, asynchronous=asynchronous,
+                             **keywords)
+    return call
+
+
+def collect(call):
+    """{sorted [rows, columns], means [rows, bands, Q], quantiles [rows, bands, P]} of a call of
+    queue() that has run (those it was given); the padding of the rows is checked to come back
+    untouched."""
+    columns, bands, q = call["columns"], call["bands"], call["q"]
+    host = call["data"].cpu().numpy()
+    rows = host.shape[0]
     assert np.all(host[:, columns:] == SENTINEL), "the padding of the rows was written"
-    flat = np.full((rows, bands*(q + 1)), np.nan)
-    flat[:, :-1] = means.cpu().numpy()
-    return {"sorted": np.ascontiguousarray(host[:, :columns]),
-            "means": np.ascontiguousarray(flat.reshape(rows, bands, q + 1)[:, :, :q]),
-            "quantiles": quantiles.cpu().numpy().reshape(rows, bands, G_POINTS.size)}
+    out = {"sorted": np.ascontiguousarray(host[:, :columns])}
+    if "means" in call:
+        flat = np.full((rows, bands*(q + 1)), np.nan)
+        flat[:, :-1] = call["means"].cpu().numpy()
+        out["means"] = np.ascontiguousarray(flat.reshape(rows, bands, q + 1)[:, :, :q])
+    if "quantiles" in call:
+        out["quantiles"] = call["quantiles"].cpu().numpy().reshape(rows, bands, call["p"])
+    return out
 
 
-def check(what, got, values, starts, finite):
+def run(engine, values, starts, layout="aligned", g_edges=G_EDGES, g_points=G_POINTS, want=WANT):
+    """{sorted [rows, columns], means [rows, bands, Q], quantiles [rows, bands, P]} of one call;
+    the padding of the rows is checked to come back untouched."""
+    call = queue(engine, values, starts, layout, g_edges, g_points, want)
+    engine.synchronize()
+    return collect(call)
+
+
+def check(what, got, values, starts, finite, g_edges=G_EDGES, g_points=G_POINTS, worst=None):
+    """finite: the means are held to their bound (in every band whose values are all finite)."""
+    worst = WORST if worst is None else worst
     expected = cases.sort_bands(values, starts)
     assert cases.same_bits(got["sorted"], expected), what
     for r in range(values.shape[0]):
         for b in range(starts.size - 1):
             band = expected[r, starts[b]:starts[b + 1]]
-            assert cases.same_bits_or_nan(got["quantiles"][r, b], cases.quantiles(band, G_POINTS)), \
+            assert cases.same_bits_or_nan(got["quantiles"][r, b], cases.quantiles(band, g_points)), \
                 (what, r, b)
             if band.size == 0:
                 assert np.all(np.isnan(got["means"][r, b])), (what, r, b)
-            if not finite or band.size == 0:
+            if not finite or band.size == 0 or not np.all(np.isfinite(band)):
                 continue
-            mean, magnitude = cases.interval_means(band, G_EDGES)
+            mean, magnitude = cases.interval_means(band, g_edges)
             empty = np.isnan(mean)
             assert np.array_equal(np.isnan(got["means"][r, b]), empty), (what, r, b)
             error = np.abs(got["means"][r, b][~empty].astype(LD) - mean[~empty])
             allowed = cases.MEAN_BOUND*magnitude[~empty]
-            WORST["means"] = max(WORST.get("means", 0.), float(np.max(error/allowed)))
+            with np.errstate(invalid="ignore"):
+                ratio = np.where(error == 0, LD(0.), error/allowed)    # (a band of zeros: 0/0)
+            worst["means"] = max(worst.get("means", 0.), float(np.max(ratio)))
             assert np.all(error <= allowed), (what, r, b)
             # counts weighted by means give the band's sum
-            counts = np.diff(cases.interval_bounds(band.size, G_EDGES))
+            counts = np.diff(cases.interval_bounds(band.size, g_edges))
             total = np.sum(counts[~empty].astype(LD)*got["means"][r, b][~empty].astype(LD))
             exact, size = np.sum(band.astype(LD)), LD(band.size)
             allowed = cases.MEAN_BOUND*np.sum(np.abs(band.astype(LD)))
-            WORST["sums"] = max(WORST.get("sums", 0.), float(abs(total - exact)/allowed))
+            if abs(total - exact) > 0:
+                worst["sums"] = max(worst.get("sums", 0.), float(abs(total - exact)/allowed))
             assert abs(total - exact) <= allowed and size > 0, (what, r, b)
 
 

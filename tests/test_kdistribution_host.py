@@ -137,3 +137,129 @@ def test_case_table_reaches_the_merge_passes(chunk):
     assert cases.merge_passes(3*chunk + 5, chunk) == 2
     assert cases.unpaired_passes(3*chunk + 5, chunk) == 0       # 4 runs: the last one short
     assert cases.unpaired_passes(2*chunk + 1, chunk) == 1
+
+
+def test_extra_lengths_reach_the_run_arithmetic():
+    """With the model of the merge tiles (cases.merge_pass_tiles, from band_sort.h's comment) the
+    lengths and the extra lengths reach every branch of the pair arithmetic at least once."""
+    chunk, tile = cases.SORT_CHUNK, cases.MERGE_TILE
+    found = set()
+    for n in cases.LENGTHS + cases.EXTRA_LENGTHS:
+        passes = cases.merge_pass_tiles(n)
+        assert len(passes) == cases.merge_passes(n, chunk)
+        assert list(cases.merge_tiles(n)) == [t for _, tiles in passes for t in tiles]
+        for p, (run, tiles) in enumerate(passes):
+            assert run == chunk << p and len(tiles) == -(-n//tile)
+            assert sum(count for _, _, _, count in tiles) == n          # the tiles tile the segment
+            for na, nb, d0, count in tiles:
+                assert 1 <= count <= tile and 0 <= nb <= na <= run and d0 % tile == 0
+                assert d0 + count <= na + nb
+                if nb == 0 and d0 > 0:
+                    found.add("copied through, d0 > 0")
+                if 0 < nb < run and nb % tile != 0:
+                    found.add("short partner, no multiple of the tile")
+                if nb == tile:
+                    found.add("partner of exactly one tile")
+                if nb == 0 and na > tile and any(
+                        b == na for _, later in passes[p + 1:] for _, b, _, _ in later):
+                    found.add("unpaired run of several tiles merged later")
+                    if na % tile != 0:
+                        found.add("that run no multiple of the tile")
+        if n == 3*chunk:
+            (_, first), (_, second) = passes
+            assert [t[:2] for t in first] == [(chunk, chunk)]*4 + [(chunk, 0)]*2
+            assert [t[:2] for t in second] == [(2*chunk, chunk)]*6
+            found.add("three full runs")
+    assert found == {"copied through, d0 > 0", "short partner, no multiple of the tile",
+                     "partner of exactly one tile", "unpaired run of several tiles merged later",
+                     "that run no multiple of the tile", "three full runs"}
+    # the lengths by name: what each is there for
+    assert list(cases.merge_tiles(6144))[-1] == (chunk, tile, 2*tile, tile)     # a full last tile
+    assert list(cases.merge_tiles(6143))[-1] == (chunk, tile - 1, 2*tile, tile - 1)
+    assert list(cases.merge_tiles(6145))[-1] == (chunk, tile + 1, 3*tile, 1)
+    assert cases.merge_pass_tiles(2*chunk + tile)[1][1][0] == (2*chunk, tile, 0, tile)
+    assert cases.merge_pass_tiles(22529)[1][1][-1] == (6145, 0, 3*tile, 1)
+    assert cases.merge_pass_tiles(22529)[2][1][0] == (4*chunk, 6145, 0, tile)
+    assert cases.merge_pass_tiles(12281)[1][1][0] == (2*chunk, chunk - 7, 0, tile)
+
+
+def sorted_blocks(values, chunk=cases.SORT_CHUNK):
+    return [np.sort(values[a:a + chunk]) for a in range(0, values.size, chunk)]
+
+
+MERGE_LENGTHS = cases.EXTRA_LENGTHS + [8192, 2**15 + 1]
+
+
+@pytest.mark.parametrize("n", MERGE_LENGTHS + [1, 5, 4096, 4097])
+def test_merge_kinds_are_what_they_say(n):
+    """Every generator of MERGE_KINDS after a chunk sort on the CPU: the interleave, the
+    plateau's place and its share of runs 0 and 1, the order of the blocks."""
+    chunk = cases.SORT_CHUNK
+    rng = np.random.default_rng(n)
+    # interleaved
+    values = cases.merge_values_of("interleaved", n, rng)
+    assert values.shape == (n,) and np.unique(values).size == n and np.all(values > 0.)
+    runs = sorted_blocks(values)
+    for a in range(0, len(runs) - 1, 2):
+        pair = np.sort(np.concatenate(runs[a:a + 2]))
+        lb = runs[a + 1].size
+        assert np.array_equal(runs[a][:lb], pair[0:2*lb:2])
+        assert np.array_equal(runs[a + 1], pair[1:2*lb:2])
+        assert np.array_equal(runs[a][lb:], pair[2*lb:])
+    if n == 8192:       # a perfect interleave: every thread's split of 8 lands mid-tile
+        assert np.array_equal(np.sort(values)[0::2], runs[0])
+    # blocks
+    values = cases.merge_values_of("blocks", n, rng)
+    assert np.unique(values).size == n
+    runs = sorted_blocks(values)
+    for a in range(len(runs) - 1):
+        assert runs[a][0] > runs[a + 1][-1]
+    # plateau, as equal bits and as signed zeros
+    lo, hi = cases.plateau_bounds(n)
+    assert lo == int(0.4*n) and hi == int(0.6*n)
+    for signed_zeros in (False, True):
+        values = cases.merge_values_of("plateau", n, rng, signed_zeros=signed_zeros)
+        ordered = cases.key_sort(values)
+        level = ordered[lo] if hi > lo else np.nan
+        on = values == level
+        assert np.count_nonzero(on) == hi - lo and np.all(ordered[lo:hi] == level)
+        assert np.all(np.diff(ordered[:lo + 1]) > 0.) and np.all(np.diff(ordered[hi - 1:]) > 0.)
+        if signed_zeros and hi > lo:
+            minus = np.signbit(ordered[lo:hi])
+            assert level == 0. and np.count_nonzero(minus) == (hi - lo)//2
+            assert np.all(minus[:(hi - lo)//2]) and not np.any(minus[(hi - lo)//2:])
+            assert np.all(ordered[:lo] < 0.) and np.all(ordered[hi:] > 0.)
+        else:
+            assert cases.same_bits(ordered[lo:hi], np.full(hi - lo, level))
+        if n > chunk and hi - lo >= 2:
+            # the plateau straddles the boundary of runs 0 and 1, and lies in no other run
+            in0, in1 = np.count_nonzero(on[:chunk]), np.count_nonzero(on[chunk:2*chunk])
+            assert in0 >= 1 and in1 >= 1 and in0 + in1 == hi - lo
+            if signed_zeros and n in MERGE_LENGTHS:
+                # both zeros on both sides: -0 of run 1 must pass +0 of run 0
+                for part in (values[:chunk], values[chunk:2*chunk]):
+                    zero = part[part == 0.]
+                    assert np.any(np.signbit(zero)) and not np.all(np.signbit(zero))
+    if n in (8192, 12288):      # the plateau of the sorted row holds a tile and a run boundary
+        assert lo < n//2 < hi and (n//2) % cases.MERGE_TILE == 0
+
+
+def test_row_oracles_are_the_band_oracles():
+    """The oracles for many rows at once give the bits of the ones for a single band."""
+    rng = np.random.default_rng(11)
+    g_edges, g_points = cases.gauss_edges(5), np.array([0., 0.013, 0.5, 0.77, 1.])
+    starts = np.array([2, 3, 12, 12, 20], dtype=np.int64)
+    values = np.stack([cases.values_of("mix" if r % 3 == 2 else "random", 23, rng)
+                       for r in range(40)])
+    ordered = cases.sort_band_rows(values, starts)
+    assert cases.same_bits(ordered, cases.sort_bands(values, starts))
+    for b in range(starts.size - 1):
+        part = ordered[:, starts[b]:starts[b + 1]]
+        quantile = cases.quantile_rows(part, g_points)
+        mean, magnitude = cases.interval_mean_rows(part, g_edges)
+        for r in range(values.shape[0]):
+            assert cases.same_bits_or_nan(quantile[r], cases.quantiles(part[r], g_points))
+            with np.errstate(invalid="ignore"):         # (NaN rows of the mix)
+                one, size = cases.interval_means(part[r], g_edges)
+            assert np.array_equal(mean[r], one, equal_nan=True)
+            assert np.array_equal(magnitude[r], size, equal_nan=True)
