@@ -41,7 +41,7 @@ def build(force=False, verbose=False):
 
 VARIANTS = {
     # name: (extra flags, what it is for) -- built beside the shipped library, loaded only when
-    # $PYLBL_AMD_LIBRARY names them (engine.library()).
+    # $PYLBL_AMD_LIBRARY names them (abi.library()).
     "ablate": (["-DLBL_ABLATE"], "engine option 'ablate' (scripts/ablate_*.sh): parts of the "
                                  "accumulate kernel switched off for timing, results wrong"),
     "asan": (["-O1", "-g", "-fsanitize=address", "-fno-gpu-sanitize", "-shared-libsan"],

@@ -186,28 +186,28 @@ class Database(object):
         library cannot be loaded (no hipcc, no HIP runtime: reading a file is not computing),
         through the standard-library sqlite3 with the same statements."""
         try:
-            from . import engine
-            status, message, fields = engine.read_line_table(self.path, name)
+            from . import abi
+            status, message, fields = abi.read_line_table(self.path, name)
         except (EngineError, OSError):
             return self._line_table_sqlite3(name)
-        if status == engine.LBL_OK:
+        if status == abi.LBL_OK:
             columns = {x: fields["columns"][i] for i, x in enumerate(LINE_COLUMNS)}
             return LineTable(
                 formula=fields["formula"], molecule_id=fields["molecule_id"],
                 local_iso_id=fields["local_iso_id"], isoid=fields["isoid"], mass=fields["mass"],
                 tips_temperature=fields["tips_temperature"], tips_data=fields["tips_data"],
                 **columns)
-        if status == engine.TABLE_NO_ALIAS:
+        if status == abi.TABLE_NO_ALIAS:
             raise AliasNotFoundError(f"{name} not found in database.")
-        if status == engine.TABLE_NO_TIPS:
+        if status == abi.TABLE_NO_TIPS:
             raise TipsDataNotFoundError(f"no tips data for {name}.")
-        if status == engine.TABLE_NOT_RECTANGULAR:
+        if status == abi.TABLE_NOT_RECTANGULAR:
             raise ValueError("tips data is not rectangular.")  # spectral_database.c:85-90
-        if status == engine.TABLE_NO_ISOTOPOLOGUES:
+        if status == abi.TABLE_NO_ISOTOPOLOGUES:
             raise IsotopologuesNotFoundError(message)
-        if status == engine.TABLE_NO_TRANSITIONS:
+        if status == abi.TABLE_NO_TRANSITIONS:
             raise TransitionsNotFoundError(message)
-        if status == engine.TABLE_OPEN_FAILED:
+        if status == abi.TABLE_OPEN_FAILED:
             raise sqlite3.OperationalError(f"unable to open database file: {self.path}")
         raise EngineError(message)
 

@@ -1,238 +1,30 @@
-"""ctypes binding of the C ABI in include/lbl_amd.h (pylbl_amd/liblbl_amd.so).
+"""Engine: one GPU's handle of the C ABI (include/lbl_amd.h), its calls as methods that check
+shapes and fill in the arguments, and the process-wide engine per device.
 
-This is the only Python<->native boundary of the package, the counterpart of
-pyLBL/c_lib/gas_optics.py:11-26,68-91 in the reference.  There is no CPU fallback: if the
-library is missing or no MI355X is visible, creating an Engine raises.
+The binding itself -- prototypes, constants, the loader -- is pylbl_amd/abi.py; the HBM and
+pinned-memory pools are pylbl_amd/device_memory.py.  There is no CPU fallback: if the library is
+missing or no MI355X is visible, creating an Engine raises.
 """
-from ctypes import CDLL, POINTER, Structure, byref, c_char_p, c_double, c_int32, c_int64, \
-                   c_void_p
+from ctypes import byref, c_double, c_int32, c_int64, c_void_p
 import os
-from pathlib import Path
 import threading
-import weakref
 
 import numpy as np
 
+# What the methods below use, and what the rest of the package, the tests and the benchmark read
+# from this module.
+from .abi import (ACCUMULATE, ASYNC, DEFER_FINISH, EXPORTED_SYMBOLS, FARFIELD, LBL_OK, MAX_BANDS,
+                  MAX_XSEC_BANDS, OUT_DEVICE, PATH_BRIGHTNESS, PATH_CONTINUE, PATH_CUMULATIVE,
+                  PATH_FLUX_UP, PATH_FROM_LAST, PATH_JACOBIAN_BOUNDARY_E,
+                  PATH_JACOBIAN_BOUNDARY_T, PATH_JACOBIAN_DEPTH, PATH_JACOBIAN_LOG_DEPTH,
+                  PATH_JACOBIAN_OUTPUTS, PATH_JACOBIAN_PER_LEVEL, PATH_JACOBIAN_TEMPERATURE,
+                  PATH_OPTICAL_DEPTH, PATH_RADIANCE, PATH_TRANSMITTANCE, RANGE_POLICIES,
+                  SCALE_DENSITY, TABLE_NO_ALIAS, TABLE_NO_ISOTOPOLOGUES, TABLE_NO_TIPS,
+                  TABLE_NO_TRANSITIONS, TABLE_NOT_RECTANGULAR, TABLE_OPEN_FAILED, VMR_COUNT,
+                  VMR_H2O, VMR_N2, VMR_O2, VMR_SELF, VMR_TOTAL, BandDescriptor, library,
+                  read_line_table)
+from .device_memory import DevicePool, DeviceSpectra, PinnedPool
 from .errors import EngineError
-
-LIBRARY_PATH = Path(__file__).resolve().parent / "liblbl_amd.so"
-
-# Mirrors of the #defines in include/lbl_amd.h.
-LBL_OK = 0
-RANGE_REFERENCE, RANGE_SKIP = 0, 1
-PREP_DEVICE, PREP_HOST = 0, 1
-OUT_DEVICE, ASYNC, SCALE_DENSITY, ACCUMULATE, FARFIELD, DEFER_FINISH = 1, 2, 4, 8, 16, 32
-RANGE_POLICIES = {"reference": RANGE_REFERENCE, "skip": RANGE_SKIP}
-# lbl_path_compute flags: a namespace of their own, clear of the call flags above.
-PATH_OPTICAL_DEPTH, PATH_TRANSMITTANCE, PATH_CUMULATIVE, PATH_FROM_LAST, PATH_CONTINUE = \
-    0x100, 0x200, 0x400, 0x800, 0x1000
-# lbl_path_radiance adds two outputs to them.
-PATH_RADIANCE, PATH_BRIGHTNESS = 0x2000, 0x4000
-# lbl_path_flux: the up sweep.
-PATH_FLUX_UP = 0x8000
-# lbl_path_jacobian: its five Jacobians, beside PATH_RADIANCE.
-PATH_JACOBIAN_DEPTH, PATH_JACOBIAN_LOG_DEPTH, PATH_JACOBIAN_TEMPERATURE, \
-    PATH_JACOBIAN_BOUNDARY_T, PATH_JACOBIAN_BOUNDARY_E = \
-    0x10000, 0x20000, 0x40000, 0x80000, 0x100000
-# Engine.path_jacobian's outputs and their flags, in the order of lbl_path_jacobian's arguments.
-PATH_JACOBIAN_OUTPUTS = (
-    ("radiance", PATH_RADIANCE), ("optical_depth_jacobian", PATH_JACOBIAN_DEPTH),
-    ("log_optical_depth_jacobian", PATH_JACOBIAN_LOG_DEPTH),
-    ("temperature_jacobian", PATH_JACOBIAN_TEMPERATURE),
-    ("boundary_temperature_jacobian", PATH_JACOBIAN_BOUNDARY_T),
-    ("boundary_emissivity_jacobian", PATH_JACOBIAN_BOUNDARY_E))
-PATH_JACOBIAN_PER_LEVEL = ("optical_depth_jacobian", "log_optical_depth_jacobian",
-                           "temperature_jacobian")
-
-EXPORTED_SYMBOLS = (
-    "lbl_engine_create", "lbl_engine_destroy", "lbl_last_error", "lbl_molecule_load",
-    "lbl_molecule_free", "lbl_compute", "lbl_compute_streamed", "lbl_finish_deferred",
-    "lbl_deferred", "lbl_cancel_deferred", "lbl_synchronize", "lbl_set_option", "lbl_timing",
-    "lbl_timing_busy",
-    "lbl_stream", "lbl_order_stream_after_engine", "lbl_order_engine_after_stream",
-    "lbl_device_alloc", "lbl_device_free", "lbl_copy_to_host",
-    "lbl_copy_rows_to_host", "lbl_host_alloc", "lbl_host_free",
-    "lbl_line_scalars", "lbl_absorption", "absorption", "lbl_compat_state", "lbl_fill_zero",
-    "lbl_version", "lbl_table_read", "lbl_table_shape", "lbl_table_copy", "lbl_table_free",
-    "lbl_molecule_load_sqlite",
-    "lbl_continuum_load", "lbl_continuum_free", "lbl_grid_load", "lbl_grid_free",
-    "lbl_continuum_compute", "lbl_continuum_compute_many", "lbl_continuum_bands",
-    "lbl_xsec_load", "lbl_xsec_free", "lbl_xsec_compute", "lbl_xsec_bands",
-    "lbl_wing_batches", "lbl_path_compute", "lbl_path_radiance", "lbl_path_flux",
-    "lbl_path_jacobian", "lbl_path_radiance_source", "lbl_path_flux_source",
-    "lbl_surface_emissivity", "lbl_path_radiance_surface",
-    "lbl_solar_spectrum", "lbl_path_solar", "lbl_band_distribution",
-    "lbl_instrument_create", "lbl_instrument_free", "lbl_instrument_apply",
-)
-
-VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
-MAX_BANDS = 8
-MAX_XSEC_BANDS = 16
-
-
-class BandDescriptor(Structure):
-    """struct lbl_band of include/lbl_amd.h."""
-    _fields_ = [("kind", c_int32), ("size", c_int32), ("lower_bound", c_double),
-                ("resolution", c_double), ("column", c_int64*4)]
-
-_library = None
-
-
-def _preload_hip_runtime():
-    """One process must hold ONE HIP runtime.  PyTorch-ROCm wheels ship their own
-    libamdhip64.so.7 (same SONAME as /opt/rocm's): when torch is imported first, this library
-    binds to torch's copy and all is well; the other way round torch finds the system runtime
-    already resident beside its own HSA libraries and sees no GPU.  So when a ROCm torch is
-    installed but not imported yet, its runtime is loaded here first (no torch import: only the
-    shared object), which makes the order irrelevant."""
-    import importlib.util
-    import os
-    import sys
-    from ctypes import RTLD_GLOBAL
-    if "torch" in sys.modules:
-        return
-    try:
-        spec = importlib.util.find_spec("torch")
-    except (ImportError, ValueError):
-        spec = None
-    if spec is None or not spec.submodule_search_locations:
-        return
-    for location in spec.submodule_search_locations:
-        candidate = os.path.join(location, "lib", "libamdhip64.so")
-        if os.path.exists(candidate):
-            try:
-                CDLL(candidate, mode=RTLD_GLOBAL)
-            except OSError:
-                pass
-            return
-
-
-def library():
-    """Loads liblbl_amd.so (once) and declares the argument types of every entry point."""
-    global _library
-    if _library is not None:
-        return _library
-    path = LIBRARY_PATH
-    if os.environ.get("PYLBL_AMD_LIBRARY"):
-        # Another build of the same engine (sanitizer / diagnostics builds, A/B of two libraries):
-        # the shipped file is never overwritten to try one.
-        path = Path(os.environ["PYLBL_AMD_LIBRARY"]).resolve()
-        if not path.exists():
-            raise EngineError(f"$PYLBL_AMD_LIBRARY names {path}, which does not exist.")
-    elif not LIBRARY_PATH.exists():
-        # A fresh checkout: compile in-tree (hipcc cross-compiles without a GPU).
-        try:
-            from . import build
-            build.build()
-        except Exception as error:
-            raise EngineError(
-                f"{LIBRARY_PATH} is missing and could not be built ({error}); build it with "
-                "`python -m pylbl_amd.build` (there is no CPU fallback).")
-    _preload_hip_runtime()
-    lib = CDLL(str(path))
-    f64p, i32p, i64p = POINTER(c_double), POINTER(c_int32), POINTER(c_int64)
-    lib.lbl_engine_create.argtypes = [c_int32, POINTER(c_void_p)]
-    lib.lbl_engine_destroy.argtypes = [c_void_p]
-    lib.lbl_last_error.argtypes = [c_void_p]
-    lib.lbl_last_error.restype = c_char_p
-    lib.lbl_molecule_load.argtypes = [c_void_p, c_int64] + [c_void_p]*7 + [c_void_p, c_void_p,
-                                     c_int32, c_int32, c_void_p, c_void_p, i32p]
-    lib.lbl_molecule_free.argtypes = [c_void_p, c_int32]
-    lib.lbl_compute.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p] + \
-                               [c_int32]*7 + [c_void_p, c_int64, i64p]
-    lib.lbl_compute_streamed.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p,
-                                         c_void_p] + [c_int32]*7 + [c_void_p, c_int64, c_void_p,
-                                                                    c_int64, c_int64, c_int32]
-    lib.lbl_finish_deferred.argtypes = [c_void_p]
-    lib.lbl_deferred.argtypes = [c_void_p]
-    lib.lbl_cancel_deferred.argtypes = [c_void_p]
-    lib.lbl_synchronize.argtypes = [c_void_p]
-    lib.lbl_set_option.argtypes = [c_void_p, c_char_p, c_int64]
-    lib.lbl_timing.argtypes = [c_void_p, f64p, i64p, c_int32]
-    lib.lbl_timing_busy.argtypes = [c_void_p, f64p]
-    lib.lbl_stream.argtypes = [c_void_p]
-    lib.lbl_stream.restype = c_void_p
-    lib.lbl_order_stream_after_engine.argtypes = [c_void_p, c_void_p]
-    lib.lbl_order_engine_after_stream.argtypes = [c_void_p, c_void_p]
-    lib.lbl_device_alloc.argtypes = [c_void_p, c_int64, POINTER(c_void_p)]
-    lib.lbl_device_free.argtypes = [c_void_p, c_void_p]
-    lib.lbl_copy_to_host.argtypes = [c_void_p, c_void_p, c_void_p, c_int64]
-    lib.lbl_copy_rows_to_host.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                          c_int64, c_int64, c_int32]
-    lib.lbl_host_alloc.argtypes = [c_void_p, c_int64, POINTER(c_void_p)]
-    lib.lbl_host_free.argtypes = [c_void_p, c_void_p]
-    lib.lbl_line_scalars.argtypes = [c_void_p, c_int32] + [c_double]*3 + [c_int32]*6 + [c_void_p]
-    lib.lbl_absorption.argtypes = [c_double]*3 + [c_int32]*3 + [c_void_p, c_char_p, c_char_p,
-                                  c_int32, c_int32]
-    lib.absorption.argtypes = lib.lbl_absorption.argtypes
-    lib.lbl_compat_state.argtypes = [i32p, i32p]
-    lib.lbl_table_read.argtypes = [c_char_p, c_char_p, POINTER(c_void_p)]
-    lib.lbl_table_shape.argtypes = [c_void_p, i64p, i32p, i32p, i32p, i32p, c_char_p, c_int32]
-    lib.lbl_table_copy.argtypes = [c_void_p] + [c_void_p]*6
-    lib.lbl_table_free.argtypes = [c_void_p]
-    lib.lbl_molecule_load_sqlite.argtypes = [c_void_p, c_char_p, c_char_p, i32p]
-    lib.lbl_fill_zero.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32]
-    lib.lbl_version.restype = c_char_p
-    lib.lbl_continuum_load.argtypes = [c_void_p, c_int32, POINTER(BandDescriptor), c_void_p,
-                                       c_int64, i32p]
-    lib.lbl_continuum_free.argtypes = [c_void_p, c_int32]
-    lib.lbl_grid_load.argtypes = [c_void_p, c_int64, c_void_p, i32p]
-    lib.lbl_grid_free.argtypes = [c_void_p, c_int32]
-    lib.lbl_continuum_compute.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p,
-                                          c_void_p, c_void_p, c_int32, c_void_p, c_int64]
-    lib.lbl_continuum_compute_many.argtypes = [c_void_p, c_int32, c_void_p, c_int32, c_int32,
-                                               c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
-                                               c_int64]
-    lib.lbl_continuum_bands.argtypes = [c_void_p, c_int32, c_double, c_double, c_void_p,
-                                        c_void_p]
-    lib.lbl_xsec_load.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, i32p]
-    lib.lbl_xsec_free.argtypes = [c_void_p, c_int32]
-    lib.lbl_xsec_compute.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
-                                     c_void_p, c_int32, c_void_p, c_int64]
-    lib.lbl_xsec_bands.argtypes = [c_void_p, c_int32, c_double, c_double, c_void_p]
-    lib.lbl_wing_batches.argtypes = [c_void_p]
-    lib.lbl_path_compute.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
-                                     c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_int32]
-    lib.lbl_path_radiance.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
-                                      c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_int32]
-    lib.lbl_path_jacobian.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
-                                      c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int32]
-    lib.lbl_path_flux.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
-                                  c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_int32]
-    # The two entries with a linear-in-tau source: edge_temperature after temperature.
-    lib.lbl_path_radiance_source.argtypes = lib.lbl_path_radiance.argtypes[:11] + [c_void_p] + \
-        lib.lbl_path_radiance.argtypes[11:]
-    lib.lbl_path_flux_source.argtypes = lib.lbl_path_flux.argtypes[:13] + [c_void_p] + \
-        lib.lbl_path_flux.argtypes[13:]
-    # The surface entries: emissivity_rows and reflection after lbl_path_radiance_source's flags.
-    lib.lbl_path_radiance_surface.argtypes = lib.lbl_path_radiance_source.argtypes + \
-        [c_void_p, c_void_p]
-    lib.lbl_surface_emissivity.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                           c_void_p, c_void_p, c_void_p, c_int64, c_int32]
-    lib.lbl_solar_spectrum.argtypes = [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
-                                       c_double, c_double, c_void_p, c_int32]
-    lib.lbl_path_solar.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
-                                   c_int32] + [c_void_p]*6 + [c_int32] + [c_void_p]*10 + [c_int32]
-    lib.lbl_band_distribution.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
-                                          c_int32, c_void_p, c_void_p, c_int32, c_void_p,
-                                          c_void_p, c_void_p, c_int32, c_void_p, c_int32]
-    lib.lbl_instrument_create.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
-                                          c_void_p, c_int32, c_void_p, c_void_p, c_int32, i32p]
-    lib.lbl_instrument_free.argtypes = [c_void_p, c_int32]
-    lib.lbl_instrument_apply.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
-                                         c_void_p]
-    for name in EXPORTED_SYMBOLS:
-        if name not in ("lbl_last_error", "lbl_stream", "lbl_version"):
-            getattr(lib, name).restype = c_int32
-    _library = lib
-    return lib
 
 
 def _f64(array):
@@ -300,44 +92,6 @@ def _address(x):
     return x.pointer if hasattr(x, "pointer") else x.ctypes.data
 
 
-# Status codes of lbl_table_read (include/lbl_amd.h).
-TABLE_OPEN_FAILED, TABLE_NO_ALIAS, TABLE_NO_TIPS, TABLE_NOT_RECTANGULAR, TABLE_NO_ISOTOPOLOGUES, \
-    TABLE_NO_TRANSITIONS = 10, 11, 12, 13, 14, 15
-
-
-def read_line_table(path, name):
-    """One molecule's rows out of an SQLite file in pyLBL's schema through the engine's own C
-    reader (lbl_table_read: the reference C reader's SELECTs, absorption.c:69-70,
-    spectral_database.c:55, :113, :143) -- no GPU involved.  Returns (status, message, fields):
-    status LBL_OK and a dict of arrays, or a TABLE_* status and the reader's message."""
-    from ctypes import create_string_buffer
-    lib = library()
-    table = c_void_p()
-    status = lib.lbl_table_read(os.fsencode(str(path)), str(name).encode(), byref(table))
-    if status != LBL_OK:
-        return status, lib.lbl_last_error(None).decode(), None
-    try:
-        n_lines, molecule_id = c_int64(), c_int32()
-        rows, num_iso, num_t = c_int32(), c_int32(), c_int32()
-        formula = create_string_buffer(256)
-        lib.lbl_table_shape(table, byref(n_lines), byref(molecule_id), byref(rows), byref(num_iso),
-                            byref(num_t), formula, 256)
-        columns = np.empty((7, n_lines.value))
-        local_iso_id = np.empty(n_lines.value, dtype=np.int32)
-        isoid = np.empty(rows.value, dtype=np.int64)
-        mass = np.empty(rows.value)
-        tips_temperature = np.empty(num_t.value)
-        tips_data = np.empty((num_iso.value, num_t.value))
-        lib.lbl_table_copy(table, columns.ctypes.data, local_iso_id.ctypes.data, isoid.ctypes.data,
-                           mass.ctypes.data, tips_temperature.ctypes.data, tips_data.ctypes.data)
-    finally:
-        lib.lbl_table_free(table)
-    return LBL_OK, "", {"formula": formula.value.decode(), "molecule_id": molecule_id.value,
-                        "columns": columns, "local_iso_id": local_iso_id, "isoid": isoid,
-                        "mass": mass, "tips_temperature": tips_temperature,
-                        "tips_data": tips_data}
-
-
 def _levels(values):
     """Per-level input as a contiguous 1-d float64 array (no copy, and none of numpy's dispatch,
     when it already is one: a call on a small grid costs the host ~35 us all told)."""
@@ -345,167 +99,6 @@ def _levels(values):
             values.flags.c_contiguous:
         return values
     return _f64(np.atleast_1d(values))
-
-
-class DeviceSpectra(object):
-    """Spectra left in HBM: [levels, n] float64 on the engine's GPU."""
-    def __init__(self, engine, levels, n):
-        self.engine = engine
-        self.shape = (int(levels), int(n))
-        self.pointer = c_void_p()
-        engine._check(engine.lib.lbl_device_alloc(engine.handle, self.shape[0]*self.shape[1]*8,
-                                                  byref(self.pointer)))
-
-    def to_host(self):
-        out = np.empty(self.shape, dtype=np.float64)
-        self.engine._check(self.engine.lib.lbl_copy_to_host(
-            self.engine.handle, out.ctypes.data, self.pointer, out.nbytes))
-        return out
-
-    def to_host_into(self, target, columns=None, asynchronous=False):
-        """Copies the first `columns` values of every row straight into `target`, a float64
-        array view [rows, columns] whose rows are contiguous (any row stride), e.g.
-        beta[:, mechanism, :].  asynchronous: queue the copy behind everything queued so far
-        and return; Engine.synchronize() waits for it (use page-locked targets,
-        Engine.host_array, or the copy blocks anyway)."""
-        columns = self.shape[1] if columns is None else int(columns)
-        if target.dtype != np.float64 or target.shape != (self.shape[0], columns) or \
-                columns > self.shape[1] or (columns > 1 and target.strides[1] != 8) or \
-                (self.shape[0] > 1 and target.strides[0] < columns*8):
-            raise ValueError("target must be float64[rows, columns] with contiguous rows.")
-        pitch = target.strides[0] if self.shape[0] > 1 else columns*8
-        self.engine._check(self.engine.lib.lbl_copy_rows_to_host(
-            self.engine.handle, target.ctypes.data, pitch, self.pointer, self.shape[1]*8,
-            columns*8, self.shape[0], ASYNC if asynchronous else 0))
-        return target
-
-    def rows(self, count):
-        """The first `count` rows of this block, as a DeviceSpectra that owns no memory (valid
-        while this block is)."""
-        if not 0 < int(count) <= self.shape[0]:
-            raise ValueError(f"rows({count}) of a block of {self.shape[0]} rows.")
-        return _DeviceRows(self, int(count))
-
-    def free(self):
-        if self.pointer:
-            self.engine.lib.lbl_device_free(self.engine.handle, self.pointer)
-            self.pointer = c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class _DeviceRows(DeviceSpectra):
-    """DeviceSpectra.rows: leading rows of a block; freeing it frees nothing."""
-    def __init__(self, block, count):
-        self.engine = block.engine
-        self.block = block
-        self.shape = (count, block.shape[1])
-        self.pointer = block.pointer
-
-    def free(self):
-        pass
-
-
-class DevicePool(object):
-    """[levels, n] blocks in HBM handed out and taken back (hipMalloc / hipFree cost more than
-    the continuum kernels that fill such a block, and hipFree stops the device)."""
-    def __init__(self, engine, limit=32 << 30):
-        self.engine = weakref.ref(engine)
-        self.limit = limit
-        self.idle = {}          # shape -> [DeviceSpectra]
-        self.idle_bytes = 0
-        self.lock = threading.RLock()       # blocks are taken and given by any thread
-
-    def take(self, levels, n):
-        shape = (int(levels), int(n))
-        with self.lock:
-            blocks = self.idle.get(shape)
-            if blocks:
-                self.idle_bytes -= shape[0]*shape[1]*8
-                return blocks.pop()
-        return DeviceSpectra(self.engine(), *shape)
-
-    def give(self, block):
-        size = block.shape[0]*block.shape[1]*8
-        with self.lock:
-            if block.pointer and self.idle_bytes + size <= self.limit:
-                self.idle.setdefault(tuple(block.shape), []).append(block)
-                self.idle_bytes += size
-                return
-        block.free()
-
-    def clear(self):
-        with self.lock:
-            idle, self.idle, self.idle_bytes = self.idle, {}, 0
-        for blocks in idle.values():
-            for block in blocks:
-                block.free()
-
-
-class PinnedPool(object):
-    """Page-locked host arrays for results.  Pinning memory is slow, so buffers are recycled:
-    when the last view of an array handed out here is garbage-collected its buffer goes back
-    to the pool (up to `limit` bytes of idle buffers are kept)."""
-    def __init__(self, engine, limit=8 << 30):
-        self.engine = weakref.ref(engine)
-        self.limit = limit
-        self.idle = []          # (capacity, pointer)
-        self.idle_bytes = 0
-        # Arrays are handed out to any thread and come back from whichever thread drops the last
-        # view (a finalizer: it may run inside array() on the same thread, hence re-entrant).
-        self.lock = threading.RLock()
-
-    def array(self, shape):
-        shape = tuple(int(x) for x in shape)
-        count = int(np.prod(shape)) if shape else 1
-        nbytes = max(count*8, 8)
-        engine = self.engine()
-        with self.lock:
-            best = None
-            for i, (capacity, _) in enumerate(self.idle):
-                if nbytes <= capacity <= 2*nbytes + (1 << 20) and \
-                        (best is None or capacity < self.idle[best][0]):
-                    best = i
-            if best is not None:
-                capacity, pointer = self.idle.pop(best)
-                self.idle_bytes -= capacity
-        if best is None:
-            capacity, handle = nbytes, c_void_p()
-            if engine.lib.lbl_host_alloc(engine.handle, capacity, byref(handle)) != LBL_OK:
-                # No more page-locked memory to be had (results held by the caller count):
-                # ordinary memory still works, copies into it are only slower.
-                self.clear()
-                return np.empty(shape, dtype=np.float64)
-            pointer = handle.value
-        from ctypes import c_char
-        buffer = (c_char*capacity).from_address(pointer)
-        weakref.finalize(buffer, PinnedPool._release, weakref.ref(self), capacity, pointer)
-        return np.frombuffer(buffer, dtype=np.float64, count=count).reshape(shape)
-
-    @staticmethod
-    def _release(pool, capacity, pointer):
-        pool = pool()
-        engine = pool.engine() if pool is not None else None
-        if engine is None or not engine.handle:
-            return                      # engine gone: the runtime reclaims the pages at exit
-        with pool.lock:
-            if pool.idle_bytes + capacity <= pool.limit:
-                pool.idle.append((capacity, pointer))
-                pool.idle_bytes += capacity
-                return
-        engine.lib.lbl_host_free(engine.handle, c_void_p(pointer))
-
-    def clear(self):
-        engine = self.engine()
-        with self.lock:
-            idle, self.idle, self.idle_bytes = self.idle, [], 0
-        for _, pointer in idle:
-            if engine is not None and engine.handle:
-                engine.lib.lbl_host_free(engine.handle, c_void_p(pointer))
 
 
 class Engine(object):

@@ -11,7 +11,7 @@ import pytest
 
 from pylbl_amd import engine as engine_module
 from pylbl_amd import spectroscopy
-from tests import jacobian_cases as jac
+from tests import abi_header, jacobian_cases as jac
 from tests import sweep_cases as cases
 from tests.test_radiance_host import make_spectroscopy
 
@@ -154,10 +154,7 @@ def test_python_mirrors_the_flags_and_binds_every_argument():
     match = re.search(r"int lbl_path_jacobian\(([^;]*)\);", HEADER)
     declared = match.group(1).count(",") + 1
     assert len(lib.lbl_path_jacobian.argtypes) == declared == 23
-    for argtype, parameter in zip(lib.lbl_path_jacobian.argtypes, match.group(1).split(",")):
-        expected = "c_void_p" if "*" in parameter else \
-            "c_long" if "int64_t" in parameter else "c_int"
-        assert argtype.__name__ == expected, parameter
+    abi_header.check_argtypes("lbl_path_jacobian", addresses=True)
     bound = inspect.signature(engine_module.Engine.path_jacobian).parameters
     for name in ("beta", "columns", "grid", "n_paths", "levels_per_path", "level_begin", "lengths",
                  "temperature", "work", "boundary_temperature", "boundary_emissivity",

@@ -12,7 +12,8 @@ import pytest
 
 from pylbl_amd import MemoryDatabase, Spectroscopy, synthetic
 from pylbl_amd import engine as engine_module, paths, spectroscopy
-from tests import linear_source_cases as linear
+from tests import abi_header, linear_source_cases as linear
+from tests.abi_header import parameters_of
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = (ROOT / "include" / "lbl_amd.h").read_text()
@@ -301,12 +302,6 @@ def test_flux_runs_get_their_slices(monkeypatch, surface):
 
 # ---------------------------------------------------------------------------------------------
 # The C ABI.
-def parameters_of(name):
-    match = re.search(r"int %s\(([^;]*)\);" % name, HEADER)
-    assert match, name
-    return [re.sub(r"\s+", " ", p).strip() for p in match.group(1).split(",")]
-
-
 @pytest.mark.parametrize("old, new, after", [
     ("lbl_path_radiance", "lbl_path_radiance_source", "const double *temperature"),
     ("lbl_path_flux", "lbl_path_flux_source", "const double *temperature"),
@@ -319,11 +314,7 @@ def test_header_declares_the_entries_beside_the_old_ones(old, new, after):
     lib = engine_module.library()
     argtypes = getattr(lib, new).argtypes
     assert len(argtypes) == len(now) == len(getattr(lib, old).argtypes) + 1
-    for argtype, parameter in zip(argtypes, now):
-        expected = "c_void_p" if "*" in parameter else \
-            "c_long" if "int64_t" in parameter else "c_int"
-        assert argtype.__name__ == expected, parameter
-    assert getattr(lib, new).restype.__name__ == "c_int"
+    abi_header.check_argtypes(new, now, addresses=True)
 
 
 def test_old_signatures_are_what_they_were():

@@ -12,7 +12,8 @@ import pytest
 
 from pylbl_amd import Spectroscopy, paths
 from pylbl_amd import engine as engine_module
-from tests import solar_cases as solar
+from tests import abi_header, solar_cases as solar
+from tests.abi_header import parameters_of
 from tests import surface_cases as surface
 from tests import sweep_cases as cases
 from tests.test_linear_source_host import make_spectroscopy
@@ -164,21 +165,9 @@ def test_requests_hold_what_the_sweep_needs():
 
 # ---------------------------------------------------------------------------------------------
 # The C ABI and the constants.
-def parameters_of(name):
-    match = re.search(r"int %s\(([^;]*)\);" % name, HEADER)
-    assert match, name
-    return [re.sub(r"\s+", " ", p).strip() for p in match.group(1).split(",")]
-
-
 def check_argtypes(name, parameters):
-    lib = engine_module.library()
-    argtypes = getattr(lib, name).argtypes
-    assert len(argtypes) == len(parameters)
-    for argtype, parameter in zip(argtypes, parameters):
-        expected = "c_void_p" if "*" in parameter else "c_double" if "double" in parameter else \
-            "c_long" if "int64_t" in parameter else "c_int"
-        assert argtype.__name__ == expected, parameter
-    assert getattr(lib, name).restype.__name__ == "c_int"
+    """The shared comparison (tests/abi_header.py); these entries take plain addresses."""
+    abi_header.check_argtypes(name, parameters, addresses=True)
     assert name in engine_module.EXPORTED_SYMBOLS
 
 
