@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/lbl_amd.h (pylbl_amd/liblbl_amd.so), and nothing else:
+"""ctypes binding of the C ABI in include/lbl_amd.h and include/lbl_amd_twostream.h
+(pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -48,6 +49,11 @@ PATH_JACOBIAN_OUTPUTS = (
     ("boundary_emissivity_jacobian", PATH_JACOBIAN_BOUNDARY_E))
 PATH_JACOBIAN_PER_LEVEL = ("optical_depth_jacobian", "log_optical_depth_jacobian",
                            "temperature_jacobian")
+# Engine.path_two_stream's outputs, in the order of lbl_path_two_stream's arguments: the fluxes at
+# the interface below each level and at interface 0 of each path, then their band means.
+PATH_TWO_STREAM_OUTPUTS = tuple(
+    prefix + name + suffix for suffix in ("_rows", "_mean") for prefix in ("", "top_")
+    for name in ("up", "down", "direct", "diffuse"))
 
 VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
 MAX_BANDS = 8
@@ -182,6 +188,17 @@ PROTOTYPES = {
 # The three that do not return int.
 RESULT_TYPES = {"lbl_last_error": c_char_p, "lbl_stream": c_void_p, "lbl_version": c_char_p}
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+# Every function of include/lbl_amd_twostream.h, the header beside lbl_amd.h that declares the
+# two-stream shortwave entries of the same library, in its order; each returns int.
+# tests/test_two_stream_host.py compares this table with that header as test_abi_host.py compares
+# PROTOTYPES with lbl_amd.h.
+TWO_STREAM_PROTOTYPES = {
+    # engine, grid, columns, cross_section, row, flags
+    "lbl_rayleigh_row": [_ptr, _i32, _i64, _ptr, _ptr, _i32],
+    # level_table, solar_zenith_cosine, solar_row, rayleigh_row, albedo_rows, albedo, n_bands,
+    # band_start, work, eight blocks of rows, their eight means, flags
+    "lbl_path_two_stream": _BLOCK + _RUN + [_ptr]*6 + [_i32] + [_ptr]*18 + [_i32],
+}
 
 _library = None
 
@@ -238,7 +255,7 @@ def library():
                 "`python -m pylbl_amd.build` (there is no CPU fallback).")
     _preload_hip_runtime()
     lib = CDLL(str(path))
-    for name, arguments in PROTOTYPES.items():
+    for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

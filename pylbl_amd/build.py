@@ -15,7 +15,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-fP
 
 
 def sources():
-    return sorted((PACKAGE / "csrc").glob("*")) + [PACKAGE.parent / "include" / "lbl_amd.h"]
+    return sorted((PACKAGE / "csrc").glob("*")) + sorted((PACKAGE.parent / "include").glob("*.h"))
 
 
 def is_stale():

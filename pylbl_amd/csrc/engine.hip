@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/lbl_amd.h"
+#include "../../include/lbl_amd_twostream.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "continuum.h"
@@ -43,6 +44,7 @@
 #include "solar.h"
 #include "surface.h"
 #include "tile_schedule.h"
+#include "twostream.h"
 
 #include "engine_core.h"
 #include "lanes_plans.inc"
@@ -498,6 +500,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "jacobian_entry.inc"
 #include "flux_entry.inc"
 #include "solar_entry.inc"
+#include "twostream_entry.inc"
 #include "band_sort_entry.inc"
 #include "instrument_entry.inc"
 #include "xsec_entry.inc"

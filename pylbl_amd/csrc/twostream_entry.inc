@@ -1,0 +1,205 @@
+// lbl_rayleigh_row: the Rayleigh scattering cross-section on the grid, from the Bucholtz fit or
+// from the caller's values; lbl_path_two_stream: two-stream shortwave fluxes at every interface of
+// whole paths through a block of absorption coefficients in HBM (kernels: twostream.h; band
+// means: path.h).  Included by engine.hip after solar_entry.inc; shares path_entry.inc's PathCall,
+// PathTables and PathBands.
+extern "C" {
+
+int lbl_rayleigh_row(lbl_engine * engine, int32_t grid, int64_t columns,
+                     const double * cross_section, double * row, int32_t flags)
+{
+    return path_entry(engine, flags, [&] {
+        PathCall call{engine, "lbl_rayleigh_row", columns, columns, 1, 1, 0, 1, flags};
+        if (row == nullptr) return call.bad("row must not be NULL.");
+        if (const char * problem = call.find_grid(grid)) return call.bad(problem);
+        if (columns < 1 || columns > call.grid->n)
+        {
+            return call.bad("need 1 <= columns <= the grid's points.");
+        }
+        if (cross_section != nullptr && !finite_at_least_zero(cross_section, columns, false))
+        {
+            return call.bad("cross-sections must be finite and >= 0.");
+        }
+
+        PathTables tables;
+        const size_t value_at = tables.add(cross_section != nullptr ? columns : 0, cross_section);
+        tables.add(1);                              // (never an empty copy)
+        const double * d_tables = call.begin(tables);
+
+        RayleighRow a;
+        a.nu = call.grid->wavenumber.data;
+        a.columns = columns;
+        a.value = cross_section != nullptr ? d_tables + value_at : nullptr;
+        a.row = row;
+        const long long per_block = (long long)kPathThreads*kPathWidth;
+        const dim3 launch((unsigned)((columns + per_block - 1)/per_block));
+        dispatch([&](auto v) {
+            hipLaunchKernelGGL(rayleigh_row_kernel<v.value>, launch, dim3(kPathThreads), 0,
+                               engine->stream, a);
+        }, path_vector(0, {row, a.nu, a.value}));
+        HIP_TRY(hipGetLastError());
+        call.note_rows(row, 1);
+        return LBL_OK;
+    });
+}
+
+int lbl_path_two_stream(lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns,
+                        int32_t n_paths, int32_t levels_per_path, int32_t level_begin,
+                        int32_t level_count, const double * level_table,
+                        const double * solar_zenith_cosine, const double * solar_row,
+                        const double * rayleigh_row, const double * albedo_rows,
+                        const double * albedo, int32_t n_bands, const int64_t * band_start,
+                        double * work, double * up_rows, double * down_rows,
+                        double * direct_rows, double * diffuse_rows, double * top_up_rows,
+                        double * top_down_rows, double * top_direct_rows,
+                        double * top_diffuse_rows, double * up_mean, double * down_mean,
+                        double * direct_mean, double * diffuse_mean, double * top_up_mean,
+                        double * top_down_mean, double * top_direct_mean,
+                        double * top_diffuse_mean, int32_t flags)
+{
+    return path_entry(engine, flags, [&] {
+        PathCall call{engine, "lbl_path_two_stream", row_stride, columns, n_paths,
+                      levels_per_path, level_begin, level_count, flags};
+        // Up, down, direct, diffuse: below each level, then at interface 0 of each path.
+        constexpr int kRows = 8, kPerLevel = 4;
+        double * const rows[kRows] = {up_rows, down_rows, direct_rows, diffuse_rows, top_up_rows,
+                                      top_down_rows, top_direct_rows, top_diffuse_rows};
+        double * const mean[kRows] = {up_mean, down_mean, direct_mean, diffuse_mean, top_up_mean,
+                                      top_down_mean, top_direct_mean, top_diffuse_mean};
+        if (beta == nullptr || level_table == nullptr || solar_zenith_cosine == nullptr ||
+            solar_row == nullptr || work == nullptr)
+        {
+            return call.bad("beta, level_table, solar_zenith_cosine, solar_row and work must not "
+                            "be NULL.");
+        }
+        if ((albedo_rows == nullptr) == (albedo == nullptr))
+        {
+            return call.bad("the surface needs an albedo: albedo_rows or albedo, not both.");
+        }
+        if (flags & ~(LBL_PATH_FROM_LAST | LBL_ASYNC))
+        {
+            return call.bad("only LBL_PATH_FROM_LAST and LBL_ASYNC may be set: a call takes "
+                            "whole paths.");
+        }
+        if (levels_per_path >= 1 &&
+            (level_begin % levels_per_path != 0 || level_count % levels_per_path != 0))
+        {
+            return call.bad("the run must consist of whole paths: level_begin and level_count "
+                            "must be multiples of levels_per_path.");
+        }
+        bool any = false;
+        for (int q = 0; q < kRows; ++q)
+        {
+            any = any || rows[q] != nullptr;
+            if (rows[q] != nullptr && (rows[q] == beta || rows[q] == work))
+            {
+                return call.bad("an output must be neither beta nor the work rows.");
+            }
+            if (mean[q] != nullptr && rows[q] == nullptr)
+            {
+                return call.bad("a band mean needs the rows it is the mean of.");
+            }
+            if (mean[q] != nullptr && n_bands == 0) return call.bad("band means need n_bands > 0.");
+        }
+        if (!any) return call.bad("no output requested.");
+        if (work == beta) return call.bad("work must not be beta.");
+        // The thicknesses are the run's lengths; the other four columns of the table follow.
+        if (level_count < 1) return call.bad("need level_count >= 1.");
+        {
+            std::vector<double> thickness((size_t)level_count);
+            for (int r = 0; r < level_count; ++r)
+            {
+                thickness[(size_t)r] = level_table[(size_t)r*kTwoStreamLevelWords];
+            }
+            if (const char * problem = call.check(thickness.data(), 1)) return call.bad(problem);
+        }
+        if (!finite_at_least_zero(level_table, (long long)level_count*kTwoStreamLevelWords, false))
+        {
+            return call.bad("the level table must be finite and >= 0.");
+        }
+        for (int r = 0; r < level_count; ++r)
+        {
+            const double * row = level_table + (size_t)r*kTwoStreamLevelWords;
+            if (!(row[3] <= row[2]) || !(row[4] <= row[3]))
+            {
+                return call.bad("the level table needs h_c <= w_c <= tau_c.");
+            }
+        }
+        for (int p = 0; p < n_paths; ++p)
+        {
+            const double mu0 = solar_zenith_cosine[p];
+            if (!(mu0 > 0. && mu0 <= 1.)) return call.bad("solar zenith cosines must lie in (0, 1].");
+            if (albedo != nullptr && !(albedo[p] >= 0. && albedo[p] <= 1.))
+            {
+                return call.bad("albedos must lie in [0, 1].");
+            }
+        }
+        PathBands bands;
+        if (const char * problem = bands.check(n_bands, band_start, columns))
+        {
+            return call.bad(problem);
+        }
+
+        const PathRun & run = call.run;
+        PathTables tables;
+        const size_t level_at =
+            tables.add((size_t)level_count*kTwoStreamLevelWords, level_table);
+        const size_t mu0_at = tables.add(run.paths, solar_zenith_cosine + run.first_path);
+        const size_t albedo_at =
+            tables.add(run.paths, albedo != nullptr ? albedo + run.first_path : nullptr);
+        tables.add(bands, band_start);
+        const double * d_tables = call.begin(tables);
+
+        PathTwoStream a;
+        call.fill(a, beta, nullptr);
+        a.level = d_tables + level_at;
+        a.mu0 = d_tables + mu0_at;
+        a.albedo = d_tables + albedo_at;
+        a.table_path = run.first_path;
+        a.solar = solar_row;
+        a.sigma = rayleigh_row;
+        a.albedo_rows = albedo_rows;
+        a.work = work;
+        for (int q = 0; q < kPerLevel; ++q)
+        {
+            a.level_out[q] = rows[q];
+            a.top_out[q] = rows[kPerLevel + q];
+        }
+        const bool vector = path_vector(row_stride, {beta, solar_row, rayleigh_row, albedo_rows,
+                                                     work, rows[0], rows[1], rows[2], rows[3],
+                                                     rows[4], rows[5], rows[6], rows[7]});
+        // Up from the surface, then down from space behind it on the same stream.  The Sun's
+        // order is from_last() (the surface is level 0); the up sweep runs against it.
+        const int sun_order = call.from_last() ? 1 : 0;
+        a.from_last = 1 - sun_order;
+        call.launch(a, [&](const dim3 & launch) {
+            dispatch([&](auto v) {
+                hipLaunchKernelGGL(two_stream_up_kernel<v.value>, launch, dim3(kPathThreads), 0,
+                                   engine->stream, a);
+            }, vector);
+        });
+        a.from_last = sun_order;
+        call.launch(a, [&](const dim3 & launch) {
+            dispatch([&](auto v) {
+                hipLaunchKernelGGL(two_stream_down_kernel<v.value>, launch, dim3(kPathThreads), 0,
+                                   engine->stream, a);
+            }, vector);
+        });
+        call.note_rows(beta, level_count);
+        call.note_rows(work, 2*(long long)level_count);
+        for (int q = 0; q < kRows; ++q)
+        {
+            call.note_rows(rows[q], q < kPerLevel ? level_count : n_paths);
+        }
+
+        // Every interface below a level of the run; interface 0 of its (whole) paths.
+        for (int q = 0; q < kRows; ++q)
+        {
+            call.means(bands, q < kPerLevel ? PathMeanRows::kLevels : PathMeanRows::kStarted,
+                       rows[q], mean[q]);
+        }
+        return LBL_OK;
+    });
+}
+
+}  // extern "C"

@@ -18,7 +18,8 @@ from .abi import (ACCUMULATE, ASYNC, DEFER_FINISH, EXPORTED_SYMBOLS, FARFIELD, L
                   PATH_FLUX_UP, PATH_FROM_LAST, PATH_JACOBIAN_BOUNDARY_E,
                   PATH_JACOBIAN_BOUNDARY_T, PATH_JACOBIAN_DEPTH, PATH_JACOBIAN_LOG_DEPTH,
                   PATH_JACOBIAN_OUTPUTS, PATH_JACOBIAN_PER_LEVEL, PATH_JACOBIAN_TEMPERATURE,
-                  PATH_OPTICAL_DEPTH, PATH_RADIANCE, PATH_TRANSMITTANCE, RANGE_POLICIES,
+                  PATH_OPTICAL_DEPTH, PATH_RADIANCE, PATH_TRANSMITTANCE, PATH_TWO_STREAM_OUTPUTS,
+                  RANGE_POLICIES,
                   SCALE_DENSITY, TABLE_NO_ALIAS, TABLE_NO_ISOTOPOLOGUES, TABLE_NO_TIPS,
                   TABLE_NO_TRANSITIONS, TABLE_NOT_RECTANGULAR, TABLE_OPEN_FAILED, VMR_COUNT,
                   VMR_H2O, VMR_N2, VMR_O2, VMR_SELF, VMR_TOTAL, BandDescriptor, library,
@@ -675,6 +676,66 @@ class Engine(object):
             _address(starts), carry.pointer, _address(interface_rows), _address(space_rows),
             _address(surface_rows), _address(reflected_rows), _address(interface_mean),
             _address(space_mean), _address(surface_mean), _address(reflected_mean), flags))
+
+    def rayleigh_row(self, grid, row, columns, cross_section=None, asynchronous=False):
+        """Fills the first `columns` values of the DeviceSpectra `row` (its first row) with the
+        Rayleigh scattering cross-section sigma [m2] on the grid (handle of load_grid) --
+        lbl_rayleigh_row: the Bucholtz (1995) fit, or cross_section [columns] (finite and >= 0)
+        as it is."""
+        values = None if cross_section is None else _f64(cross_section)
+        if values is not None and values.shape != (int(columns),):
+            raise ValueError(f"cross_section has shape {values.shape}, need [{int(columns)}].")
+        if not 0 < int(columns) <= int(row.shape[1]):
+            raise ValueError(f"{columns} columns into a row of {row.shape[1]}.")
+        self._check(self.lib.lbl_rayleigh_row(
+            self.handle, int(grid), int(columns), _address(values), row.pointer,
+            ASYNC if asynchronous else 0))
+
+    def path_two_stream(self, beta, columns, n_paths, levels_per_path, level_begin, level_table,
+                        solar_zenith_cosine, solar_row, work, rayleigh_row=None, albedo=None,
+                        albedo_rows=None, band_start=None, from_last=False, asynchronous=False,
+                        **outputs):
+        """Two-stream shortwave fluxes at every interface of the whole paths in the DeviceSpectra
+        `beta` -- lbl_path_two_stream.  Rows (whole paths), columns, band_start and asynchronous
+        as for path_jacobian; from_last: the surface lies behind level 0 of each path.
+        level_table [rows, 5]: s_l, c_l, tau_c, w_c, h_c of each row; solar_zenith_cosine one
+        per path; solar_row / rayleigh_row: DeviceSpectra whose first rows hold S and sigma
+        (rayleigh_row None: no Rayleigh scattering); albedo one per path or albedo_rows [n_paths,
+        row length], one of them; work [>= 2*rows, row length].  Outputs (DeviceSpectra
+        keywords, None: not wanted), named PATH_TWO_STREAM_OUTPUTS: up_rows, down_rows,
+        direct_rows and diffuse_rows [>= rows, row length] at the interface below each level,
+        the four top_*_rows [n_paths, row length] at interface 0, and with band_start their band
+        means *_mean [>= rows or n_paths, bands]."""
+        rows, stride = int(beta.shape[0]), int(beta.shape[1])
+        table = _f64(level_table)
+        if table.shape != (rows, 5):
+            raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
+        unknown = set(outputs) - set(PATH_TWO_STREAM_OUTPUTS)
+        if unknown:
+            raise TypeError(f"path_two_stream has no output {sorted(unknown)}.")
+        if work.shape[1] != stride or work.shape[0] < 2*rows:
+            raise ValueError(f"work has shape {work.shape}, need {2*rows} x {stride}.")
+        if solar_row.shape[1] < int(columns) or \
+                (rayleigh_row is not None and rayleigh_row.shape[1] < int(columns)):
+            raise ValueError(f"solar_row and rayleigh_row need {columns} values.")
+        mu0, albedo = _per_path(n_paths, "one cosine and one albedo per path.",
+                                solar_zenith_cosine, albedo)
+        if albedo_rows is not None and tuple(albedo_rows.shape) != (int(n_paths), stride):
+            raise ValueError("albedo_rows must be [n_paths, row length of beta].")
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path, False,
+                                           asynchronous)
+        flags |= PATH_FROM_LAST if from_last else 0
+        pointers = []
+        for name in PATH_TWO_STREAM_OUTPUTS:
+            out = outputs.get(name)
+            need = int(n_paths) if name.startswith("top_") else rows
+            _check_outputs((out,), need, n_bands if name.endswith("_mean") else stride)
+            pointers.append(_address(out))
+        self._check(self.lib.lbl_path_two_stream(
+            self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
+            int(level_begin), rows, table.ctypes.data, _address(mu0), solar_row.pointer,
+            _address(rayleigh_row), _address(albedo_rows), _address(albedo), n_bands,
+            _address(starts), work.pointer, *pointers, flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):

@@ -1,5 +1,5 @@
 """The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux,
-compute_jacobian, compute_solar and the per-level compute_kdistribution -- on the host: their quantities and units, the checks of
+compute_jacobian, compute_solar, compute_solar_flux and the per-level compute_kdistribution -- on the host: their quantities and units, the checks of
 their arguments (one request per call, made before anything touches the GPU), the run loop that sweeps the "total"
 absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
 cuts (_level_bytes) and the assembly of the results.  The sweeps themselves are the kernels of
@@ -64,6 +64,22 @@ SOLAR_PATH_QUANTITIES = ("surface_irradiance", "reflected_radiance")
 # What the sweep writes for the paths it starts beside the interface rows: F0 at the space end.
 _SPACE = "space_irradiance"
 
+# compute_solar_flux: the two-stream shortwave fluxes.  K_B: the exact SI Boltzmann constant, for
+# the air column c_l = (p_l/(K_B*T_l))*s_l of the Rayleigh optical depth.  The Bucholtz (1995) fit
+# of the Rayleigh cross-section, rows (A [cm2], B, C, D) for lambda <= and > RAYLEIGH_SPLIT um: the
+# same literals as kRayleighShort and kRayleighLong in csrc/twostream.h.
+SOLAR_FLUX_QUANTITIES = ("upward_flux", "downward_flux", "direct_irradiance",
+                         "diffuse_downward_flux", "heating_rate")
+SOLAR_FLUX_INTERFACE_QUANTITIES = SOLAR_FLUX_QUANTITIES[:4]
+K_B = 1.380649e-23                      # [J K-1]
+RAYLEIGH_SPLIT = 0.5                    # [um]
+RAYLEIGH_SHORT = (3.01577e-28, 3.55212, 1.35579, 0.11563)
+RAYLEIGH_LONG = (4.01061e-28, 3.99668, 1.10298e-3, 2.71393e-2)
+# What the entry calls the rows of a quantity, and what the sweep writes at interface 0 beside it.
+_TWO_STREAM_ROWS = {"upward_flux": "up", "downward_flux": "down", "direct_irradiance": "direct",
+                    "diffuse_downward_flux": "diffuse"}
+_TOP = "top_"
+
 # compute_kdistribution: per band and g interval, per band and g point, and on the grid.
 KDISTRIBUTION_QUANTITIES = ("absorption_g_mean", "absorption_g_quantile", "sorted_absorption")
 MAX_G_INTERVALS = 64
@@ -82,6 +98,9 @@ _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
 _FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
                "downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
                "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
+
+_SOLAR_FLUX_UNITS = dict(_FLUX_UNITS, direct_irradiance=_FLUX_UNITS["downward_flux"],
+                         diffuse_downward_flux=_FLUX_UNITS["downward_flux"])
 
 # compute_solar: on the grid (and per channel), per band.
 _SOLAR_UNITS = {"direct_irradiance": ("W m-2 (cm-1)-1", "W m-2"),
@@ -116,6 +135,14 @@ _FluxRequest = namedtuple("_FluxRequest", _COMMON + (
 _SolarRequest = namedtuple("_SolarRequest", _COMMON + (
     "surface", "mu0", "solar_lengths", "view_lengths", "albedo", "albedo_knots", "solar_knots",
     "solar_values", "scale"))
+
+# compute_solar_flux's: mu0 per path, the level table [levels, 5] of lbl_path_two_stream (s_l, c_l,
+# tau_c, w_c, h_c), the albedo per path -- [paths], or [paths, M] at albedo_knots [M] -- the Sun
+# as in _SolarRequest, and rayleigh_values: None (the fit, or no Rayleigh scattering: `rayleigh`)
+# or the caller's cross-sections [V] on the grid.
+_SolarFluxRequest = namedtuple("_SolarFluxRequest", _COMMON + (
+    "surface", "mu0", "level_table", "albedo", "albedo_knots", "solar_knots", "solar_values",
+    "scale", "rayleigh", "rayleigh_values"))
 
 # compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
 # points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
@@ -605,6 +632,115 @@ def _solar_request(spec, layer_thickness, solar_zenith_cosine, solar_irradiance,
                          solar_values=solar_values, scale=scale)
 
 
+def rayleigh_cross_section(wavenumber):
+    """sigma(nu) [m2] of compute_solar_flux in fp64, as lbl_rayleigh_row forms it: Bucholtz (1995)
+    with lambda = 1e4/nu in um, sigma = (1e-4*A)*exp(-(e*log(lambda))), e = (B + C*lambda) +
+    D/lambda, the row RAYLEIGH_SHORT for lambda <= 0.5 and RAYLEIGH_LONG above; 0 for nu <= 0."""
+    nu = np.asarray(wavenumber, dtype=np.float64)
+    positive = nu > 0.
+    lam = 1e4/np.where(positive, nu, 1.)
+    a, b, c, d = (np.where(lam <= RAYLEIGH_SPLIT, short, long)
+                  for short, long in zip(RAYLEIGH_SHORT, RAYLEIGH_LONG))
+    e = (b + c*lam) + d/lam
+    return np.where(positive, (1e-4*a)*np.exp(-(e*np.log(lam))), 0.)
+
+
+def _scatterers(spec, shape, optical_depth, single_scattering_albedo, asymmetry):
+    """(tau_c, w_c, h_c) per flat level of compute_solar_flux's grey scatterer, checked: zeros
+    without one; w_c = omega_c*tau_c and h_c = (omega_c*tau_c)*g_c in fp64."""
+    given = [x is not None for x in (optical_depth, single_scattering_albedo, asymmetry)]
+    levels = int(np.prod(shape, dtype=np.int64))
+    if not any(given):
+        return np.zeros(levels), np.zeros(levels), np.zeros(levels)
+    if not all(given):
+        raise ValueError("scatterer_optical_depth, scatterer_single_scattering_albedo and "
+                         "scatterer_asymmetry are given together or not at all.")
+    arrays = []
+    for name, value in (("scatterer_optical_depth", optical_depth),
+                        ("scatterer_single_scattering_albedo", single_scattering_albedo),
+                        ("scatterer_asymmetry", asymmetry)):
+        value = np.asarray(value, dtype=np.float64)
+        if value.shape != shape:
+            raise ValueError(f"{name} has shape {value.shape}, the atmosphere {shape}.")
+        if not np.all(np.isfinite(value)):
+            raise ValueError(f"{name} must be finite.")
+        arrays.append(value.ravel())
+    tau_c, omega_c, g_c = arrays
+    if np.any(tau_c < 0.):
+        raise ValueError("scatterer_optical_depth must be >= 0.")
+    if not np.all((omega_c >= 0.) & (omega_c <= 1.)):
+        raise ValueError("scatterer_single_scattering_albedo must lie in [0, 1].")
+    if not np.all((g_c >= 0.) & (g_c < 1.)):
+        raise ValueError("scatterer_asymmetry must lie in [0, 1).")
+    w_c = omega_c*tau_c
+    return tau_c, w_c, w_c*g_c
+
+
+def _solar_flux_request(spec, layer_thickness, solar_zenith_cosine, solar_irradiance,
+                        solar_wavenumber, distance_factor, surface, surface_albedo,
+                        albedo_wavenumber, rayleigh, rayleigh_cross_section,
+                        scatterer_optical_depth, scatterer_single_scattering_albedo,
+                        scatterer_asymmetry, quantities, band_edges, range_policy):
+    """Checks every argument of compute_solar_flux."""
+    if spec.group is not None:
+        raise NotImplementedError("compute_solar_flux does not split paths over processes yet "
+                                  "(group is set).")
+    lengths, shape = _path_geometry(spec, layer_thickness, "compute_solar_flux",
+                                    "layer_thickness", "layer thicknesses")
+    if not (isinstance(surface, str) and surface in FLUX_SURFACES):
+        raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
+    mu0 = _per_path(solar_zenith_cosine, "solar_zenith_cosine", shape)
+    if not np.all((mu0 > 0.) & (mu0 <= 1.)):
+        raise ValueError("solar_zenith_cosine must lie in (0, 1].")
+    solar_knots, solar_values, scale = _solar_spectrum(spec, solar_irradiance, solar_wavenumber,
+                                                       distance_factor)
+    albedo_knots = None
+    if albedo_wavenumber is None:
+        albedo = _per_path(surface_albedo, "surface_albedo", shape)
+        if not np.all((albedo >= 0.) & (albedo <= 1.)):
+            raise ValueError("surface albedos must lie in [0, 1].")
+    else:
+        albedo_knots, albedo = _spectral_emissivity(
+            albedo_wavenumber, surface_albedo, shape,
+            ("albedo_wavenumber", "surface_albedo", "surface albedos"))
+    if not isinstance(rayleigh, (bool, np.bool_)):
+        raise ValueError(f"rayleigh must be True or False, not {rayleigh!r}.")
+    quantities = _selection(quantities, SOLAR_FLUX_QUANTITIES)
+    rayleigh_values = None
+    if rayleigh_cross_section is not None:
+        if not rayleigh:
+            raise ValueError("rayleigh_cross_section is only used with rayleigh=True.")
+        rayleigh_values = np.asarray(rayleigh_cross_section, dtype=np.float64)
+        if rayleigh_values.shape != (spec.grid.size,):
+            raise ValueError(f"rayleigh_cross_section has shape {rayleigh_values.shape}: give "
+                             f"one value per grid point, [{spec.grid.size}].")
+        if not np.all(np.isfinite(rayleigh_values)) or np.any(rayleigh_values < 0.):
+            raise ValueError("Rayleigh cross-sections must be finite and >= 0.")
+        rayleigh_values = np.ascontiguousarray(rayleigh_values)
+    if rayleigh or "heating_rate" in quantities:
+        what = "Rayleigh scattering needs" if rayleigh else "heating rates need"
+        pressure = spec.atmosphere.pressure
+        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
+            raise ValueError(f"{what} pressures that are finite and > 0.")
+        _check_level_temperatures(spec)
+    tau_c, w_c, h_c = _scatterers(spec, shape, scatterer_optical_depth,
+                                  scatterer_single_scattering_albedo, scatterer_asymmetry)
+    column = np.zeros(lengths.size)
+    if rayleigh:
+        column = (np.asarray(spec.atmosphere.pressure, dtype=np.float64).ravel() /
+                  (K_B*np.asarray(spec.atmosphere.temperature, dtype=np.float64).ravel()))*lengths
+        if not np.all(np.isfinite(column)):
+            raise ValueError("the air columns (p/(K_B*T))*layer_thickness must be finite.")
+    _check_range_policy(range_policy)
+    edges, starts = _path_bands(spec, band_edges)
+    table = np.ascontiguousarray(np.stack([lengths, column, tau_c, w_c, h_c], axis=1))
+    return _SolarFluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                             starts=starts, instrument=None, cumulative=False, surface=surface,
+                             mu0=mu0, level_table=table, albedo=albedo, albedo_knots=albedo_knots,
+                             solar_knots=solar_knots, solar_values=solar_values, scale=scale,
+                             rayleigh=bool(rayleigh), rayleigh_values=rayleigh_values)
+
+
 def _kdistribution_request(spec, band_edges, g_edges, g_points, quantities, range_policy):
     """Checks every argument of compute_kdistribution."""
     if spec.group is not None:
@@ -869,6 +1005,48 @@ def _solar_interfaces(spec, values, request):
         out["reflected_radiance"] = np.asarray(values["reflected_radiance"]).reshape(
             shape[:-1] + [-1])
     return out
+
+
+def _solar_flux_interfaces(spec, values, request):
+    """{quantity: [..., L + 1 or L, W]} of compute_solar_flux from the sweep's rows: the fluxes at
+    the interface below each level and at interface 0 (the space end) of each path."""
+    shape = list(request.shape)
+    per_path, paths = _path_layout(request.shape)
+    widths = 1.
+    if request.starts is not None:
+        _, _, n_per_v = grid_arguments(spec.grid)
+        widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
+    fluxes = {}
+    for q in SOLAR_FLUX_INTERFACE_QUANTITIES:
+        if q not in values:
+            continue
+        width = values[q].shape[-1]
+        below = np.asarray(values[q]).reshape(paths, per_path, width)
+        space = np.asarray(values[_TOP + q]).reshape(paths, 1, width)
+        # Sweeping toward level 0 the interface below level l is interface l, toward level L-1
+        # interface l + 1.
+        fluxes[q] = np.concatenate([below, space] if request.surface == "first"
+                                   else [space, below], axis=1)*widths
+    out = {q: fluxes[q].reshape(shape[:-1] + [per_path + 1, -1])
+           for q in SOLAR_FLUX_INTERFACE_QUANTITIES if q in request.quantities}
+    if "heating_rate" in request.quantities:
+        out["heating_rate"] = heating_rate(
+            fluxes["upward_flux"], fluxes["downward_flux"],
+            spec.atmosphere.pressure.reshape(paths, per_path),
+            spec.atmosphere.temperature.reshape(paths, per_path),
+            request.lengths.reshape(paths, per_path), request.surface).reshape(shape + [-1])
+    return out
+
+
+def _create_solar_flux_dataset(spec, values, request):
+    """compute_solar_flux's result, built like _create_flux_dataset's."""
+    dims = list(spec.atmosphere.dims)
+    axis = _spectral_axis(request)
+    variables = {}
+    for q in request.quantities:
+        here = dims + [axis] if q == "heating_rate" else dims[:-1] + ["interface", axis]
+        variables[q] = (here, values[q], _SOLAR_FLUX_UNITS[q][request.edges is not None])
+    return _path_variables(spec, variables, request)
 
 
 def _create_solar_dataset(spec, values, request):

@@ -14,8 +14,8 @@ this image) -- without it the atmosphere is a plain (p, t, vmr) tuple and the re
 of numpy arrays with the same variable names.
 
 What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
-path products compute_path, compute_radiance, compute_jacobian, compute_flux and compute_solar,
-and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
+path products compute_path, compute_radiance, compute_jacobian, compute_flux, compute_solar and
+compute_solar_flux, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
 queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
 else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
 whose public names stay importable from here; their functions take the Spectroscopy first, and
@@ -32,7 +32,8 @@ from .paths import (CP_DRY, DOWNWELLING, FLUX_QUANTITIES, FLUX_SURFACES,  # noqa
                     KDISTRIBUTION_QUANTITIES, MAX_G_INTERVALS, g_intervals, g_quadrature_points,
                     interval_columns, quantile_table,
                     PATH_CUMULATIVE, PATH_QUANTITIES, PLANCK_C1, PLANCK_C2, R_DRY,
-                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOLAR_QUANTITIES,
+                    RADIANCE_DIRECTIONS, RADIANCE_QUANTITIES, SOLAR_FLUX_QUANTITIES,
+                    SOLAR_QUANTITIES,
                     SOLAR_SOLID_ANGLE, SOLAR_TEMPERATURE, SOURCES,
                     SURFACE_RADIANCE_QUANTITIES, band_columns, flux_angles,
                     heating_rate, _MAX_RUN_LEVELS, _PATH_UNITS, _Pass, _Product, _cut_runs,
@@ -805,6 +806,159 @@ class Spectroscopy(object):
                                    level_blocks=2, products=products)
         return self._create_solar_dataset(self._solar_interfaces(values, request), request)
 
+    def compute_solar_flux(self, layer_thickness, solar_zenith_cosine, solar_irradiance=None,
+                           solar_wavenumber=None, distance_factor=1., surface="first",
+                           surface_albedo=0., albedo_wavenumber=None, rayleigh=True,
+                           rayleigh_cross_section=None, scatterer_optical_depth=None,
+                           scatterer_single_scattering_albedo=None, scatterer_asymmetry=None,
+                           quantities=("upward_flux", "downward_flux"), band_edges=None,
+                           remove_pedestal=None, range_policy="reference"):
+        """Shortwave fluxes in an atmosphere that absorbs and scatters: upward and downward
+        fluxes at every layer interface, their direct and diffuse parts and heating rates, from
+        a two-stream solution of every layer (delta-scaled PIFM) and the adding method, formed
+        on the GPU in two sweeps over the "total" absorption block.  Rayleigh scattering by air
+        and one grey scatterer per level (a cloud or aerosol layer) are included; the geometry
+        is plane-parallel (there is no solar_path_length), thermal emission is not included.
+
+        Paths, levels, `surface`, layer_thickness and the Sun S(nu) as in compute_solar.  With
+        beta the absorption coefficient [m-1] of compute_absorption("total", remove_pedestal,
+        range_policy) and nu the grid [cm-1], per level l, path and grid point, each product, sum
+        and quotient rounded as written:
+            tau_a = s_l*beta ;  tau_R = c_l*sigma(nu) ;  tau = (tau_a + tau_R) + tau_c
+                  s_l = layer_thickness [m]; c_l = (p_l/(K_B*T_l))*s_l [m-2] in fp64 on the host,
+                  K_B = 1.380649e-23, 0 with rayleigh=False; tau_c the scatterer's extinction
+                  optical depth of the level (0 without);
+            tau_s = tau_R + w_c ;  omega = tau_s/tau ;  g = h_c/tau_s  (g = 0 where tau_s == 0)
+                  w_c = omega_c*tau_c and h_c = (omega_c*tau_c)*g_c, formed on the host;
+            tau == 0: the layer is the identity (Rdif = Rdir = Tdp = 0, Tdif = D = 1).
+        sigma(nu) [m2] is Bucholtz (1995) with lambda = 1e4/nu in um,
+            sigma = 1e-4*A*lambda^-(B + C*lambda + D/lambda), formed as
+            (1e-4*A)*exp(-(e*log(lambda))), e = (B + C*lambda) + D/lambda;
+            lambda <= 0.5: A = 3.01577e-28, B = 3.55212, C = 1.35579, D = 0.11563;
+            lambda > 0.5: A = 4.01061e-28, B = 3.99668, C = 1.10298e-3, D = 2.71393e-2;
+            used as they are outside 0.2 .. 4 um; 0 for nu <= 0 (paths.rayleigh_cross_section).
+        Delta scaling and PIFM coefficients (Zdunkowski, as in RRTMG_SW):
+            f = g*g ; sc = 1 - omega*f ; t = sc*tau ; w = ((1 - f)*omega)/sc ; gp = g/(1 + g)
+            g2 = (3*(w*(1 - gp)))/4 ; dif = 2*(1 - w) ; g1 = g2 + dif ; su = g1 + g2
+            g3 = (2 - 3*(mu0*gp))/4 ; g4 = 1 - g3 ; k2 = dif*su ; D = exp(-t/mu0)
+        Conservative branch, where k2*(1 + t*t) <= 1e-10:
+            x = g1*t ; Rdif = x/(1 + x) ; Tdif = 1/(1 + x)
+            Rdir = (x + (g3 - g1*mu0)*(-expm1(-t/mu0)))/(1 + x) ; Tdp = (1 - Rdir) - D
+        General branch (Meador and Weaver 1980, scaled by exp(-k t) so that nothing overflows):
+            k = sqrt(k2) ; m = mu0 ; x = k*m
+            if |1 - x| < 1e-4: m = (x >= 1 ? (1 + 1e-4) : (1 - 1e-4))/k ; x = k*m
+            Dm = exp(-t/m) ; E = exp(-(k*t)) ; E2 = E*E ; o1 = -expm1(-(2*(k*t)))
+            den = k*(1 + E2) + g1*o1 ; q = ((1 - x)*(1 + x))*den
+            Rdif = (g2*o1)/den ; Tdif = (2*(k*E))/den
+            a1 = g1*g4 + g2*g3 ; a2 = g1*g3 + g2*g4
+            Rdir = w*((1 - x)*(a2 + k*g3) - ((1 + x)*(a2 - k*g3))*E2 - (2*(k*(g3 - a2*m)))*(E*Dm))/q
+            Ttot = Dm*(1 - w*((1 + x)*(a1 + k*g4) - ((1 - x)*(a1 - k*g4))*E2)/q) + w*((2*(k*(g4 + a1*m)))*E)/q
+            Tdp = Ttot - Dm
+        Adding: interface 0 faces space, level i lies between interfaces i and i + 1 in the Sun's
+        order, A is the Lambertian albedo and F0 = mu0*S(nu):
+            up, from the surface:  Rup[L] = Rupd[L] = A ;  for i = L-1 .. 0:
+                m1 = 1/(1 - Rdif_i*Rupd[i+1])
+                Rup[i] = Rdir_i + Tdif_i*((Tdp_i*Rupd[i+1] + D_i*Rup[i+1])*m1)
+                Rupd[i] = Rdif_i + Tdif_i*((Tdif_i*Rupd[i+1])*m1)
+            down, from space:  Tb = 1, Td = 0, Rd = 0 ;  at every interface i = 0 .. L:
+                m2 = 1/(1 - Rd*Rupd[i])
+                direct[i] = F0*Tb ; diffuse_down[i] = F0*((Td + (Tb*Rup[i])*Rd)*m2)
+                up[i] = F0*((Tb*Rup[i] + Td*Rupd[i])*m2)
+                then through level i:  m3 = 1/(1 - Rd*Rdif_i)
+                Td = Tb*Tdp_i + Tdif_i*((Td + (Tb*Rd)*Rdir_i)*m3)
+                Rd = Rdif_i + Tdif_i*((Tdif_i*Rd)*m3) ; Tb = Tb*D_i
+            downward_flux = direct + diffuse_down
+        Band fluxes F_b = (band mean of F)*(n_b/n_per_v) and the heating rate, paths.heating_rate
+        of the returned upward and downward fluxes, as in compute_flux.
+        With g > 0 the direct irradiance is the delta-scaled beam: it contains the forward peak
+        of the scattered light, so it differs from compute_solar's.
+
+        Args:
+            layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
+            distance_factor, surface, band_edges: as in compute_solar.
+            surface_albedo: the Lambertian albedo A in [0, 1]: a scalar or one per path; with
+                         albedo_wavenumber [..., M] or [M], as in compute_solar.
+            rayleigh: True (needs finite pressures > 0 and temperatures > 0) or False.
+            rayleigh_cross_section: None (the fit above), or [V] values [m2] on the grid, finite
+                         and >= 0, in its place.
+            scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry:
+                         tau_c >= 0, omega_c in [0, 1] and g_c in [0, 1), shaped like the
+                         atmosphere's temperature, finite; together or not at all.
+            quantities: any of "upward_flux", "downward_flux", "direct_irradiance",
+                         "diffuse_downward_flux" (at every interface) and "heating_rate".
+
+        Returns:
+            Like compute_flux: the fluxes on the "interface" dim (L + 1: interface i of the
+            result lies between levels i-1 and i), then "wavenumber" ("W m-2 (cm-1)-1") or "band"
+            ("W m-2"); "heating_rate" with the level dim ("K day-1 (cm-1)-1" / "K day-1").
+        Raises ValueError where the blocks of one path (beta, two work blocks and one block per
+        interface quantity) exceed device_output_limit: a run holds whole paths.
+        """
+        request = paths._solar_flux_request(
+            self, layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
+            distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
+            rayleigh_cross_section, scatterer_optical_depth, scatterer_single_scattering_albedo,
+            scatterer_asymmetry, quantities, band_edges, range_policy)
+        bands = request.starts is not None
+        heating = "heating_rate" in request.quantities
+        wanted = tuple(q for q in paths.SOLAR_FLUX_INTERFACE_QUANTITIES
+                       if q in request.quantities or
+                       (heating and q in ("upward_flux", "downward_flux")))
+        # In the Sun's order, from space to the surface: "first" has its surface at level 0.
+        step = _Pass(request.surface == "first", wanted, tuple(paths._TOP + q for q in wanted))
+        names = paths._TWO_STREAM_ROWS
+
+        def sweeper(call, run):
+            grid = call.grid()
+            work = call.take(2*run)
+            solar = call.take(1)
+            sigma = call.take(1) if request.rayleigh else None
+            spectral = request.albedo_knots is not None
+            albedo_rows = call.take(call.paths) if spectral else None
+            # With bands the sweep's rows on the grid are blocks of this call, and the outputs
+            # their means; without, the outputs themselves.
+            fine = {q: call.take(run if q in step.level_quantities else call.paths)
+                    for q in step.level_quantities + step.path_quantities} if bands else {}
+            filled = []
+
+            def sweep(index, beta, a, b, outputs):
+                if not filled:
+                    call.engine.solar_spectrum(
+                        grid, solar, call.columns, irradiance=request.solar_values,
+                        wavenumber=request.solar_knots, temperature=SOLAR_TEMPERATURE,
+                        scale=request.scale, asynchronous=True)
+                    if sigma is not None:
+                        call.engine.rayleigh_row(grid, sigma, call.columns,
+                                                 cross_section=request.rayleigh_values,
+                                                 asynchronous=True)
+                    if spectral:
+                        call.engine.surface_emissivity(grid, albedo_rows, request.albedo_knots,
+                                                       request.albedo, asynchronous=True)
+                    filled.append(True)
+                blocks = {}
+                for q in wanted:
+                    for source, name in ((q, names[q]), (paths._TOP + q, paths._TOP + names[q])):
+                        if bands:
+                            block = fine[source]
+                            if source in step.level_quantities and b - a != run:
+                                block = block.rows(b - a)
+                            blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[source]
+                        else:
+                            blocks[name + "_rows"] = outputs[source]
+                call.engine.path_two_stream(
+                    beta, call.columns, call.paths, call.per_path, a, request.level_table[a:b],
+                    request.mu0, solar, work if b - a == run else work.rows(2*(b - a)),
+                    rayleigh_row=sigma, albedo=None if spectral else request.albedo,
+                    albedo_rows=albedo_rows, band_start=request.starts,
+                    from_last=step.from_last, asynchronous=True, **blocks)
+            return sweep
+        # Three blocks per level: beta and the two work rows; the interface rows on the grid
+        # count as compute_jacobian's do.
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                   level_blocks=3, grid_outputs=True, whole_paths=True)
+        return paths._create_solar_flux_dataset(
+            self, paths._solar_flux_interfaces(self, values, request), request)
+
     def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
                               quantities=("absorption_g_mean",), remove_pedestal=None,
                               range_policy="reference"):
@@ -886,6 +1040,7 @@ class Spectroscopy(object):
     _flux_interfaces = paths._flux_interfaces
     _solar_request, _solar_interfaces = paths._solar_request, paths._solar_interfaces
     _create_solar_dataset = paths._create_solar_dataset
+    _solar_flux_request = paths._solar_flux_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
 
