@@ -23,9 +23,11 @@
 //   [c1,c2):             the tile may hold points of the line's core -> core_lines(): per line
 //                        a bit mask of the rows that lie wholly in w4 region 1 (one rational
 //                        function, no selection), of the rows that may hold core points (the
-//                        reference's region chain lane by lane) and of the rest (far wing); the
-//                        inner points (|x| < xlim1) of all of them in a pass of their own,
-//                        inner_ranges();
+//                        reference's region chain lane by lane) and of the rest (far wing); a row
+//                        of the first or the last kind is a quotient in (v - centre)^2 whose
+//                        constants come with the line record, and two lines share a reciprocal
+//                        (core_pair); the inner points (|x| < xlim1) of all of them in a pass
+//                        of their own, inner_ranges();
 //   [lo,a1) and [a2,hi): the window ends inside the tile -> clipped_ranges(): eight lines with
 //                        the same window as one far-wing group with the row masked; what does not
 //                        group, and the 0-3 left-over lines of the fast ranges, line by line

@@ -1,7 +1,7 @@
 // The hot kernel's line loops: what a wavefront does with each of the cut-point ranges of its
 // tile (accumulate.h states the ranges) -- fast_ranges (far wing, eight lines per reciprocal),
-// clipped_ranges / general_line (windows that end inside the tile), core_lines / core_line (tiles
-// that may hold a line's core: voigt.c:74-189 row by row) and inner_ranges / inner_batch (the
+// clipped_ranges / general_line (windows that end inside the tile), core_lines / core_pair (tiles
+// that may hold a line's core: voigt.c:74-189 row by row, two lines per reciprocal) and inner_ranges / inner_batch (the
 // points nearer than xlim1, packed by class through LDS).  Included by accumulate.h after its
 // argument structs.
 #pragma once
@@ -135,8 +135,80 @@ __device__ __forceinline__ unsigned rows_inside(int a, int b, int i0, int rows)
     return b < a ? 0u : row_bits((a - i0 + 63) >> 6, (b - 63 - i0) >> 6, rows);
 }
 
+// One row of one line as a quotient N/T in D = (v - centre)^2, for rows on which no lane has a
+// selection to make (line_prep.h, LineCore): the far wing bl/(D + g2), or w4 region 1
+// (voigt.c:95-96 times the amplitude of voigt.c:188) bl (A + D)/(A2 + D (B + D)).  `d` = v - centre.
+struct RegionOne
+{
+    double A, B, A2;        // LineCore's, fetched once per line
+};
+
+__device__ __forceinline__ RegionOne region_one_of(const LineCore * __restrict__ c)
+{
+    return RegionOne{c->A, c->B, c->A2};
+}
+
+__device__ __forceinline__ void far_quotient(const LineWing & l, double d, double & num,
+                                             double & den)
+{
+    num = l.bl;
+    den = __builtin_fma(d, d, l.g2);
+}
+
+__device__ __forceinline__ void region_one_quotient(const LineWing & l, const RegionOne & q,
+                                                    double d, double & num, double & den)
+{
+    const double D = d*d;
+    const double n = q.A + D;
+    const double u = q.B + D;
+    den = __builtin_fma(D, u, q.A2);
+    num = l.bl*n;
+}
+
+// Bit 0 of `kind`: region 1, else the far wing (rows that take the chain do not come here).
+__device__ __forceinline__ void row_quotient(const LineWing & l, const RegionOne & q,
+                                             unsigned kind, double d, double & num, double & den)
+{
+    if (kind & 1u)
+    {
+        region_one_quotient(l, q, d, num, den);
+    }
+    else
+    {
+        far_quotient(l, d, num, den);
+    }
+}
+
+// A row that may hold a point of the line's core: the reference's chain on xi = (v-nu')*repwid
+// (voigt.c:76-84), comparison for comparison; region 0 and w4 region 1 are evaluated here, lanes
+// nearer than xlim1 add nothing (inner_ranges).  repwid and the limits are fetched only here.
+__device__ __forceinline__ double chain_row(const LineWing & l,
+                                            const LineCore * __restrict__ c, double d)
+{
+    const double xi = d*c->repwid;                  // voigt.c:76
+    const double abx = fabs(xi);
+    const bool far = abx >= c->xlim0;
+    const bool mid = !far && abx >= c->xlim1;
+    double value = 0.;
+    if (__any(far))
+    {
+        // voigt.c:82 / :24 in wavenumber units.
+        const double wing = l.bl*rcp_newton(__builtin_fma(d, d, l.g2));
+        value = far ? wing : value;
+    }
+    if (__any(mid))
+    {
+        double num, den;
+        region_one_quotient(l, region_one_of(c), d, num, den);
+        const double w4 = num*rcp_newton(den);
+        value = mid ? w4 : value;
+    }
+    return value;
+}
+
 template <int P>
-__device__ __forceinline__ void general_line(const LineWing & l, const LineCore & c,
+__device__ __forceinline__ void general_line(const LineWing & l,
+                                             const LineCore * __restrict__ c,
                                              int i0, int i1, int lane,
                                              const double (&v)[P], double (&acc)[P])
 {
@@ -147,15 +219,9 @@ __device__ __forceinline__ void general_line(const LineWing & l, const LineCore 
     }
     // Rows wholly inside the window and in w4 region 1 on every lane (line_prep.h), and rows
     // that may hold a point of the core.
-    const unsigned all_region_one = rows_inside(c.mid_first, c.mid_last, i0, P) &
-                                    ~rows_meeting(c.hole_first, c.hole_last, i0, P);
-    const unsigned near_core = rows_meeting(c.core_first, c.core_last, i0, P);
-    const double rsqrpi = 0.56418958354775628695;   // 1/sqrt(pi)
-    const double yq = c.y*c.y;
-    const double a0 = yq + 0.5;                      // voigt.c:91-93
-    const double d0 = a0*a0;
-    const double d2 = yq + yq - 1.;
-    const double r1_scale = c.amp*rsqrpi*c.y;
+    const unsigned all_region_one = rows_inside(c->mid_first, c->mid_last, i0, P) &
+                                    ~rows_meeting(c->hole_first, c->hole_last, i0, P);
+    const unsigned near_core = rows_meeting(c->core_first, c->core_last, i0, P);
 #pragma unroll
     for (int p = 0; p < P; ++p)
     {
@@ -168,9 +234,9 @@ __device__ __forceinline__ void general_line(const LineWing & l, const LineCore 
         if (all_region_one & (1u << p))
         {
             // voigt.c:95-96 with no selection left to make.
-            const double xi = d*c.repwid;
-            const double xq = xi*xi;
-            acc[p] += r1_scale*(a0 + xq)*rcp_newton(__builtin_fma(xq, d2 + xq, d0));
+            double num, den;
+            region_one_quotient(l, region_one_of(c), d, num, den);
+            acc[p] = __builtin_fma(num, rcp_newton(den), acc[p]);
             continue;
         }
         const int i = r0 + lane;
@@ -183,24 +249,7 @@ __device__ __forceinline__ void general_line(const LineWing & l, const LineCore 
         }
         else
         {
-            const double xi = d*c.repwid;               // voigt.c:76
-            const double abx = fabs(xi);
-            const double xq = abx*abx;
-            const bool far = abx >= c.xlim0;
-            const bool mid = !far && abx >= c.xlim1;
-            value = 0.;
-            if (__any(far))
-            {
-                const double wing = l.bl*rcp_newton(__builtin_fma(d, d, l.g2));
-                value = far ? wing : value;
-            }
-            if (__any(mid))
-            {
-                // voigt.c:95-96: buf = rsqrpi/(d0 + xq(d2 + xq)) * y * (a0 + xq)
-                const double w4 = r1_scale*(a0 + xq)*
-                                  rcp_newton(__builtin_fma(xq, d2 + xq, d0));
-                value = mid ? w4 : value;
-            }
+            value = chain_row(l, c, d);
         }
         acc[p] += inside ? value : 0.;
     }
@@ -431,61 +480,53 @@ __device__ __forceinline__ bool inner_batch(const LineWing * __restrict__ wing,
     return true;
 }
 
-// A line of the core range [c1, c2): its window covers the whole tile (the range lies inside
-// [a1, a2)), so what is left to decide per row is `rows`, prepared by core_lines():
+// Two lines of the core range [c1, c2): their windows cover the whole tile (the range lies inside
+// [a1, a2)), so what is left to decide per row and line is `rows`, prepared by core_lines():
 //   bit p       row p lies wholly in w4 region 1 (and inside the window): no selection at all;
-//   bit 8 + p   row p may hold a point of the core: the reference's chain lane by lane;
+//   bit 8 + p   row p may hold a point of the core and is not of the first kind: the reference's
+//               chain lane by lane;
 //   neither     the whole row is in the far wing.
+// A row of the first or the last kind is a quotient N/T in (v - centre)^2 (far_quotient,
+// region_one_quotient).  Where both lines have one, the two are merged -- N = Na Tb + Nb Ta,
+// T = Ta Tb, the far-wing loop's three operations -- and share one reciprocal and one FMA into
+// acc, whatever the kinds.  Where a line takes the chain on a row, each line goes alone there
+// (single_row): the chain for the one, its own reciprocal for the other.  The order of the
+// operations is fixed: results are bitwise the same from run to run.
+__device__ __forceinline__ double single_row(const LineWing & l, const RegionOne & q,
+                                             const LineCore * __restrict__ c, unsigned kind,
+                                             double d, double sum)
+{
+    if (kind & 0x100u)
+    {
+        return sum + chain_row(l, c, d);
+    }
+    double num, den;
+    row_quotient(l, q, kind, d, num, den);
+    return __builtin_fma(num, rcp_newton(den), sum);
+}
+
 template <int P>
-__device__ __forceinline__ void core_line(const LineWing & l, const LineCore & c, unsigned rows,
+__device__ __forceinline__ void core_pair(const LineWing & la, const LineWing & lb,
+                                          const LineCore * __restrict__ pair,
+                                          unsigned rows_a, unsigned rows_b,
                                           const double (&v)[P], double (&acc)[P])
 {
-    const double rsqrpi = 0.56418958354775628695;   // 1/sqrt(pi)
-    const double yq = c.y*c.y;
-    const double a0 = yq + 0.5;                      // voigt.c:91-93
-    const double d0 = a0*a0;
-    const double d2 = yq + yq - 1.;
-    const double r1_scale = c.amp*rsqrpi*c.y;
-    // (rows that are neither: the far wing -- most rows of most lines, so that is the path the
-    // wavefront falls through to: a taken branch costs it its instruction buffer, and the chain
-    // "region 1? / near the core? / else" took two per far-wing row)
-    const unsigned special = rows | (rows >> 8);
+    const RegionOne qa = region_one_of(pair), qb = region_one_of(pair + 1);
 #pragma unroll
     for (int p = 0; p < P; ++p)
     {
-        const double d = v[p] - l.centre;
-        if (__builtin_expect(!(special & (1u << p)), 1))
+        const double da = v[p] - la.centre, db = v[p] - lb.centre;
+        if (__builtin_expect(((rows_a | rows_b) & (0x100u << p)) == 0, 1))
         {
-            // voigt.c:82 / :24 in wavenumber units: the whole row is in the far wing.
-            acc[p] = __builtin_fma(l.bl, rcp_newton(__builtin_fma(d, d, l.g2)), acc[p]);
-        }
-        else if (rows & (1u << p))
-        {
-            // voigt.c:95-96 with no selection left to make.
-            const double xi = d*c.repwid;
-            const double xq = xi*xi;
-            acc[p] += r1_scale*(a0 + xq)*rcp_newton(__builtin_fma(xq, d2 + xq, d0));
+            double na, ta, nb, tb;
+            row_quotient(la, qa, rows_a >> p, da, na, ta);
+            row_quotient(lb, qb, rows_b >> p, db, nb, tb);
+            acc[p] = __builtin_fma(__builtin_fma(na, tb, nb*ta), rcp_newton(ta*tb), acc[p]);
         }
         else
         {
-            const double xi = d*c.repwid;               // voigt.c:76
-            const double abx = fabs(xi);
-            const double xq = abx*abx;
-            const bool far = abx >= c.xlim0;
-            const bool mid = !far && abx >= c.xlim1;
-            double value = 0.;
-            if (__any(far))
-            {
-                const double wing = l.bl*rcp_newton(__builtin_fma(d, d, l.g2));
-                value = far ? wing : value;
-            }
-            if (__any(mid))
-            {
-                const double w4 = r1_scale*(a0 + xq)*
-                                  rcp_newton(__builtin_fma(xq, d2 + xq, d0));
-                value = mid ? w4 : value;
-            }
-            acc[p] += value;
+            acc[p] = single_row(la, qa, pair, rows_a >> p, da, acc[p]);
+            acc[p] = single_row(lb, qb, pair + 1, rows_b >> p, db, acc[p]);
         }
     }
 }
@@ -506,14 +547,14 @@ __device__ __forceinline__ void core_lines(const LineWing * __restrict__ wing,
         const unsigned all_region_one = rows_inside(mine->mid_first, mine->mid_last, i0, P) &
                                         ~rows_meeting(mine->hole_first, mine->hole_last, i0, P);
         const unsigned near_core = rows_meeting(mine->core_first, mine->core_last, i0, P);
-        const unsigned packed = all_region_one | (near_core << 8);
+        const unsigned packed = all_region_one | ((near_core & ~all_region_one) << 8);
         for (int k = 0; k < n; k += 2)
         {
             const int j = begin + base + k;
             const LineWing la = wing[j], lb = wing[j + 1];
-            const LineCore ca = core[j], cb = core[j + 1];
-            core_line<P>(la, ca, (unsigned)__builtin_amdgcn_readlane((int)packed, k), v, acc);
-            core_line<P>(lb, cb, (unsigned)__builtin_amdgcn_readlane((int)packed, k + 1), v, acc);
+            core_pair<P>(la, lb, core + j,
+                         (unsigned)__builtin_amdgcn_readlane((int)packed, k),
+                         (unsigned)__builtin_amdgcn_readlane((int)packed, k + 1), v, acc);
         }
     }
 }
@@ -536,7 +577,7 @@ __device__ __forceinline__ void general_ranges(const LineWing * __restrict__ win
         const int j = general_index(rest, k);
         const LineWing l = wing[j];
         const LineCore c = core[j];
-        general_line<P>(l, c, i0, i1, lane, v, acc);
+        general_line<P>(l, &c, i0, i1, lane, v, acc);
     }
 }
 
@@ -597,7 +638,7 @@ __device__ __forceinline__ void clipped_ranges(const LineWing * __restrict__ win
         }
         const LineWing w = wing[j];
         const LineCore c = core[j];
-        general_line<P>(w, c, i0, i1, lane, v, acc);
+        general_line<P>(w, &c, i0, i1, lane, v, acc);
         k += 1;
     }
 }

@@ -56,13 +56,24 @@ struct alignas(32) LineWing
     int first, last;        // window [first, last] inclusive    spectra.c:48-62; empty if first > last
 };
 
-struct alignas(16) LineCore
+// 128 bytes, read by scalar loads a part at a time: the first 24 bytes by every row of the core
+// range that has no selection to make, the next 24 as well by a row that takes the reference's
+// chain, y and amp by the inner pass alone, the index ranges lane = line.
+//
+// A, B, A2: w4 region 1 (voigt.c:91-96) times the amplitude of voigt.c:188 as one quotient in
+// D = (v - centre)^2 -- numerator and denominator of (a0 + xq)/(d0 + xq(d2 + xq)), xq = D repwid^2,
+// divided by repwid^4, and amp rsqrpi y/repwid^2 = bl:
+//   bl (A + D)/(A2 + D (B + D)),  A = g2 + 1/(2 repwid^2),  B = 2 g2 - 1/repwid^2,  A2 = A A.
+// B + D never cancels where region 1 is evaluated (y < 8.425: D >= 164/repwid^2; else B > 0) and
+// the denominator is at least D^2 or g2^2.
+struct alignas(128) LineCore
 {
+    double A, B, A2;        // region 1 as a quotient (above)
     double repwid;          // sqrt(ln2)/alpha                   voigt.c:13
-    double y;               // repwid*gamma                      voigt.c:14
-    double amp;             // S/sqrt(pi)*repwid                 voigt.c:188
     double xlim0;           // far-wing limit                    voigt.c:34
     double xlim1;           // w4 region-1 limit                 voigt.c:35-43, :48-53
+    double y;               // repwid*gamma                      voigt.c:14
+    double amp;             // S/sqrt(pi)*repwid                 voigt.c:188
     int core_first, core_last;  // grid indices that may fall inside |x| < xlim0 (conservative)
     // Grid indices that CERTAINLY lie inside the window and inside |x| < xlim0 (one index and
     // 1e-9 of the reach inside the limit), and the indices that may lie inside |x| < xlim1 (the
@@ -71,8 +82,9 @@ struct alignas(16) LineCore
     // (voigt.c:95-96): accumulate.h evaluates it without the per-lane region chain.
     int mid_first, mid_last;
     int hole_first, hole_last;
+    int pad[10];
 };
-static_assert(sizeof(LineCore) == 64, "LineCore is read by scalar loads: 64 bytes");
+static_assert(sizeof(LineCore) == 128, "LineCore is read by scalar loads: 128 bytes");
 
 // An empty index range that intersects no row, tile or grid (including index 0).
 constexpr int kEmptyFirst = 0x3fffffff;
@@ -81,10 +93,12 @@ constexpr int kEmptyLast = -0x3fffffff;
 __host__ __device__ inline void mark_empty(LineWing & w, LineCore & c)
 {
     w.centre = 0.; w.g2 = 1.; w.bl = 0.; w.first = kEmptyFirst; w.last = kEmptyLast;
+    c.A = 1.; c.B = 0.; c.A2 = 1.;      // with bl = 0: 0 over 1 + D^2
     c.repwid = 1.; c.y = 100.; c.amp = 0.; c.xlim0 = 0.; c.xlim1 = 0.;
     c.core_first = kEmptyFirst; c.core_last = kEmptyLast;
     c.mid_first = kEmptyFirst; c.mid_last = kEmptyLast;
     c.hole_first = kEmptyFirst; c.hole_last = kEmptyLast;
+    for (int i = 0; i < 10; ++i) c.pad[i] = 0;
 }
 
 // Grid indices that may fall inside |x| < xlim1, the inner regions of a line (w4 regions 2-3,
@@ -271,6 +285,10 @@ __host__ __device__ inline int prepare_line(const LevelScalars & lv, const GridS
     c.repwid = repwid;
     c.y = y;
     c.amp = strength*rsqrpi*repwid;
+    const double inverse_r2 = 1./(repwid*repwid);
+    c.A = w.g2 + 0.5*inverse_r2;
+    c.B = (w.g2 + w.g2) - inverse_r2;
+    c.A2 = c.A*c.A;
     if (y < 70.55)
     {
         // voigt.c:34: beyond xlim0 Doppler half-widths the profile is the Lorentz wing.
