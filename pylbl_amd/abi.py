@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/lbl_amd.h and include/lbl_amd_twostream.h
-(pylbl_amd/liblbl_amd.so), and nothing else:
+"""ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h and
+include/lbl_amd_thermal.h (pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -54,6 +54,10 @@ PATH_JACOBIAN_PER_LEVEL = ("optical_depth_jacobian", "log_optical_depth_jacobian
 PATH_TWO_STREAM_OUTPUTS = tuple(
     prefix + name + suffix for suffix in ("_rows", "_mean") for prefix in ("", "top_")
     for name in ("up", "down", "direct", "diffuse"))
+# Engine.path_thermal_two_stream's, in the order of lbl_path_thermal_two_stream's arguments.
+PATH_THERMAL_OUTPUTS = tuple(
+    prefix + name + suffix for suffix in ("_rows", "_mean") for prefix in ("", "top_")
+    for name in ("up", "down"))
 
 VMR_SELF, VMR_H2O, VMR_O2, VMR_N2, VMR_TOTAL, VMR_COUNT = 0, 1, 2, 3, 4, 5
 MAX_BANDS = 8
@@ -199,6 +203,14 @@ TWO_STREAM_PROTOTYPES = {
     # band_start, work, eight blocks of rows, their eight means, flags
     "lbl_path_two_stream": _BLOCK + _RUN + [_ptr]*6 + [_i32] + [_ptr]*18 + [_i32],
 }
+# Every function of include/lbl_amd_thermal.h, the header of the two-stream longwave entry of the
+# same library; each returns int.  tests/test_thermal_host.py compares this table with that header.
+THERMAL_PROTOTYPES = {
+    # grid, the run, level_table, diffusivity, surface_temperature, emissivity_rows, emissivity,
+    # n_bands, band_start, work, four blocks of rows, their four means, flags
+    "lbl_path_thermal_two_stream": _BLOCK + [_i32] + _RUN + [_ptr, _f64, _ptr, _ptr, _ptr, _i32] +
+                                   [_ptr]*10 + [_i32],
+}
 
 _library = None
 
@@ -255,7 +267,8 @@ def library():
                 "`python -m pylbl_amd.build` (there is no CPU fallback).")
     _preload_hip_runtime()
     lib = CDLL(str(path))
-    for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()):
+    for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()) + \
+            list(THERMAL_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

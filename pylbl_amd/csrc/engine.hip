@@ -29,6 +29,7 @@
 
 #include "../../include/lbl_amd.h"
 #include "../../include/lbl_amd_twostream.h"
+#include "../../include/lbl_amd_thermal.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "continuum.h"
@@ -45,6 +46,7 @@
 #include "surface.h"
 #include "tile_schedule.h"
 #include "twostream.h"
+#include "twostream_thermal.h"
 
 #include "engine_core.h"
 #include "lanes_plans.inc"
@@ -501,6 +503,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "flux_entry.inc"
 #include "solar_entry.inc"
 #include "twostream_entry.inc"
+#include "thermal_entry.inc"
 #include "band_sort_entry.inc"
 #include "instrument_entry.inc"
 #include "xsec_entry.inc"

@@ -1,0 +1,317 @@
+// Two-stream longwave fluxes through clouds (Spectroscopy.compute_thermal_flux,
+// lbl_path_thermal_two_stream): upward and downward fluxes at every interface of whole paths, from
+// a delta-scaled two-stream layer solution with a thermal source and the adding recurrences, over
+// the "total" absorption block in HBM.  The TU builds with -ffp-contract=off: every product, sum
+// and quotient below is rounded as written.
+//
+// Per level l the table row is (s_l, tau_c, w_c, g_c, T_l); D is the diffusivity factor, one
+// scalar per call; piB(T) = kFluxPi*planck(nu, c1nu3, c2nu, T) (radiance.h, flux.h).
+//   tau_a = s_l*beta ; tau = tau_a + tau_c
+//   clear level (w_c == 0, the same for the whole wavefront):
+//     x = D*tau ; R = 0 ; T = exp(-x) ; em = -expm1(-x)
+//   cloudy level (w_c > 0; f = g_c*g_c and gp = g_c/(1 + g_c) are level scalars):
+//     omega = w_c/tau ; sc = 1 - omega*f ; t = sc*tau ; w = ((1 - f)*omega)/sc
+//     g2 = (D*(w*(1 - gp)))/2 ; dif = D*(1 - w) ; g1 = g2 + dif ; su = g1 + g2 ; k2 = dif*su
+//     conservative, where k2*(1 + t*t) <= 1e-10:
+//       x = g1*t ; R = x/(1 + x) ; T = 1/(1 + x) ; em = (dif*t)/(1 + x)
+//     general:
+//       k = sqrt(k2) ; E = exp(-(k*t)) ; E2 = E*E ; o1 = -expm1(-(2*(k*t)))
+//       den = k*(1 + E2) + g1*o1 ; R = (g2*o1)/den ; T = (2*(k*E))/den
+//       em = (k*((1 - E)*(1 - E)) + dif*o1)/den        (= 1 - R - T, without the cancellation)
+//   S = piB(T_l)*em        the layer's own emission, the same upward and downward
+// Adding, interface 0 facing space, level i between interfaces i and i + 1 in the order space ->
+// surface, eps the surface emissivity and T_s its temperature:
+//   up, from the surface:  Rs[L] = 1 - eps ; U[L] = eps*piB(T_s) ;  for i = L-1 .. 0:
+//     m1 = 1/(1 - R_i*Rs[i+1])
+//     U[i] = S_i + T_i*((U[i+1] + Rs[i+1]*S_i)*m1)
+//     Rs[i] = R_i + T_i*((T_i*Rs[i+1])*m1)
+//   down, from space:  Dn = 0, Rd = 0 ;  at every interface i = 0 .. L:
+//     m2 = 1/(1 - Rd*Rs[i])
+//     down[i] = (Dn + Rd*U[i])*m2 ; up[i] = (U[i] + Rs[i]*Dn)*m2
+//     then through level i:  m3 = 1/(1 - Rd*R_i)
+//     Dn = S_i + T_i*((Dn + Rd*S_i)*m3) ; Rd = R_i + T_i*((T_i*Rd)*m3)
+// A clear level has R = 0, so m1 = m3 = 1 exactly, x*1 = x and 0 + x = x: thermal_through leaves
+// those out where the level is clear and gives the bits of the lines above.
+//
+// thermal_layer is the layer written once; both kernels call it.  w_c == 0 is a wave-uniform
+// branch (the level's scalars are the same for the whole wavefront): a clear level costs one exp,
+// one expm1 and the Planck function, no square root and no division of the layer or the adding.
+// The kernels run on path.h's sweep skeleton, whole paths only, as twostream.h's do:
+// thermal_up_kernel sweeps surface -> space with U and Rs in registers and writes them to the work
+// rows at the interface above each level; thermal_down_kernel, queued behind it on the same
+// stream, sweeps space -> surface with Dn and Rd in registers, reads beta again and recomputes the
+// layer instead of reading three stored quantities (48 B per element beside beta's 8 B), reads the
+// work rows and stores the flux rows asked for; the lane that starts a path writes the rows of
+// interface 0.  nu, C2*nu and C1*nu^3 are formed once per lane, as in flux.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/lbl_amd.h"
+#include "flux.h"
+#include "path.h"
+#include "radiance.h"
+
+namespace lbl {
+
+constexpr double kThermalConservative = 1e-10;      // k2*(1 + t*t) at most: the conservative branch
+constexpr int kThermalLevelWords = 5;               // s_l, tau_c, w_c, g_c, T_l per level
+constexpr int kThermalUpAhead = kPathAhead;         // rows of beta in flight per lane, going up
+constexpr int kThermalDownAhead = 1;              // going down: more rows spill scalar registers
+
+struct PathThermal : PathLevels
+{
+    const double * nu;          // [columns]: the grid [cm-1]
+    const double * level;       // [count][5]: s_l, tau_c, w_c, g_c, T_l of flat level first + i
+    double diffusivity;         // D
+    const double * surface_t;   // [paths of the run]: surface temperature [K]
+    const double * surface_e;   // [paths of the run]: scalar emissivity (without emissivity_rows)
+    int table_path;             // path of surface_t[0] / surface_e[0]
+    const double * emissivity_rows; // [paths][stride]: eps per path and column, or null
+    double * work;              // [count][2][stride]: U, Rs at the interface above each level
+    double * level_out[2];      // up, down at the interface below each level (null: not wanted)
+    double * top_out[2];        // [paths][stride]: the same at interface 0
+};
+
+// What a layer does to diffuse light, and the fraction of piB(T_l) it emits either way.
+struct ThermalLayer
+{
+    double r, t, em;
+};
+
+// The level's scalars, read once per level and wavefront.
+struct ThermalLevel
+{
+    double s, tau_c, w_c, f, gp, temperature;
+    bool clear;
+};
+
+__device__ __forceinline__ ThermalLevel thermal_level(const double * row)
+{
+    ThermalLevel v;
+    v.s = row[0];
+    v.tau_c = row[1];
+    v.w_c = row[2];
+    v.temperature = row[4];
+    v.clear = v.w_c == 0.;
+    v.f = 0.;
+    v.gp = 0.;
+    if (!v.clear)
+    {
+        const double g_c = row[3];
+        v.f = g_c*g_c;
+        v.gp = g_c/(1. + g_c);
+    }
+    return v;
+}
+
+// The layer of one level and grid point (the formulas in the head of this file).  v: the level's
+// scalars; d: the diffusivity factor; b: beta.
+__device__ __forceinline__ ThermalLayer thermal_layer(const ThermalLevel & v, double d, double b)
+{
+    ThermalLayer y;
+    const double tau_a = v.s*b;
+    const double tau = tau_a + v.tau_c;
+    if (v.clear)
+    {
+        const double x = d*tau;
+        y.r = 0.;
+        y.t = exp(-x);
+        y.em = -expm1(-x);
+        return y;
+    }
+    const double omega = v.w_c/tau;
+    const double sc = 1. - omega*v.f;
+    const double t = sc*tau;
+    const double w = ((1. - v.f)*omega)/sc;
+    const double g2 = (d*(w*(1. - v.gp)))/2.;
+    const double dif = d*(1. - w);
+    const double g1 = g2 + dif;
+    const double su = g1 + g2;
+    const double k2 = dif*su;
+    if (k2*(1. + t*t) <= kThermalConservative)
+    {
+        const double x = g1*t;
+        y.r = x/(1. + x);
+        y.t = 1./(1. + x);
+        y.em = (dif*t)/(1. + x);
+        return y;
+    }
+    const double k = sqrt(k2);
+    const double e = exp(-(k*t));
+    const double e2 = e*e;
+    const double o1 = -expm1(-(2.*(k*t)));
+    const double den = k*(1. + e2) + g1*o1;
+    y.r = (g2*o1)/den;
+    y.t = (2.*(k*e))/den;
+    y.em = (k*((1. - e)*(1. - e)) + dif*o1)/den;
+    return y;
+}
+
+// One adding step through a level, the same lines upward and downward: what arrives (flux, with
+// the reflectance refl of what lies behind it) becomes what leaves on the level's other side.
+//   m = 1/(1 - R*refl) ; flux = S + T*((flux + refl*S)*m) ; refl = R + T*((T*refl)*m)
+// clear: R = 0 and m = 1 exactly, left out.
+__device__ __forceinline__ void thermal_through(bool clear, const ThermalLayer & y, double source,
+                                                double & flux, double & refl)
+{
+    if (clear)
+    {
+        flux = source + y.t*(flux + refl*source);
+        refl = y.t*(y.t*refl);
+        return;
+    }
+    const double m = 1./(1. - y.r*refl);
+    flux = source + y.t*((flux + refl*source)*m);
+    refl = y.r + y.t*((y.t*refl)*m);
+}
+
+// What a lane forms once of its columns of the grid.
+struct ThermalColumns
+{
+    double nu[kPathWidth], c1nu3[kPathWidth], c2nu[kPathWidth];
+};
+
+template <bool kVector>
+__device__ __forceinline__ ThermalColumns thermal_columns(const PathThermal & a, const PathLane & l)
+{
+    ThermalColumns c;
+    path_load<kVector>(a.nu + l.j, l.width, c.nu);
+#pragma unroll
+    for (int i = 0; i < kPathWidth; ++i)
+    {
+        c.c1nu3[i] = ((LBL_PLANCK_C1*c.nu[i])*c.nu[i])*c.nu[i];
+        c.c2nu[i] = LBL_PLANCK_C2*c.nu[i];
+    }
+    return c;
+}
+
+__device__ __forceinline__ double thermal_pi_planck(const ThermalColumns & c, int i, double t)
+{
+    return kFluxPi*planck(c.nu[i], c.c1nu3[i], c.c2nu[i], t);
+}
+
+// The surface of path l.p: U[L] = eps*piB(T_s) and Rs[L] = 1 - eps.
+template <bool kVector>
+__device__ __forceinline__ void thermal_surface(const PathThermal & a, const PathLane & l,
+                                                const ThermalColumns & c, double (&u)[kPathWidth],
+                                                double (&rs)[kPathWidth])
+{
+    double eps[kPathWidth];
+    if (a.emissivity_rows != nullptr)
+    {
+        path_load<kVector>(a.emissivity_rows + (long long)l.p*a.stride + l.j, l.width, eps);
+    }
+    else
+    {
+        const double scalar = a.surface_e[l.p - a.table_path];
+#pragma unroll
+        for (int i = 0; i < kPathWidth; ++i) eps[i] = scalar;
+    }
+    const double ts = a.surface_t[l.p - a.table_path];
+#pragma unroll
+    for (int i = 0; i < kPathWidth; ++i)
+    {
+        rs[i] = 1. - eps[i];
+        u[i] = eps[i]*thermal_pi_planck(c, i, ts);
+    }
+}
+
+// The two fluxes of an interface where what comes from above is (dn, rd) and what lies below
+// sends up u and reflects rs, stored at offset `at` of the rows `out` (null: not wanted).
+template <bool kVector>
+__device__ __forceinline__ void thermal_interface(
+    double * const (&out)[2], long long at, int width, const double (&dn)[kPathWidth],
+    const double (&rd)[kPathWidth], const double (&u)[kPathWidth], const double (&rs)[kPathWidth])
+{
+    double up[kPathWidth], down[kPathWidth];
+#pragma unroll
+    for (int i = 0; i < kPathWidth; ++i)
+    {
+        const double m2 = 1./(1. - rd[i]*rs[i]);
+        down[i] = (dn[i] + rd[i]*u[i])*m2;
+        up[i] = (u[i] + rs[i]*dn[i])*m2;
+    }
+    if (out[0] != nullptr) path_store<kVector>(out[0] + at, width, up);
+    if (out[1] != nullptr) path_store<kVector>(out[1] + at, width, down);
+}
+
+// grid and kVector as for path_sweep_kernel; a.from_last is the order of this sweep, surface to
+// space.  Whole paths: every lane starts and finishes its path.
+template <bool kVector>
+__global__ __launch_bounds__(kPathThreads) void thermal_up_kernel(PathThermal a)
+{
+    const PathLane l = path_lane(a);
+    if (l.idle) return;
+    const double * level = a.level + (long long)l.index0*kThermalLevelWords;
+    const int width = l.width;
+    const double d = a.diffusivity;
+    const ThermalColumns c = thermal_columns<kVector>(a, l);
+
+    double u[kPathWidth], rs[kPathWidth];
+    thermal_surface<kVector>(a, l, c, u, rs);
+
+    path_levels<kThermalUpAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
+                                                      long long at) {
+        const ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
+#pragma unroll
+        for (int i = 0; i < kPathWidth; ++i)
+        {
+            const ThermalLayer y = thermal_layer(v, d, b[i]);
+            const double source = thermal_pi_planck(c, i, v.temperature)*y.em;
+            thermal_through(v.clear, y, source, u[i], rs[i]);
+        }
+        double * work = a.work + (2*at - l.j);
+        path_store<kVector>(work, width, u);
+        path_store<kVector>(work + a.stride, width, rs);
+    });
+}
+
+// grid and kVector as for path_sweep_kernel; a.from_last is the order space to surface.
+template <bool kVector>
+__global__ __launch_bounds__(kPathThreads) void thermal_down_kernel(PathThermal a)
+{
+    const PathLane l = path_lane(a);
+    if (l.idle) return;
+    const double * level = a.level + (long long)l.index0*kThermalLevelWords;
+    const int width = l.width;
+    const double d = a.diffusivity;
+    const ThermalColumns c = thermal_columns<kVector>(a, l);
+
+    double dn[kPathWidth], rd[kPathWidth], u[kPathWidth], rs[kPathWidth];
+#pragma unroll
+    for (int i = 0; i < kPathWidth; ++i) dn[i] = rd[i] = 0.;
+    // Interface 0: what the whole path sends up and reflects is in the work rows of the first
+    // level.
+    {
+        const double * work = a.work + (2*l.level0 - l.j);
+        path_load<kVector>(work, width, u);
+        path_load<kVector>(work + a.stride, width, rs);
+        thermal_interface<kVector>(a.top_out, (long long)l.p*a.stride + l.j, width, dn, rd, u, rs);
+    }
+    path_levels<kThermalDownAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
+                                                        long long at) {
+        const ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
+#pragma unroll
+        for (int i = 0; i < kPathWidth; ++i)
+        {
+            const ThermalLayer y = thermal_layer(v, d, b[i]);
+            const double source = thermal_pi_planck(c, i, v.temperature)*y.em;
+            thermal_through(v.clear, y, source, dn[i], rd[i]);
+        }
+        // What lies below this level: the next level's work rows, or the surface.
+        if (k + 1 < l.n)
+        {
+            const double * work = a.work + (2*(at + l.row_step) - l.j);
+            path_load<kVector>(work, width, u);
+            path_load<kVector>(work + a.stride, width, rs);
+        }
+        else
+        {
+            thermal_surface<kVector>(a, l, c, u, rs);
+        }
+        thermal_interface<kVector>(a.level_out, at, width, dn, rd, u, rs);
+    });
+}
+
+}  // namespace lbl

@@ -18,8 +18,8 @@ from .abi import (ACCUMULATE, ASYNC, DEFER_FINISH, EXPORTED_SYMBOLS, FARFIELD, L
                   PATH_FLUX_UP, PATH_FROM_LAST, PATH_JACOBIAN_BOUNDARY_E,
                   PATH_JACOBIAN_BOUNDARY_T, PATH_JACOBIAN_DEPTH, PATH_JACOBIAN_LOG_DEPTH,
                   PATH_JACOBIAN_OUTPUTS, PATH_JACOBIAN_PER_LEVEL, PATH_JACOBIAN_TEMPERATURE,
-                  PATH_OPTICAL_DEPTH, PATH_RADIANCE, PATH_TRANSMITTANCE, PATH_TWO_STREAM_OUTPUTS,
-                  RANGE_POLICIES,
+                  PATH_OPTICAL_DEPTH, PATH_RADIANCE, PATH_THERMAL_OUTPUTS, PATH_TRANSMITTANCE,
+                  PATH_TWO_STREAM_OUTPUTS, RANGE_POLICIES,
                   SCALE_DENSITY, TABLE_NO_ALIAS, TABLE_NO_ISOTOPOLOGUES, TABLE_NO_TIPS,
                   TABLE_NO_TRANSITIONS, TABLE_NOT_RECTANGULAR, TABLE_OPEN_FAILED, VMR_COUNT,
                   VMR_H2O, VMR_N2, VMR_O2, VMR_SELF, VMR_TOTAL, BandDescriptor, library,
@@ -735,6 +735,48 @@ class Engine(object):
             self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
             int(level_begin), rows, table.ctypes.data, _address(mu0), solar_row.pointer,
             _address(rayleigh_row), _address(albedo_rows), _address(albedo), n_bands,
+            _address(starts), work.pointer, *pointers, flags))
+
+    def path_thermal_two_stream(self, beta, columns, grid, n_paths, levels_per_path, level_begin,
+                                level_table, surface_temperature, work, diffusivity=1.66,
+                                emissivity=None, emissivity_rows=None, band_start=None,
+                                from_last=False, asynchronous=False, **outputs):
+        """Two-stream longwave fluxes at every interface of the whole paths in the DeviceSpectra
+        `beta` -- lbl_path_thermal_two_stream.  Rows (whole paths), columns, band_start,
+        from_last and asynchronous as for path_two_stream; grid as for path_flux.
+        level_table [rows, 5]: s_l, tau_c, w_c, g_c, T_l of each row; diffusivity: D in [1, 2];
+        surface_temperature one per path; emissivity one per path or emissivity_rows [n_paths,
+        row length], one of them; work [>= 2*rows, row length].  Outputs (DeviceSpectra
+        keywords, None: not wanted), named PATH_THERMAL_OUTPUTS: up_rows and down_rows [>= rows,
+        row length] at the interface below each level, top_up_rows and top_down_rows [n_paths,
+        row length] at interface 0, and with band_start their band means *_mean [>= rows or
+        n_paths, bands]."""
+        rows, stride = int(beta.shape[0]), int(beta.shape[1])
+        table = _f64(level_table)
+        if table.shape != (rows, 5):
+            raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
+        unknown = set(outputs) - set(PATH_THERMAL_OUTPUTS)
+        if unknown:
+            raise TypeError(f"path_thermal_two_stream has no output {sorted(unknown)}.")
+        if work.shape[1] != stride or work.shape[0] < 2*rows:
+            raise ValueError(f"work has shape {work.shape}, need {2*rows} x {stride}.")
+        ts, emissivity = _per_path(n_paths, "one surface temperature and one emissivity per "
+                                   "path.", surface_temperature, emissivity)
+        if emissivity_rows is not None and tuple(emissivity_rows.shape) != (int(n_paths), stride):
+            raise ValueError("emissivity_rows must be [n_paths, row length of beta].")
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path, False,
+                                           asynchronous)
+        flags |= PATH_FROM_LAST if from_last else 0
+        pointers = []
+        for name in PATH_THERMAL_OUTPUTS:
+            out = outputs.get(name)
+            need = int(n_paths) if name.startswith("top_") else rows
+            _check_outputs((out,), need, n_bands if name.endswith("_mean") else stride)
+            pointers.append(_address(out))
+        self._check(self.lib.lbl_path_thermal_two_stream(
+            self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
+            int(levels_per_path), int(level_begin), rows, table.ctypes.data, float(diffusivity),
+            _address(ts), _address(emissivity_rows), _address(emissivity), n_bands,
             _address(starts), work.pointer, *pointers, flags))
 
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,

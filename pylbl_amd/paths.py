@@ -1,5 +1,6 @@
 """The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux,
-compute_jacobian, compute_solar, compute_solar_flux and the per-level compute_kdistribution -- on the host: their quantities and units, the checks of
+compute_jacobian, compute_solar, compute_solar_flux, compute_thermal_flux and the per-level
+compute_kdistribution -- on the host: their quantities and units, the checks of
 their arguments (one request per call, made before anything touches the GPU), the run loop that sweeps the "total"
 absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
 cuts (_level_bytes) and the assembly of the results.  The sweeps themselves are the kernels of
@@ -80,6 +81,12 @@ _TWO_STREAM_ROWS = {"upward_flux": "up", "downward_flux": "down", "direct_irradi
                     "diffuse_downward_flux": "diffuse"}
 _TOP = "top_"
 
+# compute_thermal_flux: the two-stream longwave fluxes.  The diffusivity factor D lies in
+# DIFFUSIVITY_RANGE; 1.66 is Elsasser's, 2 the hemispheric mean of Toon et al. (1989).
+THERMAL_FLUX_QUANTITIES = FLUX_QUANTITIES
+DIFFUSIVITY = 1.66
+DIFFUSIVITY_RANGE = (1., 2.)
+
 # compute_kdistribution: per band and g interval, per band and g point, and on the grid.
 KDISTRIBUTION_QUANTITIES = ("absorption_g_mean", "absorption_g_quantile", "sorted_absorption")
 MAX_G_INTERVALS = 64
@@ -143,6 +150,13 @@ _SolarRequest = namedtuple("_SolarRequest", _COMMON + (
 _SolarFluxRequest = namedtuple("_SolarFluxRequest", _COMMON + (
     "surface", "mu0", "level_table", "albedo", "albedo_knots", "solar_knots", "solar_values",
     "scale", "rayleigh", "rayleigh_values"))
+
+# compute_thermal_flux's: the level table [levels, 5] of lbl_path_thermal_two_stream (s_l, tau_c,
+# w_c, g_c, T_l), D, the surface temperature per path and its emissivity -- [paths], or [paths, M]
+# at emissivity_knots [M].
+_ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
+    "surface", "level_table", "diffusivity", "surface_temperature", "surface_emissivity",
+    "emissivity_knots"))
 
 # compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
 # points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
@@ -739,6 +753,51 @@ def _solar_flux_request(spec, layer_thickness, solar_zenith_cosine, solar_irradi
                              mu0=mu0, level_table=table, albedo=albedo, albedo_knots=albedo_knots,
                              solar_knots=solar_knots, solar_values=solar_values, scale=scale,
                              rayleigh=bool(rayleigh), rayleigh_values=rayleigh_values)
+
+
+def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_emissivity,
+                          emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
+                          scatterer_single_scattering_albedo, scatterer_asymmetry, quantities,
+                          band_edges, range_policy):
+    """Checks every argument of compute_thermal_flux."""
+    if spec.group is not None:
+        raise NotImplementedError("compute_thermal_flux does not split paths over processes yet "
+                                  "(group is set).")
+    lengths, shape = _path_geometry(spec, layer_thickness, "compute_thermal_flux",
+                                    "layer_thickness", "layer thicknesses")
+    _check_level_temperatures(spec)
+    if not (isinstance(surface, str) and surface in FLUX_SURFACES):
+        raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
+    factor = np.asarray(diffusivity, dtype=np.float64)
+    low, high = DIFFUSIVITY_RANGE
+    if factor.shape != () or not low <= factor <= high:
+        raise ValueError(f"diffusivity must be one number in [{low:g}, {high:g}].")
+    emissivity_knots = None
+    if emissivity_wavenumber is None:
+        ts, es = _emitter(surface_temperature, surface_emissivity, "surface", shape)
+    else:
+        ts, _ = _emitter(surface_temperature, 1., "surface", shape)
+        emissivity_knots, es = _spectral_emissivity(
+            emissivity_wavenumber, surface_emissivity, shape,
+            ("emissivity_wavenumber", "surface_emissivity", "surface emissivities"))
+    quantities = _selection(quantities, THERMAL_FLUX_QUANTITIES)
+    if "heating_rate" in quantities:
+        pressure = spec.atmosphere.pressure
+        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
+            raise ValueError("heating rates need pressures that are finite and > 0.")
+    tau_c, w_c, _ = _scatterers(spec, shape, scatterer_optical_depth,
+                                scatterer_single_scattering_albedo, scatterer_asymmetry)
+    g_c = np.zeros(lengths.size) if scatterer_asymmetry is None else \
+        np.asarray(scatterer_asymmetry, dtype=np.float64).ravel()
+    _check_range_policy(range_policy)
+    edges, starts = _path_bands(spec, band_edges)
+    temperature = np.asarray(spec.atmosphere.temperature, dtype=np.float64).ravel()
+    table = np.ascontiguousarray(np.stack([lengths, tau_c, w_c, g_c, temperature], axis=1))
+    return _ThermalFluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
+                               starts=starts, instrument=None, cumulative=False, surface=surface,
+                               level_table=table, diffusivity=float(factor),
+                               surface_temperature=ts, surface_emissivity=es,
+                               emissivity_knots=emissivity_knots)
 
 
 def _kdistribution_request(spec, band_edges, g_edges, g_points, quantities, range_policy):

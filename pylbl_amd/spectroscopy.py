@@ -15,7 +15,7 @@ of numpy arrays with the same variable names.
 
 What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
 path products compute_path, compute_radiance, compute_jacobian, compute_flux, compute_solar and
-compute_solar_flux, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
+compute_solar_flux, compute_thermal_flux, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
 queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
 else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
 whose public names stay importable from here; their functions take the Spectroscopy first, and
@@ -959,6 +959,134 @@ class Spectroscopy(object):
         return paths._create_solar_flux_dataset(
             self, paths._solar_flux_interfaces(self, values, request), request)
 
+    def compute_thermal_flux(self, layer_thickness, surface_temperature, surface_emissivity=1.,
+                             emissivity_wavenumber=None, surface="first", diffusivity=1.66,
+                             scatterer_optical_depth=None,
+                             scatterer_single_scattering_albedo=None, scatterer_asymmetry=None,
+                             quantities=("upward_flux", "downward_flux"), band_edges=None,
+                             remove_pedestal=None, range_policy="reference"):
+        """Longwave fluxes in an atmosphere that absorbs, emits and holds a cloud: upward and
+        downward fluxes at every layer interface and heating rates, from a two-stream solution
+        of every layer with a thermal source (delta-scaled, one grey scatterer per level: a cloud
+        or aerosol layer) and the adding method, formed on the GPU in two sweeps over the "total"
+        absorption block.  The longwave counterpart of compute_solar_flux; without scatterers it
+        is compute_flux with the one angle mu = 1/D.  Levels are isothermal (there is no
+        source="linear_in_tau"); sunlight is not included.
+
+        Paths, levels, `surface` and layer_thickness as in compute_flux.  With beta the absorption
+        coefficient [m-1] of compute_absorption("total", remove_pedestal, range_policy), nu the
+        grid [cm-1], D the diffusivity factor and piB(T) = pi*B(nu, T) (pi = numpy.pi, B as in
+        compute_radiance, 0 for nu <= 0), per level l with the row (s_l, tau_c, w_c, g_c, T_l) --
+        s_l = layer_thickness [m], tau_c the scatterer's extinction optical depth, w_c =
+        omega_c*tau_c formed on the host, g_c its asymmetry, T_l the level temperature -- per path
+        and grid point, each product, sum and quotient rounded as written:
+            tau_a = s_l*beta ; tau = tau_a + tau_c
+            clear level (w_c == 0, the same for the whole wavefront):
+              x = D*tau ; R = 0 ; T = exp(-x) ; em = -expm1(-x)
+            cloudy level (w_c > 0; f = g_c*g_c and gp = g_c/(1 + g_c) are level scalars):
+              omega = w_c/tau ; sc = 1 - omega*f ; t = sc*tau ; w = ((1 - f)*omega)/sc
+              g2 = (D*(w*(1 - gp)))/2 ; dif = D*(1 - w) ; g1 = g2 + dif ; su = g1 + g2 ; k2 = dif*su
+              conservative, where k2*(1 + t*t) <= 1e-10:
+                x = g1*t ; R = x/(1 + x) ; T = 1/(1 + x) ; em = (dif*t)/(1 + x)
+              general:
+                k = sqrt(k2) ; E = exp(-(k*t)) ; E2 = E*E ; o1 = -expm1(-(2*(k*t)))
+                den = k*(1 + E2) + g1*o1 ; R = (g2*o1)/den ; T = (2*(k*E))/den
+                em = (k*((1 - E)*(1 - E)) + dif*o1)/den     (= 1 - R - T, without the cancellation)
+            S = piB(T_l)*em        the layer's own emission, the same upward and downward
+        This is the two-stream system with gamma1 = D(1 - omega(1 + g)/2) and gamma2 =
+        D*omega(1 - g)/2 after compute_solar_flux's delta scaling; gamma1 - gamma2 = D(1 - omega),
+        so F = piB solves an isothermal layer and the layer emits piB*(1 - R - T).
+        Adding: interface 0 faces space, level i lies between interfaces i and i + 1 in the order
+        space -> surface, eps is the surface emissivity and T_s its temperature:
+            up, from the surface:  Rs[L] = 1 - eps ; U[L] = eps*piB(T_s) ;  for i = L-1 .. 0:
+              m1 = 1/(1 - R_i*Rs[i+1])
+              U[i] = S_i + T_i*((U[i+1] + Rs[i+1]*S_i)*m1)
+              Rs[i] = R_i + T_i*((T_i*Rs[i+1])*m1)
+            down, from space:  Dn = 0, Rd = 0 ;  at every interface i = 0 .. L:
+              m2 = 1/(1 - Rd*Rs[i])
+              down[i] = (Dn + Rd*U[i])*m2 ; up[i] = (U[i] + Rs[i]*Dn)*m2
+              then through level i:  m3 = 1/(1 - Rd*R_i)
+              Dn = S_i + T_i*((Dn + Rd*S_i)*m3) ; Rd = R_i + T_i*((T_i*Rd)*m3)
+        Band fluxes F_b = (band mean of F)*(n_b/n_per_v) and the heating rate, paths.heating_rate
+        of the returned upward and downward fluxes, as in compute_flux.
+
+        Args:
+            layer_thickness, surface_temperature, surface, band_edges: as in compute_flux.
+            surface_emissivity: eps in [0, 1]: a scalar or one per path; with
+                         emissivity_wavenumber [..., M] or [M], interpolated onto the grid as
+                         compute_radiance's boundary_emissivity.
+            emissivity_wavenumber: None, or [M] knots [cm-1], finite and strictly ascending,
+                         2 <= M <= 1024.
+            diffusivity: D, one number in [1, 2]: 1.66, or 2 for the hemispheric mean of Toon
+                         et al. (1989).
+            scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry:
+                         as in compute_solar_flux.
+            quantities: any of "upward_flux", "downward_flux" (at every interface) and
+                         "heating_rate".
+
+        Returns:
+            Like compute_solar_flux: the fluxes on the "interface" dim (L + 1: interface i of the
+            result lies between levels i-1 and i), then "wavenumber" ("W m-2 (cm-1)-1") or "band"
+            ("W m-2"); "heating_rate" with the level dim ("K day-1 (cm-1)-1" / "K day-1").
+        Raises ValueError where the blocks of one path (beta, two work blocks and one block per
+        flux) exceed device_output_limit: a run holds whole paths.
+        """
+        request = paths._thermal_flux_request(
+            self, layer_thickness, surface_temperature, surface_emissivity,
+            emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
+            scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
+            range_policy)
+        bands = request.starts is not None
+        heating = "heating_rate" in request.quantities
+        wanted = tuple(q for q in ("upward_flux", "downward_flux")
+                       if q in request.quantities or heating)
+        # From space to the surface: "first" has its surface at level 0.
+        step = _Pass(request.surface == "first", wanted, tuple(paths._TOP + q for q in wanted))
+        names = paths._TWO_STREAM_ROWS
+
+        def sweeper(call, run):
+            grid = call.grid()
+            work = call.take(2*run)
+            spectral = request.emissivity_knots is not None
+            emissivity_rows = call.take(call.paths) if spectral else None
+            # With bands the sweep's rows on the grid are blocks of this call, and the outputs
+            # their means; without, the outputs themselves.
+            fine = {q: call.take(run if q in step.level_quantities else call.paths)
+                    for q in step.level_quantities + step.path_quantities} if bands else {}
+            filled = []
+
+            def sweep(index, beta, a, b, outputs):
+                if spectral and not filled:
+                    call.engine.surface_emissivity(grid, emissivity_rows,
+                                                   request.emissivity_knots,
+                                                   request.surface_emissivity, asynchronous=True)
+                    filled.append(True)
+                blocks = {}
+                for q in wanted:
+                    for source, name in ((q, names[q]), (paths._TOP + q, paths._TOP + names[q])):
+                        if bands:
+                            block = fine[source]
+                            if source in step.level_quantities and b - a != run:
+                                block = block.rows(b - a)
+                            blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[source]
+                        else:
+                            blocks[name + "_rows"] = outputs[source]
+                call.engine.path_thermal_two_stream(
+                    beta, call.columns, grid, call.paths, call.per_path, a,
+                    request.level_table[a:b], request.surface_temperature,
+                    work if b - a == run else work.rows(2*(b - a)),
+                    diffusivity=request.diffusivity,
+                    emissivity=None if spectral else request.surface_emissivity,
+                    emissivity_rows=emissivity_rows, band_start=request.starts,
+                    from_last=step.from_last, asynchronous=True, **blocks)
+            return sweep
+        # Three blocks per level: beta and the two work rows; the interface rows on the grid
+        # count as compute_jacobian's do.
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                   level_blocks=3, grid_outputs=True, whole_paths=True)
+        return paths._create_solar_flux_dataset(
+            self, paths._solar_flux_interfaces(self, values, request), request)
+
     def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
                               quantities=("absorption_g_mean",), remove_pedestal=None,
                               range_policy="reference"):
@@ -1041,6 +1169,7 @@ class Spectroscopy(object):
     _solar_request, _solar_interfaces = paths._solar_request, paths._solar_interfaces
     _create_solar_dataset = paths._create_solar_dataset
     _solar_flux_request = paths._solar_flux_request
+    _thermal_flux_request = paths._thermal_flux_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
 

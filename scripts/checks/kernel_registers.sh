@@ -2,7 +2,9 @@
 # Register and scratch use of the library's kernels, read from the gfx950 code object inside
 # pylbl_amd/liblbl_amd.so (no GPU needed).  Usage: scripts/checks/kernel_registers.sh [pattern]
 # (a substring of the mangled name: "path_" lists the sweeps -- path_sweep_kernel,
-# path_radiance_kernel, path_flux_kernel, path_jacobian_kernel -- in both instantiations).
+# path_radiance_kernel, path_flux_kernel, path_jacobian_kernel -- in both instantiations;
+# "two_stream" the shortwave two-stream kernels, "thermal" the longwave ones: thermal_up_kernel and
+# thermal_down_kernel, vector and scalar rows).
 # Also prints the md5 of the device code's .text: unchanged by edits that only move host code.
 set -e
 LIB=${LIB:-pylbl_amd/liblbl_amd.so}
