@@ -95,7 +95,9 @@ __host__ __device__ inline double tile_centre(int v0, double dv, long long i0, l
 #define LBL_FAR_TERMS 21
 #define LBL_FAR_RATIO 4.
 #endif
-constexpr int kFarTerms = LBL_FAR_TERMS;     // series order 20: truncation <= ~1.5e-11 relative at ratio 1/4
+// Series order 20: per line a relative remainder <= rho^21 (22 + 21 rho), 6.2e-12 at the hand-over
+// ratio rho = 1/4 (farfield.h; tests/test_gpu_farfield_lines.py).
+constexpr int kFarTerms = LBL_FAR_TERMS;
 constexpr double kFarRatio = LBL_FAR_RATIO;  // far lines are at least 4 tile half-widths from the centre
 
 // One unit of work for a workgroup: part `part` of `parts` of tile `tile`'s lines.  Dense

@@ -9,9 +9,14 @@
 //     q_0 = b/D,  q_1 = (2a/D) q_0,  q_k = (2a/D) q_{k-1} - (1/D) q_{k-2},
 //
 // a power series with convergence radius sqrt(D) >= |a|.  The schedule kernel only hands
-// over lines with |a| >= kFarRatio x the tile's half width, so |u|/|a| <= 1/4 and kFarTerms
-// = 21 terms leave a relative truncation below ~1.5e-11 (measured on the 5 M-point benchmark:
-// max 2.8e-12 against the direct kernel) -- five orders inside the 1e-6 parity bar.  The series
+// over lines with |a| >= kFarRatio x the tile's half width, so rho = |u|/|a| <= 1/4 and the
+// kFarTerms = 21 terms leave, per line, a relative remainder of at most
+//     rho^21 (22 + 21 rho) = 6.2e-12 at rho = 1/4
+// (the remainder of 1/(a - u)^2 at u = -rho a, the edge of the tile away from the line; 3.8e-12 at
+// the near edge; gamma > 0 only lowers both) -- five orders inside the 1e-6 parity bar.
+// tests/test_gpu_farfield_lines.py holds single lines placed at the hand-over distance of tiles
+// and groups to that bound plus rounding (tests/farfield_cases.py derives it and mirrors the cuts;
+// measured on the 5 M-point benchmark: max 2.8e-12 against the direct kernel).  The series
 // of all far lines of a tile are ADDED coefficient by coefficient (3 flops per line and term
 // instead of ~5 flops per line and grid point), and the accumulate kernel evaluates the summed
 // polynomial once per point.
