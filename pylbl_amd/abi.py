@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h and
-include/lbl_amd_thermal.h (pylbl_amd/liblbl_amd.so), and nothing else:
+"""ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h,
+include/lbl_amd_thermal.h and include/lbl_amd_kdist.h (pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -211,6 +211,18 @@ THERMAL_PROTOTYPES = {
     "lbl_path_thermal_two_stream": _BLOCK + [_i32] + _RUN + [_ptr, _f64, _ptr, _ptr, _ptr, _i32] +
                                    [_ptr]*10 + [_i32],
 }
+# Every function of include/lbl_amd_kdist.h, the header of the weighted band k-distribution entry
+# of the same library; each returns int.  tests/test_kdistribution_weighted_host.py compares this
+# table with that header.
+KDIST_PROTOTYPES = {
+    # engine, values, row_stride, columns, n_rows, band_start, n_bands, scratch, grid,
+    # row_temperature, weight_row, index_rows, index_scratch, index_stride, weight_rows,
+    # weighted_rows, interval_start, n_intervals, weight_sums, weighted_sums, means, point_index,
+    # point_fraction, n_points, quantiles, flags
+    "lbl_band_distribution_weighted": [_ptr, _ptr, _i64, _i64, _i32, _ptr, _i32, _ptr, _i32,
+                                       _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
+                                       _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _i32],
+}
 
 _library = None
 
@@ -268,7 +280,7 @@ def library():
     _preload_hip_runtime()
     lib = CDLL(str(path))
     for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()) + \
-            list(THERMAL_PROTOTYPES.items()):
+            list(THERMAL_PROTOTYPES.items()) + list(KDIST_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

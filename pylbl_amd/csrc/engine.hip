@@ -30,8 +30,10 @@
 #include "../../include/lbl_amd.h"
 #include "../../include/lbl_amd_twostream.h"
 #include "../../include/lbl_amd_thermal.h"
+#include "../../include/lbl_amd_kdist.h"
 #include "accumulate.h"
 #include "band_sort.h"
+#include "band_sort_pairs.h"
 #include "continuum.h"
 #include "xsec.h"
 #include "farfield.h"
@@ -505,6 +507,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "twostream_entry.inc"
 #include "thermal_entry.inc"
 #include "band_sort_entry.inc"
+#include "band_sort_pairs_entry.inc"
 #include "instrument_entry.inc"
 #include "xsec_entry.inc"
 #include "sqlite_entry.inc"

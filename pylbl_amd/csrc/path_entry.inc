@@ -187,9 +187,11 @@ struct PathBands
 
     // Queues out[r][b] = the mean over band b of row r of `values` (of exp(-value) with
     // `transmittance`) for `rows` rows `row_stride` apart, and records the write of `out`.
-    // d_tables: the call's tables on the device.
+    // d_tables: the call's tables on the device.  sums: the sums in place of the means, added in
+    // the same order (band_interval_sum_kernel, band_sort_pairs.h): 0 for a band without points.
     void means(lbl_engine * engine, const double * d_tables, const double * values,
-               long long row_stride, int rows, bool transmittance, double * out) const
+               long long row_stride, int rows, bool transmittance, double * out,
+               bool sums = false) const
     {
         if (rows <= 0) return;
         const long long * d_table = reinterpret_cast<const long long *>(d_tables + at);
@@ -219,9 +221,18 @@ struct PathBands
             }
             const dim3 mean_grid((unsigned)((n_bands + kPathThreads - 1)/kPathThreads),
                                  (unsigned)chunk);
-            hipLaunchKernelGGL(path_band_mean_kernel, mean_grid, dim3(kPathThreads), 0,
-                               stream, w.partial.data, (int)n_segments, d_band_segment,
-                               d_band_start, (int)n_bands, out + (long long)r0*n_bands);
+            if (sums)
+            {
+                hipLaunchKernelGGL(band_interval_sum_kernel, mean_grid, dim3(kPathThreads), 0,
+                                   stream, w.partial.data, (int)n_segments, d_band_segment,
+                                   (int)n_bands, out + (long long)r0*n_bands);
+            }
+            else
+            {
+                hipLaunchKernelGGL(path_band_mean_kernel, mean_grid, dim3(kPathThreads), 0,
+                                   stream, w.partial.data, (int)n_segments, d_band_segment,
+                                   d_band_start, (int)n_bands, out + (long long)r0*n_bands);
+            }
             HIP_TRY(hipGetLastError());
         }
         engine->lanes[0].note_write(out, (long long)rows*n_bands*8, stream);

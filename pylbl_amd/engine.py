@@ -86,6 +86,39 @@ def _check_outputs(outputs, rows, width):
             raise ValueError(f"an output has shape {out.shape}, need rows x {width}.")
 
 
+def _interval_table(interval_start, outputs, rows):
+    """(int64 interval starts or None, n_intervals) of band_distribution's interval_start, which
+    goes together with at least one of `outputs` (DeviceSpectra [rows, n_intervals] or None)."""
+    wanted = [out for out in outputs if out is not None]
+    if (interval_start is None) != (not wanted):
+        raise ValueError("interval_start and means go together.")
+    if not wanted:
+        return None, 0
+    intervals = np.ascontiguousarray(interval_start, dtype=np.int64)
+    if intervals.ndim != 1 or intervals.size < 2:
+        raise ValueError("interval_start must hold n_intervals + 1 >= 2 column starts.")
+    _check_outputs(wanted, rows, intervals.size - 1)
+    return intervals, intervals.size - 1
+
+
+def _point_tables(point_index, point_fraction, quantiles, rows, n_bands):
+    """(int64 index, float64 fraction, n_points) of band_distribution's quantile tables [n_bands,
+    n_points], which go together with quantiles (DeviceSpectra [rows, n_bands*n_points]);
+    (None, None, 0) without them."""
+    if (point_index is None) != (quantiles is None) or \
+            (point_fraction is None) != (quantiles is None):
+        raise ValueError("point_index, point_fraction and quantiles go together.")
+    if quantiles is None:
+        return None, None, 0
+    index = np.ascontiguousarray(point_index, dtype=np.int64)
+    fraction = _f64(point_fraction)
+    if index.ndim != 2 or index.shape[0] != n_bands or index.shape[1] < 1 or \
+            fraction.shape != index.shape:
+        raise ValueError("point_index and point_fraction must be [n_bands, n_points].")
+    _check_outputs((quantiles,), rows, n_bands*index.shape[1])
+    return index, fraction, index.shape[1]
+
+
 def _address(x):
     """What a C entry takes for a DeviceSpectra or an array: None for None."""
     if x is None:
@@ -391,33 +424,71 @@ class Engine(object):
         n_bands = starts.size - 1
         if scratch is not None and tuple(scratch.shape) != (rows, stride):
             raise ValueError("scratch must be shaped like values.")
-        intervals, n_intervals = None, 0
-        if (interval_start is None) != (means is None):
-            raise ValueError("interval_start and means go together.")
-        if means is not None:
-            intervals = np.ascontiguousarray(interval_start, dtype=np.int64)
-            if intervals.ndim != 1 or intervals.size < 2:
-                raise ValueError("interval_start must hold n_intervals + 1 >= 2 column starts.")
-            n_intervals = intervals.size - 1
-            _check_outputs((means,), rows, n_intervals)
-        index = fraction = None
-        n_points = 0
-        if (point_index is None) != (quantiles is None) or \
-                (point_fraction is None) != (quantiles is None):
-            raise ValueError("point_index, point_fraction and quantiles go together.")
-        if quantiles is not None:
-            index = np.ascontiguousarray(point_index, dtype=np.int64)
-            fraction = _f64(point_fraction)
-            if index.ndim != 2 or index.shape[0] != n_bands or index.shape[1] < 1 or \
-                    fraction.shape != index.shape:
-                raise ValueError("point_index and point_fraction must be [n_bands, n_points].")
-            n_points = index.shape[1]
-            _check_outputs((quantiles,), rows, n_bands*n_points)
+        intervals, n_intervals = _interval_table(interval_start, (means,), rows)
+        index, fraction, n_points = _point_tables(point_index, point_fraction, quantiles, rows,
+                                                  n_bands)
         self._check(self.lib.lbl_band_distribution(
             self.handle, values.pointer, stride, int(columns), rows, starts.ctypes.data, n_bands,
             _address(scratch), _address(intervals), n_intervals, _address(means),
             _address(index), _address(fraction), n_points, _address(quantiles),
             ASYNC if asynchronous else 0))
+
+    def band_distribution_weighted(self, values, columns, band_start, index_rows, scratch=None,
+                                   index_scratch=None, index_stride=None, grid=-1,
+                                   row_temperature=None, weight_row=None, weight_rows=None,
+                                   weighted_rows=None, interval_start=None, weight_sums=None,
+                                   weighted_sums=None, means=None, point_index=None,
+                                   point_fraction=None, quantiles=None, asynchronous=False):
+        """band_distribution with the permutation kept and weights carried through it --
+        lbl_band_distribution_weighted.  values, columns, band_start, scratch, interval_start,
+        means, point_index, point_fraction and quantiles as for band_distribution, with the same
+        bits.  index_rows: where pi goes, as int32 [rows, index_stride], column band start + i
+        holding the offset in its band of the column that the sorted value i came from
+        (numpy.argsort(keys, kind="stable")); index_scratch: shaped like it (with scratch: None is
+        enough while no band is longer than 4096 columns).  Both are blocks that hold
+        rows*index_stride int32 values from their `pointer`; index_stride None: DeviceSpectra
+        [rows, m] read as int32 [rows, 2 m].  The weights, exactly one of: row_temperature [K]
+        one per row with grid, a handle of load_grid -- w = B(nu, T) -- or weight_row, a
+        DeviceSpectra whose first row holds w on the columns.  weight_rows / weighted_rows:
+        DeviceSpectra shaped like values (both or neither) for W_i = w_pi(i) and W_i*k_i;
+        weight_sums / weighted_sums: DeviceSpectra [rows, n_intervals] for their sums over each
+        interval of columns (they need weight_rows and weighted_rows)."""
+        rows, stride = int(values.shape[0]), int(values.shape[1])
+        starts = np.ascontiguousarray(band_start, dtype=np.int64)
+        if starts.ndim != 1 or starts.size < 2:
+            raise ValueError("band_start must hold n_bands + 1 >= 2 column starts.")
+        n_bands = starts.size - 1
+        for block in (scratch, weight_rows, weighted_rows):
+            if block is not None and tuple(block.shape) != (rows, stride):
+                raise ValueError("scratch, weight_rows and weighted_rows must be shaped like "
+                                 "values.")
+        if index_stride is None:
+            index_stride = 2*int(index_rows.shape[1])
+        for block in (index_rows, index_scratch):
+            if block is not None and (int(block.shape[0]) < rows or
+                                      tuple(block.shape) != tuple(index_rows.shape)):
+                raise ValueError("index_rows and index_scratch must be shaped alike, one row "
+                                 "per row of values.")
+        if (row_temperature is None) == (weight_row is None):
+            raise ValueError("exactly one of row_temperature and weight_row must be given.")
+        temperature = None
+        if row_temperature is not None:
+            temperature = _f64(row_temperature)
+            if temperature.shape != (rows,):
+                raise ValueError("one temperature per row of values.")
+        elif int(weight_row.shape[1]) < int(columns):
+            raise ValueError("weight_row must hold `columns` values.")
+        intervals, n_intervals = _interval_table(interval_start,
+                                                 (weight_sums, weighted_sums, means), rows)
+        index, fraction, n_points = _point_tables(point_index, point_fraction, quantiles, rows,
+                                                  n_bands)
+        self._check(self.lib.lbl_band_distribution_weighted(
+            self.handle, values.pointer, stride, int(columns), rows, starts.ctypes.data, n_bands,
+            _address(scratch), int(grid), _address(temperature), _address(weight_row),
+            index_rows.pointer, _address(index_scratch), int(index_stride),
+            _address(weight_rows), _address(weighted_rows), _address(intervals), n_intervals,
+            _address(weight_sums), _address(weighted_sums), _address(means), _address(index),
+            _address(fraction), n_points, _address(quantiles), ASYNC if asynchronous else 0))
 
     def path_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin, lengths,
                       temperature, carry, boundary_temperature=None, boundary_emissivity=None,

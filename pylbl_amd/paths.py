@@ -89,6 +89,12 @@ DIFFUSIVITY_RANGE = (1., 2.)
 
 # compute_kdistribution: per band and g interval, per band and g point, and on the grid.
 KDISTRIBUTION_QUANTITIES = ("absorption_g_mean", "absorption_g_quantile", "sorted_absorption")
+# ... and those that need compute_kdistribution's `weighting`; the interval sums of W and W*k
+# they are formed from on the host (_create_kdistribution_dataset).
+KDISTRIBUTION_WEIGHTED_QUANTITIES = ("weight_g_fraction", "absorption_g_weighted_mean",
+                                     "sorted_column")
+KDISTRIBUTION_WEIGHTINGS = ("planck",)
+_WEIGHT_SUMS, _WEIGHTED_SUMS = "weight_sums", "weighted_sums"
 MAX_G_INTERVALS = 64
 # _sweep_runs: the product source that stands for the run's block of beta itself.
 _BETA = "beta"
@@ -160,9 +166,11 @@ _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
 
 # compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
 # points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
-# quantile tables [B, P] (quantile_table).
+# quantile tables [B, P] (quantile_table).  weighting: None, "planck" or "array"; weights: the
+# caller's [V] with "array"; weight_temperature: the flat [levels] T of B(nu, T) with "planck".
 _KDistributionRequest = namedtuple("_KDistributionRequest", _COMMON + (
-    "g_edges", "g_points", "interval_starts", "point_index", "point_fraction"))
+    "g_edges", "g_points", "interval_starts", "point_index", "point_fraction", "weighting",
+    "weights", "weight_temperature"), defaults=(None, None, None))
 
 # One pass of _sweep_runs over the levels: its order, and what it writes per level and per path.
 _Pass = namedtuple("_Pass", ["from_last", "level_quantities", "path_quantities"])
@@ -800,7 +808,42 @@ def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_em
                                emissivity_knots=emissivity_knots)
 
 
-def _kdistribution_request(spec, band_edges, g_edges, g_points, quantities, range_policy):
+def _kdistribution_weighting(spec, weighting, weighting_temperature):
+    """(weighting, weights, weight_temperature) of a _KDistributionRequest from
+    compute_kdistribution's `weighting` and `weighting_temperature`, checked."""
+    if weighting is None:
+        if weighting_temperature is not None:
+            raise ValueError('weighting_temperature needs weighting="planck".')
+        return None, None, None
+    if isinstance(weighting, str):
+        if weighting not in KDISTRIBUTION_WEIGHTINGS:
+            raise ValueError(f"weighting must be one of {KDISTRIBUTION_WEIGHTINGS} or an array "
+                             f"of one weight per grid point, not {weighting!r}.")
+        shape = spec.atmosphere.temperature.shape
+        if weighting_temperature is None:
+            temperature = np.asarray(spec.atmosphere.temperature, dtype=np.float64)
+        else:
+            temperature = np.asarray(weighting_temperature, dtype=np.float64)
+            if temperature.shape not in ((), shape):
+                raise ValueError(f"weighting_temperature has shape {temperature.shape}: give one "
+                                 f"number or the atmosphere's shape {shape}.")
+            temperature = np.broadcast_to(temperature, shape)
+        if not np.all(np.isfinite(temperature)) or not np.all(temperature > 0.):
+            raise ValueError("the temperatures of the Planck weighting must be finite and > 0.")
+        return weighting, None, np.ascontiguousarray(temperature.ravel())
+    if weighting_temperature is not None:
+        raise ValueError('weighting_temperature needs weighting="planck".')
+    weights = np.asarray(weighting, dtype=np.float64)
+    if weights.shape != (spec.grid.size,):
+        raise ValueError(f"weighting has shape {weights.shape}: give one weight per grid point, "
+                         f"[{spec.grid.size}].")
+    if not np.all(np.isfinite(weights)) or np.any(weights < 0.):
+        raise ValueError("weights must be finite and >= 0.")
+    return "array", np.ascontiguousarray(weights), None
+
+
+def _kdistribution_request(spec, band_edges, g_edges, g_points, quantities, range_policy,
+                           weighting=None, weighting_temperature=None):
     """Checks every argument of compute_kdistribution."""
     if spec.group is not None:
         raise NotImplementedError("compute_kdistribution does not split levels over processes "
@@ -810,7 +853,13 @@ def _kdistribution_request(spec, band_edges, g_edges, g_points, quantities, rang
         raise ValueError("the atmosphere has no levels.")
     if band_edges is None:
         raise ValueError("compute_kdistribution needs band_edges.")
-    quantities = _selection(quantities, KDISTRIBUTION_QUANTITIES)
+    kind, weights, weight_temperature = _kdistribution_weighting(spec, weighting,
+                                                                 weighting_temperature)
+    asked = (quantities,) if isinstance(quantities, str) else tuple(quantities)
+    if kind is None and any(q in KDISTRIBUTION_WEIGHTED_QUANTITIES for q in asked):
+        raise ValueError(f"the quantities {KDISTRIBUTION_WEIGHTED_QUANTITIES} need a weighting.")
+    quantities = _selection(asked, KDISTRIBUTION_QUANTITIES + (
+        KDISTRIBUTION_WEIGHTED_QUANTITIES if kind is not None else ()))
     _check_range_policy(range_policy)
     edges, starts = _path_bands(spec, band_edges)
     g = g_intervals(g_edges)
@@ -819,7 +868,8 @@ def _kdistribution_request(spec, band_edges, g_edges, g_points, quantities, rang
     return _KDistributionRequest(
         lengths=None, shape=shape, quantities=quantities, edges=edges, starts=starts,
         instrument=None, cumulative=False, g_edges=g, g_points=points,
-        interval_starts=interval_columns(starts, g), point_index=index, point_fraction=fraction)
+        interval_starts=interval_columns(starts, g), point_index=index, point_fraction=fraction,
+        weighting=kind, weights=weights, weight_temperature=weight_temperature)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1151,20 +1201,33 @@ def _create_flux_dataset(spec, values, request):
 def _create_kdistribution_dataset(spec, values, request):
     """compute_kdistribution's result from the sweeps' rows: the means of the device's flat
     interval list [levels, B (Q + 1) - 1] (the last of every band's Q + 1 is the gap to the next
-    band), the quantiles [levels, B P] and the sorted block [levels, grid]."""
+    band), the quantiles [levels, B P] and the sorted block [levels, grid]; with a weighting the
+    interval sums of W and W*k, flat like the means, and pi as int32 pairs in float64 rows."""
     from .spectroscopy import _optional_xarray
     dims, shape = list(spec.atmosphere.dims), list(request.shape)
     bands, q, p = request.starts.size - 1, request.g_edges.size - 1, request.g_points.size
     levels = int(np.prod(shape, dtype=np.int64))
     units = {"units": "m-1"}
     variables = {}
-    if "absorption_g_mean" in request.quantities:
+
+    def per_interval(name):
         flat = np.full((levels, bands*(q + 1)), np.nan)
-        flat[:, :-1] = values["absorption_g_mean"]
-        variables["absorption_g_mean"] = (
-            dims + ["band", "g_interval"],
-            np.ascontiguousarray(flat.reshape(levels, bands, q + 1)[:, :, :q]).reshape(
-                shape + [bands, q]), units)
+        flat[:, :-1] = values[name]
+        return np.ascontiguousarray(flat.reshape(levels, bands, q + 1)[:, :, :q]).reshape(
+            shape + [bands, q])
+    if "absorption_g_mean" in request.quantities:
+        variables["absorption_g_mean"] = (dims + ["band", "g_interval"],
+                                          per_interval("absorption_g_mean"), units)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if "weight_g_fraction" in request.quantities:
+            sums = per_interval(_WEIGHT_SUMS)
+            variables["weight_g_fraction"] = (dims + ["band", "g_interval"],
+                                              sums/np.sum(sums, axis=-1, keepdims=True), {})
+        if "absorption_g_weighted_mean" in request.quantities:
+            sums = per_interval(_WEIGHT_SUMS)
+            variables["absorption_g_weighted_mean"] = (
+                dims + ["band", "g_interval"],
+                np.where(sums == 0., np.nan, per_interval(_WEIGHTED_SUMS)/sums), units)
     if "absorption_g_quantile" in request.quantities:
         variables["absorption_g_quantile"] = (
             dims + ["band", "g_point"],
@@ -1180,6 +1243,12 @@ def _create_kdistribution_dataset(spec, values, request):
         block[:, ~in_band] = np.nan
         variables["sorted_absorption"] = (dims + ["wavenumber"],
                                           block.reshape(shape + [spec.grid.size]), units)
+    if "sorted_column" in request.quantities:
+        pairs = np.ascontiguousarray(values["sorted_column"]).view(np.int32)
+        block = np.array(pairs[:, :spec.grid.size])
+        block[:, ~in_band] = -1
+        variables["sorted_column"] = (dims + ["wavenumber"],
+                                      block.reshape(shape + [spec.grid.size]), {})
     coords = {"band_lower": (("band",), request.edges[:-1], {"units": "cm-1"}),
               "band_upper": (("band",), request.edges[1:], {"units": "cm-1"}),
               "band_points": (("band",), np.diff(request.starts), {}),
@@ -1189,20 +1258,22 @@ def _create_kdistribution_dataset(spec, values, request):
               "g_interval_points": (("band", "g_interval"),
                                     np.diff(request.interval_starts, axis=1), {}),
               "g_point": (("g_point",), request.g_points, {})}
-    if "sorted_absorption" in request.quantities:
+    if "sorted_absorption" in request.quantities or "sorted_column" in request.quantities:
         coords["wavenumber"] = (("wavenumber",), spec.grid, {"units": "cm-1"})
         coords["g"] = (("wavenumber",), g, {})
+    given = {} if request.weighting is None else {"weighting": request.weighting}
     xarray = _optional_xarray()
     if xarray is None:
         out = {name: value for name, (_, value, _) in coords.items()}
         out.update({name: value for name, (_, value, _) in variables.items()})
+        out.update(given)
         return out
     DataArray, Dataset = xarray.DataArray, xarray.Dataset
     return Dataset(
         data_vars={name: DataArray(value, dims=d, attrs=attrs)
                    for name, (d, value, attrs) in variables.items()},
         coords={name: DataArray(value, dims=d, attrs=attrs)
-                for name, (d, value, attrs) in coords.items()})
+                for name, (d, value, attrs) in coords.items()}, attrs=given)
 
 
 def _path_variables(spec, variables, request):

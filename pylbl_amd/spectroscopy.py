@@ -1089,11 +1089,18 @@ class Spectroscopy(object):
 
     def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
                               quantities=("absorption_g_mean",), remove_pedestal=None,
-                              range_policy="reference"):
+                              range_policy="reference", weighting=None,
+                              weighting_temperature=None):
         """Band k-distributions, what a correlated-k table is built from: within every band and
         at every level the absorption coefficient re-ordered by size and summarised on intervals
         of the cumulative probability g, formed on the GPU from the "total" absorption block
         without handing that block to the host.  A per-level product: no path lengths.
+
+        A table stores k(g) and, beside it, the share of the band's source that falls into
+        each g interval (RRTMG's `fracs`, RRTMGP's `planck_frac`; for the shortwave the same of
+        the solar spectrum), and averages k within an interval with that source as the weight.
+        `weighting` gives both: the sort then carries every value's column, and a weight per
+        column travels through the permutation.
 
         With beta the absorption coefficient [m-1] of compute_absorption("total",
         remove_pedestal, range_policy), band b the N grid points e_b <= grid < e_b+1, and
@@ -1101,7 +1108,11 @@ class Spectroscopy(object):
         of the fp64 bits u read as keys, u ^ 2^63 for a clear sign bit and ~u for a set one,
         compared unsigned (-inf < negatives < -0 < +0 < positives < +inf < NaN; numpy.sort
         apart from +-0 ties and NaN payloads), which makes the result unique: repeated calls
-        and any device_output_limit give the same bits.
+        and any device_output_limit give the same bits.  pi is the permutation that sorts the
+        pairs (key, column offset j in the band) lexicographically,
+        numpy.argsort(keys, kind="stable"): k_i = beta_pi(i).  With a weight w_j >= 0 per column,
+        W_i = w_pi(i) and WK_i = W_i*k_i (one rounding); sw_q and swk_q are the sums of W and WK
+        over interval q, added in a fixed order on the GPU.
 
         Args:
             band_edges: strictly increasing finite edges e_0 < ... < e_B, as compute_path's.
@@ -1117,17 +1128,36 @@ class Spectroscopy(object):
                     N - 1), i = floor(x), f = x - i: k_i + f*(k_min(i+1, N-1) - k_i), each
                     operation rounded as written (NaN for a band without points);
                 "sorted_absorption" [..., wavenumber]: every band's columns holding its sorted
-                    values, NaN in the columns of no band.
+                    values, NaN in the columns of no band;
+                and, with `weighting` only (ValueError without it),
+                "weight_g_fraction" [..., band, g_interval]: sw_q / sum_q sw_q -- 0 for an
+                    interval without points, NaN where the band's sum is 0 or the band is empty;
+                "absorption_g_weighted_mean" [..., band, g_interval]: swk_q / sw_q, NaN where
+                    sw_q is 0;
+                "sorted_column" [..., wavenumber], int32: pi(i) in column band start + i, an
+                    offset from the band's first column; -1 in the columns of no band.  Like
+                    "sorted_absorption" it travels to the host only when asked for.
+            weighting: None; "planck" -- w_j = B(nu_j, T) [W m-2 sr-1 (cm-1)-1] as
+                    compute_radiance forms it (0 for nu <= 0), T the level's own temperature or
+                    `weighting_temperature`; or an array of one finite weight >= 0 per grid
+                    point, the same for every level, uploaded once per call.  The default Sun of
+                    compute_solar, for one:
+                    weighting=paths.SOLAR_SOLID_ANGLE*planck(grid, paths.SOLAR_TEMPERATURE) with
+                    planck(nu, T) = (((paths.PLANCK_C1*nu)*nu)*nu)/numpy.expm1(
+                    (paths.PLANCK_C2*nu)/T).
+            weighting_temperature: with weighting="planck" only: one number, or an array of the
+                    atmosphere's shape, finite and > 0 [K].
 
         Returns:
             Like compute_absorption: an xarray Dataset when xarray is installed, else a dict of
             numpy arrays [m-1], with the coordinates "band_lower", "band_upper", "band_points",
             "g_lower", "g_upper", "g_weight" (the interval widths), "g_interval_points"
-            [band, g_interval], "g_point", and with "sorted_absorption" also "wavenumber" and
-            "g" = (i + 0.5)/N on the wavenumber dim.
+            [band, g_interval], "g_point", and with "sorted_absorption" or "sorted_column" also
+            "wavenumber" and "g" = (i + 0.5)/N on the wavenumber dim.  With a weighting the
+            result carries it as the attribute (the key) "weighting": "planck" or "array".
         """
         request = paths._kdistribution_request(self, band_edges, g_edges, g_points, quantities,
-                                               range_policy)
+                                               range_policy, weighting, weighting_temperature)
         want_means = "absorption_g_mean" in request.quantities
         want_quantiles = "absorption_g_quantile" in request.quantities
         bands, points = request.starts.size - 1, request.g_points.size
@@ -1136,6 +1166,14 @@ class Spectroscopy(object):
         intervals = request.interval_starts.ravel()
         level_quantities = tuple(q for q in ("absorption_g_mean", "absorption_g_quantile")
                                  if q in request.quantities)
+        widths = {"absorption_g_mean": intervals.size - 1,
+                  "absorption_g_quantile": bands*points, paths._BETA: self.grid.size}
+        products = [_Product(q, q, True) for q in level_quantities]
+        if "sorted_absorption" in request.quantities:
+            products.append(_Product("sorted_absorption", paths._BETA, True))
+        if request.weighting is not None:
+            return self._weighted_kdistribution(request, intervals, level_quantities, widths,
+                                                products, remove_pedestal, range_policy)
 
         def sweeper(call, run):
             scratch = call.take(run)
@@ -1149,15 +1187,71 @@ class Spectroscopy(object):
                     point_fraction=request.point_fraction if want_quantiles else None,
                     quantiles=outputs.get("absorption_g_quantile"), asynchronous=True)
             return sweep
-        products = [_Product(q, q, True) for q in level_quantities]
-        if "sorted_absorption" in request.quantities:
-            products.append(_Product("sorted_absorption", paths._BETA, True))
         # Two blocks per level: beta, sorted in place, and the sort's scratch.
         values = self._sweep_runs(
             request, [_Pass(False, level_quantities, ())], remove_pedestal, range_policy, sweeper,
-            level_blocks=2, products=products,
-            widths={"absorption_g_mean": intervals.size - 1,
-                    "absorption_g_quantile": bands*points, paths._BETA: self.grid.size})
+            level_blocks=2, products=products, widths=widths)
+        return paths._create_kdistribution_dataset(self, values, request)
+
+    def _weighted_kdistribution(self, request, intervals, level_quantities, widths, products,
+                                remove_pedestal, range_policy):
+        """compute_kdistribution with a weighting: the same sweep through
+        Engine.band_distribution_weighted."""
+        want_means = "absorption_g_mean" in request.quantities
+        want_quantiles = "absorption_g_quantile" in request.quantities
+        want_weighted = "absorption_g_weighted_mean" in request.quantities
+        want_sums = want_weighted or "weight_g_fraction" in request.quantities
+        want_columns = "sorted_column" in request.quantities
+        # pi as int32: two to a float64 of a block, rows of 2*pairs >= grid points.
+        pairs = (self.grid.size + 1)//2
+        sums = ((paths._WEIGHT_SUMS,) if want_sums else ()) + \
+            ((paths._WEIGHTED_SUMS,) if want_weighted else ())
+        level_quantities = level_quantities + sums + (("sorted_column",) if want_columns else ())
+        widths = dict(widths, sorted_column=pairs,
+                      **{name: intervals.size - 1 for name in sums})
+        products = products + [_Product(name, name, True) for name in sums]
+        if want_columns:
+            products.append(_Product("sorted_column", "sorted_column", True))
+
+        def sweeper(call, run):
+            grid = call.grid()
+            scratch, index_scratch = call.take(run), call.take(run, columns=pairs)
+            index_rows = None if want_columns else call.take(run, columns=pairs)
+            weight_rows = call.take(run) if want_sums else None
+            weighted_rows = call.take(run) if want_sums else None
+            weight_row = call.take(1) if request.weights is not None else None
+            filled = []
+
+            def sweep(index, beta, a, b, outputs):
+                if weight_row is not None and not filled:
+                    # scale*irradiance with scale = 1: the caller's weights, bit for bit.
+                    call.engine.solar_spectrum(grid, weight_row, call.columns,
+                                               irradiance=request.weights, scale=1.,
+                                               asynchronous=True)
+                    filled.append(True)
+                rows = b - a
+                call.engine.band_distribution_weighted(
+                    beta, call.columns, request.starts,
+                    outputs["sorted_column"] if want_columns else index_rows.rows(rows),
+                    scratch=scratch.rows(rows), index_scratch=index_scratch.rows(rows), grid=grid,
+                    row_temperature=None if weight_row is not None
+                    else request.weight_temperature[a:b],
+                    weight_row=weight_row,
+                    weight_rows=weight_rows.rows(rows) if want_sums else None,
+                    weighted_rows=weighted_rows.rows(rows) if want_sums else None,
+                    interval_start=intervals if want_means or want_sums else None,
+                    weight_sums=outputs.get(paths._WEIGHT_SUMS),
+                    weighted_sums=outputs.get(paths._WEIGHTED_SUMS),
+                    means=outputs.get("absorption_g_mean"),
+                    point_index=request.point_index if want_quantiles else None,
+                    point_fraction=request.point_fraction if want_quantiles else None,
+                    quantiles=outputs.get("absorption_g_quantile"), asynchronous=True)
+            return sweep
+        # Five blocks per level: beta, sorted in place, the sort's scratch, W and W*k on the
+        # grid, and pi with its scratch, half a block each.
+        values = self._sweep_runs(
+            request, [_Pass(False, level_quantities, ())], remove_pedestal, range_policy, sweeper,
+            level_blocks=5, products=products, widths=widths)
         return paths._create_kdistribution_dataset(self, values, request)
 
     # The host side of the path products is paths.py and that of compute_absorption is
