@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h,
-include/lbl_amd_thermal.h and include/lbl_amd_kdist.h (pylbl_amd/liblbl_amd.so), and nothing else:
+include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h and include/lbl_amd_kdist.h
+(pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -211,6 +212,15 @@ THERMAL_PROTOTYPES = {
     "lbl_path_thermal_two_stream": _BLOCK + [_i32] + _RUN + [_ptr, _f64, _ptr, _ptr, _ptr, _i32] +
                                    [_ptr]*10 + [_i32],
 }
+# Every function of include/lbl_amd_thermal_source.h, the header of the same entry with the
+# linear-in-tau source; each returns int.  tests/test_thermal_source_host.py compares this table
+# with that header.
+THERMAL_SOURCE_PROTOTYPES = {
+    # lbl_path_thermal_two_stream's with edge_temperature after level_table
+    "lbl_path_thermal_two_stream_source": _BLOCK + [_i32] + _RUN + [_ptr, _ptr, _f64, _ptr, _ptr,
+                                                                    _ptr, _i32] + [_ptr]*10 +
+                                          [_i32],
+}
 # Every function of include/lbl_amd_kdist.h, the header of the weighted band k-distribution entry
 # of the same library; each returns int.  tests/test_kdistribution_weighted_host.py compares this
 # table with that header.
@@ -280,7 +290,8 @@ def library():
     _preload_hip_runtime()
     lib = CDLL(str(path))
     for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()) + \
-            list(THERMAL_PROTOTYPES.items()) + list(KDIST_PROTOTYPES.items()):
+            list(THERMAL_PROTOTYPES.items()) + list(THERMAL_SOURCE_PROTOTYPES.items()) + \
+            list(KDIST_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

@@ -30,6 +30,7 @@
 #include "../../include/lbl_amd.h"
 #include "../../include/lbl_amd_twostream.h"
 #include "../../include/lbl_amd_thermal.h"
+#include "../../include/lbl_amd_thermal_source.h"
 #include "../../include/lbl_amd_kdist.h"
 #include "accumulate.h"
 #include "band_sort.h"
@@ -49,6 +50,7 @@
 #include "tile_schedule.h"
 #include "twostream.h"
 #include "twostream_thermal.h"
+#include "twostream_thermal_source.h"
 
 #include "engine_core.h"
 #include "lanes_plans.inc"
@@ -506,6 +508,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "solar_entry.inc"
 #include "twostream_entry.inc"
 #include "thermal_entry.inc"
+#include "thermal_source_entry.inc"
 #include "band_sort_entry.inc"
 #include "band_sort_pairs_entry.inc"
 #include "instrument_entry.inc"

@@ -822,13 +822,40 @@ class Engine(object):
         row length] at the interface below each level, top_up_rows and top_down_rows [n_paths,
         row length] at interface 0, and with band_start their band means *_mean [>= rows or
         n_paths, bands]."""
+        self._path_thermal("path_thermal_two_stream", beta, columns, grid, n_paths,
+                           levels_per_path, level_begin, level_table, None, surface_temperature,
+                           work, diffusivity, emissivity, emissivity_rows, band_start, from_last,
+                           asynchronous, outputs)
+
+    def path_thermal_two_stream_source(self, beta, columns, grid, n_paths, levels_per_path,
+                                       level_begin, level_table, edge_temperature,
+                                       surface_temperature, work, diffusivity=1.66,
+                                       emissivity=None, emissivity_rows=None, band_start=None,
+                                       from_last=False, asynchronous=False, **outputs):
+        """path_thermal_two_stream with the linear-in-tau source --
+        lbl_path_thermal_two_stream_source.  edge_temperature [rows, 2]: the interface
+        temperatures of each row on its first-level and its last-level side [K], as for
+        path_flux; everything else as for path_thermal_two_stream."""
+        if edge_temperature is None:
+            raise ValueError("path_thermal_two_stream_source needs edge_temperature.")
+        self._path_thermal("path_thermal_two_stream_source", beta, columns, grid, n_paths,
+                           levels_per_path, level_begin, level_table, edge_temperature,
+                           surface_temperature, work, diffusivity, emissivity, emissivity_rows,
+                           band_start, from_last, asynchronous, outputs)
+
+    def _path_thermal(self, name, beta, columns, grid, n_paths, levels_per_path, level_begin,
+                      level_table, edge_temperature, surface_temperature, work, diffusivity,
+                      emissivity, emissivity_rows, band_start, from_last, asynchronous, outputs):
+        """The call of path_thermal_two_stream (edge_temperature None) and of
+        path_thermal_two_stream_source: lbl_<name>."""
         rows, stride = int(beta.shape[0]), int(beta.shape[1])
         table = _f64(level_table)
         if table.shape != (rows, 5):
             raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
+        edges = _edge_rows(edge_temperature, rows)
         unknown = set(outputs) - set(PATH_THERMAL_OUTPUTS)
         if unknown:
-            raise TypeError(f"path_thermal_two_stream has no output {sorted(unknown)}.")
+            raise TypeError(f"{name} has no output {sorted(unknown)}.")
         if work.shape[1] != stride or work.shape[0] < 2*rows:
             raise ValueError(f"work has shape {work.shape}, need {2*rows} x {stride}.")
         ts, emissivity = _per_path(n_paths, "one surface temperature and one emissivity per "
@@ -839,14 +866,15 @@ class Engine(object):
                                            asynchronous)
         flags |= PATH_FROM_LAST if from_last else 0
         pointers = []
-        for name in PATH_THERMAL_OUTPUTS:
-            out = outputs.get(name)
-            need = int(n_paths) if name.startswith("top_") else rows
-            _check_outputs((out,), need, n_bands if name.endswith("_mean") else stride)
+        for output in PATH_THERMAL_OUTPUTS:
+            out = outputs.get(output)
+            need = int(n_paths) if output.startswith("top_") else rows
+            _check_outputs((out,), need, n_bands if output.endswith("_mean") else stride)
             pointers.append(_address(out))
-        self._check(self.lib.lbl_path_thermal_two_stream(
+        tables = [table.ctypes.data] + ([] if edges is None else [edges.ctypes.data])
+        self._check(getattr(self.lib, "lbl_" + name)(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
-            int(levels_per_path), int(level_begin), rows, table.ctypes.data, float(diffusivity),
+            int(levels_per_path), int(level_begin), rows, *tables, float(diffusivity),
             _address(ts), _address(emissivity_rows), _address(emissivity), n_bands,
             _address(starts), work.pointer, *pointers, flags))
 

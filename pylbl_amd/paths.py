@@ -1,5 +1,6 @@
 """The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux,
-compute_jacobian, compute_solar, compute_solar_flux, compute_thermal_flux and the per-level
+compute_jacobian, compute_solar, compute_solar_flux, compute_thermal_flux,
+compute_thermal_flux_linear and the per-level
 compute_kdistribution -- on the host: their quantities and units, the checks of
 their arguments (one request per call, made before anything touches the GPU), the run loop that sweeps the "total"
 absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
@@ -159,10 +160,11 @@ _SolarFluxRequest = namedtuple("_SolarFluxRequest", _COMMON + (
 
 # compute_thermal_flux's: the level table [levels, 5] of lbl_path_thermal_two_stream (s_l, tau_c,
 # w_c, g_c, T_l), D, the surface temperature per path and its emissivity -- [paths], or [paths, M]
-# at emissivity_knots [M].
+# at emissivity_knots [M].  edge_temperature: None (compute_thermal_flux: isothermal levels) or
+# compute_thermal_flux_linear's interface temperatures per flat level, as above.
 _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
     "surface", "level_table", "diffusivity", "surface_temperature", "surface_emissivity",
-    "emissivity_knots"))
+    "emissivity_knots", "edge_temperature"), defaults=(None,))
 
 # compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
 # points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
@@ -766,12 +768,12 @@ def _solar_flux_request(spec, layer_thickness, solar_zenith_cosine, solar_irradi
 def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_emissivity,
                           emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
                           scatterer_single_scattering_albedo, scatterer_asymmetry, quantities,
-                          band_edges, range_policy):
-    """Checks every argument of compute_thermal_flux."""
+                          band_edges, range_policy, caller="compute_thermal_flux"):
+    """Checks every argument of compute_thermal_flux (of `caller`, which shares them)."""
     if spec.group is not None:
-        raise NotImplementedError("compute_thermal_flux does not split paths over processes yet "
+        raise NotImplementedError(f"{caller} does not split paths over processes yet "
                                   "(group is set).")
-    lengths, shape = _path_geometry(spec, layer_thickness, "compute_thermal_flux",
+    lengths, shape = _path_geometry(spec, layer_thickness, caller,
                                     "layer_thickness", "layer thicknesses")
     _check_level_temperatures(spec)
     if not (isinstance(surface, str) and surface in FLUX_SURFACES):
@@ -806,6 +808,16 @@ def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_em
                                level_table=table, diffusivity=float(factor),
                                surface_temperature=ts, surface_emissivity=es,
                                emissivity_knots=emissivity_knots)
+
+
+def _thermal_flux_linear_request(spec, layer_thickness, surface_temperature,
+                                 interface_temperature, *arguments):
+    """Checks every argument of compute_thermal_flux_linear: compute_thermal_flux's request with
+    the interface temperatures of the linear-in-tau source."""
+    request = _thermal_flux_request(spec, layer_thickness, surface_temperature, *arguments,
+                                    caller="compute_thermal_flux_linear")
+    return request._replace(edge_temperature=_edge_temperatures(
+        "linear_in_tau", interface_temperature, request.shape))
 
 
 def _kdistribution_weighting(spec, weighting, weighting_temperature):

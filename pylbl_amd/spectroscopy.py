@@ -15,7 +15,7 @@ of numpy arrays with the same variable names.
 
 What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
 path products compute_path, compute_radiance, compute_jacobian, compute_flux, compute_solar and
-compute_solar_flux, compute_thermal_flux, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
+compute_solar_flux, compute_thermal_flux, compute_thermal_flux_linear, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
 queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
 else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
 whose public names stay importable from here; their functions take the Spectroscopy first, and
@@ -971,7 +971,7 @@ class Spectroscopy(object):
         or aerosol layer) and the adding method, formed on the GPU in two sweeps over the "total"
         absorption block.  The longwave counterpart of compute_solar_flux; without scatterers it
         is compute_flux with the one angle mu = 1/D.  Levels are isothermal (there is no
-        source="linear_in_tau"); sunlight is not included.
+        source="linear_in_tau": that is compute_thermal_flux_linear); sunlight is not included.
 
         Paths, levels, `surface` and layer_thickness as in compute_flux.  With beta the absorption
         coefficient [m-1] of compute_absorption("total", remove_pedestal, range_policy), nu the
@@ -1036,7 +1036,73 @@ class Spectroscopy(object):
             emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
             scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
             range_policy)
+        return self._thermal_flux(request, remove_pedestal, range_policy)
+
+    def compute_thermal_flux_linear(self, layer_thickness, surface_temperature,
+                                    interface_temperature, surface_emissivity=1.,
+                                    emissivity_wavenumber=None, surface="first",
+                                    diffusivity=1.66, scatterer_optical_depth=None,
+                                    scatterer_single_scattering_albedo=None,
+                                    scatterer_asymmetry=None,
+                                    quantities=("upward_flux", "downward_flux"),
+                                    band_edges=None, remove_pedestal=None,
+                                    range_policy="reference"):
+        """compute_thermal_flux with a source that is linear in optical depth: within every
+        level the Planck function runs linearly in the layer's optical depth between its values
+        at the level's two interfaces, as compute_flux(source="linear_in_tau") has it for the
+        clear sky (line-by-line benchmark work; RRTMGP's lw_source_2str), so that cloudy and
+        clear fluxes -- a cloud radiative effect -- share one source treatment.  The isothermal
+        layer's error goes as the Planck difference across the layer and does not shrink with
+        spectral resolution.
+
+        Everything up to em is compute_thermal_flux's, bit for bit; the level temperature enters
+        beta only.  Per level and grid point, Bt = piB(T at the level's space-side interface),
+        Bb = piB(T at its surface-side interface) and dB = Bb - Bt, each product, sum and
+        quotient rounded as written:
+            S_up = Bt*em + dB*q        what the layer sends out of its space-side face
+            S_dn = Bb*em - dB*q        what it sends out of its surface-side face
+        q = (1 - T + R)/(su*t) - T comes from the particular solution F+- = pi*(B(tau) +- B'/su)
+        and is formed without the difference, which cancels in thin layers:
+            clear level (w_c == 0):
+              q = a - linear_weight(x, a)
+                (a = em; linear_weight is compute_radiance's w = 1 - a/x in its two-branch form)
+            cloudy, general:  y = k*t ; z = y*y
+              p = o1 - 2*(y*E)        for y >= 1/2, and for y < 1/2
+              p = E*(((y*z)/3)*(1 + z*(1/20 + z*(1/840 + z*(1/60480 + z*(1/6652800
+                  + z*(1/1037836800 + z*(1/217945728000 + z*(1/59281238016000)))))))))
+              q = ((k*(o1*o1))/(su*((1 + E)*(1 + E))) + p)/(den*t)
+            cloudy, conservative:
+              q = ((dif*t)*(1 + (su*t)/3))/(2*(1 + x))
+        Adding is compute_thermal_flux's with the two sources told apart:
+            U[i] = S_up_i + T_i*((U[i+1] + Rs[i+1]*S_dn_i)*m1)
+            Dn = S_dn_i + T_i*((Dn + Rd*S_up_i)*m3)
+        and Rs, Rd, m1, m2, m3, the interface lines and the surface unchanged.  With dB = 0 both
+        sources are Bt*em: where all interface and level temperatures of a path are equal the
+        fluxes are compute_thermal_flux's bit for bit.
+
+        Args:
+            interface_temperature: the atmosphere's shape with L + 1 along the last axis, finite
+                         and > 0 [K]; interface i lies between levels i-1 and i, as in
+                         compute_flux.  surface_temperature stays apart from the interface
+                         temperature at the surface: a skin-temperature jump is allowed.
+            Everything else as in compute_thermal_flux.
+
+        Returns:
+            Like compute_thermal_flux, with the attribute (the key) "source": "linear_in_tau".
+        Raises ValueError like compute_thermal_flux, all of them before the GPU is touched.
+        """
+        request = paths._thermal_flux_linear_request(
+            self, layer_thickness, surface_temperature, interface_temperature,
+            surface_emissivity, emissivity_wavenumber, surface, diffusivity,
+            scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry,
+            quantities, band_edges, range_policy)
+        return self._thermal_flux(request, remove_pedestal, range_policy)
+
+    def _thermal_flux(self, request, remove_pedestal, range_policy):
+        """The sweeps of compute_thermal_flux and, where the request holds interface
+        temperatures, of compute_thermal_flux_linear."""
         bands = request.starts is not None
+        linear = request.edge_temperature is not None
         heating = "heating_rate" in request.quantities
         wanted = tuple(q for q in ("upward_flux", "downward_flux")
                        if q in request.quantities or heating)
@@ -1071,9 +1137,14 @@ class Spectroscopy(object):
                             blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[source]
                         else:
                             blocks[name + "_rows"] = outputs[source]
-                call.engine.path_thermal_two_stream(
-                    beta, call.columns, grid, call.paths, call.per_path, a,
-                    request.level_table[a:b], request.surface_temperature,
+                entry = call.engine.path_thermal_two_stream
+                tables = (request.level_table[a:b],)
+                if linear:
+                    entry = call.engine.path_thermal_two_stream_source
+                    tables += (request.edge_temperature[a:b],)
+                entry(
+                    beta, call.columns, grid, call.paths, call.per_path, a, *tables,
+                    request.surface_temperature,
                     work if b - a == run else work.rows(2*(b - a)),
                     diffusivity=request.diffusivity,
                     emissivity=None if spectral else request.surface_emissivity,
@@ -1264,6 +1335,7 @@ class Spectroscopy(object):
     _create_solar_dataset = paths._create_solar_dataset
     _solar_flux_request = paths._solar_flux_request
     _thermal_flux_request = paths._thermal_flux_request
+    _thermal_flux_linear_request = paths._thermal_flux_linear_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
 
