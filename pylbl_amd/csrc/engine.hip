@@ -50,7 +50,6 @@
 #include "tile_schedule.h"
 #include "twostream.h"
 #include "twostream_thermal.h"
-#include "twostream_thermal_source.h"
 
 #include "engine_core.h"
 #include "lanes_plans.inc"
@@ -508,7 +507,6 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "solar_entry.inc"
 #include "twostream_entry.inc"
 #include "thermal_entry.inc"
-#include "thermal_source_entry.inc"
 #include "band_sort_entry.inc"
 #include "band_sort_pairs_entry.inc"
 #include "instrument_entry.inc"

@@ -1,7 +1,8 @@
 // What the path entries share (lbl_path_compute here, lbl_path_radiance, lbl_path_jacobian,
 // lbl_path_flux, lbl_path_solar) -- the checks of a run, of its bands, boundaries and knots, the
 // staged tables, the PathLevels part of the kernel arguments, the launches, the choice of outputs
-// and the band means -- and lbl_path_compute: optical depth and transmittance along paths through
+// and the band means --, what the three whole-path two-stream entries share beyond that
+// (TwoStreamCall), and lbl_path_compute: optical depth and transmittance along paths through
 // a block of absorption coefficients in HBM (kernels: path.h).  Included by engine.hip after
 // slot_entry.inc (grid handles).
 #include "dispatch.h"
@@ -472,6 +473,115 @@ struct PathCall
         bands.means(engine, d_tables, values + (long long)rows.first*row_stride,
                     (long long)row_stride, rows.count, transmittance,
                     out + (long long)rows.first*bands.n_bands);
+    }
+};
+
+// What the whole-path two-stream entries share (lbl_path_two_stream, lbl_path_thermal_two_stream,
+// lbl_path_thermal_two_stream_source): `count` outputs, the first `per_level` of them rows below
+// every level of the run and the rest rows at interface 0 of every path, each with its band mean
+// (null: not wanted); an up sweep that leaves what lies below every level in the work rows, and a
+// down sweep behind it that writes the outputs.  The checks return nullptr or what is wrong, in
+// the order the entries call them.
+struct TwoStreamCall
+{
+    PathCall & call;
+    int count, per_level;
+    double * const * rows;
+    double * const * mean;
+
+    const char * check_whole_paths() const
+    {
+        if (call.flags & ~(LBL_PATH_FROM_LAST | LBL_ASYNC))
+        {
+            return "only LBL_PATH_FROM_LAST and LBL_ASYNC may be set: a call takes whole paths.";
+        }
+        if (call.levels_per_path >= 1 && (call.level_begin % call.levels_per_path != 0 ||
+                                          call.level_count % call.levels_per_path != 0))
+        {
+            return "the run must consist of whole paths: level_begin and level_count must be "
+                   "multiples of levels_per_path.";
+        }
+        return nullptr;
+    }
+
+    const char * check_outputs(const double * beta, const double * work, int32_t n_bands) const
+    {
+        bool any = false;
+        for (int q = 0; q < count; ++q)
+        {
+            any = any || rows[q] != nullptr;
+            if (rows[q] != nullptr && (rows[q] == beta || rows[q] == work))
+            {
+                return "an output must be neither beta nor the work rows.";
+            }
+            if (mean[q] != nullptr && rows[q] == nullptr)
+            {
+                return "a band mean needs the rows it is the mean of.";
+            }
+            if (mean[q] != nullptr && n_bands == 0) return "band means need n_bands > 0.";
+        }
+        if (!any) return "no output requested.";
+        if (work == beta) return "work must not be beta.";
+        return nullptr;
+    }
+
+    // The level table [level_count][words]: its first column, the thicknesses, are the run's
+    // lengths (call.check); the other columns follow.
+    const char * check_levels(const double * level_table, int words) const
+    {
+        if (call.level_count < 1) return "need level_count >= 1.";
+        std::vector<double> thickness((size_t)call.level_count);
+        for (int r = 0; r < call.level_count; ++r)
+        {
+            thickness[(size_t)r] = level_table[(size_t)r*words];
+        }
+        if (const char * problem = call.check(thickness.data(), 1)) return problem;
+        if (!finite_at_least_zero(level_table, (long long)call.level_count*words, false))
+        {
+            return "the level table must be finite and >= 0.";
+        }
+        return nullptr;
+    }
+
+    // Up from the surface, then down from space behind it on the same stream.  The order space ->
+    // surface is from_last() (the surface is level 0); the up sweep runs against it.  up(v) and
+    // down(v): the kernels for rows that are 16-byte aligned (v: std::true_type) or not.
+    template <typename Args, typename Up, typename Down>
+    void sweeps(Args & a, bool vector, Up up, Down down) const
+    {
+        const int down_order = call.from_last() ? 1 : 0;
+        a.from_last = 1 - down_order;
+        sweep(a, vector, up);
+        a.from_last = down_order;
+        sweep(a, vector, down);
+    }
+
+    template <typename Args, typename Kernel>
+    void sweep(Args & a, bool vector, Kernel kernel) const
+    {
+        call.launch(a, [&](const dim3 & grid) {
+            dispatch([&](auto v) {
+                hipLaunchKernelGGL((kernel(v)), grid, dim3(kPathThreads), 0, call.engine->stream,
+                                   a);
+            }, vector);
+        });
+    }
+
+    // Records what the sweeps touched and queues the means: every interface below a level of the
+    // run; interface 0 of its (whole) paths.
+    void finish(const PathBands & bands, const double * beta, const double * work) const
+    {
+        call.note_rows(beta, call.level_count);
+        call.note_rows(work, 2*(long long)call.level_count);
+        for (int q = 0; q < count; ++q)
+        {
+            call.note_rows(rows[q], q < per_level ? call.level_count : call.n_paths);
+        }
+        for (int q = 0; q < count; ++q)
+        {
+            call.means(bands, q < per_level ? PathMeanRows::kLevels : PathMeanRows::kStarted,
+                       rows[q], mean[q]);
+        }
     }
 };
 

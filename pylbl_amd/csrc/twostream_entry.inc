@@ -2,7 +2,7 @@
 // from the caller's values; lbl_path_two_stream: two-stream shortwave fluxes at every interface of
 // whole paths through a block of absorption coefficients in HBM (kernels: twostream.h; band
 // means: path.h).  Included by engine.hip after solar_entry.inc; shares path_entry.inc's PathCall,
-// PathTables and PathBands.
+// TwoStreamCall, PathTables and PathBands.
 extern "C" {
 
 int lbl_rayleigh_row(lbl_engine * engine, int32_t grid, int64_t columns,
@@ -66,6 +66,7 @@ int lbl_path_two_stream(lbl_engine * engine, double * beta, int64_t row_stride, 
                                       top_down_rows, top_direct_rows, top_diffuse_rows};
         double * const mean[kRows] = {up_mean, down_mean, direct_mean, diffuse_mean, top_up_mean,
                                       top_down_mean, top_direct_mean, top_diffuse_mean};
+        const TwoStreamCall two{call, kRows, kPerLevel, rows, mean};
         if (beta == nullptr || level_table == nullptr || solar_zenith_cosine == nullptr ||
             solar_row == nullptr || work == nullptr)
         {
@@ -76,46 +77,14 @@ int lbl_path_two_stream(lbl_engine * engine, double * beta, int64_t row_stride, 
         {
             return call.bad("the surface needs an albedo: albedo_rows or albedo, not both.");
         }
-        if (flags & ~(LBL_PATH_FROM_LAST | LBL_ASYNC))
+        if (const char * problem = two.check_whole_paths()) return call.bad(problem);
+        if (const char * problem = two.check_outputs(beta, work, n_bands))
         {
-            return call.bad("only LBL_PATH_FROM_LAST and LBL_ASYNC may be set: a call takes "
-                            "whole paths.");
+            return call.bad(problem);
         }
-        if (levels_per_path >= 1 &&
-            (level_begin % levels_per_path != 0 || level_count % levels_per_path != 0))
+        if (const char * problem = two.check_levels(level_table, kTwoStreamLevelWords))
         {
-            return call.bad("the run must consist of whole paths: level_begin and level_count "
-                            "must be multiples of levels_per_path.");
-        }
-        bool any = false;
-        for (int q = 0; q < kRows; ++q)
-        {
-            any = any || rows[q] != nullptr;
-            if (rows[q] != nullptr && (rows[q] == beta || rows[q] == work))
-            {
-                return call.bad("an output must be neither beta nor the work rows.");
-            }
-            if (mean[q] != nullptr && rows[q] == nullptr)
-            {
-                return call.bad("a band mean needs the rows it is the mean of.");
-            }
-            if (mean[q] != nullptr && n_bands == 0) return call.bad("band means need n_bands > 0.");
-        }
-        if (!any) return call.bad("no output requested.");
-        if (work == beta) return call.bad("work must not be beta.");
-        // The thicknesses are the run's lengths; the other four columns of the table follow.
-        if (level_count < 1) return call.bad("need level_count >= 1.");
-        {
-            std::vector<double> thickness((size_t)level_count);
-            for (int r = 0; r < level_count; ++r)
-            {
-                thickness[(size_t)r] = level_table[(size_t)r*kTwoStreamLevelWords];
-            }
-            if (const char * problem = call.check(thickness.data(), 1)) return call.bad(problem);
-        }
-        if (!finite_at_least_zero(level_table, (long long)level_count*kTwoStreamLevelWords, false))
-        {
-            return call.bad("the level table must be finite and >= 0.");
+            return call.bad(problem);
         }
         for (int r = 0; r < level_count; ++r)
         {
@@ -168,36 +137,10 @@ int lbl_path_two_stream(lbl_engine * engine, double * beta, int64_t row_stride, 
         const bool vector = path_vector(row_stride, {beta, solar_row, rayleigh_row, albedo_rows,
                                                      work, rows[0], rows[1], rows[2], rows[3],
                                                      rows[4], rows[5], rows[6], rows[7]});
-        // Up from the surface, then down from space behind it on the same stream.  The Sun's
-        // order is from_last() (the surface is level 0); the up sweep runs against it.
-        const int sun_order = call.from_last() ? 1 : 0;
-        a.from_last = 1 - sun_order;
-        call.launch(a, [&](const dim3 & launch) {
-            dispatch([&](auto v) {
-                hipLaunchKernelGGL(two_stream_up_kernel<v.value>, launch, dim3(kPathThreads), 0,
-                                   engine->stream, a);
-            }, vector);
-        });
-        a.from_last = sun_order;
-        call.launch(a, [&](const dim3 & launch) {
-            dispatch([&](auto v) {
-                hipLaunchKernelGGL(two_stream_down_kernel<v.value>, launch, dim3(kPathThreads), 0,
-                                   engine->stream, a);
-            }, vector);
-        });
-        call.note_rows(beta, level_count);
-        call.note_rows(work, 2*(long long)level_count);
-        for (int q = 0; q < kRows; ++q)
-        {
-            call.note_rows(rows[q], q < kPerLevel ? level_count : n_paths);
-        }
-
-        // Every interface below a level of the run; interface 0 of its (whole) paths.
-        for (int q = 0; q < kRows; ++q)
-        {
-            call.means(bands, q < kPerLevel ? PathMeanRows::kLevels : PathMeanRows::kStarted,
-                       rows[q], mean[q]);
-        }
+        // The Sun's order is the down sweep's.
+        two.sweeps(a, vector, [](auto v) { return two_stream_up_kernel<v.value>; },
+                   [](auto v) { return two_stream_down_kernel<v.value>; });
+        two.finish(bands, beta, work);
         return LBL_OK;
     });
 }

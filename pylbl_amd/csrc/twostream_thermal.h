@@ -1,8 +1,11 @@
 // Two-stream longwave fluxes through clouds (Spectroscopy.compute_thermal_flux,
-// lbl_path_thermal_two_stream): upward and downward fluxes at every interface of whole paths, from
-// a delta-scaled two-stream layer solution with a thermal source and the adding recurrences, over
-// the "total" absorption block in HBM.  The TU builds with -ffp-contract=off: every product, sum
-// and quotient below is rounded as written.
+// lbl_path_thermal_two_stream; with kLinear Spectroscopy.compute_thermal_flux_linear,
+// lbl_path_thermal_two_stream_source): upward and downward fluxes at every interface of whole
+// paths, from a delta-scaled two-stream layer solution with a thermal source and the adding
+// recurrences, over the "total" absorption block in HBM.  The source is the Planck function of the
+// level temperature or, with kLinear, linear in the layer's (scaled) optical depth between its
+// two faces.  The TU builds with -ffp-contract=off: every product, sum and quotient below is
+// rounded as written.
 //
 // Per level l the table row is (s_l, tau_c, w_c, g_c, T_l); D is the diffusivity factor, one
 // scalar per call; piB(T) = kFluxPi*planck(nu, c1nu3, c2nu, T) (radiance.h, flux.h).
@@ -33,16 +36,49 @@
 // A clear level has R = 0, so m1 = m3 = 1 exactly, x*1 = x and 0 + x = x: thermal_through leaves
 // those out where the level is clear and gives the bits of the lines above.
 //
-// thermal_layer is the layer written once; both kernels call it.  w_c == 0 is a wave-uniform
-// branch (the level's scalars are the same for the whole wavefront): a clear level costs one exp,
-// one expm1 and the Planck function, no square root and no division of the layer or the adding.
-// The kernels run on path.h's sweep skeleton, whole paths only, as twostream.h's do:
-// thermal_up_kernel sweeps surface -> space with U and Rs in registers and writes them to the work
-// rows at the interface above each level; thermal_down_kernel, queued behind it on the same
-// stream, sweeps space -> surface with Dn and Rd in registers, reads beta again and recomputes the
-// layer instead of reading three stored quantities (48 B per element beside beta's 8 B), reads the
-// work rows and stores the flux rows asked for; the lane that starts a path writes the rows of
-// interface 0.  nu, C2*nu and C1*nu^3 are formed once per lane, as in flux.h.
+//
+// kLinear: the table row, D, tau, t, w, g1, g2, dif, su, k2, k, E, E2, o1, den, R, T, em, x and the
+// branch conditions are the ones above, bit for bit; T_l is not read.  Per level and column,
+// Bt = piB(T at the level's space-side interface), Bb = piB(T at its surface-side interface),
+// dB = Bb - Bt, and the layer sends
+//   S_up = Bt*em + dB*q        out of its space-side face
+//   S_dn = Bb*em - dB*q        out of its surface-side face
+// q = (1 - T + R)/(su*t) - T from the particular solution F+- = pi*(B(tau) +- B'/su), formed
+// without the difference, which cancels to O(t) in a thin layer:
+//   clear level (w_c == 0):  q = a - linear_weight(x, a)
+//     (a = em = -expm1(-x); radiance.h's linear_weight: the u_in of lbl_path_flux_source)
+//   cloudy, general:  y = k*t ; z = y*y
+//     p = o1 - 2*(y*E)                                        for y >= 1/2
+//     p = E*(((y*z)/3)*(1 + z*(1/20 + z*(1/840 + z*(1/60480 + z*(1/6652800 + z*(1/1037836800
+//         + z*(1/217945728000 + z*(1/59281238016000)))))))))    for y < 1/2
+//       (p = 2*E*(sinh y - y) = 1 - E2 - 2*y*E; the direct form loses y's leading digits)
+//     q = ((k*(o1*o1))/(su*((1 + E)*(1 + E))) + p)/(den*t)
+//       (o1/(1 + E) is 1 - E without its cancellation: em's (1 - E)*(1 - E) loses y's leading
+//       digits, which em does not feel beside dif*o1 and q does, 1.4e-8 relative at y = 1e-8)
+//   cloudy, conservative:  q = ((dif*t)*(1 + (su*t)/3))/(2*(1 + x))
+// With dB = 0 both sources are Bt*em exactly: a path whose interface and level temperatures are
+// all equal has the bits of the source above.  Adding is the one above with the two sources told
+// apart:
+//   up:    U[i] = S_up_i + T_i*((U[i+1] + Rs[i+1]*S_dn_i)*m1)
+//   down:  Dn   = S_dn_i + T_i*((Dn + Rd*S_up_i)*m3)
+// Rs, Rd, m1, m2, m3, the interface lines and the surface (eps*piB(T_s), 1 - eps) are unchanged:
+// T_s is not the interface temperature at the surface.
+//
+// thermal_layer is the layer written once, with q where kLinear; ThermalFaces::through, the step
+// through one level, calls it for both sweeps and both sources.  w_c == 0 is a wave-uniform branch
+// (the level's scalars are the same for the whole wavefront): a clear level costs one exp, one
+// expm1 and the Planck function, no square root and no division of the layer or the adding (with
+// kLinear: one division, linear_weight's).  The kernels run on path.h's sweep skeleton, whole paths
+// only, as twostream.h's do: thermal_up_kernel sweeps surface -> space with U and Rs in registers
+// and writes them to the work rows at the interface above each level; thermal_down_kernel, queued
+// behind it on the same stream, sweeps space -> surface with Dn and Rd in registers, reads beta
+// again and recomputes the layer instead of reading three stored quantities (48 B per element
+// beside beta's 8 B), reads the work rows and stores the flux rows asked for; the lane that starts
+// a path writes the rows of interface 0.  nu, C2*nu and C1*nu^3 are formed once per lane, as in
+// flux.h.  With kLinear, as in radiance.h's kLinear sweeps, a lane evaluates Planck once at the
+// face it enters its path through and then once per level at the exit face, which it keeps as the
+// next level's entry value (the table is continuous within a path: the entry checks it): one
+// Planck per element and level, as without.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -58,6 +94,10 @@ constexpr double kThermalConservative = 1e-10;      // k2*(1 + t*t) at most: the
 constexpr int kThermalLevelWords = 5;               // s_l, tau_c, w_c, g_c, T_l per level
 constexpr int kThermalUpAhead = kPathAhead;         // rows of beta in flight per lane, going up
 constexpr int kThermalDownAhead = 1;              // going down: more rows spill scalar registers
+constexpr double kThermalSourceSeriesBelow = 1./2.; // y = k*t below which p comes from its series
+constexpr int kThermalSourceUpAhead = 1;            // kLinear, going up: more rows spill scalar registers
+constexpr int kThermalSourceDownAhead = 1;          // going down
+static_assert(kThermalSourceDownAhead == kThermalDownAhead, "the down kernel takes one for both");
 
 struct PathThermal : PathLevels
 {
@@ -71,12 +111,15 @@ struct PathThermal : PathLevels
     double * work;              // [count][2][stride]: U, Rs at the interface above each level
     double * level_out[2];      // up, down at the interface below each level (null: not wanted)
     double * top_out[2];        // [paths][stride]: the same at interface 0
+    const double * edge;        // kLinear: [count][2], interface temperatures of flat level
+                                // first + i on its first-level / last-level side [K]; else null
 };
 
-// What a layer does to diffuse light, and the fraction of piB(T_l) it emits either way.
+// What a layer does to diffuse light, the fraction of piB(T_l) it emits either way and, with
+// kLinear, the weight q of the Planck difference across it.
 struct ThermalLayer
 {
-    double r, t, em;
+    double r, t, em, q;
 };
 
 // The level's scalars, read once per level and wavefront.
@@ -105,8 +148,19 @@ __device__ __forceinline__ ThermalLevel thermal_level(const double * row)
     return v;
 }
 
+// p = 2*E*(sinh y - y) for y = k*t >= 0, E = exp(-y) and o1 = 1 - E*E.
+__device__ __forceinline__ double thermal_source_p(double y, double e, double o1)
+{
+    const double z = y*y;
+    const double series =
+        1. + z*(1./20. + z*(1./840. + z*(1./60480. + z*(1./6652800. + z*(1./1037836800. +
+        z*(1./217945728000. + z*(1./59281238016000.)))))));
+    return y < kThermalSourceSeriesBelow ? e*(((y*z)/3.)*series) : o1 - 2.*(y*e);
+}
+
 // The layer of one level and grid point (the formulas in the head of this file).  v: the level's
 // scalars; d: the diffusivity factor; b: beta.
+template <bool kLinear>
 __device__ __forceinline__ ThermalLayer thermal_layer(const ThermalLevel & v, double d, double b)
 {
     ThermalLayer y;
@@ -118,6 +172,7 @@ __device__ __forceinline__ ThermalLayer thermal_layer(const ThermalLevel & v, do
         y.r = 0.;
         y.t = exp(-x);
         y.em = -expm1(-x);
+        if constexpr (kLinear) y.q = y.em - linear_weight(x, y.em);
         return y;
     }
     const double omega = v.w_c/tau;
@@ -135,6 +190,7 @@ __device__ __forceinline__ ThermalLayer thermal_layer(const ThermalLevel & v, do
         y.r = x/(1. + x);
         y.t = 1./(1. + x);
         y.em = (dif*t)/(1. + x);
+        if constexpr (kLinear) y.q = ((dif*t)*(1. + (su*t)/3.))/(2.*(1. + x));
         return y;
     }
     const double k = sqrt(k2);
@@ -145,24 +201,30 @@ __device__ __forceinline__ ThermalLayer thermal_layer(const ThermalLevel & v, do
     y.r = (g2*o1)/den;
     y.t = (2.*(k*e))/den;
     y.em = (k*((1. - e)*(1. - e)) + dif*o1)/den;
+    if constexpr (kLinear)
+    {
+        y.q = ((k*(o1*o1))/(su*((1. + e)*(1. + e))) + thermal_source_p(k*t, e, o1))/(den*t);
+    }
     return y;
 }
 
 // One adding step through a level, the same lines upward and downward: what arrives (flux, with
 // the reflectance refl of what lies behind it) becomes what leaves on the level's other side.
-//   m = 1/(1 - R*refl) ; flux = S + T*((flux + refl*S)*m) ; refl = R + T*((T*refl)*m)
+// `out` is the layer's source through the face the sweep leaves the level by, `back` through the
+// one it entered by (the level-temperature source: the same S twice).
+//   m = 1/(1 - R*refl) ; flux = out + T*((flux + refl*back)*m) ; refl = R + T*((T*refl)*m)
 // clear: R = 0 and m = 1 exactly, left out.
-__device__ __forceinline__ void thermal_through(bool clear, const ThermalLayer & y, double source,
-                                                double & flux, double & refl)
+__device__ __forceinline__ void thermal_through(bool clear, const ThermalLayer & y, double out,
+                                                double back, double & flux, double & refl)
 {
     if (clear)
     {
-        flux = source + y.t*(flux + refl*source);
+        flux = out + y.t*(flux + refl*back);
         refl = y.t*(y.t*refl);
         return;
     }
     const double m = 1./(1. - y.r*refl);
-    flux = source + y.t*((flux + refl*source)*m);
+    flux = out + y.t*((flux + refl*back)*m);
     refl = y.r + y.t*((y.t*refl)*m);
 }
 
@@ -236,46 +298,98 @@ __device__ __forceinline__ void thermal_interface(
     if (out[1] != nullptr) path_store<kVector>(out[1] + at, width, down);
 }
 
+// The step of a sweep through one level, for both sweeps and both sources, and what a lane
+// carries from level to level for it: with kLinear piB at the face it enters the next level by.
+template <bool kLinear>
+struct ThermalFaces
+{
+    const double * level;       // the table rows, at the lane's first level
+    const double * edge;        // kLinear: the interface temperatures, likewise
+    int side;                   // kLinear: which of a level's two it is entered by
+    double d;
+    double entry[kPathWidth];
+
+    __device__ __forceinline__ ThermalFaces(const PathThermal & a, const PathLane & l,
+                                            const ThermalColumns & c)
+        : level(a.level + (long long)l.index0*kThermalLevelWords), edge(nullptr), side(0),
+          d(a.diffusivity)
+    {
+        if constexpr (kLinear)
+        {
+            side = entry_side(l.direction);
+            edge = a.edge + 2*(long long)l.index0;
+            const double t = edge[side];
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i) entry[i] = thermal_pi_planck(c, i, t);
+        }
+    }
+
+    // Level k of the sweep with beta b: (flux, refl) on the side the lane came from become those
+    // on the side it goes to.  The exit face has the level temperature or, with kLinear, its
+    // interface's; there, with S_up and S_dn of the head in terms of the face the lane enters by
+    // and the one it leaves by,
+    //   db = entry - leave ; out = leave*em + db*q ; back = entry*em - db*q
+    // Going up (entry Bb, leave Bt) that is the head's text.  Going down (entry Bt, leave Bb) db
+    // is -dB, out = Bb*em + (-dB)*q and back = Bt*em - (-dB)*q, which are the head's
+    // S_dn = Bb*em - dB*q and S_up = Bt*em + dB*q to the bit: -(a - b) == b - a,
+    // (-d)*q == -(d*q) and x + (-p) == x - p are exact in IEEE arithmetic, signed zeros included.
+    __device__ __forceinline__ void through(const PathLane & l, const ThermalColumns & c, int k,
+                                            const double (&b)[kPathWidth],
+                                            double (&flux)[kPathWidth], double (&refl)[kPathWidth])
+    {
+        const ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
+        double t_leave = v.temperature;
+        if constexpr (kLinear) t_leave = edge[2*(long long)(k*l.direction) + (1 - side)];
+#pragma unroll
+        for (int i = 0; i < kPathWidth; ++i)
+        {
+            const ThermalLayer y = thermal_layer<kLinear>(v, d, b[i]);
+            const double leave = thermal_pi_planck(c, i, t_leave);
+            double out = leave*y.em, back = out;
+            if constexpr (kLinear)
+            {
+                const double db = entry[i] - leave;
+                out = leave*y.em + db*y.q;
+                back = entry[i]*y.em - db*y.q;
+                entry[i] = leave;
+            }
+            thermal_through(v.clear, y, out, back, flux[i], refl[i]);
+        }
+    }
+};
+
 // grid and kVector as for path_sweep_kernel; a.from_last is the order of this sweep, surface to
-// space.  Whole paths: every lane starts and finishes its path.
-template <bool kVector>
+// space: a level is entered through its surface-side face (Bb) and left through the other (Bt).
+// Whole paths: every lane starts and finishes its path.
+template <bool kVector, bool kLinear>
 __global__ __launch_bounds__(kPathThreads) void thermal_up_kernel(PathThermal a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
-    const double * level = a.level + (long long)l.index0*kThermalLevelWords;
     const int width = l.width;
-    const double d = a.diffusivity;
     const ThermalColumns c = thermal_columns<kVector>(a, l);
 
     double u[kPathWidth], rs[kPathWidth];
     thermal_surface<kVector>(a, l, c, u, rs);
 
-    path_levels<kThermalUpAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
-                                                      long long at) {
-        const ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
-#pragma unroll
-        for (int i = 0; i < kPathWidth; ++i)
-        {
-            const ThermalLayer y = thermal_layer(v, d, b[i]);
-            const double source = thermal_pi_planck(c, i, v.temperature)*y.em;
-            thermal_through(v.clear, y, source, u[i], rs[i]);
-        }
+    ThermalFaces<kLinear> faces(a, l, c);
+    constexpr int kAhead = kLinear ? kThermalSourceUpAhead : kThermalUpAhead;
+    path_levels<kAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth], long long at) {
+        faces.through(l, c, k, b, u, rs);
         double * work = a.work + (2*at - l.j);
         path_store<kVector>(work, width, u);
         path_store<kVector>(work + a.stride, width, rs);
     });
 }
 
-// grid and kVector as for path_sweep_kernel; a.from_last is the order space to surface.
-template <bool kVector>
+// grid and kVector as for path_sweep_kernel; a.from_last is the order space to surface: a level is
+// entered through its space-side face (Bt) and left through the other (Bb).
+template <bool kVector, bool kLinear>
 __global__ __launch_bounds__(kPathThreads) void thermal_down_kernel(PathThermal a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
-    const double * level = a.level + (long long)l.index0*kThermalLevelWords;
     const int width = l.width;
-    const double d = a.diffusivity;
     const ThermalColumns c = thermal_columns<kVector>(a, l);
 
     double dn[kPathWidth], rd[kPathWidth], u[kPathWidth], rs[kPathWidth];
@@ -289,16 +403,10 @@ __global__ __launch_bounds__(kPathThreads) void thermal_down_kernel(PathThermal 
         path_load<kVector>(work + a.stride, width, rs);
         thermal_interface<kVector>(a.top_out, (long long)l.p*a.stride + l.j, width, dn, rd, u, rs);
     }
+    ThermalFaces<kLinear> faces(a, l, c);
     path_levels<kThermalDownAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
                                                         long long at) {
-        const ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
-#pragma unroll
-        for (int i = 0; i < kPathWidth; ++i)
-        {
-            const ThermalLayer y = thermal_layer(v, d, b[i]);
-            const double source = thermal_pi_planck(c, i, v.temperature)*y.em;
-            thermal_through(v.clear, y, source, dn[i], rd[i]);
-        }
+        faces.through(l, c, k, b, dn, rd);
         // What lies below this level: the next level's work rows, or the surface.
         if (k + 1 < l.n)
         {

@@ -4,8 +4,8 @@
 # (a substring of the mangled name: "path_" lists the sweeps -- path_sweep_kernel,
 # path_radiance_kernel, path_flux_kernel, path_jacobian_kernel -- in both instantiations;
 # "two_stream" the shortwave two-stream kernels, "thermal" the longwave ones: thermal_up_kernel and
-# thermal_down_kernel, vector and scalar rows -- and with them the linear-in-tau ones, which
-# "thermal_source" lists alone).
+# thermal_down_kernel, vector and scalar rows, each with the source of the level temperatures
+# (Lb0E as the second template argument) and with the linear-in-tau one (Lb1E)).
 # Also prints the md5 of the device code's .text: unchanged by edits that only move host code.
 set -e
 LIB=${LIB:-pylbl_amd/liblbl_amd.so}

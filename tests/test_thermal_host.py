@@ -305,9 +305,11 @@ def test_header_docstring_design_and_kernel_state_the_same_formulas():
         for formula in tc.FORMULAS:
             assert formula in text, formula
     # The layer is written once and both kernels call it; the clear branch is uniform.
-    assert KERNELS.count("ThermalLayer thermal_layer(") == 1
-    assert KERNELS.count("= thermal_layer(") == 2
-    assert "path_levels<kThermalUpAhead, kVector>" in KERNELS
+    assert KERNELS.count("ThermalLayer thermal_layer(") == KERNELS.count(" thermal_layer(") == 1
+    assert KERNELS.count("= thermal_layer<kLinear>(") == KERNELS.count("thermal_layer<") == 1
+    assert KERNELS.count("faces.through(") == 2
+    assert "kAhead = kLinear ? kThermalSourceUpAhead : kThermalUpAhead;" in KERNELS
+    assert "path_levels<kAhead, kVector>" in KERNELS
     assert "path_levels<kThermalDownAhead, kVector>" in KERNELS
     assert "kThermalLevelWords = 5" in KERNELS
     signature = inspect.signature(Spectroscopy.compute_thermal_flux).parameters

@@ -1,5 +1,5 @@
 """CPU-only checks of Spectroscopy.compute_thermal_flux_linear: the weight q of
-csrc/twostream_thermal_source.h in float64 against long double, that the case tables of
+csrc/twostream_thermal.h's kLinear layer in float64 against long double, that the case tables of
 tests/thermal_source_cases.py reach what they are named for, the float64-vs-long-double scan of
 the numpy mirror that measures E_cpu (printed; thermal_source_cases.E_CPU records it and the GPU
 tests take their bound from it), the mirror against what the linear source demands of it, the
@@ -25,7 +25,7 @@ from tests.test_linear_source_host import make_spectroscopy
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER_PATH = ROOT / "include" / "lbl_amd_thermal_source.h"
-KERNEL_PATH = ROOT / "pylbl_amd" / "csrc" / "twostream_thermal_source.h"
+KERNEL_PATH = ROOT / "pylbl_amd" / "csrc" / "twostream_thermal.h"
 F64, LD = np.float64, np.longdouble
 ONES = np.ones((3, 5))
 INTERFACES = np.linspace(210., 290., 18).reshape(3, 6)
@@ -354,19 +354,32 @@ def test_header_docstring_design_and_kernel_state_the_same_formulas():
     for formula in tc.FORMULAS:
         if not formula.startswith(("S = ", "U[i] = ", "Dn = ")):
             assert formula in squeeze(HEADER_PATH.read_text()), formula
-    # The layer is written once and both kernels call it; twostream_thermal.h is included.
-    assert kernels.count("ThermalSourceLayer thermal_source_layer(") == 1
-    assert kernels.count("= thermal_source_layer(") == 2
-    assert '#include "twostream_thermal.h"' in kernels
-    assert "path_levels<kThermalSourceUpAhead, kVector>" in kernels
-    assert "path_levels<kThermalSourceDownAhead, kVector>" in kernels
+    # One layer, one adding step and one pair of kernels serve both sources: the layer is written
+    # once and called once, each of its results is assigned once per branch (no second copy to
+    # drift), and nothing of the separate linear-source files is left.
+    assert kernels.count("ThermalLayer thermal_layer(") == kernels.count(" thermal_layer(") == 1
+    assert kernels.count("thermal_layer<kLinear>(") == kernels.count("thermal_layer<") == 1
+    for member in ("y.r = ", "y.t = ", "y.em = ", "y.q = "):
+        assert kernels.count(member) == 3, member
+    assert len(re.findall(r"if constexpr \(kLinear\)\s*\{?\s*y\.q = ", kernels)) == 3
+    assert kernels.count("void thermal_through(") == 1
+    assert kernels.count("thermal_through(v.clear, y, out, back, flux[i], refl[i]);") == 1
+    assert kernels.count("thermal_through(") == 2
+    assert kernels.count("__global__") == 2 and kernels.count(".through(l, c, k, b, ") == 2
+    csrc = ROOT / "pylbl_amd" / "csrc"
+    for path in csrc.iterdir():
+        for gone in ("thermal_source_layer", "thermal_source_through", "PathThermalSource",
+                     "ThermalSourceLayer"):
+            assert gone not in path.read_text(), (path.name, gone)
+    assert not (csrc / "twostream_thermal_source.h").exists()
+    assert not (csrc / "thermal_source_entry.inc").exists()
+    assert "kLinear ? kThermalSourceUpAhead : kThermalUpAhead" in kernels
+    assert "path_levels<kAhead, kVector>" in kernels
+    assert "path_levels<kThermalDownAhead, kVector>" in kernels
+    assert "kThermalSourceDownAhead == kThermalDownAhead" in kernels
     for reused in ("thermal_level(", "thermal_columns<kVector>(", "thermal_pi_planck(",
                    "thermal_surface<kVector>(", "thermal_interface<kVector>("):
         assert reused in kernels, reused
-    # r, t and em are thermal_layer's expressions, term for term.
-    old = (ROOT / "pylbl_amd" / "csrc" / "twostream_thermal.h").read_text()
-    for line in re.findall(r"^\s+y\.(?:r|t|em) = .*;$", old, re.M):
-        assert line in kernels, line
 
 
 def test_signature_and_defaults():
