@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h,
-include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h and include/lbl_amd_kdist.h
-(pylbl_amd/liblbl_amd.so), and nothing else:
+include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h, include/lbl_amd_kdist.h and
+include/lbl_amd_scatterer.h (pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -233,6 +233,19 @@ KDIST_PROTOTYPES = {
                                        _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
                                        _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _i32],
 }
+# Every function of include/lbl_amd_scatterer.h, the header of the two-stream entries with spectral
+# cloud and aerosol optics of the same library, in its order; each returns int.
+# tests/test_scatterer_host.py compares this table with that header.
+SCATTERER_PROTOTYPES = {
+    # lbl_path_two_stream's with grid, n_knots, knot_wavenumber and knot_optics after level_table
+    "lbl_path_two_stream_spectral": _BLOCK + _RUN + [_ptr, _i32, _i32, _ptr, _ptr] + [_ptr]*5 +
+                                    [_i32] + [_ptr]*18 + [_i32],
+    # lbl_path_thermal_two_stream_source's with n_knots, knot_wavenumber and knot_optics after
+    # edge_temperature
+    "lbl_path_thermal_two_stream_spectral": _BLOCK + [_i32] + _RUN + [_ptr, _ptr, _i32, _ptr, _ptr,
+                                                                      _f64, _ptr, _ptr, _ptr,
+                                                                      _i32] + [_ptr]*10 + [_i32],
+}
 
 _library = None
 
@@ -291,7 +304,7 @@ def library():
     lib = CDLL(str(path))
     for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()) + \
             list(THERMAL_PROTOTYPES.items()) + list(THERMAL_SOURCE_PROTOTYPES.items()) + \
-            list(KDIST_PROTOTYPES.items()):
+            list(KDIST_PROTOTYPES.items()) + list(SCATTERER_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

@@ -32,6 +32,7 @@
 #include "../../include/lbl_amd_thermal.h"
 #include "../../include/lbl_amd_thermal_source.h"
 #include "../../include/lbl_amd_kdist.h"
+#include "../../include/lbl_amd_scatterer.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "band_sort_pairs.h"

@@ -2,17 +2,21 @@
 // at every interface of whole paths through a block of absorption coefficients in HBM, with one
 // grey scatterer per level; the second with a source that is linear in optical depth between the
 // Planck values at every level's two interfaces (kernels: twostream_thermal.h; band means:
-// path.h).  Included by engine.hip after twostream_entry.inc; shares path_entry.inc's PathCall,
-// TwoStreamCall, PathTables, PathBands and check_edge_temperatures.
+// path.h); lbl_path_thermal_two_stream_spectral: either source with the scatterer of every level
+// as a table over wavenumber (include/lbl_amd_scatterer.h; kernels: scatterer.h).  Included by
+// engine.hip after twostream_entry.inc; shares path_entry.inc's PathCall, TwoStreamCall,
+// PathTables, PathBands and check_edge_temperatures, and twostream_entry.inc's ScattererTable.
 namespace {
 
-// Both entries.  name: the entry's; edge_temperature: [level_count][2], or null for the source of
-// the level temperatures.
+// All three entries.  name: the entry's; edge_temperature: [level_count][2], or null for the
+// source of the level temperatures; spectral: the scatterer's knot table, or null for the grey
+// scatterer of the level table.
 int path_thermal_two_stream(lbl_engine * engine, const char * name, double * beta,
                             int64_t row_stride, int64_t columns, int32_t grid, int32_t n_paths,
                             int32_t levels_per_path, int32_t level_begin, int32_t level_count,
                             const double * level_table, const double * edge_temperature,
-                            bool linear, double diffusivity, const double * surface_temperature,
+                            bool linear, ScattererTable * spectral, double diffusivity,
+                            const double * surface_temperature,
                             const double * emissivity_rows, const double * emissivity,
                             int32_t n_bands, const int64_t * band_start, double * work,
                             double * const (&rows)[4], double * const (&mean)[4], int32_t flags)
@@ -79,6 +83,14 @@ int path_thermal_two_stream(lbl_engine * engine, const char * name, double * bet
         {
             return call.bad(problem);
         }
+        if (spectral != nullptr)
+        {
+            if (const char * problem = spectral->check(level_table, level_count,
+                                                       kThermalLevelWords, 1))
+            {
+                return call.bad(problem);
+            }
+        }
 
         const PathRun & run = call.run;
         PathTables tables;
@@ -88,9 +100,10 @@ int path_thermal_two_stream(lbl_engine * engine, const char * name, double * bet
             tables.add(run.paths, emissivity != nullptr ? emissivity + run.first_path : nullptr);
         tables.add(bands, band_start);
         const size_t edge_at = tables.add(linear ? 2*(size_t)level_count : 0, edge_temperature);
+        if (spectral != nullptr) spectral->stage(tables, level_count);
         const double * d_tables = call.begin(tables);
 
-        PathThermal a;
+        PathThermalSpectral a;
         call.fill(a, beta, nullptr);
         a.nu = call.grid->wavenumber.data;
         a.level = d_tables + level_at;
@@ -108,12 +121,23 @@ int path_thermal_two_stream(lbl_engine * engine, const char * name, double * bet
         }
         const bool vector = path_vector(row_stride, {beta, a.nu, emissivity_rows, work, rows[0],
                                                      rows[1], rows[2], rows[3]});
-        dispatch([&](auto source) {
+        if (spectral != nullptr)
+        {
+            a.scatterer = spectral->on_device(d_tables, a.nu);
+            a.scatters = d_tables + spectral->scatters_at;
+        }
+        dispatch([&](auto source, auto knots) {
             constexpr bool kLinear = decltype(source)::value;
-            two.sweeps(a, vector,
-                       [](auto v) { return thermal_up_kernel<decltype(v)::value, kLinear>; },
-                       [](auto v) { return thermal_down_kernel<decltype(v)::value, kLinear>; });
-        }, linear);
+            constexpr bool kSpectral = decltype(knots)::value;
+            ThermalArguments<kSpectral> & arguments = a;
+            two.sweeps(arguments, vector,
+                       [](auto v) {
+                           return thermal_up_kernel<decltype(v)::value, kLinear, kSpectral>;
+                       },
+                       [](auto v) {
+                           return thermal_down_kernel<decltype(v)::value, kLinear, kSpectral>;
+                       });
+        }, linear, spectral != nullptr);
         two.finish(bands, beta, work);
         return LBL_OK;
     });
@@ -136,7 +160,8 @@ int lbl_path_thermal_two_stream(lbl_engine * engine, double * beta, int64_t row_
 {
     return path_thermal_two_stream(
         engine, "lbl_path_thermal_two_stream", beta, row_stride, columns, grid, n_paths,
-        levels_per_path, level_begin, level_count, level_table, nullptr, false, diffusivity,
+        levels_per_path, level_begin, level_count, level_table, nullptr, false, nullptr,
+        diffusivity,
         surface_temperature, emissivity_rows, emissivity, n_bands, band_start, work,
         {up_rows, down_rows, top_up_rows, top_down_rows},
         {up_mean, down_mean, top_up_mean, top_down_mean}, flags);
@@ -153,9 +178,28 @@ int lbl_path_thermal_two_stream_source(
 {
     return path_thermal_two_stream(
         engine, "lbl_path_thermal_two_stream_source", beta, row_stride, columns, grid, n_paths,
-        levels_per_path, level_begin, level_count, level_table, edge_temperature, true,
+        levels_per_path, level_begin, level_count, level_table, edge_temperature, true, nullptr,
         diffusivity, surface_temperature, emissivity_rows, emissivity, n_bands, band_start, work,
         {up_rows, down_rows, top_up_rows, top_down_rows},
+        {up_mean, down_mean, top_up_mean, top_down_mean}, flags);
+}
+
+int lbl_path_thermal_two_stream_spectral(
+    lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns, int32_t grid,
+    int32_t n_paths, int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+    const double * level_table, const double * edge_temperature, int32_t n_knots,
+    const double * knot_wavenumber, const double * knot_optics, double diffusivity,
+    const double * surface_temperature, const double * emissivity_rows, const double * emissivity,
+    int32_t n_bands, const int64_t * band_start, double * work, double * up_rows,
+    double * down_rows, double * top_up_rows, double * top_down_rows, double * up_mean,
+    double * down_mean, double * top_up_mean, double * top_down_mean, int32_t flags)
+{
+    ScattererTable spectral{n_knots, knot_wavenumber, knot_optics};
+    return path_thermal_two_stream(
+        engine, "lbl_path_thermal_two_stream_spectral", beta, row_stride, columns, grid, n_paths,
+        levels_per_path, level_begin, level_count, level_table, edge_temperature,
+        edge_temperature != nullptr, &spectral, diffusivity, surface_temperature, emissivity_rows,
+        emissivity, n_bands, band_start, work, {up_rows, down_rows, top_up_rows, top_down_rows},
         {up_mean, down_mean, top_up_mean, top_down_mean}, flags);
 }
 

@@ -46,6 +46,13 @@
 // element beside beta's 8 B), reads the work rows and stores the flux rows asked for; the lane that
 // starts a path writes the rows of interface 0.  The level's
 // scalars and mu0 are the same for the whole wavefront.
+// kSpectral (lbl_path_two_stream_spectral): tau_c, w_c and h_c of a level are no level scalars but
+// come per grid point from the scatterer's knot table (scatterer.h): a lane finds where its
+// columns lie among the knots once, before its sweep, reads the six knot values of the level's
+// three rows per column and level, interpolates and limits them, forms w_c = omega_c*tau_c and
+// h_c = w_c*g_c and calls the same two_stream_layer.  Without kSpectral nothing of this is read
+// or compiled: the grey kernels are as they were.  Going up the spectral kernel keeps four rows in
+// flight (kTwoStreamSpectralUpAhead): with eight it spills scalar registers.
 // rayleigh_row_kernel fills sigma(nu) [m2] once per column: Bucholtz (1995) with lambda = 1e4/nu
 // in um, sigma = 1e-4*A*lambda^-(B + C*lambda + D/lambda) formed as (1e-4*A)*exp(-(e*log(lambda))),
 // 0 for nu <= 0; or the caller's values as they are.
@@ -53,7 +60,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "path.h"
+#include "scatterer.h"
 
 namespace lbl {
 
@@ -62,6 +72,7 @@ constexpr double kTwoStreamResonance = 1e-4;        // |1 - k*mu0| below which m
 constexpr int kTwoStreamLevelWords = 5;             // s_l, c_l, tau_c, w_c, h_c per level
 constexpr int kTwoStreamUpAhead = kPathAhead;       // rows of beta in flight per lane, going up
 constexpr int kTwoStreamDownAhead = 1;              // going down: more rows spill scalar registers
+constexpr int kTwoStreamSpectralUpAhead = 4;        // kSpectral, going up: 8 spill scalar registers
 
 struct PathTwoStream : PathLevels
 {
@@ -76,6 +87,16 @@ struct PathTwoStream : PathLevels
     double * level_out[4];      // up, down, direct, diffuse at the interface below each level
     double * top_out[4];        // [paths][stride]: the same at interface 0 (null: not wanted)
 };
+
+// lbl_path_two_stream_spectral's: the same with the scatterer's knot table, which replaces tau_c,
+// w_c and h_c of the level rows (0 there) per grid point.
+struct PathTwoStreamSpectral : PathTwoStream
+{
+    ScattererKnots scatterer;
+};
+
+template <bool kSpectral>
+using TwoStreamArguments = std::conditional_t<kSpectral, PathTwoStreamSpectral, PathTwoStream>;
 
 // What a layer does to light: its diffuse reflectance and transmittance, the reflectance for the
 // direct beam, the diffuse part of the transmitted beam and the beam's own transmittance.
@@ -212,10 +233,36 @@ __device__ __forceinline__ void two_stream_interface(
     two_stream_store<kVector>(out[3], at, width, diffuse);
 }
 
-// grid and kVector as for path_sweep_kernel; a.from_last is the order of this sweep, surface to
-// space.  Whole paths: every lane starts and finishes its path.
+// kSpectral: where the lane's columns lie among the scatterer's knots.
 template <bool kVector>
-__global__ __launch_bounds__(kPathThreads) void two_stream_up_kernel(PathTwoStream a)
+__device__ __forceinline__ ScattererLane two_stream_knots(const PathTwoStreamSpectral & a,
+                                                          const PathLane & l)
+{
+    double nu[kPathWidth];
+    path_load<kVector>(a.scatterer.nu + l.j, l.width, nu);
+    return scatterer_lane(a.scatterer, nu);
+}
+
+// kSpectral: the layer of one level and grid point with the scatterer interpolated from the
+// level's three knot rows `optics`: tau_c, omega_c and g_c at the column, then w_c = omega_c*tau_c
+// and h_c = w_c*g_c as the host forms them for the grey scatterer.
+__device__ __forceinline__ TwoStreamLayer two_stream_spectral_layer(
+    double s, double c, const double * optics, int n_knots, int j, double u, double mu0, double b,
+    double sigma)
+{
+    const double tau_c = scatterer_value(optics, j, u);
+    const double omega_c = scatterer_value(optics + n_knots, j, u);
+    const double g_c = scatterer_value(optics + 2*n_knots, j, u);
+    const double w_c = omega_c*tau_c;
+    return two_stream_layer(s, c, tau_c, w_c, w_c*g_c, mu0, b, sigma);
+}
+
+// grid and kVector as for path_sweep_kernel; a.from_last is the order of this sweep, surface to
+// space.  Whole paths: every lane starts and finishes its path.  kSpectral: the scatterer comes
+// from its knot table (scatterer.h) in place of the level rows; without it nothing of that is read.
+template <bool kVector, bool kSpectral = false>
+__global__ __launch_bounds__(kPathThreads) void two_stream_up_kernel(
+    TwoStreamArguments<kSpectral> a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
@@ -227,15 +274,26 @@ __global__ __launch_bounds__(kPathThreads) void two_stream_up_kernel(PathTwoStre
     two_stream_columns<kVector>(a, l, sigma, rup);
 #pragma unroll
     for (int i = 0; i < kPathWidth; ++i) rupd[i] = rup[i];
+    ScattererLane knots;
+    if constexpr (kSpectral) knots = two_stream_knots<kVector>(a, l);
 
-    path_levels<kTwoStreamUpAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
-                                                        long long at) {
+    const auto step = [&](int k, const double (&b)[kPathWidth], long long at) {
         const double * row = level + (long long)(k*l.direction)*kTwoStreamLevelWords;
         const double s = row[0], c = row[1], tau_c = row[2], w_c = row[3], h_c = row[4];
 #pragma unroll
         for (int i = 0; i < kPathWidth; ++i)
         {
-            const TwoStreamLayer y = two_stream_layer(s, c, tau_c, w_c, h_c, mu0, b[i], sigma[i]);
+            TwoStreamLayer y;
+            if constexpr (kSpectral)
+            {
+                y = two_stream_spectral_layer(
+                    s, c, scatterer_rows(a.scatterer, l.index0 + k*l.direction),
+                    a.scatterer.n_knots, knots.j[i], knots.u[i], mu0, b[i], sigma[i]);
+            }
+            else
+            {
+                y = two_stream_layer(s, c, tau_c, w_c, h_c, mu0, b[i], sigma[i]);
+            }
             const double m1 = 1./(1. - y.rdif*rupd[i]);
             const double up = y.rdir + y.tdif*((y.tdp*rupd[i] + y.d*rup[i])*m1);
             rupd[i] = y.rdif + y.tdif*((y.tdif*rupd[i])*m1);
@@ -244,12 +302,22 @@ __global__ __launch_bounds__(kPathThreads) void two_stream_up_kernel(PathTwoStre
         double * work = a.work + (2*at - l.j);
         path_store<kVector>(work, width, rup);
         path_store<kVector>(work + a.stride, width, rupd);
-    });
+    };
+    if constexpr (kSpectral)
+    {
+        path_levels<kTwoStreamSpectralUpAhead, kVector>(a, l, step);
+    }
+    else
+    {
+        path_levels<kTwoStreamUpAhead, kVector>(a, l, step);
+    }
 }
 
 // grid and kVector as for path_sweep_kernel; a.from_last is the Sun's order, space to surface.
-template <bool kVector>
-__global__ __launch_bounds__(kPathThreads) void two_stream_down_kernel(PathTwoStream a)
+// kSpectral as for two_stream_up_kernel.
+template <bool kVector, bool kSpectral = false>
+__global__ __launch_bounds__(kPathThreads) void two_stream_down_kernel(
+    TwoStreamArguments<kSpectral> a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
@@ -276,6 +344,8 @@ __global__ __launch_bounds__(kPathThreads) void two_stream_down_kernel(PathTwoSt
         two_stream_interface<kVector>(a.top_out, (long long)l.p*a.stride + l.j, width, f0, tb,
                                       td, rd, rup, rupd);
     }
+    ScattererLane knots;
+    if constexpr (kSpectral) knots = two_stream_knots<kVector>(a, l);
     path_levels<kTwoStreamDownAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
                                                           long long at) {
         const double * row = level + (long long)(k*l.direction)*kTwoStreamLevelWords;
@@ -283,7 +353,17 @@ __global__ __launch_bounds__(kPathThreads) void two_stream_down_kernel(PathTwoSt
 #pragma unroll
         for (int i = 0; i < kPathWidth; ++i)
         {
-            const TwoStreamLayer y = two_stream_layer(s, c, tau_c, w_c, h_c, mu0, b[i], sigma[i]);
+            TwoStreamLayer y;
+            if constexpr (kSpectral)
+            {
+                y = two_stream_spectral_layer(
+                    s, c, scatterer_rows(a.scatterer, l.index0 + k*l.direction),
+                    a.scatterer.n_knots, knots.j[i], knots.u[i], mu0, b[i], sigma[i]);
+            }
+            else
+            {
+                y = two_stream_layer(s, c, tau_c, w_c, h_c, mu0, b[i], sigma[i]);
+            }
             const double m3 = 1./(1. - rd[i]*y.rdif);
             td[i] = tb[i]*y.tdp + y.tdif*((td[i] + (tb[i]*rd[i])*y.rdir)*m3);
             rd[i] = y.rdif + y.tdif*((y.tdif*rd[i])*m3);

@@ -79,14 +79,30 @@
 // face it enters its path through and then once per level at the exit face, which it keeps as the
 // next level's entry value (the table is continuous within a path: the entry checks it): one
 // Planck per element and level, as without.
+//
+// kSpectral (lbl_path_thermal_two_stream_spectral, either source): tau_c, w_c and g_c of a level
+// come per grid point from the scatterer's knot table (scatterer.h) in place of the level row: a
+// lane finds where its columns lie among the knots once, before its sweep; per level and column
+// it fills the ThermalLevel the one thermal_layer takes -- tau_c interpolated and limited, and in a
+// level that scatters w_c = omega_c*tau_c, f = g_c*g_c and gp = g_c/(1 + g_c) of the column.
+// Whether a level scatters (some knot has omega_c*tau_c != 0) is one word per level from the
+// host: a level that does not stays clear for the whole wavefront, with its tau_c(nu).  In a level
+// that scatters an element whose tau = s_l*beta + tau_c is 0 takes the clear branch (x = 0: the
+// identity), where the cloudy one would form 0/0 -- a grey cloudy level has tau >= tau_c > 0.
+// Without kSpectral nothing of this is read or compiled.  Going up with the level-temperature
+// source the spectral kernel keeps two rows in flight (kThermalSpectralUpAhead): four and eight
+// spill scalar registers.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/lbl_amd.h"
 #include "flux.h"
 #include "path.h"
 #include "radiance.h"
+#include "scatterer.h"
 
 namespace lbl {
 
@@ -97,6 +113,7 @@ constexpr int kThermalDownAhead = 1;              // going down: more rows spill
 constexpr double kThermalSourceSeriesBelow = 1./2.; // y = k*t below which p comes from its series
 constexpr int kThermalSourceUpAhead = 1;            // kLinear, going up: more rows spill scalar registers
 constexpr int kThermalSourceDownAhead = 1;          // going down
+constexpr int kThermalSpectralUpAhead = 2;          // kSpectral, going up: 4 spill scalar registers
 static_assert(kThermalSourceDownAhead == kThermalDownAhead, "the down kernel takes one for both");
 
 struct PathThermal : PathLevels
@@ -114,6 +131,18 @@ struct PathThermal : PathLevels
     const double * edge;        // kLinear: [count][2], interface temperatures of flat level
                                 // first + i on its first-level / last-level side [K]; else null
 };
+
+// lbl_path_thermal_two_stream_spectral's: the same with the scatterer's knot table, which replaces
+// tau_c, w_c and g_c of the level rows (0 there) per grid point.
+struct PathThermalSpectral : PathThermal
+{
+    ScattererKnots scatterer;
+    const double * scatters;    // [count]: 0 where every knot of flat level first + i has
+                                // omega_c*tau_c == 0 (a clear level), else 1
+};
+
+template <bool kSpectral>
+using ThermalArguments = std::conditional_t<kSpectral, PathThermalSpectral, PathThermal>;
 
 // What a layer does to diffuse light, the fraction of piB(T_l) it emits either way and, with
 // kLinear, the weight q of the Planck difference across it.
@@ -300,7 +329,7 @@ __device__ __forceinline__ void thermal_interface(
 
 // The step of a sweep through one level, for both sweeps and both sources, and what a lane
 // carries from level to level for it: with kLinear piB at the face it enters the next level by.
-template <bool kLinear>
+template <bool kLinear, bool kSpectral = false>
 struct ThermalFaces
 {
     const double * level;       // the table rows, at the lane's first level
@@ -308,9 +337,12 @@ struct ThermalFaces
     int side;                   // kLinear: which of a level's two it is entered by
     double d;
     double entry[kPathWidth];
+    ScattererKnots scatterer;   // kSpectral: the knot table, its rows at the lane's first level,
+    const double * scatters;    // whether a level scatters, likewise, and where the lane's
+    ScattererLane knots;        // columns lie among the knots
 
-    __device__ __forceinline__ ThermalFaces(const PathThermal & a, const PathLane & l,
-                                            const ThermalColumns & c)
+    __device__ __forceinline__ ThermalFaces(const ThermalArguments<kSpectral> & a,
+                                            const PathLane & l, const ThermalColumns & c)
         : level(a.level + (long long)l.index0*kThermalLevelWords), edge(nullptr), side(0),
           d(a.diffusivity)
     {
@@ -322,6 +354,34 @@ struct ThermalFaces
 #pragma unroll
             for (int i = 0; i < kPathWidth; ++i) entry[i] = thermal_pi_planck(c, i, t);
         }
+        if constexpr (kSpectral)
+        {
+            scatterer = a.scatterer;
+            scatterer.optics = scatterer_rows(a.scatterer, l.index0);
+            scatters = a.scatters + l.index0;
+            knots = scatterer_lane(a.scatterer, c.nu);
+        }
+    }
+
+    // kSpectral: the scalars of level k of the sweep at the lane's column i with beta b, from the
+    // level's three knot rows.  A level none of whose knots scatters stays clear for the whole
+    // wavefront, with its absorption tau_c(nu); in a level that scatters every element takes the
+    // cloudy branches with w_c = omega_c*tau_c, f = g_c*g_c and gp = g_c/(1 + g_c) of its own
+    // column -- also one whose w_c is 0 --, but where tau = s*beta + tau_c is 0 the cloudy
+    // branches would form 0/0 and the element takes the clear one: x = 0, the identity.
+    __device__ __forceinline__ void element(const PathLane & l, int k, int i, double b,
+                                            ThermalLevel & v) const
+    {
+        const int m = scatterer.n_knots;
+        const double * rows = scatterer.optics + (long long)(k*l.direction)*(kScattererWords*m);
+        v.tau_c = scatterer_value(rows, knots.j[i], knots.u[i]);
+        if (v.clear) return;
+        const double omega_c = scatterer_value(rows + m, knots.j[i], knots.u[i]);
+        const double g_c = scatterer_value(rows + 2*m, knots.j[i], knots.u[i]);
+        v.w_c = omega_c*v.tau_c;
+        v.f = g_c*g_c;
+        v.gp = g_c/(1. + g_c);
+        v.clear = v.s*b + v.tau_c == 0.;
     }
 
     // Level k of the sweep with beta b: (flux, refl) on the side the lane came from become those
@@ -337,12 +397,15 @@ struct ThermalFaces
                                             const double (&b)[kPathWidth],
                                             double (&flux)[kPathWidth], double (&refl)[kPathWidth])
     {
-        const ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
-        double t_leave = v.temperature;
+        ThermalLevel scalars = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
+        if constexpr (kSpectral) scalars.clear = scatters[k*l.direction] == 0.;
+        double t_leave = scalars.temperature;
         if constexpr (kLinear) t_leave = edge[2*(long long)(k*l.direction) + (1 - side)];
 #pragma unroll
         for (int i = 0; i < kPathWidth; ++i)
         {
+            ThermalLevel v = scalars;
+            if constexpr (kSpectral) element(l, k, i, b[i], v);
             const ThermalLayer y = thermal_layer<kLinear>(v, d, b[i]);
             const double leave = thermal_pi_planck(c, i, t_leave);
             double out = leave*y.em, back = out;
@@ -361,8 +424,8 @@ struct ThermalFaces
 // grid and kVector as for path_sweep_kernel; a.from_last is the order of this sweep, surface to
 // space: a level is entered through its surface-side face (Bb) and left through the other (Bt).
 // Whole paths: every lane starts and finishes its path.
-template <bool kVector, bool kLinear>
-__global__ __launch_bounds__(kPathThreads) void thermal_up_kernel(PathThermal a)
+template <bool kVector, bool kLinear, bool kSpectral = false>
+__global__ __launch_bounds__(kPathThreads) void thermal_up_kernel(ThermalArguments<kSpectral> a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
@@ -372,20 +435,29 @@ __global__ __launch_bounds__(kPathThreads) void thermal_up_kernel(PathThermal a)
     double u[kPathWidth], rs[kPathWidth];
     thermal_surface<kVector>(a, l, c, u, rs);
 
-    ThermalFaces<kLinear> faces(a, l, c);
+    ThermalFaces<kLinear, kSpectral> faces(a, l, c);
     constexpr int kAhead = kLinear ? kThermalSourceUpAhead : kThermalUpAhead;
-    path_levels<kAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth], long long at) {
+    const auto step = [&](int k, const double (&b)[kPathWidth], long long at) {
         faces.through(l, c, k, b, u, rs);
         double * work = a.work + (2*at - l.j);
         path_store<kVector>(work, width, u);
         path_store<kVector>(work + a.stride, width, rs);
-    });
+    };
+    if constexpr (kSpectral)
+    {
+        constexpr int kRows = kLinear ? kThermalSourceUpAhead : kThermalSpectralUpAhead;
+        path_levels<kRows, kVector>(a, l, step);
+    }
+    else
+    {
+        path_levels<kAhead, kVector>(a, l, step);
+    }
 }
 
 // grid and kVector as for path_sweep_kernel; a.from_last is the order space to surface: a level is
 // entered through its space-side face (Bt) and left through the other (Bb).
-template <bool kVector, bool kLinear>
-__global__ __launch_bounds__(kPathThreads) void thermal_down_kernel(PathThermal a)
+template <bool kVector, bool kLinear, bool kSpectral = false>
+__global__ __launch_bounds__(kPathThreads) void thermal_down_kernel(ThermalArguments<kSpectral> a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
@@ -403,7 +475,7 @@ __global__ __launch_bounds__(kPathThreads) void thermal_down_kernel(PathThermal 
         path_load<kVector>(work + a.stride, width, rs);
         thermal_interface<kVector>(a.top_out, (long long)l.p*a.stride + l.j, width, dn, rd, u, rs);
     }
-    ThermalFaces<kLinear> faces(a, l, c);
+    ThermalFaces<kLinear, kSpectral> faces(a, l, c);
     path_levels<kThermalDownAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
                                                         long long at) {
         faces.through(l, c, k, b, dn, rd);

@@ -80,6 +80,15 @@ def _edge_rows(edge_temperature, rows):
     return edges
 
 
+def _knot_table(knot_wavenumber, knot_optics, rows):
+    """(float64 knots [M], float64 optics [rows, M, 3], M) of a spectral scatterer's table."""
+    knots, optics = _f64(knot_wavenumber), _f64(knot_optics)
+    if knots.ndim != 1 or optics.shape != (rows, knots.size, 3):
+        raise ValueError(f"knot_wavenumber has shape {knots.shape} and knot_optics "
+                         f"{optics.shape}, need [M] and {rows} x M x 3.")
+    return knots, optics, knots.size
+
+
 def _check_outputs(outputs, rows, width):
     for out in outputs:
         if out is not None and (out.shape[1] != width or out.shape[0] < rows):
@@ -777,13 +786,39 @@ class Engine(object):
         direct_rows and diffuse_rows [>= rows, row length] at the interface below each level,
         the four top_*_rows [n_paths, row length] at interface 0, and with band_start their band
         means *_mean [>= rows or n_paths, bands]."""
+        self._path_two_stream("path_two_stream", beta, columns, n_paths, levels_per_path,
+                              level_begin, level_table, None, solar_zenith_cosine, solar_row,
+                              work, rayleigh_row, albedo, albedo_rows, band_start, from_last,
+                              asynchronous, outputs)
+
+    def path_two_stream_spectral(self, beta, columns, grid, n_paths, levels_per_path, level_begin,
+                                 level_table, knot_wavenumber, knot_optics, solar_zenith_cosine,
+                                 solar_row, work, rayleigh_row=None, albedo=None, albedo_rows=None,
+                                 band_start=None, from_last=False, asynchronous=False, **outputs):
+        """path_two_stream with the scatterer of every level as a table over wavenumber --
+        lbl_path_two_stream_spectral.  grid as for path_flux; knot_wavenumber [M] and knot_optics
+        [rows, M, 3]: tau_c, omega_c and g_c of each row at every knot, interpolated onto the
+        grid; tau_c, w_c and h_c of level_table are 0; everything else as for path_two_stream."""
+        rows = int(beta.shape[0])
+        self._path_two_stream("path_two_stream_spectral", beta, columns, n_paths, levels_per_path,
+                              level_begin, level_table,
+                              (int(grid),) + _knot_table(knot_wavenumber, knot_optics, rows),
+                              solar_zenith_cosine, solar_row, work, rayleigh_row, albedo,
+                              albedo_rows, band_start, from_last, asynchronous, outputs)
+
+    def _path_two_stream(self, name, beta, columns, n_paths, levels_per_path, level_begin,
+                         level_table, spectral, solar_zenith_cosine, solar_row, work,
+                         rayleigh_row, albedo, albedo_rows, band_start, from_last, asynchronous,
+                         outputs):
+        """The call of path_two_stream (spectral None) and of path_two_stream_spectral (spectral:
+        grid, knots, optics, M): lbl_<name>."""
         rows, stride = int(beta.shape[0]), int(beta.shape[1])
         table = _f64(level_table)
         if table.shape != (rows, 5):
             raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
         unknown = set(outputs) - set(PATH_TWO_STREAM_OUTPUTS)
         if unknown:
-            raise TypeError(f"path_two_stream has no output {sorted(unknown)}.")
+            raise TypeError(f"{name} has no output {sorted(unknown)}.")
         if work.shape[1] != stride or work.shape[0] < 2*rows:
             raise ValueError(f"work has shape {work.shape}, need {2*rows} x {stride}.")
         if solar_row.shape[1] < int(columns) or \
@@ -797,14 +832,18 @@ class Engine(object):
                                            asynchronous)
         flags |= PATH_FROM_LAST if from_last else 0
         pointers = []
-        for name in PATH_TWO_STREAM_OUTPUTS:
-            out = outputs.get(name)
-            need = int(n_paths) if name.startswith("top_") else rows
-            _check_outputs((out,), need, n_bands if name.endswith("_mean") else stride)
+        for output in PATH_TWO_STREAM_OUTPUTS:
+            out = outputs.get(output)
+            need = int(n_paths) if output.startswith("top_") else rows
+            _check_outputs((out,), need, n_bands if output.endswith("_mean") else stride)
             pointers.append(_address(out))
-        self._check(self.lib.lbl_path_two_stream(
+        knots = []
+        if spectral is not None:
+            grid, knot, optics, n_knots = spectral
+            knots = [grid, n_knots, knot.ctypes.data, optics.ctypes.data]
+        self._check(getattr(self.lib, "lbl_" + name)(
             self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
-            int(level_begin), rows, table.ctypes.data, _address(mu0), solar_row.pointer,
+            int(level_begin), rows, table.ctypes.data, *knots, _address(mu0), solar_row.pointer,
             _address(rayleigh_row), _address(albedo_rows), _address(albedo), n_bands,
             _address(starts), work.pointer, *pointers, flags))
 
@@ -843,11 +882,31 @@ class Engine(object):
                            surface_temperature, work, diffusivity, emissivity, emissivity_rows,
                            band_start, from_last, asynchronous, outputs)
 
+    def path_thermal_two_stream_spectral(self, beta, columns, grid, n_paths, levels_per_path,
+                                         level_begin, level_table, knot_wavenumber, knot_optics,
+                                         surface_temperature, work, edge_temperature=None,
+                                         diffusivity=1.66, emissivity=None, emissivity_rows=None,
+                                         band_start=None, from_last=False, asynchronous=False,
+                                         **outputs):
+        """path_thermal_two_stream (edge_temperature None) or path_thermal_two_stream_source with
+        the scatterer of every level as a table over wavenumber --
+        lbl_path_thermal_two_stream_spectral.  knot_wavenumber [M] and knot_optics [rows, M, 3]:
+        tau_c, omega_c and g_c of each row at every knot, interpolated onto the grid; tau_c, w_c
+        and g_c of level_table are 0; everything else as for those two."""
+        rows = int(beta.shape[0])
+        self._path_thermal("path_thermal_two_stream_spectral", beta, columns, grid, n_paths,
+                           levels_per_path, level_begin, level_table, edge_temperature,
+                           surface_temperature, work, diffusivity, emissivity, emissivity_rows,
+                           band_start, from_last, asynchronous, outputs,
+                           spectral=_knot_table(knot_wavenumber, knot_optics, rows))
+
     def _path_thermal(self, name, beta, columns, grid, n_paths, levels_per_path, level_begin,
                       level_table, edge_temperature, surface_temperature, work, diffusivity,
-                      emissivity, emissivity_rows, band_start, from_last, asynchronous, outputs):
-        """The call of path_thermal_two_stream (edge_temperature None) and of
-        path_thermal_two_stream_source: lbl_<name>."""
+                      emissivity, emissivity_rows, band_start, from_last, asynchronous, outputs,
+                      spectral=None):
+        """The call of path_thermal_two_stream (edge_temperature None), of
+        path_thermal_two_stream_source and of path_thermal_two_stream_spectral (spectral: knots,
+        optics, M; its edge_temperature goes as NULL where None): lbl_<name>."""
         rows, stride = int(beta.shape[0]), int(beta.shape[1])
         table = _f64(level_table)
         if table.shape != (rows, 5):
@@ -872,6 +931,10 @@ class Engine(object):
             _check_outputs((out,), need, n_bands if output.endswith("_mean") else stride)
             pointers.append(_address(out))
         tables = [table.ctypes.data] + ([] if edges is None else [edges.ctypes.data])
+        if spectral is not None:
+            knot, optics, n_knots = spectral
+            tables = [table.ctypes.data, _address(edges), n_knots, knot.ctypes.data,
+                      optics.ctypes.data]
         self._check(getattr(self.lib, "lbl_" + name)(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
             int(levels_per_path), int(level_begin), rows, *tables, float(diffusivity),

@@ -27,6 +27,7 @@ RADIANCE_DIRECTIONS = ("toward_last", "toward_first")
 DOWNWELLING = "boundary_downwelling_radiance"
 SURFACE_RADIANCE_QUANTITIES = RADIANCE_QUANTITIES + (DOWNWELLING,)
 MAX_EMISSIVITY_KNOTS = 1024             # kSurfaceMaxKnots of csrc/surface.h
+MAX_SCATTERER_KNOTS = 1024              # kScattererMaxKnots of csrc/scatterer.h
 
 # Planck's function per wavenumber, B(nu, T) = C1 nu^3 / expm1(C2 nu / T) [W m-2 sr-1 (cm-1)-1]
 # for nu in cm-1: from the exact CODATA 2018 h, c and k (the same literals as LBL_PLANCK_C1 and
@@ -153,18 +154,24 @@ _SolarRequest = namedtuple("_SolarRequest", _COMMON + (
 # compute_solar_flux's: mu0 per path, the level table [levels, 5] of lbl_path_two_stream (s_l, c_l,
 # tau_c, w_c, h_c), the albedo per path -- [paths], or [paths, M] at albedo_knots [M] -- the Sun
 # as in _SolarRequest, and rayleigh_values: None (the fit, or no Rayleigh scattering: `rayleigh`)
-# or the caller's cross-sections [V] on the grid.
+# or the caller's cross-sections [V] on the grid.  scatterer_knots [M] and scatterer_optics
+# [levels, M, 3] (tau_c, omega_c, g_c at every knot): None, or the spectral scatterer of
+# lbl_path_two_stream_spectral, beside which tau_c, w_c and h_c of the level table are 0.
 _SolarFluxRequest = namedtuple("_SolarFluxRequest", _COMMON + (
     "surface", "mu0", "level_table", "albedo", "albedo_knots", "solar_knots", "solar_values",
-    "scale", "rayleigh", "rayleigh_values"))
+    "scale", "rayleigh", "rayleigh_values", "scatterer_knots", "scatterer_optics"),
+    defaults=(None, None))
 
 # compute_thermal_flux's: the level table [levels, 5] of lbl_path_thermal_two_stream (s_l, tau_c,
 # w_c, g_c, T_l), D, the surface temperature per path and its emissivity -- [paths], or [paths, M]
 # at emissivity_knots [M].  edge_temperature: None (compute_thermal_flux: isothermal levels) or
-# compute_thermal_flux_linear's interface temperatures per flat level, as above.
+# compute_thermal_flux_linear's interface temperatures per flat level, as above.  scatterer_knots
+# and scatterer_optics as in _SolarFluxRequest (lbl_path_thermal_two_stream_spectral: tau_c, w_c
+# and g_c of the level table are 0 beside them).
 _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
     "surface", "level_table", "diffusivity", "surface_temperature", "surface_emissivity",
-    "emissivity_knots", "edge_temperature"), defaults=(None,))
+    "emissivity_knots", "edge_temperature", "scatterer_knots", "scatterer_optics"),
+    defaults=(None, None, None))
 
 # compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
 # points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
@@ -669,26 +676,31 @@ def rayleigh_cross_section(wavenumber):
     return np.where(positive, (1e-4*a)*np.exp(-(e*np.log(lam))), 0.)
 
 
-def _scatterers(spec, shape, optical_depth, single_scattering_albedo, asymmetry):
-    """(tau_c, w_c, h_c) per flat level of compute_solar_flux's grey scatterer, checked: zeros
-    without one; w_c = omega_c*tau_c and h_c = (omega_c*tau_c)*g_c in fp64."""
+def _scatterer_arrays(shape, optical_depth, single_scattering_albedo, asymmetry, knots=None):
+    """None without a scatterer, or its (tau_c, omega_c, g_c), checked: each shaped like the
+    atmosphere -- with `knots` [M] like the atmosphere with one more axis of M at the end --,
+    finite and in its range."""
     given = [x is not None for x in (optical_depth, single_scattering_albedo, asymmetry)]
-    levels = int(np.prod(shape, dtype=np.int64))
     if not any(given):
-        return np.zeros(levels), np.zeros(levels), np.zeros(levels)
+        return None
     if not all(given):
         raise ValueError("scatterer_optical_depth, scatterer_single_scattering_albedo and "
                          "scatterer_asymmetry are given together or not at all.")
+    expected = tuple(shape) + (() if knots is None else (knots.size,))
     arrays = []
     for name, value in (("scatterer_optical_depth", optical_depth),
                         ("scatterer_single_scattering_albedo", single_scattering_albedo),
                         ("scatterer_asymmetry", asymmetry)):
         value = np.asarray(value, dtype=np.float64)
-        if value.shape != shape:
+        if value.shape != expected:
+            if knots is not None:
+                raise ValueError(f"{name} has shape {value.shape}: with scatterer_wavenumber "
+                                 f"give the atmosphere's shape and one value per knot, "
+                                 f"{expected}.")
             raise ValueError(f"{name} has shape {value.shape}, the atmosphere {shape}.")
         if not np.all(np.isfinite(value)):
             raise ValueError(f"{name} must be finite.")
-        arrays.append(value.ravel())
+        arrays.append(value)
     tau_c, omega_c, g_c = arrays
     if np.any(tau_c < 0.):
         raise ValueError("scatterer_optical_depth must be >= 0.")
@@ -696,6 +708,46 @@ def _scatterers(spec, shape, optical_depth, single_scattering_albedo, asymmetry)
         raise ValueError("scatterer_single_scattering_albedo must lie in [0, 1].")
     if not np.all((g_c >= 0.) & (g_c < 1.)):
         raise ValueError("scatterer_asymmetry must lie in [0, 1).")
+    return tau_c, omega_c, g_c
+
+
+def _given_knots(wavenumber):
+    """scatterer_wavenumber of the *_spectral calls, which need it."""
+    if wavenumber is None:
+        raise ValueError("scatterer_wavenumber must be given: [M] knots in cm-1.")
+    return wavenumber
+
+
+def _spectral_scatterers(shape, wavenumber, optical_depth, single_scattering_albedo, asymmetry):
+    """(None, None) without scatterer_wavenumber, or (knots [M], optics [levels, M, 3]) of the
+    spectral scatterer, checked: M knots [cm-1], finite and strictly ascending, 2 <= M <= 1024,
+    and tau_c, omega_c and g_c of every level at every knot, which the kernels interpolate
+    linearly in wavenumber and hold constant outside the knots (include/lbl_amd_scatterer.h)."""
+    if wavenumber is None:
+        return None, None
+    knots = np.asarray(wavenumber, dtype=np.float64)
+    if knots.ndim != 1 or not 2 <= knots.size <= MAX_SCATTERER_KNOTS:
+        raise ValueError(f"scatterer_wavenumber must be a 1-d array of 2..{MAX_SCATTERER_KNOTS} "
+                         f"knots, not of shape {knots.shape}.")
+    if not np.all(np.isfinite(knots)) or not np.all(np.diff(knots) > 0.):
+        raise ValueError("scatterer_wavenumber must be finite and strictly ascending.")
+    arrays = _scatterer_arrays(shape, optical_depth, single_scattering_albedo, asymmetry, knots)
+    if arrays is None:
+        raise ValueError("scatterer_wavenumber needs scatterer_optical_depth, "
+                         "scatterer_single_scattering_albedo and scatterer_asymmetry at its "
+                         "knots.")
+    optics = np.stack([x.reshape(-1, knots.size) for x in arrays], axis=2)
+    return np.ascontiguousarray(knots), np.ascontiguousarray(optics)
+
+
+def _scatterers(spec, shape, optical_depth, single_scattering_albedo, asymmetry):
+    """(tau_c, w_c, h_c) per flat level of compute_solar_flux's grey scatterer, checked: zeros
+    without one; w_c = omega_c*tau_c and h_c = (omega_c*tau_c)*g_c in fp64."""
+    levels = int(np.prod(shape, dtype=np.int64))
+    arrays = _scatterer_arrays(shape, optical_depth, single_scattering_albedo, asymmetry)
+    if arrays is None:
+        return np.zeros(levels), np.zeros(levels), np.zeros(levels)
+    tau_c, omega_c, g_c = (x.ravel() for x in arrays)
     w_c = omega_c*tau_c
     return tau_c, w_c, w_c*g_c
 
@@ -704,12 +756,13 @@ def _solar_flux_request(spec, layer_thickness, solar_zenith_cosine, solar_irradi
                         solar_wavenumber, distance_factor, surface, surface_albedo,
                         albedo_wavenumber, rayleigh, rayleigh_cross_section,
                         scatterer_optical_depth, scatterer_single_scattering_albedo,
-                        scatterer_asymmetry, quantities, band_edges, range_policy):
-    """Checks every argument of compute_solar_flux."""
+                        scatterer_asymmetry, quantities, band_edges, range_policy,
+                        scatterer_wavenumber=None, caller="compute_solar_flux"):
+    """Checks every argument of compute_solar_flux (of `caller`, which shares them)."""
     if spec.group is not None:
-        raise NotImplementedError("compute_solar_flux does not split paths over processes yet "
+        raise NotImplementedError(f"{caller} does not split paths over processes yet "
                                   "(group is set).")
-    lengths, shape = _path_geometry(spec, layer_thickness, "compute_solar_flux",
+    lengths, shape = _path_geometry(spec, layer_thickness, caller,
                                     "layer_thickness", "layer thicknesses")
     if not (isinstance(surface, str) and surface in FLUX_SURFACES):
         raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
@@ -747,8 +800,11 @@ def _solar_flux_request(spec, layer_thickness, solar_zenith_cosine, solar_irradi
         if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
             raise ValueError(f"{what} pressures that are finite and > 0.")
         _check_level_temperatures(spec)
-    tau_c, w_c, h_c = _scatterers(spec, shape, scatterer_optical_depth,
-                                  scatterer_single_scattering_albedo, scatterer_asymmetry)
+    knots, optics = _spectral_scatterers(shape, scatterer_wavenumber, scatterer_optical_depth,
+                                         scatterer_single_scattering_albedo, scatterer_asymmetry)
+    grey = (None, None, None) if knots is not None else (
+        scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry)
+    tau_c, w_c, h_c = _scatterers(spec, shape, *grey)
     column = np.zeros(lengths.size)
     if rayleigh:
         column = (np.asarray(spec.atmosphere.pressure, dtype=np.float64).ravel() /
@@ -762,13 +818,15 @@ def _solar_flux_request(spec, layer_thickness, solar_zenith_cosine, solar_irradi
                              starts=starts, instrument=None, cumulative=False, surface=surface,
                              mu0=mu0, level_table=table, albedo=albedo, albedo_knots=albedo_knots,
                              solar_knots=solar_knots, solar_values=solar_values, scale=scale,
-                             rayleigh=bool(rayleigh), rayleigh_values=rayleigh_values)
+                             rayleigh=bool(rayleigh), rayleigh_values=rayleigh_values,
+                             scatterer_knots=knots, scatterer_optics=optics)
 
 
 def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_emissivity,
                           emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
                           scatterer_single_scattering_albedo, scatterer_asymmetry, quantities,
-                          band_edges, range_policy, caller="compute_thermal_flux"):
+                          band_edges, range_policy, scatterer_wavenumber=None,
+                          caller="compute_thermal_flux"):
     """Checks every argument of compute_thermal_flux (of `caller`, which shares them)."""
     if spec.group is not None:
         raise NotImplementedError(f"{caller} does not split paths over processes yet "
@@ -795,6 +853,10 @@ def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_em
         pressure = spec.atmosphere.pressure
         if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
             raise ValueError("heating rates need pressures that are finite and > 0.")
+    knots, optics = _spectral_scatterers(shape, scatterer_wavenumber, scatterer_optical_depth,
+                                         scatterer_single_scattering_albedo, scatterer_asymmetry)
+    if knots is not None:
+        scatterer_optical_depth = scatterer_single_scattering_albedo = scatterer_asymmetry = None
     tau_c, w_c, _ = _scatterers(spec, shape, scatterer_optical_depth,
                                 scatterer_single_scattering_albedo, scatterer_asymmetry)
     g_c = np.zeros(lengths.size) if scatterer_asymmetry is None else \
@@ -807,15 +869,17 @@ def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_em
                                starts=starts, instrument=None, cumulative=False, surface=surface,
                                level_table=table, diffusivity=float(factor),
                                surface_temperature=ts, surface_emissivity=es,
-                               emissivity_knots=emissivity_knots)
+                               emissivity_knots=emissivity_knots, scatterer_knots=knots,
+                               scatterer_optics=optics)
 
 
 def _thermal_flux_linear_request(spec, layer_thickness, surface_temperature,
-                                 interface_temperature, *arguments):
+                                 interface_temperature, *arguments, scatterer_wavenumber=None,
+                                 caller="compute_thermal_flux_linear"):
     """Checks every argument of compute_thermal_flux_linear: compute_thermal_flux's request with
     the interface temperatures of the linear-in-tau source."""
     request = _thermal_flux_request(spec, layer_thickness, surface_temperature, *arguments,
-                                    caller="compute_thermal_flux_linear")
+                                    scatterer_wavenumber=scatterer_wavenumber, caller=caller)
     return request._replace(edge_temperature=_edge_temperatures(
         "linear_in_tau", interface_temperature, request.shape))
 
@@ -917,7 +981,8 @@ def _level_bytes(n, request, level_quantities, level_blocks, grid_outputs):
     level (compute_path and compute_radiance 1, compute_flux 2: the fluxes of a level,
     compute_jacobian 1 and its work blocks) -- and one block per per-level quantity of the passes
     where an instrument reduces it from the grid, or where the caller says its `grid_outputs`
-    count (compute_jacobian) and there are no bands.
+    count (compute_jacobian) and there are no bands; and the knot table of a spectral scatterer,
+    24 bytes per level and knot.
     Known undercount, kept because it decides where runs are cut: without an instrument the
     per-level grid outputs of compute_path and compute_radiance (cumulative=) are not counted,
     and compute_flux counts one output block where it holds two on the grid; neither are the
@@ -925,7 +990,9 @@ def _level_bytes(n, request, level_quantities, level_blocks, grid_outputs):
     blocks = level_blocks
     if request.instrument is not None or (grid_outputs and request.starts is None):
         blocks += len(level_quantities)
-    return blocks*n*8
+    # The knot table of a spectral scatterer travels with its run: 3 float64 per level and knot.
+    knots = getattr(request, "scatterer_knots", None)
+    return blocks*n*8 + (0 if knots is None else knots.size*24)
 
 
 def _first_rows(block, count):
@@ -1315,6 +1382,8 @@ def _path_variables(spec, variables, request):
         marks["surface"] = "reflecting"
     if getattr(request, "emissivity_knots", None) is not None:
         marks["emissivity"] = "spectral"
+    if getattr(request, "scatterer_knots", None) is not None:
+        marks["scatterer"] = "spectral"
     xarray = _optional_xarray()
     if xarray is None:
         out = {name: value for name, (value, _) in coords.items()}

@@ -872,6 +872,7 @@ class Spectroscopy(object):
         of the returned upward and downward fluxes, as in compute_flux.
         With g > 0 the direct irradiance is the delta-scaled beam: it contains the forward peak
         of the scattered light, so it differs from compute_solar's.
+        A scatterer whose optics vary with wavenumber: compute_solar_flux_spectral.
 
         Args:
             layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
@@ -899,6 +900,58 @@ class Spectroscopy(object):
             distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
             rayleigh_cross_section, scatterer_optical_depth, scatterer_single_scattering_albedo,
             scatterer_asymmetry, quantities, band_edges, range_policy)
+        return self._solar_flux(request, remove_pedestal, range_policy)
+
+    def compute_solar_flux_spectral(self, layer_thickness, solar_zenith_cosine,
+                                    scatterer_wavenumber, scatterer_optical_depth,
+                                    scatterer_single_scattering_albedo, scatterer_asymmetry,
+                                    solar_irradiance=None, solar_wavenumber=None,
+                                    distance_factor=1., surface="first", surface_albedo=0.,
+                                    albedo_wavenumber=None, rayleigh=True,
+                                    rayleigh_cross_section=None,
+                                    quantities=("upward_flux", "downward_flux"),
+                                    band_edges=None, remove_pedestal=None,
+                                    range_policy="reference"):
+        """compute_solar_flux with cloud and aerosol optics that vary with wavenumber: no real
+        cloud or aerosol is grey (liquid water goes from omega = 0.999999 in the visible to 0.5 at
+        3 um, aerosol extinction falls roughly as nu^1.3).  The scatterer of every level is a
+        table over wavenumber, as the surface's albedo_wavenumber is: k_0 < ... < k_{M-1} [cm-1]
+        with tau_c, omega_c and g_c of the level at every knot.  At grid point nu (the optics are
+        constant outside the knots), each operation rounded as written:
+            j = the largest index with k_j <= nu, limited to 0 .. M-2
+            u = (nu - k_j)/(k_{j+1} - k_j), limited to [0, 1]
+            for each of e in {tau_c, omega_c, g_c} of the level:
+              v = e_j + u*(e_{j+1} - e_j), then limited to [min(e_j, e_{j+1}), max(e_j, e_{j+1})]
+        (the limit keeps tau_c >= 0, 0 <= omega_c <= 1 and 0 <= g_c < 1 whatever the rounding
+        does), and w_c = omega_c*tau_c, h_c = w_c*g_c are formed per grid point on the GPU; the
+        layer and the adding are compute_solar_flux's, line by line.  A table that is flat in nu
+        gives compute_solar_flux's fluxes for the grey scatterer bit for bit.
+
+        Args:
+            scatterer_wavenumber: [M] knots [cm-1], finite and strictly ascending,
+                         2 <= M <= 1024.
+            scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry:
+                         tau_c >= 0, omega_c in [0, 1] and g_c in [0, 1), finite, shaped like the
+                         atmosphere's temperature with one more axis of M at the end.
+            Everything else as in compute_solar_flux.
+
+        Returns:
+            Like compute_solar_flux, with the attribute (the key) "scatterer": "spectral".
+        Raises ValueError like compute_solar_flux, all of them before the GPU is touched; the
+        knot table (24 bytes per level and knot) counts against device_output_limit.
+        """
+        request = paths._solar_flux_request(
+            self, layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
+            distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
+            rayleigh_cross_section, scatterer_optical_depth, scatterer_single_scattering_albedo,
+            scatterer_asymmetry, quantities, band_edges, range_policy,
+            scatterer_wavenumber=paths._given_knots(scatterer_wavenumber),
+            caller="compute_solar_flux_spectral")
+        return self._solar_flux(request, remove_pedestal, range_policy)
+
+    def _solar_flux(self, request, remove_pedestal, range_policy):
+        """The sweeps of compute_solar_flux and, where the request holds a knot table, of
+        compute_solar_flux_spectral."""
         bands = request.starts is not None
         heating = "heating_rate" in request.quantities
         wanted = tuple(q for q in paths.SOLAR_FLUX_INTERFACE_QUANTITIES
@@ -945,8 +998,14 @@ class Spectroscopy(object):
                             blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[source]
                         else:
                             blocks[name + "_rows"] = outputs[source]
-                call.engine.path_two_stream(
-                    beta, call.columns, call.paths, call.per_path, a, request.level_table[a:b],
+                entry = call.engine.path_two_stream
+                block, tables = (beta, call.columns), (request.level_table[a:b],)
+                if request.scatterer_knots is not None:
+                    entry = call.engine.path_two_stream_spectral
+                    block += (grid,)
+                    tables += (request.scatterer_knots, request.scatterer_optics[a:b])
+                entry(
+                    *block, call.paths, call.per_path, a, *tables,
                     request.mu0, solar, work if b - a == run else work.rows(2*(b - a)),
                     rayleigh_row=sigma, albedo=None if spectral else request.albedo,
                     albedo_rows=albedo_rows, band_start=request.starts,
@@ -1009,6 +1068,7 @@ class Spectroscopy(object):
               Dn = S_i + T_i*((Dn + Rd*S_i)*m3) ; Rd = R_i + T_i*((T_i*Rd)*m3)
         Band fluxes F_b = (band mean of F)*(n_b/n_per_v) and the heating rate, paths.heating_rate
         of the returned upward and downward fluxes, as in compute_flux.
+        A scatterer whose optics vary with wavenumber: compute_thermal_flux_spectral.
 
         Args:
             layer_thickness, surface_temperature, surface, band_edges: as in compute_flux.
@@ -1098,6 +1158,52 @@ class Spectroscopy(object):
             quantities, band_edges, range_policy)
         return self._thermal_flux(request, remove_pedestal, range_policy)
 
+    def compute_thermal_flux_spectral(self, layer_thickness, surface_temperature,
+                                      scatterer_wavenumber, scatterer_optical_depth,
+                                      scatterer_single_scattering_albedo, scatterer_asymmetry,
+                                      interface_temperature=None, surface_emissivity=1.,
+                                      emissivity_wavenumber=None, surface="first",
+                                      diffusivity=1.66,
+                                      quantities=("upward_flux", "downward_flux"),
+                                      band_edges=None, remove_pedestal=None,
+                                      range_policy="reference"):
+        """compute_thermal_flux -- with interface_temperature compute_thermal_flux_linear -- with
+        cloud and aerosol optics that vary with wavenumber.  The scatterer of every level is a
+        table over the knots scatterer_wavenumber, interpolated and limited per grid point as in
+        compute_solar_flux_spectral; w_c = omega_c*tau_c, f = g_c*g_c and gp = g_c/(1 + g_c) are
+        then formed per grid point on the GPU, and the layer and the adding are those of the grey
+        call, line by line.  A level whose knots all have omega_c*tau_c == 0 (no scatterer, or one
+        that only absorbs) is a clear level, with tau = tau_a + tau_c(nu); in any other level
+        every grid point takes the cloudy branches, but where tau == 0 (which a grey cloudy level
+        cannot have, and where omega = w_c/tau would be 0/0) the clear one: x = 0, the identity.
+        A table that is flat in nu gives the grey call's fluxes bit for bit.
+
+        Args:
+            scatterer_wavenumber, scatterer_optical_depth, scatterer_single_scattering_albedo,
+            scatterer_asymmetry: as in compute_solar_flux_spectral.
+            interface_temperature: None (isothermal levels, compute_thermal_flux's source) or
+                         compute_thermal_flux_linear's interface temperatures.
+            Everything else as in compute_thermal_flux.
+
+        Returns:
+            Like compute_thermal_flux or compute_thermal_flux_linear, with the attribute (the
+            key) "scatterer": "spectral".
+        Raises ValueError like them, all of them before the GPU is touched.
+        """
+        arguments = (surface_emissivity, emissivity_wavenumber, surface, diffusivity,
+                     scatterer_optical_depth, scatterer_single_scattering_albedo,
+                     scatterer_asymmetry, quantities, band_edges, range_policy)
+        knots = paths._given_knots(scatterer_wavenumber)
+        if interface_temperature is None:
+            request = paths._thermal_flux_request(
+                self, layer_thickness, surface_temperature, *arguments,
+                scatterer_wavenumber=knots, caller="compute_thermal_flux_spectral")
+        else:
+            request = paths._thermal_flux_linear_request(
+                self, layer_thickness, surface_temperature, interface_temperature, *arguments,
+                scatterer_wavenumber=knots, caller="compute_thermal_flux_spectral")
+        return self._thermal_flux(request, remove_pedestal, range_policy)
+
     def _thermal_flux(self, request, remove_pedestal, range_policy):
         """The sweeps of compute_thermal_flux and, where the request holds interface
         temperatures, of compute_thermal_flux_linear."""
@@ -1138,14 +1244,19 @@ class Spectroscopy(object):
                         else:
                             blocks[name + "_rows"] = outputs[source]
                 entry = call.engine.path_thermal_two_stream
-                tables = (request.level_table[a:b],)
-                if linear:
+                tables, source = (request.level_table[a:b],), {}
+                if request.scatterer_knots is not None:
+                    entry = call.engine.path_thermal_two_stream_spectral
+                    tables += (request.scatterer_knots, request.scatterer_optics[a:b])
+                    if linear:
+                        source["edge_temperature"] = request.edge_temperature[a:b]
+                elif linear:
                     entry = call.engine.path_thermal_two_stream_source
                     tables += (request.edge_temperature[a:b],)
                 entry(
                     beta, call.columns, grid, call.paths, call.per_path, a, *tables,
                     request.surface_temperature,
-                    work if b - a == run else work.rows(2*(b - a)),
+                    work if b - a == run else work.rows(2*(b - a)), **source,
                     diffusivity=request.diffusivity,
                     emissivity=None if spectral else request.surface_emissivity,
                     emissivity_rows=emissivity_rows, band_start=request.starts,

@@ -5,7 +5,8 @@
 # path_radiance_kernel, path_flux_kernel, path_jacobian_kernel -- in both instantiations;
 # "two_stream" the shortwave two-stream kernels, "thermal" the longwave ones: thermal_up_kernel and
 # thermal_down_kernel, vector and scalar rows, each with the source of the level temperatures
-# (Lb0E as the second template argument) and with the linear-in-tau one (Lb1E)).
+# (Lb0E as the second template argument) and with the linear-in-tau one (Lb1E); the last template
+# argument of the two-stream kernels is Lb1E with the spectral scatterer and Lb0E with the grey one).
 # Also prints the md5 of the device code's .text: unchanged by edits that only move host code.
 set -e
 LIB=${LIB:-pylbl_amd/liblbl_amd.so}
