@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h,
-include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h, include/lbl_amd_kdist.h and
-include/lbl_amd_scatterer.h (pylbl_amd/liblbl_amd.so), and nothing else:
+include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h, include/lbl_amd_kdist.h,
+include/lbl_amd_scatterer.h and include/lbl_amd_thermal_radiance.h (pylbl_amd/liblbl_amd.so), and
+nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -246,6 +247,16 @@ SCATTERER_PROTOTYPES = {
                                                                       _f64, _ptr, _ptr, _ptr,
                                                                       _i32] + [_ptr]*10 + [_i32],
 }
+# Every function of include/lbl_amd_thermal_radiance.h, the header of the all-sky radiance entry of
+# the same library; each returns int.  tests/test_thermal_radiance_host.py compares this table with
+# that header.
+THERMAL_RADIANCE_PROTOTYPES = {
+    # grid, the run, level_table, diffusivity, view_cosine, surface_temperature, emissivity_rows,
+    # emissivity, up_rows, down_rows, n_bands, band_start, radiance_rows, brightness_rows,
+    # radiance_mean, flags
+    "lbl_path_thermal_radiance": _BLOCK + [_i32] + _RUN + [_ptr, _f64] + [_ptr]*6 + [_i32] +
+                                 [_ptr]*4 + [_i32],
+}
 
 _library = None
 
@@ -304,7 +315,8 @@ def library():
     lib = CDLL(str(path))
     for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()) + \
             list(THERMAL_PROTOTYPES.items()) + list(THERMAL_SOURCE_PROTOTYPES.items()) + \
-            list(KDIST_PROTOTYPES.items()) + list(SCATTERER_PROTOTYPES.items()):
+            list(KDIST_PROTOTYPES.items()) + list(SCATTERER_PROTOTYPES.items()) + \
+            list(THERMAL_RADIANCE_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

@@ -33,6 +33,7 @@
 #include "../../include/lbl_amd_thermal_source.h"
 #include "../../include/lbl_amd_kdist.h"
 #include "../../include/lbl_amd_scatterer.h"
+#include "../../include/lbl_amd_thermal_radiance.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "band_sort_pairs.h"
@@ -51,6 +52,7 @@
 #include "tile_schedule.h"
 #include "twostream.h"
 #include "twostream_thermal.h"
+#include "thermal_radiance.h"
 
 #include "engine_core.h"
 #include "lanes_plans.inc"
@@ -508,6 +510,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "solar_entry.inc"
 #include "twostream_entry.inc"
 #include "thermal_entry.inc"
+#include "thermal_radiance_entry.inc"
 #include "band_sort_entry.inc"
 #include "band_sort_pairs_entry.inc"
 #include "instrument_entry.inc"

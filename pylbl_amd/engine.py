@@ -941,6 +941,41 @@ class Engine(object):
             _address(ts), _address(emissivity_rows), _address(emissivity), n_bands,
             _address(starts), work.pointer, *pointers, flags))
 
+    def path_thermal_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin,
+                              level_table, view_cosine, surface_temperature, up_rows, down_rows,
+                              diffusivity=1.66, emissivity=None, emissivity_rows=None,
+                              band_start=None, from_last=False, asynchronous=False,
+                              radiance_rows=None, brightness_rows=None, radiance_mean=None):
+        """The radiance a viewer above the atmosphere sees through the whole paths in the
+        DeviceSpectra `beta`, from the two-stream fluxes path_thermal_two_stream left in up_rows
+        and down_rows [>= rows, row length] (read only) -- lbl_path_thermal_radiance.  Rows,
+        columns, grid, level_table, diffusivity, surface_temperature, emissivity /
+        emissivity_rows, band_start, from_last and asynchronous as for path_thermal_two_stream;
+        view_cosine one per path, in (0, 1].  Outputs (DeviceSpectra, None: not wanted):
+        radiance_rows and brightness_rows [n_paths, row length], and with band_start
+        radiance_mean [n_paths, bands]."""
+        rows, stride = int(beta.shape[0]), int(beta.shape[1])
+        table = _f64(level_table)
+        if table.shape != (rows, 5):
+            raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
+        mu, ts, emissivity = _per_path(n_paths, "one view cosine, one surface temperature and one "
+                                       "emissivity per path.", view_cosine, surface_temperature,
+                                       emissivity)
+        if emissivity_rows is not None and tuple(emissivity_rows.shape) != (int(n_paths), stride):
+            raise ValueError("emissivity_rows must be [n_paths, row length of beta].")
+        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path, False,
+                                           asynchronous)
+        flags |= PATH_FROM_LAST if from_last else 0
+        _check_outputs((up_rows, down_rows), rows, stride)
+        _check_outputs((radiance_rows, brightness_rows), int(n_paths), stride)
+        _check_outputs((radiance_mean,), int(n_paths), n_bands)
+        self._check(self.lib.lbl_path_thermal_radiance(
+            self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
+            int(levels_per_path), int(level_begin), rows, table.ctypes.data, float(diffusivity),
+            _address(mu), _address(ts), _address(emissivity_rows), _address(emissivity),
+            _address(up_rows), _address(down_rows), n_bands, _address(starts),
+            _address(radiance_rows), _address(brightness_rows), _address(radiance_mean), flags))
+
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):
         """Several continua in one pass over the grid (lbl_continuum_compute_many): summed, in

@@ -1,6 +1,6 @@
 """The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux,
 compute_jacobian, compute_solar, compute_solar_flux, compute_thermal_flux,
-compute_thermal_flux_linear and the per-level
+compute_thermal_flux_linear, compute_thermal_radiance and the per-level
 compute_kdistribution -- on the host: their quantities and units, the checks of
 their arguments (one request per call, made before anything touches the GPU), the run loop that sweeps the "total"
 absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
@@ -172,6 +172,11 @@ _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
     "surface", "level_table", "diffusivity", "surface_temperature", "surface_emissivity",
     "emissivity_knots", "edge_temperature", "scatterer_knots", "scatterer_optics"),
     defaults=(None, None, None))
+
+# compute_thermal_radiance's: _ThermalFluxRequest's (edge_temperature and the scatterer knots stay
+# None) with mu, the viewing zenith cosine of every path; its quantities are RADIANCE_QUANTITIES.
+_ThermalRadianceRequest = namedtuple("_ThermalRadianceRequest",
+                                     _ThermalFluxRequest._fields + ("mu",))
 
 # compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
 # points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
@@ -882,6 +887,31 @@ def _thermal_flux_linear_request(spec, layer_thickness, surface_temperature,
                                     scatterer_wavenumber=scatterer_wavenumber, caller=caller)
     return request._replace(edge_temperature=_edge_temperatures(
         "linear_in_tau", interface_temperature, request.shape))
+
+
+def _thermal_radiance_request(spec, layer_thickness, surface_temperature, view_zenith_cosine,
+                              surface_emissivity, emissivity_wavenumber, surface, diffusivity,
+                              scatterer_optical_depth, scatterer_single_scattering_albedo,
+                              scatterer_asymmetry, quantities, band_edges, instrument,
+                              range_policy):
+    """Checks every argument of compute_thermal_radiance: compute_thermal_flux's checks of the
+    atmosphere, the surface, D and the scatterer, the view, and compute_radiance's rules for the
+    quantities, the bands and the instrument."""
+    flux = _thermal_flux_request(
+        spec, layer_thickness, surface_temperature, surface_emissivity, emissivity_wavenumber,
+        surface, diffusivity, scatterer_optical_depth, scatterer_single_scattering_albedo,
+        scatterer_asymmetry, THERMAL_FLUX_QUANTITIES[:2], None, range_policy,
+        caller="compute_thermal_radiance")
+    mu = _per_path(view_zenith_cosine, "view_zenith_cosine", flux.shape)
+    if not np.all((mu > 0.) & (mu <= 1.)):
+        raise ValueError("view_zenith_cosine must lie in (0, 1].")
+    quantities = _selection(quantities, RADIANCE_QUANTITIES)
+    if band_edges is not None and "brightness_temperature" in quantities:
+        raise ValueError("brightness_temperature is only available on the grid: band means "
+                         "are formed of the radiance alone.")
+    edges, starts = _path_bands(spec, band_edges, instrument)
+    return _ThermalRadianceRequest(*flux._replace(quantities=quantities, edges=edges,
+                                                  starts=starts, instrument=instrument), mu=mu)
 
 
 def _kdistribution_weighting(spec, weighting, weighting_temperature):

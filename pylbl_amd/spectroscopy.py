@@ -15,7 +15,7 @@ of numpy arrays with the same variable names.
 
 What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
 path products compute_path, compute_radiance, compute_jacobian, compute_flux, compute_solar and
-compute_solar_flux, compute_thermal_flux, compute_thermal_flux_linear, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
+compute_solar_flux, compute_thermal_flux, compute_thermal_flux_linear, compute_thermal_radiance, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
 queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
 else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
 whose public names stay importable from here; their functions take the Spectroscopy first, and
@@ -1269,6 +1269,131 @@ class Spectroscopy(object):
         return paths._create_solar_flux_dataset(
             self, paths._solar_flux_interfaces(self, values, request), request)
 
+    def compute_thermal_radiance(self, layer_thickness, surface_temperature,
+                                 view_zenith_cosine=1., surface_emissivity=1.,
+                                 emissivity_wavenumber=None, surface="first", diffusivity=1.66,
+                                 scatterer_optical_depth=None,
+                                 scatterer_single_scattering_albedo=None,
+                                 scatterer_asymmetry=None, quantities=("radiance",),
+                                 band_edges=None, instrument=None, remove_pedestal=None,
+                                 range_policy="reference"):
+        """Sounder radiances through clouds: the radiance a viewer above the atmosphere sees
+        along the zenith cosine mu of each path, in an atmosphere that absorbs, emits and holds
+        one grey scatterer per level, by the two-stream source-function technique (Toon et al.
+        1989): compute_thermal_flux's two-stream fluxes are the scattering source and the
+        transfer equation is integrated exactly along the viewing direction, on the GPU, in one
+        more sweep behind the two of compute_thermal_flux.  The all-sky counterpart of
+        compute_radiance: without scatterers, with eps = 1 and mu = 1 it returns
+        compute_radiance(layer_thickness, boundary_temperature=surface_temperature) bit for bit.
+
+        Paths, levels, `surface`, layer_thickness, the level row (s_l, tau_c, w_c, g_c, T_l), D,
+        tau, the clear/cloudy branch and omega, sc, t, w, g2, dif, g1, su, k2, the conservative
+        criterion and k, E of the general branch are compute_thermal_flux's, bit for bit.  up[i]
+        and down[i] are its fluxes at interface i: level i lies between interfaces i and i + 1,
+        interface 0 faces space, down[0] = 0.  B = B(nu, T_l) as in compute_radiance, piB = pi*B,
+            gp = g_c/(1 + g_c) ; a = (3*(gp*mu))/2
+        Within a level the source is
+            J(tau) = B + (w/(2 pi))*[f+(tau)(1 + a) + f-(tau)(1 - a)],  f+- = F+- - piB
+        (the two-stream phase function 1 + 3 g' mu mu' with hemispherically isotropic I+- =
+        F+-/pi).  Per path and grid point, each product, sum and quotient rounded as written, with
+            u1 = up[i+1] - piB ; d0 = down[i] - piB ; Dm = exp(-t/mu) ; Em = -expm1(-t/mu)
+        the level maps the radiance entering its surface-side face, I_bot, to
+            I_top = I_bot*Dm + B*Em + (w/(2 pi))*C
+            clear level (w_c == 0):  x = tau/mu and C = 0:
+              I_top = I_bot*exp(-x) + B*(-expm1(-x))
+            cloudy, general:
+              Gamma = g2/(g1 + k) ; n = 1 - (Gamma*E)*(Gamma*E)
+              P = (u1 - (Gamma*E)*d0)/n ; Q = (d0 - (Gamma*E)*u1)/n
+              C = P*((1 + a) + Gamma*(1 - a))*h + Q*(Gamma*(1 + a) + (1 - a))*((1 - E*Dm)/(1 + k*mu))
+              h = (E - Dm)/(1 - k mu), formed without its pole and without overflow:
+                y = ((1 - k*mu)*t)/mu ; phi(z) = -expm1(-z)/z for z > 0, phi(0) = 1
+                h = E*((t/mu)*phi(y)) for y >= 0 ; h = Dm*((t/mu)*phi(-y)) for y < 0
+            cloudy, conservative:
+              x = g1*t ; N = (u1 - d0)/(1 + x)
+              C = ((u1 + d0) - x*N + a*N)*Em + (2*(g1*N))*(mu*W)
+              W = Em - (t/mu)*Dm, formed without its cancellation as
+                W = (t/mu)*(Em - linear_weight(t/mu, Em))
+                (compute_radiance's w = 1 - Em/(t/mu) of the linear source, in its two-branch form)
+        The surface is Lambertian: I_L = eps*B(T_s) + (1 - eps)*(down[L]/pi); the result is I at
+        interface 0.  Levels are isothermal, the scatterers grey, the view is upward from above
+        the atmosphere with one cosine per path; sunlight is not included.
+
+        Args:
+            layer_thickness, surface_temperature, surface_emissivity, emissivity_wavenumber,
+            surface, diffusivity, scatterer_optical_depth, scatterer_single_scattering_albedo,
+            scatterer_asymmetry: as in compute_thermal_flux.
+            view_zenith_cosine: mu in (0, 1]: a scalar or one per path.
+            quantities: any of "radiance" and "brightness_temperature".
+            band_edges, instrument: as in compute_radiance: band means of the radiance alone;
+                         with an instrument channel radiances are formed on the GPU and their
+                         brightness temperatures at the channel centres on the host.
+
+        Returns:
+            Like compute_radiance: "radiance" ("W m-2 sr-1 (cm-1)-1") / "brightness_temperature"
+            ("K") with the atmosphere's dims without the last, then "wavenumber", "band" or
+            "channel".
+        Raises ValueError, before the GPU is touched, like compute_thermal_flux and
+        compute_radiance, and where the blocks of one path (beta, two work blocks and the two
+        flux blocks) exceed device_output_limit: a run holds whole paths.
+        """
+        request = paths._thermal_radiance_request(
+            self, layer_thickness, surface_temperature, view_zenith_cosine, surface_emissivity,
+            emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
+            scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
+            instrument, range_policy)
+        bands = request.starts is not None
+        swept = request.quantities
+        if request.instrument is not None:
+            # Channel radiances on the GPU; their brightness temperatures at the centres here.
+            swept = ("radiance",)
+        # From space to the surface: "first" has its surface at level 0.
+        step = _Pass(request.surface == "first", (), swept)
+
+        def sweeper(call, run):
+            grid = call.grid()
+            work, up, down = call.take(2*run), call.take(run), call.take(run)
+            spectral = request.emissivity_knots is not None
+            emissivity_rows = call.take(call.paths) if spectral else None
+            # With bands the radiance on the grid is a block of this call, the output its means.
+            fine = call.take(call.paths) if bands else None
+            filled = []
+
+            def sweep(index, beta, a, b, outputs):
+                if spectral and not filled:
+                    call.engine.surface_emissivity(grid, emissivity_rows,
+                                                   request.emissivity_knots,
+                                                   request.surface_emissivity, asynchronous=True)
+                    filled.append(True)
+                whole = b - a == run
+                fluxes = dict(up_rows=up if whole else up.rows(b - a),
+                              down_rows=down if whole else down.rows(b - a))
+                surface = dict(diffusivity=request.diffusivity,
+                               emissivity=None if spectral else request.surface_emissivity,
+                               emissivity_rows=emissivity_rows, from_last=step.from_last,
+                               asynchronous=True)
+                call.engine.path_thermal_two_stream(
+                    beta, call.columns, grid, call.paths, call.per_path, a,
+                    request.level_table[a:b], request.surface_temperature,
+                    work if whole else work.rows(2*(b - a)), **surface, **fluxes)
+                blocks = dict(radiance_rows=fine, radiance_mean=outputs["radiance"]) if bands \
+                    else dict(radiance_rows=outputs.get("radiance"),
+                              brightness_rows=outputs.get("brightness_temperature"))
+                call.engine.path_thermal_radiance(
+                    beta, call.columns, grid, call.paths, call.per_path, a,
+                    request.level_table[a:b], request.mu, request.surface_temperature,
+                    band_start=request.starts, **surface, **fluxes, **blocks)
+            return sweep
+        products = None if request.instrument is None else \
+            [_Product(q, q, False) for q in swept]
+        # Five blocks per level: beta, the two work rows and the two flux rows.
+        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                                   level_blocks=5, products=products, whole_paths=True)
+        if request.instrument is not None and "brightness_temperature" in request.quantities:
+            from .instrument import brightness_temperature
+            values["brightness_temperature"] = brightness_temperature(
+                values["radiance"], request.instrument.centers)
+        return self._create_path_dataset(values, request)
+
     def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
                               quantities=("absorption_g_mean",), remove_pedestal=None,
                               range_policy="reference", weighting=None,
@@ -1447,6 +1572,7 @@ class Spectroscopy(object):
     _solar_flux_request = paths._solar_flux_request
     _thermal_flux_request = paths._thermal_flux_request
     _thermal_flux_linear_request = paths._thermal_flux_linear_request
+    _thermal_radiance_request = paths._thermal_radiance_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
 
