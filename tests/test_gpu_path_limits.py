@@ -1,6 +1,8 @@
 """Spectroscopy.compute_path within its limits: runs of levels hold one run's block in HBM, not
 the whole atmosphere, and atmospheres with more paths (or band-mean rows) than a launch grid's y
-dimension takes are done in several launches with the same results."""
+dimension takes are done in several runs with the same results.  A run holds at most 65 535 levels
+(paths._cut_runs), so each of them is one launch of the sweep and one chunk of band means: the
+later launches of a run are reached by tests/test_gpu_many_paths.py, which feeds the entries."""
 import numpy as np
 import pytest
 
@@ -74,9 +76,11 @@ def test_runs_hold_one_run_of_levels(monkeypatch, cumulative, run_levels):
 
 @pytest.mark.parametrize("cumulative", [None, "from_first"])
 def test_more_paths_than_the_grid_y_limit(cumulative):
-    """70 000 paths of two levels: the sweep and (cumulative: 140 000 rows of) band means take
-    several launches, and the 140 000 levels several runs.  The reference absorption comes from
-    four Spectroscopy objects of 17 500 paths each (one call takes at most 65 535 levels)."""
+    """70 000 paths of two levels: the 140 000 levels take several runs, and the sweep and
+    (cumulative: 140 000 rows of) band means one launch in each of them -- a run holds at most
+    65 535 levels, so at most 32 768 paths and 65 535 rows of means.  The reference absorption
+    comes from four Spectroscopy objects of 17 500 paths each (one call takes at most 65 535
+    levels)."""
     shape = (70000, 2)
     grid = np.arange(600., 600.64, 0.01)
     atmos = atmosphere(shape)
