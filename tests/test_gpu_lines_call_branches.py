@@ -17,7 +17,8 @@ Where the other branches of compute() (csrc/compute_call.inc) are reached:
                                             test_deferred_finish_queued_first_adds_last
   evals                                     test_gpu_parity: test_eval_count_matches_oracle;
                                             test_gpu_baseline_configs
-  derived, prep on the device and the host  test_gpu_parity: test_line_scalars_match_oracle
+  derived, prep on the device and the host  test_gpu_parity: test_line_scalars_match_oracle;
+                                            test_gpu_line_scalars (slots, window edges, row order)
   inline / copied levels (kInlineLevels 4)  test_gpu_fuzz_delivery (1-5 levels); test_gpu_api:
                                             test_level_chunking_and_strides (7 levels, then fewer
                                             per pass)
