@@ -70,6 +70,42 @@ def _per_path(n_paths, message, *values):
     return arrays
 
 
+def _whole_paths(beta, level_table, n_paths, surface_rows, surface_name, band_start, level_begin,
+                 levels_per_path, from_last, asynchronous, work=None):
+    """(rows, row length, float64 level table, int64 band starts or None, n_bands, flags) of a
+    two-stream call on the whole paths in `beta`, checked: level_table [rows, 5], work (where
+    the entry has one) [>= 2*rows, row length], the surface's rows -- albedo_rows or
+    emissivity_rows, named by surface_name -- None or [n_paths, row length]; the flags are
+    _path_run's of a run that starts at a path's end, with PATH_FROM_LAST."""
+    rows, stride = int(beta.shape[0]), int(beta.shape[1])
+    table = _f64(level_table)
+    if table.shape != (rows, 5):
+        raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
+    if work is not None and (work.shape[1] != stride or work.shape[0] < 2*rows):
+        raise ValueError(f"work has shape {work.shape}, need {2*rows} x {stride}.")
+    if surface_rows is not None and tuple(surface_rows.shape) != (int(n_paths), stride):
+        raise ValueError(f"{surface_name} must be [n_paths, row length of beta].")
+    starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path, False,
+                                       asynchronous)
+    return rows, stride, table, starts, n_bands, flags | (PATH_FROM_LAST if from_last else 0)
+
+
+def _output_pointers(name, names, outputs, rows, n_paths, stride, n_bands):
+    """The addresses of a two-stream entry's outputs in the order of `names`
+    (PATH_TWO_STREAM_OUTPUTS, PATH_THERMAL_OUTPUTS), None for one not wanted, checked: *_rows
+    [>= rows, or n_paths for top_*, row length], *_mean [the same, bands]."""
+    unknown = set(outputs) - set(names)
+    if unknown:
+        raise TypeError(f"{name} has no output {sorted(unknown)}.")
+    pointers = []
+    for output in names:
+        out = outputs.get(output)
+        need = int(n_paths) if output.startswith("top_") else rows
+        _check_outputs((out,), need, n_bands if output.endswith("_mean") else stride)
+        pointers.append(_address(out))
+    return pointers
+
+
 def _edge_rows(edge_temperature, rows):
     """None, or the interface temperatures of a path call as a float64 array [rows, 2]."""
     if edge_temperature is None:
@@ -812,31 +848,16 @@ class Engine(object):
                          outputs):
         """The call of path_two_stream (spectral None) and of path_two_stream_spectral (spectral:
         grid, knots, optics, M): lbl_<name>."""
-        rows, stride = int(beta.shape[0]), int(beta.shape[1])
-        table = _f64(level_table)
-        if table.shape != (rows, 5):
-            raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
-        unknown = set(outputs) - set(PATH_TWO_STREAM_OUTPUTS)
-        if unknown:
-            raise TypeError(f"{name} has no output {sorted(unknown)}.")
-        if work.shape[1] != stride or work.shape[0] < 2*rows:
-            raise ValueError(f"work has shape {work.shape}, need {2*rows} x {stride}.")
+        rows, stride, table, starts, n_bands, flags = _whole_paths(
+            beta, level_table, n_paths, albedo_rows, "albedo_rows", band_start, level_begin,
+            levels_per_path, from_last, asynchronous, work)
         if solar_row.shape[1] < int(columns) or \
                 (rayleigh_row is not None and rayleigh_row.shape[1] < int(columns)):
             raise ValueError(f"solar_row and rayleigh_row need {columns} values.")
         mu0, albedo = _per_path(n_paths, "one cosine and one albedo per path.",
                                 solar_zenith_cosine, albedo)
-        if albedo_rows is not None and tuple(albedo_rows.shape) != (int(n_paths), stride):
-            raise ValueError("albedo_rows must be [n_paths, row length of beta].")
-        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path, False,
-                                           asynchronous)
-        flags |= PATH_FROM_LAST if from_last else 0
-        pointers = []
-        for output in PATH_TWO_STREAM_OUTPUTS:
-            out = outputs.get(output)
-            need = int(n_paths) if output.startswith("top_") else rows
-            _check_outputs((out,), need, n_bands if output.endswith("_mean") else stride)
-            pointers.append(_address(out))
+        pointers = _output_pointers(name, PATH_TWO_STREAM_OUTPUTS, outputs, rows, n_paths, stride,
+                                    n_bands)
         knots = []
         if spectral is not None:
             grid, knot, optics, n_knots = spectral
@@ -907,29 +928,14 @@ class Engine(object):
         """The call of path_thermal_two_stream (edge_temperature None), of
         path_thermal_two_stream_source and of path_thermal_two_stream_spectral (spectral: knots,
         optics, M; its edge_temperature goes as NULL where None): lbl_<name>."""
-        rows, stride = int(beta.shape[0]), int(beta.shape[1])
-        table = _f64(level_table)
-        if table.shape != (rows, 5):
-            raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
+        rows, stride, table, starts, n_bands, flags = _whole_paths(
+            beta, level_table, n_paths, emissivity_rows, "emissivity_rows", band_start,
+            level_begin, levels_per_path, from_last, asynchronous, work)
         edges = _edge_rows(edge_temperature, rows)
-        unknown = set(outputs) - set(PATH_THERMAL_OUTPUTS)
-        if unknown:
-            raise TypeError(f"{name} has no output {sorted(unknown)}.")
-        if work.shape[1] != stride or work.shape[0] < 2*rows:
-            raise ValueError(f"work has shape {work.shape}, need {2*rows} x {stride}.")
         ts, emissivity = _per_path(n_paths, "one surface temperature and one emissivity per "
                                    "path.", surface_temperature, emissivity)
-        if emissivity_rows is not None and tuple(emissivity_rows.shape) != (int(n_paths), stride):
-            raise ValueError("emissivity_rows must be [n_paths, row length of beta].")
-        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path, False,
-                                           asynchronous)
-        flags |= PATH_FROM_LAST if from_last else 0
-        pointers = []
-        for output in PATH_THERMAL_OUTPUTS:
-            out = outputs.get(output)
-            need = int(n_paths) if output.startswith("top_") else rows
-            _check_outputs((out,), need, n_bands if output.endswith("_mean") else stride)
-            pointers.append(_address(out))
+        pointers = _output_pointers(name, PATH_THERMAL_OUTPUTS, outputs, rows, n_paths, stride,
+                                    n_bands)
         tables = [table.ctypes.data] + ([] if edges is None else [edges.ctypes.data])
         if spectral is not None:
             knot, optics, n_knots = spectral
@@ -954,18 +960,12 @@ class Engine(object):
         view_cosine one per path, in (0, 1].  Outputs (DeviceSpectra, None: not wanted):
         radiance_rows and brightness_rows [n_paths, row length], and with band_start
         radiance_mean [n_paths, bands]."""
-        rows, stride = int(beta.shape[0]), int(beta.shape[1])
-        table = _f64(level_table)
-        if table.shape != (rows, 5):
-            raise ValueError(f"level_table has shape {table.shape}, need {rows} x 5.")
+        rows, stride, table, starts, n_bands, flags = _whole_paths(
+            beta, level_table, n_paths, emissivity_rows, "emissivity_rows", band_start,
+            level_begin, levels_per_path, from_last, asynchronous)
         mu, ts, emissivity = _per_path(n_paths, "one view cosine, one surface temperature and one "
                                        "emissivity per path.", view_cosine, surface_temperature,
                                        emissivity)
-        if emissivity_rows is not None and tuple(emissivity_rows.shape) != (int(n_paths), stride):
-            raise ValueError("emissivity_rows must be [n_paths, row length of beta].")
-        starts, n_bands, flags = _path_run(band_start, level_begin, rows, levels_per_path, False,
-                                           asynchronous)
-        flags |= PATH_FROM_LAST if from_last else 0
         _check_outputs((up_rows, down_rows), rows, stride)
         _check_outputs((radiance_rows, brightness_rows), int(n_paths), stride)
         _check_outputs((radiance_mean,), int(n_paths), n_bands)

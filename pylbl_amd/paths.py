@@ -1,12 +1,12 @@
 """The path products of Spectroscopy -- compute_path, compute_radiance, compute_flux,
-compute_jacobian, compute_solar, compute_solar_flux, compute_thermal_flux,
-compute_thermal_flux_linear, compute_thermal_radiance and the per-level
-compute_kdistribution -- on the host: their quantities and units, the checks of
-their arguments (one request per call, made before anything touches the GPU), the run loop that sweeps the "total"
-absorption block of a run of levels at a time (_sweep_runs), the HBM accounting behind its run
-cuts (_level_bytes) and the assembly of the results.  The sweeps themselves are the kernels of
-csrc/path.h behind Engine.path_*; the "total" block is queued by Spectroscopy.total_into
-(absorption.py, whose pipeline guard the run loop shares).
+compute_jacobian, compute_solar and the per-level compute_kdistribution -- on the host: their
+quantities and units, the checks of their arguments (one request per call, made before anything
+touches the GPU), the run loop that sweeps the "total" absorption block of a run of levels at a
+time (_sweep_runs), the HBM accounting behind its run cuts (_level_bytes), what the sweepers of
+several products share (_FilledOnce, _Rows, _first_rows) and the assembly of the results.  The
+two-stream products build on these in two_stream.py; their public constants are here.  The
+sweeps themselves are the kernels of csrc/path.h behind Engine.path_*; the "total" block is
+queued by Spectroscopy.total_into (absorption.py, whose pipeline guard the run loop shares).
 """
 from collections import namedtuple
 
@@ -78,10 +78,6 @@ K_B = 1.380649e-23                      # [J K-1]
 RAYLEIGH_SPLIT = 0.5                    # [um]
 RAYLEIGH_SHORT = (3.01577e-28, 3.55212, 1.35579, 0.11563)
 RAYLEIGH_LONG = (4.01061e-28, 3.99668, 1.10298e-3, 2.71393e-2)
-# What the entry calls the rows of a quantity, and what the sweep writes at interface 0 beside it.
-_TWO_STREAM_ROWS = {"upward_flux": "up", "downward_flux": "down", "direct_irradiance": "direct",
-                    "diffuse_downward_flux": "diffuse"}
-_TOP = "top_"
 
 # compute_thermal_flux: the two-stream longwave fluxes.  The diffusivity factor D lies in
 # DIFFUSIVITY_RANGE; 1.66 is Elsasser's, 2 the hemispheric mean of Toon et al. (1989).
@@ -109,19 +105,15 @@ _PATH_UNITS = {"optical_depth": "1", "transmittance": "1",
                "temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
                "boundary_temperature_jacobian": "W m-2 sr-1 (cm-1)-1 K-1",
                "boundary_emissivity_jacobian": "W m-2 sr-1 (cm-1)-1"}
-# compute_flux: on the grid, per band.
+# compute_flux, compute_solar and the two-stream flux products: on the grid (and per channel), per
+# band.
 _FLUX_UNITS = {"upward_flux": ("W m-2 (cm-1)-1", "W m-2"),
                "downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
+               "direct_irradiance": ("W m-2 (cm-1)-1", "W m-2"),
+               "diffuse_downward_flux": ("W m-2 (cm-1)-1", "W m-2"),
+               "surface_irradiance": ("W m-2 (cm-1)-1", "W m-2"),
+               "reflected_radiance": ("W m-2 sr-1 (cm-1)-1", "W m-2 sr-1 (cm-1)-1"),
                "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
-
-_SOLAR_FLUX_UNITS = dict(_FLUX_UNITS, direct_irradiance=_FLUX_UNITS["downward_flux"],
-                         diffuse_downward_flux=_FLUX_UNITS["downward_flux"])
-
-# compute_solar: on the grid (and per channel), per band.
-_SOLAR_UNITS = {"direct_irradiance": ("W m-2 (cm-1)-1", "W m-2"),
-                "surface_irradiance": ("W m-2 (cm-1)-1", "W m-2"),
-                "reflected_radiance": ("W m-2 sr-1 (cm-1)-1", "W m-2 sr-1 (cm-1)-1"),
-                "heating_rate": ("K day-1 (cm-1)-1", "K day-1")}
 
 # What every product checked and derived from its arguments: flat lengths, the atmosphere's shape,
 # the quantities asked for, band edges and their column starts (or None), the Instrument (or
@@ -150,33 +142,6 @@ _FluxRequest = namedtuple("_FluxRequest", _COMMON + (
 _SolarRequest = namedtuple("_SolarRequest", _COMMON + (
     "surface", "mu0", "solar_lengths", "view_lengths", "albedo", "albedo_knots", "solar_knots",
     "solar_values", "scale"))
-
-# compute_solar_flux's: mu0 per path, the level table [levels, 5] of lbl_path_two_stream (s_l, c_l,
-# tau_c, w_c, h_c), the albedo per path -- [paths], or [paths, M] at albedo_knots [M] -- the Sun
-# as in _SolarRequest, and rayleigh_values: None (the fit, or no Rayleigh scattering: `rayleigh`)
-# or the caller's cross-sections [V] on the grid.  scatterer_knots [M] and scatterer_optics
-# [levels, M, 3] (tau_c, omega_c, g_c at every knot): None, or the spectral scatterer of
-# lbl_path_two_stream_spectral, beside which tau_c, w_c and h_c of the level table are 0.
-_SolarFluxRequest = namedtuple("_SolarFluxRequest", _COMMON + (
-    "surface", "mu0", "level_table", "albedo", "albedo_knots", "solar_knots", "solar_values",
-    "scale", "rayleigh", "rayleigh_values", "scatterer_knots", "scatterer_optics"),
-    defaults=(None, None))
-
-# compute_thermal_flux's: the level table [levels, 5] of lbl_path_thermal_two_stream (s_l, tau_c,
-# w_c, g_c, T_l), D, the surface temperature per path and its emissivity -- [paths], or [paths, M]
-# at emissivity_knots [M].  edge_temperature: None (compute_thermal_flux: isothermal levels) or
-# compute_thermal_flux_linear's interface temperatures per flat level, as above.  scatterer_knots
-# and scatterer_optics as in _SolarFluxRequest (lbl_path_thermal_two_stream_spectral: tau_c, w_c
-# and g_c of the level table are 0 beside them).
-_ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
-    "surface", "level_table", "diffusivity", "surface_temperature", "surface_emissivity",
-    "emissivity_knots", "edge_temperature", "scatterer_knots", "scatterer_optics"),
-    defaults=(None, None, None))
-
-# compute_thermal_radiance's: _ThermalFluxRequest's (edge_temperature and the scatterer knots stay
-# None) with mu, the viewing zenith cosine of every path; its quantities are RADIANCE_QUANTITIES.
-_ThermalRadianceRequest = namedtuple("_ThermalRadianceRequest",
-                                     _ThermalFluxRequest._fields + ("mu",))
 
 # compute_kdistribution's (lengths: None, it is a per-level product): the g edges [Q + 1] and
 # points [P], the column starts of every band's intervals [B, Q + 1] (interval_columns) and the
@@ -371,6 +336,12 @@ def _check_level_temperatures(spec):
         raise ValueError("the atmosphere's temperatures must be finite and > 0.")
 
 
+def _check_pressures(spec, what="heating rates need"):
+    pressure = spec.atmosphere.pressure
+    if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
+        raise ValueError(f"{what} pressures that are finite and > 0.")
+
+
 def _per_path(value, name, shape):
     """A scalar or one value per path (shaped like the atmosphere without its last dimension), as
     a flat float64 array of one value per path."""
@@ -562,9 +533,7 @@ def _flux_request(spec, layer_thickness, surface_temperature, surface_emissivity
     _check_level_temperatures(spec)
     edge_temperature = _edge_temperatures(source, interface_temperature, shape)
     if "heating_rate" in (quantities if not isinstance(quantities, str) else (quantities,)):
-        pressure = spec.atmosphere.pressure
-        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
-            raise ValueError("heating rates need pressures that are finite and > 0.")
+        _check_pressures(spec)
     ts, es = _emitter(surface_temperature, surface_emissivity, "surface", shape)
     if not (isinstance(surface, str) and surface in FLUX_SURFACES):
         raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
@@ -653,9 +622,7 @@ def _solar_request(spec, layer_thickness, solar_zenith_cosine, solar_irradiance,
                 ("albedo_wavenumber", "surface_albedo", "surface albedos"))
     if "heating_rate" in quantities:
         _check_level_temperatures(spec)
-        pressure = spec.atmosphere.pressure
-        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
-            raise ValueError("heating rates need pressures that are finite and > 0.")
+        _check_pressures(spec)
     _check_range_policy(range_policy)
     edges, starts = _path_bands(spec, band_edges, instrument)
     if instrument is not None and any(q not in SOLAR_PATH_QUANTITIES for q in quantities):
@@ -679,239 +646,6 @@ def rayleigh_cross_section(wavenumber):
                   for short, long in zip(RAYLEIGH_SHORT, RAYLEIGH_LONG))
     e = (b + c*lam) + d/lam
     return np.where(positive, (1e-4*a)*np.exp(-(e*np.log(lam))), 0.)
-
-
-def _scatterer_arrays(shape, optical_depth, single_scattering_albedo, asymmetry, knots=None):
-    """None without a scatterer, or its (tau_c, omega_c, g_c), checked: each shaped like the
-    atmosphere -- with `knots` [M] like the atmosphere with one more axis of M at the end --,
-    finite and in its range."""
-    given = [x is not None for x in (optical_depth, single_scattering_albedo, asymmetry)]
-    if not any(given):
-        return None
-    if not all(given):
-        raise ValueError("scatterer_optical_depth, scatterer_single_scattering_albedo and "
-                         "scatterer_asymmetry are given together or not at all.")
-    expected = tuple(shape) + (() if knots is None else (knots.size,))
-    arrays = []
-    for name, value in (("scatterer_optical_depth", optical_depth),
-                        ("scatterer_single_scattering_albedo", single_scattering_albedo),
-                        ("scatterer_asymmetry", asymmetry)):
-        value = np.asarray(value, dtype=np.float64)
-        if value.shape != expected:
-            if knots is not None:
-                raise ValueError(f"{name} has shape {value.shape}: with scatterer_wavenumber "
-                                 f"give the atmosphere's shape and one value per knot, "
-                                 f"{expected}.")
-            raise ValueError(f"{name} has shape {value.shape}, the atmosphere {shape}.")
-        if not np.all(np.isfinite(value)):
-            raise ValueError(f"{name} must be finite.")
-        arrays.append(value)
-    tau_c, omega_c, g_c = arrays
-    if np.any(tau_c < 0.):
-        raise ValueError("scatterer_optical_depth must be >= 0.")
-    if not np.all((omega_c >= 0.) & (omega_c <= 1.)):
-        raise ValueError("scatterer_single_scattering_albedo must lie in [0, 1].")
-    if not np.all((g_c >= 0.) & (g_c < 1.)):
-        raise ValueError("scatterer_asymmetry must lie in [0, 1).")
-    return tau_c, omega_c, g_c
-
-
-def _given_knots(wavenumber):
-    """scatterer_wavenumber of the *_spectral calls, which need it."""
-    if wavenumber is None:
-        raise ValueError("scatterer_wavenumber must be given: [M] knots in cm-1.")
-    return wavenumber
-
-
-def _spectral_scatterers(shape, wavenumber, optical_depth, single_scattering_albedo, asymmetry):
-    """(None, None) without scatterer_wavenumber, or (knots [M], optics [levels, M, 3]) of the
-    spectral scatterer, checked: M knots [cm-1], finite and strictly ascending, 2 <= M <= 1024,
-    and tau_c, omega_c and g_c of every level at every knot, which the kernels interpolate
-    linearly in wavenumber and hold constant outside the knots (include/lbl_amd_scatterer.h)."""
-    if wavenumber is None:
-        return None, None
-    knots = np.asarray(wavenumber, dtype=np.float64)
-    if knots.ndim != 1 or not 2 <= knots.size <= MAX_SCATTERER_KNOTS:
-        raise ValueError(f"scatterer_wavenumber must be a 1-d array of 2..{MAX_SCATTERER_KNOTS} "
-                         f"knots, not of shape {knots.shape}.")
-    if not np.all(np.isfinite(knots)) or not np.all(np.diff(knots) > 0.):
-        raise ValueError("scatterer_wavenumber must be finite and strictly ascending.")
-    arrays = _scatterer_arrays(shape, optical_depth, single_scattering_albedo, asymmetry, knots)
-    if arrays is None:
-        raise ValueError("scatterer_wavenumber needs scatterer_optical_depth, "
-                         "scatterer_single_scattering_albedo and scatterer_asymmetry at its "
-                         "knots.")
-    optics = np.stack([x.reshape(-1, knots.size) for x in arrays], axis=2)
-    return np.ascontiguousarray(knots), np.ascontiguousarray(optics)
-
-
-def _scatterers(spec, shape, optical_depth, single_scattering_albedo, asymmetry):
-    """(tau_c, w_c, h_c) per flat level of compute_solar_flux's grey scatterer, checked: zeros
-    without one; w_c = omega_c*tau_c and h_c = (omega_c*tau_c)*g_c in fp64."""
-    levels = int(np.prod(shape, dtype=np.int64))
-    arrays = _scatterer_arrays(shape, optical_depth, single_scattering_albedo, asymmetry)
-    if arrays is None:
-        return np.zeros(levels), np.zeros(levels), np.zeros(levels)
-    tau_c, omega_c, g_c = (x.ravel() for x in arrays)
-    w_c = omega_c*tau_c
-    return tau_c, w_c, w_c*g_c
-
-
-def _solar_flux_request(spec, layer_thickness, solar_zenith_cosine, solar_irradiance,
-                        solar_wavenumber, distance_factor, surface, surface_albedo,
-                        albedo_wavenumber, rayleigh, rayleigh_cross_section,
-                        scatterer_optical_depth, scatterer_single_scattering_albedo,
-                        scatterer_asymmetry, quantities, band_edges, range_policy,
-                        scatterer_wavenumber=None, caller="compute_solar_flux"):
-    """Checks every argument of compute_solar_flux (of `caller`, which shares them)."""
-    if spec.group is not None:
-        raise NotImplementedError(f"{caller} does not split paths over processes yet "
-                                  "(group is set).")
-    lengths, shape = _path_geometry(spec, layer_thickness, caller,
-                                    "layer_thickness", "layer thicknesses")
-    if not (isinstance(surface, str) and surface in FLUX_SURFACES):
-        raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
-    mu0 = _per_path(solar_zenith_cosine, "solar_zenith_cosine", shape)
-    if not np.all((mu0 > 0.) & (mu0 <= 1.)):
-        raise ValueError("solar_zenith_cosine must lie in (0, 1].")
-    solar_knots, solar_values, scale = _solar_spectrum(spec, solar_irradiance, solar_wavenumber,
-                                                       distance_factor)
-    albedo_knots = None
-    if albedo_wavenumber is None:
-        albedo = _per_path(surface_albedo, "surface_albedo", shape)
-        if not np.all((albedo >= 0.) & (albedo <= 1.)):
-            raise ValueError("surface albedos must lie in [0, 1].")
-    else:
-        albedo_knots, albedo = _spectral_emissivity(
-            albedo_wavenumber, surface_albedo, shape,
-            ("albedo_wavenumber", "surface_albedo", "surface albedos"))
-    if not isinstance(rayleigh, (bool, np.bool_)):
-        raise ValueError(f"rayleigh must be True or False, not {rayleigh!r}.")
-    quantities = _selection(quantities, SOLAR_FLUX_QUANTITIES)
-    rayleigh_values = None
-    if rayleigh_cross_section is not None:
-        if not rayleigh:
-            raise ValueError("rayleigh_cross_section is only used with rayleigh=True.")
-        rayleigh_values = np.asarray(rayleigh_cross_section, dtype=np.float64)
-        if rayleigh_values.shape != (spec.grid.size,):
-            raise ValueError(f"rayleigh_cross_section has shape {rayleigh_values.shape}: give "
-                             f"one value per grid point, [{spec.grid.size}].")
-        if not np.all(np.isfinite(rayleigh_values)) or np.any(rayleigh_values < 0.):
-            raise ValueError("Rayleigh cross-sections must be finite and >= 0.")
-        rayleigh_values = np.ascontiguousarray(rayleigh_values)
-    if rayleigh or "heating_rate" in quantities:
-        what = "Rayleigh scattering needs" if rayleigh else "heating rates need"
-        pressure = spec.atmosphere.pressure
-        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
-            raise ValueError(f"{what} pressures that are finite and > 0.")
-        _check_level_temperatures(spec)
-    knots, optics = _spectral_scatterers(shape, scatterer_wavenumber, scatterer_optical_depth,
-                                         scatterer_single_scattering_albedo, scatterer_asymmetry)
-    grey = (None, None, None) if knots is not None else (
-        scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry)
-    tau_c, w_c, h_c = _scatterers(spec, shape, *grey)
-    column = np.zeros(lengths.size)
-    if rayleigh:
-        column = (np.asarray(spec.atmosphere.pressure, dtype=np.float64).ravel() /
-                  (K_B*np.asarray(spec.atmosphere.temperature, dtype=np.float64).ravel()))*lengths
-        if not np.all(np.isfinite(column)):
-            raise ValueError("the air columns (p/(K_B*T))*layer_thickness must be finite.")
-    _check_range_policy(range_policy)
-    edges, starts = _path_bands(spec, band_edges)
-    table = np.ascontiguousarray(np.stack([lengths, column, tau_c, w_c, h_c], axis=1))
-    return _SolarFluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
-                             starts=starts, instrument=None, cumulative=False, surface=surface,
-                             mu0=mu0, level_table=table, albedo=albedo, albedo_knots=albedo_knots,
-                             solar_knots=solar_knots, solar_values=solar_values, scale=scale,
-                             rayleigh=bool(rayleigh), rayleigh_values=rayleigh_values,
-                             scatterer_knots=knots, scatterer_optics=optics)
-
-
-def _thermal_flux_request(spec, layer_thickness, surface_temperature, surface_emissivity,
-                          emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
-                          scatterer_single_scattering_albedo, scatterer_asymmetry, quantities,
-                          band_edges, range_policy, scatterer_wavenumber=None,
-                          caller="compute_thermal_flux"):
-    """Checks every argument of compute_thermal_flux (of `caller`, which shares them)."""
-    if spec.group is not None:
-        raise NotImplementedError(f"{caller} does not split paths over processes yet "
-                                  "(group is set).")
-    lengths, shape = _path_geometry(spec, layer_thickness, caller,
-                                    "layer_thickness", "layer thicknesses")
-    _check_level_temperatures(spec)
-    if not (isinstance(surface, str) and surface in FLUX_SURFACES):
-        raise ValueError(f"surface must be one of {FLUX_SURFACES}, not {surface!r}.")
-    factor = np.asarray(diffusivity, dtype=np.float64)
-    low, high = DIFFUSIVITY_RANGE
-    if factor.shape != () or not low <= factor <= high:
-        raise ValueError(f"diffusivity must be one number in [{low:g}, {high:g}].")
-    emissivity_knots = None
-    if emissivity_wavenumber is None:
-        ts, es = _emitter(surface_temperature, surface_emissivity, "surface", shape)
-    else:
-        ts, _ = _emitter(surface_temperature, 1., "surface", shape)
-        emissivity_knots, es = _spectral_emissivity(
-            emissivity_wavenumber, surface_emissivity, shape,
-            ("emissivity_wavenumber", "surface_emissivity", "surface emissivities"))
-    quantities = _selection(quantities, THERMAL_FLUX_QUANTITIES)
-    if "heating_rate" in quantities:
-        pressure = spec.atmosphere.pressure
-        if not np.all(np.isfinite(pressure)) or np.any(pressure <= 0.):
-            raise ValueError("heating rates need pressures that are finite and > 0.")
-    knots, optics = _spectral_scatterers(shape, scatterer_wavenumber, scatterer_optical_depth,
-                                         scatterer_single_scattering_albedo, scatterer_asymmetry)
-    if knots is not None:
-        scatterer_optical_depth = scatterer_single_scattering_albedo = scatterer_asymmetry = None
-    tau_c, w_c, _ = _scatterers(spec, shape, scatterer_optical_depth,
-                                scatterer_single_scattering_albedo, scatterer_asymmetry)
-    g_c = np.zeros(lengths.size) if scatterer_asymmetry is None else \
-        np.asarray(scatterer_asymmetry, dtype=np.float64).ravel()
-    _check_range_policy(range_policy)
-    edges, starts = _path_bands(spec, band_edges)
-    temperature = np.asarray(spec.atmosphere.temperature, dtype=np.float64).ravel()
-    table = np.ascontiguousarray(np.stack([lengths, tau_c, w_c, g_c, temperature], axis=1))
-    return _ThermalFluxRequest(lengths=lengths, shape=shape, quantities=quantities, edges=edges,
-                               starts=starts, instrument=None, cumulative=False, surface=surface,
-                               level_table=table, diffusivity=float(factor),
-                               surface_temperature=ts, surface_emissivity=es,
-                               emissivity_knots=emissivity_knots, scatterer_knots=knots,
-                               scatterer_optics=optics)
-
-
-def _thermal_flux_linear_request(spec, layer_thickness, surface_temperature,
-                                 interface_temperature, *arguments, scatterer_wavenumber=None,
-                                 caller="compute_thermal_flux_linear"):
-    """Checks every argument of compute_thermal_flux_linear: compute_thermal_flux's request with
-    the interface temperatures of the linear-in-tau source."""
-    request = _thermal_flux_request(spec, layer_thickness, surface_temperature, *arguments,
-                                    scatterer_wavenumber=scatterer_wavenumber, caller=caller)
-    return request._replace(edge_temperature=_edge_temperatures(
-        "linear_in_tau", interface_temperature, request.shape))
-
-
-def _thermal_radiance_request(spec, layer_thickness, surface_temperature, view_zenith_cosine,
-                              surface_emissivity, emissivity_wavenumber, surface, diffusivity,
-                              scatterer_optical_depth, scatterer_single_scattering_albedo,
-                              scatterer_asymmetry, quantities, band_edges, instrument,
-                              range_policy):
-    """Checks every argument of compute_thermal_radiance: compute_thermal_flux's checks of the
-    atmosphere, the surface, D and the scatterer, the view, and compute_radiance's rules for the
-    quantities, the bands and the instrument."""
-    flux = _thermal_flux_request(
-        spec, layer_thickness, surface_temperature, surface_emissivity, emissivity_wavenumber,
-        surface, diffusivity, scatterer_optical_depth, scatterer_single_scattering_albedo,
-        scatterer_asymmetry, THERMAL_FLUX_QUANTITIES[:2], None, range_policy,
-        caller="compute_thermal_radiance")
-    mu = _per_path(view_zenith_cosine, "view_zenith_cosine", flux.shape)
-    if not np.all((mu > 0.) & (mu <= 1.)):
-        raise ValueError("view_zenith_cosine must lie in (0, 1].")
-    quantities = _selection(quantities, RADIANCE_QUANTITIES)
-    if band_edges is not None and "brightness_temperature" in quantities:
-        raise ValueError("brightness_temperature is only available on the grid: band means "
-                         "are formed of the radiance alone.")
-    edges, starts = _path_bands(spec, band_edges, instrument)
-    return _ThermalRadianceRequest(*flux._replace(quantities=quantities, edges=edges,
-                                                  starts=starts, instrument=instrument), mu=mu)
 
 
 def _kdistribution_weighting(spec, weighting, weighting_temperature):
@@ -1027,6 +761,87 @@ def _level_bytes(n, request, level_quantities, level_blocks, grid_outputs):
 
 def _first_rows(block, count):
     return block if count == block.shape[0] else block.rows(count)
+
+
+class _FilledOnce(object):
+    """The blocks of a call that do not depend on the run -- S, sigma, the rows of a spectral
+    surface, a row of weights -- and are filled once, before its first sweep.  A sweeper makes
+    one first of all (that fetches the grid's handle), takes these blocks through it in the
+    order of its other blocks (the order is the call's HBM layout), and every sweep begins with
+    queue(): the first one queues the fills in the order they were taken, the others nothing."""
+    def __init__(self, call):
+        self.call, self.grid, self.pending = call, call.grid(), []
+
+    def take(self, rows, fill):
+        """A block of `rows` rows of the call that fill(block) queues the filling of."""
+        block = self.call.take(rows)
+        self.pending.append(lambda: fill(block))
+        return block
+
+    def queue(self):
+        while self.pending:
+            self.pending.pop(0)()
+
+    def solar_row(self, request):
+        """S on the grid, of a request with _SolarRequest's Sun."""
+        return self.take(1, lambda row: self.call.engine.solar_spectrum(
+            self.grid, row, self.call.columns, irradiance=request.solar_values,
+            wavenumber=request.solar_knots, temperature=SOLAR_TEMPERATURE, scale=request.scale,
+            asynchronous=True))
+
+    def rayleigh_row(self, cross_section):
+        """sigma on the grid: the caller's values, or the fit for None."""
+        return self.take(1, lambda row: self.call.engine.rayleigh_row(
+            self.grid, row, self.call.columns, cross_section=cross_section, asynchronous=True))
+
+    def surface_rows(self, knots, values):
+        """One row per path of a surface's emissivity or albedo table on the grid; None, and no
+        block, without knots."""
+        if knots is None:
+            return None
+        return self.take(self.call.paths, lambda rows: self.call.engine.surface_emissivity(
+            self.grid, rows, knots, values, asynchronous=True))
+
+
+class _Rows(object):
+    """Where the entry of a pass writes its rows on the grid.  Without bands they are the outputs
+    themselves; with bands they are blocks of this call, taken here in the order of
+    step.level_quantities + step.path_quantities, and the outputs receive their means."""
+    def __init__(self, call, step, run, bands):
+        self.per_level = step.level_quantities
+        self.fine = {q: call.take(run if q in self.per_level else call.paths)
+                     for q in step.level_quantities + step.path_quantities} if bands else {}
+
+    def keywords(self, names, outputs, rows):
+        """The <name>_rows (and, with bands, <name>_mean) keywords of a run of `rows` levels for
+        the quantities among `outputs`; names: {quantity: what the entry calls it}."""
+        blocks = {}
+        for q, name in names.items():
+            if q not in outputs:
+                continue
+            blocks[name + "_rows"] = outputs[q]
+            if q in self.fine:
+                fine = self.fine[q]
+                blocks[name + "_rows"] = _first_rows(fine, rows) if q in self.per_level else fine
+                blocks[name + "_mean"] = outputs[q]
+        return blocks
+
+
+def _swept_radiance(request, quantities):
+    """What the sweeps of a radiance call form of `quantities` (those of its up pass): with an
+    instrument the radiance alone, as channel radiances on the GPU -- their brightness
+    temperatures are formed at the channel centres on the host (_channel_brightness)."""
+    return ("radiance",) if request.instrument is not None and quantities else quantities
+
+
+def _channel_brightness(values, request):
+    """`values` of a radiance call, with an instrument's brightness temperatures where asked
+    for."""
+    if request.instrument is not None and "brightness_temperature" in request.quantities:
+        from .instrument import brightness_temperature
+        values["brightness_temperature"] = brightness_temperature(
+            values["radiance"], request.instrument.centers)
+    return values
 
 
 def _sweep_runs(spec, request, passes, remove_pedestal, range_policy, sweeper, level_blocks=1,
@@ -1150,6 +965,38 @@ def _spectral_axis(request):
     return "wavenumber" if request.edges is None else "band"
 
 
+def _band_widths(spec, request):
+    """What turns a band mean into the band's integral: the band's width in grid steps over
+    n_per_v [bands]; 1. on the grid."""
+    if request.starts is None:
+        return 1.
+    _, _, n_per_v = grid_arguments(spec.grid)
+    return np.diff(request.starts).astype(np.float64)/float(n_per_v)
+
+
+def _interface_rows(below, space, request):
+    """[paths, L + 1, W] at the interfaces from a sweep's rows in the Sun's order: `below`
+    [levels, W] at the interface below each level and `space` [paths, W] at the space end."""
+    per_path, paths = _path_layout(request.shape)
+    width = below.shape[-1]
+    below = np.asarray(below).reshape(paths, per_path, width)
+    space = np.asarray(space).reshape(paths, 1, width)
+    # Sweeping toward level 0 the interface below level l is interface l, toward level L-1
+    # interface l + 1.
+    return np.concatenate([below, space] if request.surface == "first" else [space, below],
+                          axis=1)
+
+
+def _level_heating(spec, upward, downward, request):
+    """heating_rate of the fluxes [paths, L + 1, W] in the atmosphere's shape, [..., L, W]."""
+    per_path, paths = _path_layout(request.shape)
+    return heating_rate(
+        upward, downward, spec.atmosphere.pressure.reshape(paths, per_path),
+        spec.atmosphere.temperature.reshape(paths, per_path),
+        request.lengths.reshape(paths, per_path), request.surface).reshape(
+            list(request.shape) + [-1])
+
+
 def _flux_interfaces(spec, values, request):
     """{quantity: [..., L + 1 or L, W]} of compute_flux from the sweeps' per-level rows (the
     flux just after each level in sweep order) and the surface rows."""
@@ -1172,8 +1019,7 @@ def _flux_interfaces(spec, values, request):
         fluxes = {"downward_flux": np.concatenate([space, down], axis=1),
                   "upward_flux": np.concatenate([up, surface], axis=1)}
     if request.starts is not None:
-        _, _, n_per_v = grid_arguments(spec.grid)
-        widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
+        widths = _band_widths(spec, request)
         fluxes = {q: f*widths for q, f in fluxes.items()}
     out = {}
     lead = shape[:-1] + [per_path + 1, width]
@@ -1181,12 +1027,8 @@ def _flux_interfaces(spec, values, request):
         if q in request.quantities:
             out[q] = fluxes[q].reshape(lead)
     if "heating_rate" in request.quantities:
-        out["heating_rate"] = heating_rate(
-            fluxes["upward_flux"], fluxes["downward_flux"],
-            spec.atmosphere.pressure.reshape(paths, per_path),
-            spec.atmosphere.temperature.reshape(paths, per_path),
-            request.lengths.reshape(paths, per_path),
-            request.surface).reshape(shape + [width])
+        out["heating_rate"] = _level_heating(spec, fluxes["upward_flux"],
+                                             fluxes["downward_flux"], request)
     return out
 
 
@@ -1194,27 +1036,15 @@ def _solar_interfaces(spec, values, request):
     """{quantity: array} of compute_solar from the sweep's rows: the direct irradiance below each
     level and at the space end of each path, the surface rows and the reflected rows."""
     shape = list(request.shape)
-    per_path, paths = _path_layout(request.shape)
-    widths = 1.
-    if request.starts is not None:
-        _, _, n_per_v = grid_arguments(spec.grid)
-        widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
+    per_path, _ = _path_layout(request.shape)
+    widths = _band_widths(spec, request)
     out = {}
     if "direct_irradiance" in values:
-        width = values["direct_irradiance"].shape[-1]
-        below = np.asarray(values["direct_irradiance"]).reshape(paths, per_path, width)
-        space = np.asarray(values[_SPACE]).reshape(paths, 1, width)
-        # Sweeping toward level 0 the irradiance below level l is at interface l, toward level
-        # L-1 at interface l + 1.
-        direct = np.concatenate([below, space] if request.surface == "first" else [space, below],
-                                axis=1)*widths
+        direct = _interface_rows(values["direct_irradiance"], values[_SPACE], request)*widths
         if "direct_irradiance" in request.quantities:
-            out["direct_irradiance"] = direct.reshape(shape[:-1] + [per_path + 1, width])
+            out["direct_irradiance"] = direct.reshape(shape[:-1] + [per_path + 1, -1])
         if "heating_rate" in request.quantities:
-            out["heating_rate"] = heating_rate(
-                np.zeros_like(direct), direct, spec.atmosphere.pressure.reshape(paths, per_path),
-                spec.atmosphere.temperature.reshape(paths, per_path),
-                request.lengths.reshape(paths, per_path), request.surface).reshape(shape + [width])
+            out["heating_rate"] = _level_heating(spec, np.zeros_like(direct), direct, request)
     if "surface_irradiance" in request.quantities:
         scale = 1. if request.instrument is not None else widths
         out["surface_irradiance"] = (np.asarray(values["surface_irradiance"])*scale).reshape(
@@ -1223,61 +1053,6 @@ def _solar_interfaces(spec, values, request):
         out["reflected_radiance"] = np.asarray(values["reflected_radiance"]).reshape(
             shape[:-1] + [-1])
     return out
-
-
-def _solar_flux_interfaces(spec, values, request):
-    """{quantity: [..., L + 1 or L, W]} of compute_solar_flux from the sweep's rows: the fluxes at
-    the interface below each level and at interface 0 (the space end) of each path."""
-    shape = list(request.shape)
-    per_path, paths = _path_layout(request.shape)
-    widths = 1.
-    if request.starts is not None:
-        _, _, n_per_v = grid_arguments(spec.grid)
-        widths = np.diff(request.starts).astype(np.float64)/float(n_per_v)
-    fluxes = {}
-    for q in SOLAR_FLUX_INTERFACE_QUANTITIES:
-        if q not in values:
-            continue
-        width = values[q].shape[-1]
-        below = np.asarray(values[q]).reshape(paths, per_path, width)
-        space = np.asarray(values[_TOP + q]).reshape(paths, 1, width)
-        # Sweeping toward level 0 the interface below level l is interface l, toward level L-1
-        # interface l + 1.
-        fluxes[q] = np.concatenate([below, space] if request.surface == "first"
-                                   else [space, below], axis=1)*widths
-    out = {q: fluxes[q].reshape(shape[:-1] + [per_path + 1, -1])
-           for q in SOLAR_FLUX_INTERFACE_QUANTITIES if q in request.quantities}
-    if "heating_rate" in request.quantities:
-        out["heating_rate"] = heating_rate(
-            fluxes["upward_flux"], fluxes["downward_flux"],
-            spec.atmosphere.pressure.reshape(paths, per_path),
-            spec.atmosphere.temperature.reshape(paths, per_path),
-            request.lengths.reshape(paths, per_path), request.surface).reshape(shape + [-1])
-    return out
-
-
-def _create_solar_flux_dataset(spec, values, request):
-    """compute_solar_flux's result, built like _create_flux_dataset's."""
-    dims = list(spec.atmosphere.dims)
-    axis = _spectral_axis(request)
-    variables = {}
-    for q in request.quantities:
-        here = dims + [axis] if q == "heating_rate" else dims[:-1] + ["interface", axis]
-        variables[q] = (here, values[q], _SOLAR_FLUX_UNITS[q][request.edges is not None])
-    return _path_variables(spec, variables, request)
-
-
-def _create_solar_dataset(spec, values, request):
-    """compute_solar's result, built like _create_flux_dataset's: the direct irradiance on the
-    "interface" dim in place of the atmosphere's last, heating rates on it, the others per path."""
-    dims = list(spec.atmosphere.dims)
-    axis = _spectral_axis(request)
-    variables = {}
-    for q in request.quantities:
-        here = {"direct_irradiance": dims[:-1] + ["interface", axis],
-                "heating_rate": dims + [axis]}.get(q, dims[:-1] + [axis])
-        variables[q] = (here, values[q], _SOLAR_UNITS[q][request.edges is not None])
-    return _path_variables(spec, variables, request)
 
 
 def _create_path_dataset(spec, values, request):
@@ -1296,15 +1071,22 @@ def _create_path_dataset(spec, values, request):
 
 
 def _create_flux_dataset(spec, values, request):
-    """compute_flux's result from {quantity: [..., interfaces or levels, columns or bands]}:
-    fluxes on the "interface" dim in place of the atmosphere's last, heating rates on it."""
+    """The result of compute_flux, of compute_solar and of the two-stream flux products from
+    {quantity: [..., interfaces or levels, columns or bands]}: fluxes and irradiances on the
+    "interface" dim in place of the atmosphere's last, heating rates on it, compute_solar's
+    SOLAR_PATH_QUANTITIES per path."""
     dims = list(spec.atmosphere.dims)
     axis = _spectral_axis(request)
     variables = {}
     for q in request.quantities:
         here = dims + [axis] if q == "heating_rate" else dims[:-1] + ["interface", axis]
+        if q in SOLAR_PATH_QUANTITIES:
+            here = dims[:-1] + [axis]
         variables[q] = (here, values[q], _FLUX_UNITS[q][request.edges is not None])
     return _path_variables(spec, variables, request)
+
+
+_create_solar_dataset = _create_flux_dataset
 
 
 def _create_kdistribution_dataset(spec, values, request):

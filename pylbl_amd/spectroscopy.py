@@ -13,20 +13,25 @@ number-density scaling happens in the kernel epilogue; xarray is optional (not i
 this image) -- without it the atmosphere is a plain (p, t, vmr) tuple and the result a dict
 of numpy arrays with the same variable names.
 
-What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- compute_absorption and the
-path products compute_path, compute_radiance, compute_jacobian, compute_flux, compute_solar and
-compute_solar_flux, compute_thermal_flux, compute_thermal_flux_linear, compute_thermal_radiance, and the per-level compute_kdistribution: their documentation and their sweeps.  The host side of compute_absorption (the gases present, the
-queue orders of its formats, total_into, the pipeline guard) is in absorption.py, everything
-else of the path products (argument checks, the run loop, HBM accounting, results) in paths.py,
-whose public names stay importable from here; their functions take the Spectroscopy first, and
-total_into, _compute_levels and paths.py's request, run-loop and result functions are its methods.
+What is in this module: Atmosphere, MoleculeCache and Spectroscopy -- every compute_* method
+with its definition, and the sweeps of compute_path, compute_radiance, compute_jacobian,
+compute_flux, compute_solar and compute_kdistribution.  Which module holds the rest:
+    absorption.py   the host side of compute_absorption: the gases present, the queue orders of
+                    its formats, total_into, the pipeline guard;
+    paths.py        the path products' argument checks, the run loop, the HBM accounting, what
+                    their sweepers share and their results; its public names stay importable
+                    from here;
+    two_stream.py   the requests, sweeps and results of the two-stream products:
+                    compute_solar_flux, compute_thermal_flux, their _linear and _spectral
+                    variants and compute_thermal_radiance.
+Their functions take the Spectroscopy first; those a test reaches through it are its methods.
 """
 from collections import namedtuple
 import os
 
 import numpy as np
 
-from . import absorption, errors, paths
+from . import absorption, errors, paths, two_stream
 from .paths import (CP_DRY, DOWNWELLING, FLUX_QUANTITIES, FLUX_SURFACES,  # noqa: F401
                     JACOBIAN_LEVEL_QUANTITIES, JACOBIAN_PATH_QUANTITIES, JACOBIAN_QUANTITIES, MAX_FLUX_ANGLES,
                     KDISTRIBUTION_QUANTITIES, MAX_G_INTERVALS, g_intervals, g_quadrature_points,
@@ -423,22 +428,21 @@ class Spectroscopy(object):
         spectral = request.emissivity_knots is not None
         wanted = DOWNWELLING in request.quantities
         banded = request.starts is not None
-        up_quantities = tuple(q for q in request.quantities if q != DOWNWELLING)
-        if request.instrument is not None and up_quantities:
-            # Channel radiances on the GPU; their brightness temperatures at the centres here.
-            up_quantities = ("radiance",)
+        up_quantities = paths._swept_radiance(
+            request, tuple(q for q in request.quantities if q != DOWNWELLING))
         down = _Pass(not request.from_last, (), (DOWNWELLING,) if wanted else ())
         up = _sweep_pass(up_quantities, request.cumulative, request.from_last)
         passes = ([down] if reflecting else []) + ([up] if up_quantities else [])
 
         def sweeper(call, run):
-            grid = call.grid()
+            fills = paths._FilledOnce(call)
+            grid = fills.grid
             carry = call.take(call.paths)
             # D on the grid: the returned rows themselves where they are on the grid; else a
             # block of its own, which with bands is the down pass's carry (D stays in it).
             reflection = call.take(call.paths) if reflecting and (banded or not wanted) else None
-            emissivity = call.take(call.paths) if spectral else None
-            filled = []
+            # The emissivity rows are filled before the first sweep of the up pass.
+            emissivity = fills.surface_rows(request.emissivity_knots, request.boundary_emissivity)
 
             def sweep(index, beta, a, b, outputs):
                 rows = None
@@ -454,11 +458,7 @@ class Spectroscopy(object):
                         band_start=request.starts if means else None, cumulative=False,
                         from_last=down.from_last, asynchronous=True, **_run_edges(request, a, b))
                     return
-                if spectral and not filled:
-                    call.engine.surface_emissivity(grid, emissivity, request.emissivity_knots,
-                                                   request.boundary_emissivity,
-                                                   asynchronous=True)
-                    filled.append(True)
+                fills.queue()
                 # (a call that uses nothing of the surface passes neither keyword)
                 surface = {} if emissivity is None and rows is None else \
                     dict(emissivity_rows=emissivity, reflection=rows)
@@ -479,11 +479,7 @@ class Spectroscopy(object):
                 ([_Product(DOWNWELLING, DOWNWELLING, False)] if wanted else [])
         values = self._sweep_runs(request, passes, remove_pedestal, range_policy, sweeper,
                                    products=products)
-        if request.instrument is not None and "brightness_temperature" in request.quantities:
-            from .instrument import brightness_temperature
-            values["brightness_temperature"] = brightness_temperature(
-                values["radiance"], request.instrument.centers)
-        return self._create_path_dataset(values, request)
+        return self._create_path_dataset(paths._channel_brightness(values, request), request)
 
     def compute_jacobian(self, path_length, boundary_temperature=None, boundary_emissivity=1.,
                          direction="toward_last",
@@ -758,46 +754,23 @@ class Spectroscopy(object):
                 "surface_irradiance": "surface", "reflected_radiance": "reflected"}
 
         def sweeper(call, run):
-            grid = call.grid()
+            fills = paths._FilledOnce(call)
             carry = call.take(2*call.paths)
-            solar = call.take(1)
-            spectral = request.albedo_knots is not None
-            albedo_rows = call.take(call.paths) if spectral else None
-            # With bands the sweep's rows on the grid are blocks of this call, and the outputs
-            # their means; without, the outputs themselves.
-            fine = {q: call.take(run if q in step.level_quantities else call.paths)
-                    for q in step.level_quantities + step.path_quantities} if bands else {}
-            filled = []
+            solar = fills.solar_row(request)
+            albedo_rows = fills.surface_rows(request.albedo_knots, request.albedo)
+            fine = paths._Rows(call, step, run, bands)
 
             def sweep(index, beta, a, b, outputs):
-                if not filled:
-                    call.engine.solar_spectrum(
-                        grid, solar, call.columns, irradiance=request.solar_values,
-                        wavenumber=request.solar_knots, temperature=SOLAR_TEMPERATURE,
-                        scale=request.scale, asynchronous=True)
-                    if spectral:
-                        call.engine.surface_emissivity(grid, albedo_rows, request.albedo_knots,
-                                                       request.albedo, asynchronous=True)
-                    filled.append(True)
-                blocks = {}
-                for q, name in rows.items():
-                    if q not in outputs:
-                        continue
-                    if bands:
-                        block = fine[q]
-                        if q in step.level_quantities and b - a != run:
-                            block = block.rows(b - a)
-                        blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[q]
-                    else:
-                        blocks[name + "_rows"] = outputs[q]
+                fills.queue()
                 call.engine.path_solar(
                     beta, call.columns, call.paths, call.per_path, a,
                     request.solar_lengths[a:b], request.mu0, solar, carry,
                     view_lengths=None if request.view_lengths is None
                     else request.view_lengths[a:b],
-                    albedo=None if spectral else request.albedo, albedo_rows=albedo_rows,
-                    band_start=request.starts, from_last=step.from_last, asynchronous=True,
-                    **blocks)
+                    albedo=None if albedo_rows is not None else request.albedo,
+                    albedo_rows=albedo_rows, band_start=request.starts,
+                    from_last=step.from_last, asynchronous=True,
+                    **fine.keywords(rows, outputs, b - a))
             return sweep
         products = None if request.instrument is None else \
             [_Product(q, q, False) for q in request.quantities]
@@ -895,12 +868,12 @@ class Spectroscopy(object):
         Raises ValueError where the blocks of one path (beta, two work blocks and one block per
         interface quantity) exceed device_output_limit: a run holds whole paths.
         """
-        request = paths._solar_flux_request(
+        request = two_stream._solar_flux_request(
             self, layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
             distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
             rayleigh_cross_section, scatterer_optical_depth, scatterer_single_scattering_albedo,
             scatterer_asymmetry, quantities, band_edges, range_policy)
-        return self._solar_flux(request, remove_pedestal, range_policy)
+        return two_stream.solar_flux(self, request, remove_pedestal, range_policy)
 
     def compute_solar_flux_spectral(self, layer_thickness, solar_zenith_cosine,
                                     scatterer_wavenumber, scatterer_optical_depth,
@@ -940,83 +913,14 @@ class Spectroscopy(object):
         Raises ValueError like compute_solar_flux, all of them before the GPU is touched; the
         knot table (24 bytes per level and knot) counts against device_output_limit.
         """
-        request = paths._solar_flux_request(
+        request = two_stream._solar_flux_request(
             self, layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
             distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
             rayleigh_cross_section, scatterer_optical_depth, scatterer_single_scattering_albedo,
             scatterer_asymmetry, quantities, band_edges, range_policy,
-            scatterer_wavenumber=paths._given_knots(scatterer_wavenumber),
+            scatterer_wavenumber=two_stream._given_knots(scatterer_wavenumber),
             caller="compute_solar_flux_spectral")
-        return self._solar_flux(request, remove_pedestal, range_policy)
-
-    def _solar_flux(self, request, remove_pedestal, range_policy):
-        """The sweeps of compute_solar_flux and, where the request holds a knot table, of
-        compute_solar_flux_spectral."""
-        bands = request.starts is not None
-        heating = "heating_rate" in request.quantities
-        wanted = tuple(q for q in paths.SOLAR_FLUX_INTERFACE_QUANTITIES
-                       if q in request.quantities or
-                       (heating and q in ("upward_flux", "downward_flux")))
-        # In the Sun's order, from space to the surface: "first" has its surface at level 0.
-        step = _Pass(request.surface == "first", wanted, tuple(paths._TOP + q for q in wanted))
-        names = paths._TWO_STREAM_ROWS
-
-        def sweeper(call, run):
-            grid = call.grid()
-            work = call.take(2*run)
-            solar = call.take(1)
-            sigma = call.take(1) if request.rayleigh else None
-            spectral = request.albedo_knots is not None
-            albedo_rows = call.take(call.paths) if spectral else None
-            # With bands the sweep's rows on the grid are blocks of this call, and the outputs
-            # their means; without, the outputs themselves.
-            fine = {q: call.take(run if q in step.level_quantities else call.paths)
-                    for q in step.level_quantities + step.path_quantities} if bands else {}
-            filled = []
-
-            def sweep(index, beta, a, b, outputs):
-                if not filled:
-                    call.engine.solar_spectrum(
-                        grid, solar, call.columns, irradiance=request.solar_values,
-                        wavenumber=request.solar_knots, temperature=SOLAR_TEMPERATURE,
-                        scale=request.scale, asynchronous=True)
-                    if sigma is not None:
-                        call.engine.rayleigh_row(grid, sigma, call.columns,
-                                                 cross_section=request.rayleigh_values,
-                                                 asynchronous=True)
-                    if spectral:
-                        call.engine.surface_emissivity(grid, albedo_rows, request.albedo_knots,
-                                                       request.albedo, asynchronous=True)
-                    filled.append(True)
-                blocks = {}
-                for q in wanted:
-                    for source, name in ((q, names[q]), (paths._TOP + q, paths._TOP + names[q])):
-                        if bands:
-                            block = fine[source]
-                            if source in step.level_quantities and b - a != run:
-                                block = block.rows(b - a)
-                            blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[source]
-                        else:
-                            blocks[name + "_rows"] = outputs[source]
-                entry = call.engine.path_two_stream
-                block, tables = (beta, call.columns), (request.level_table[a:b],)
-                if request.scatterer_knots is not None:
-                    entry = call.engine.path_two_stream_spectral
-                    block += (grid,)
-                    tables += (request.scatterer_knots, request.scatterer_optics[a:b])
-                entry(
-                    *block, call.paths, call.per_path, a, *tables,
-                    request.mu0, solar, work if b - a == run else work.rows(2*(b - a)),
-                    rayleigh_row=sigma, albedo=None if spectral else request.albedo,
-                    albedo_rows=albedo_rows, band_start=request.starts,
-                    from_last=step.from_last, asynchronous=True, **blocks)
-            return sweep
-        # Three blocks per level: beta and the two work rows; the interface rows on the grid
-        # count as compute_jacobian's do.
-        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
-                                   level_blocks=3, grid_outputs=True, whole_paths=True)
-        return paths._create_solar_flux_dataset(
-            self, paths._solar_flux_interfaces(self, values, request), request)
+        return two_stream.solar_flux(self, request, remove_pedestal, range_policy)
 
     def compute_thermal_flux(self, layer_thickness, surface_temperature, surface_emissivity=1.,
                              emissivity_wavenumber=None, surface="first", diffusivity=1.66,
@@ -1091,12 +995,12 @@ class Spectroscopy(object):
         Raises ValueError where the blocks of one path (beta, two work blocks and one block per
         flux) exceed device_output_limit: a run holds whole paths.
         """
-        request = paths._thermal_flux_request(
+        request = two_stream._thermal_flux_request(
             self, layer_thickness, surface_temperature, surface_emissivity,
             emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
             scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
             range_policy)
-        return self._thermal_flux(request, remove_pedestal, range_policy)
+        return two_stream.thermal_flux(self, request, remove_pedestal, range_policy)
 
     def compute_thermal_flux_linear(self, layer_thickness, surface_temperature,
                                     interface_temperature, surface_emissivity=1.,
@@ -1151,12 +1055,12 @@ class Spectroscopy(object):
             Like compute_thermal_flux, with the attribute (the key) "source": "linear_in_tau".
         Raises ValueError like compute_thermal_flux, all of them before the GPU is touched.
         """
-        request = paths._thermal_flux_linear_request(
+        request = two_stream._thermal_flux_linear_request(
             self, layer_thickness, surface_temperature, interface_temperature,
             surface_emissivity, emissivity_wavenumber, surface, diffusivity,
             scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry,
             quantities, band_edges, range_policy)
-        return self._thermal_flux(request, remove_pedestal, range_policy)
+        return two_stream.thermal_flux(self, request, remove_pedestal, range_policy)
 
     def compute_thermal_flux_spectral(self, layer_thickness, surface_temperature,
                                       scatterer_wavenumber, scatterer_optical_depth,
@@ -1193,81 +1097,16 @@ class Spectroscopy(object):
         arguments = (surface_emissivity, emissivity_wavenumber, surface, diffusivity,
                      scatterer_optical_depth, scatterer_single_scattering_albedo,
                      scatterer_asymmetry, quantities, band_edges, range_policy)
-        knots = paths._given_knots(scatterer_wavenumber)
+        knots = two_stream._given_knots(scatterer_wavenumber)
         if interface_temperature is None:
-            request = paths._thermal_flux_request(
+            request = two_stream._thermal_flux_request(
                 self, layer_thickness, surface_temperature, *arguments,
                 scatterer_wavenumber=knots, caller="compute_thermal_flux_spectral")
         else:
-            request = paths._thermal_flux_linear_request(
+            request = two_stream._thermal_flux_linear_request(
                 self, layer_thickness, surface_temperature, interface_temperature, *arguments,
                 scatterer_wavenumber=knots, caller="compute_thermal_flux_spectral")
-        return self._thermal_flux(request, remove_pedestal, range_policy)
-
-    def _thermal_flux(self, request, remove_pedestal, range_policy):
-        """The sweeps of compute_thermal_flux and, where the request holds interface
-        temperatures, of compute_thermal_flux_linear."""
-        bands = request.starts is not None
-        linear = request.edge_temperature is not None
-        heating = "heating_rate" in request.quantities
-        wanted = tuple(q for q in ("upward_flux", "downward_flux")
-                       if q in request.quantities or heating)
-        # From space to the surface: "first" has its surface at level 0.
-        step = _Pass(request.surface == "first", wanted, tuple(paths._TOP + q for q in wanted))
-        names = paths._TWO_STREAM_ROWS
-
-        def sweeper(call, run):
-            grid = call.grid()
-            work = call.take(2*run)
-            spectral = request.emissivity_knots is not None
-            emissivity_rows = call.take(call.paths) if spectral else None
-            # With bands the sweep's rows on the grid are blocks of this call, and the outputs
-            # their means; without, the outputs themselves.
-            fine = {q: call.take(run if q in step.level_quantities else call.paths)
-                    for q in step.level_quantities + step.path_quantities} if bands else {}
-            filled = []
-
-            def sweep(index, beta, a, b, outputs):
-                if spectral and not filled:
-                    call.engine.surface_emissivity(grid, emissivity_rows,
-                                                   request.emissivity_knots,
-                                                   request.surface_emissivity, asynchronous=True)
-                    filled.append(True)
-                blocks = {}
-                for q in wanted:
-                    for source, name in ((q, names[q]), (paths._TOP + q, paths._TOP + names[q])):
-                        if bands:
-                            block = fine[source]
-                            if source in step.level_quantities and b - a != run:
-                                block = block.rows(b - a)
-                            blocks[name + "_rows"], blocks[name + "_mean"] = block, outputs[source]
-                        else:
-                            blocks[name + "_rows"] = outputs[source]
-                entry = call.engine.path_thermal_two_stream
-                tables, source = (request.level_table[a:b],), {}
-                if request.scatterer_knots is not None:
-                    entry = call.engine.path_thermal_two_stream_spectral
-                    tables += (request.scatterer_knots, request.scatterer_optics[a:b])
-                    if linear:
-                        source["edge_temperature"] = request.edge_temperature[a:b]
-                elif linear:
-                    entry = call.engine.path_thermal_two_stream_source
-                    tables += (request.edge_temperature[a:b],)
-                entry(
-                    beta, call.columns, grid, call.paths, call.per_path, a, *tables,
-                    request.surface_temperature,
-                    work if b - a == run else work.rows(2*(b - a)), **source,
-                    diffusivity=request.diffusivity,
-                    emissivity=None if spectral else request.surface_emissivity,
-                    emissivity_rows=emissivity_rows, band_start=request.starts,
-                    from_last=step.from_last, asynchronous=True, **blocks)
-            return sweep
-        # Three blocks per level: beta and the two work rows; the interface rows on the grid
-        # count as compute_jacobian's do.
-        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
-                                   level_blocks=3, grid_outputs=True, whole_paths=True)
-        return paths._create_solar_flux_dataset(
-            self, paths._solar_flux_interfaces(self, values, request), request)
+        return two_stream.thermal_flux(self, request, remove_pedestal, range_policy)
 
     def compute_thermal_radiance(self, layer_thickness, surface_temperature,
                                  view_zenith_cosine=1., surface_emissivity=1.,
@@ -1336,63 +1175,12 @@ class Spectroscopy(object):
         compute_radiance, and where the blocks of one path (beta, two work blocks and the two
         flux blocks) exceed device_output_limit: a run holds whole paths.
         """
-        request = paths._thermal_radiance_request(
+        request = two_stream._thermal_radiance_request(
             self, layer_thickness, surface_temperature, view_zenith_cosine, surface_emissivity,
             emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
             scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
             instrument, range_policy)
-        bands = request.starts is not None
-        swept = request.quantities
-        if request.instrument is not None:
-            # Channel radiances on the GPU; their brightness temperatures at the centres here.
-            swept = ("radiance",)
-        # From space to the surface: "first" has its surface at level 0.
-        step = _Pass(request.surface == "first", (), swept)
-
-        def sweeper(call, run):
-            grid = call.grid()
-            work, up, down = call.take(2*run), call.take(run), call.take(run)
-            spectral = request.emissivity_knots is not None
-            emissivity_rows = call.take(call.paths) if spectral else None
-            # With bands the radiance on the grid is a block of this call, the output its means.
-            fine = call.take(call.paths) if bands else None
-            filled = []
-
-            def sweep(index, beta, a, b, outputs):
-                if spectral and not filled:
-                    call.engine.surface_emissivity(grid, emissivity_rows,
-                                                   request.emissivity_knots,
-                                                   request.surface_emissivity, asynchronous=True)
-                    filled.append(True)
-                whole = b - a == run
-                fluxes = dict(up_rows=up if whole else up.rows(b - a),
-                              down_rows=down if whole else down.rows(b - a))
-                surface = dict(diffusivity=request.diffusivity,
-                               emissivity=None if spectral else request.surface_emissivity,
-                               emissivity_rows=emissivity_rows, from_last=step.from_last,
-                               asynchronous=True)
-                call.engine.path_thermal_two_stream(
-                    beta, call.columns, grid, call.paths, call.per_path, a,
-                    request.level_table[a:b], request.surface_temperature,
-                    work if whole else work.rows(2*(b - a)), **surface, **fluxes)
-                blocks = dict(radiance_rows=fine, radiance_mean=outputs["radiance"]) if bands \
-                    else dict(radiance_rows=outputs.get("radiance"),
-                              brightness_rows=outputs.get("brightness_temperature"))
-                call.engine.path_thermal_radiance(
-                    beta, call.columns, grid, call.paths, call.per_path, a,
-                    request.level_table[a:b], request.mu, request.surface_temperature,
-                    band_start=request.starts, **surface, **fluxes, **blocks)
-            return sweep
-        products = None if request.instrument is None else \
-            [_Product(q, q, False) for q in swept]
-        # Five blocks per level: beta, the two work rows and the two flux rows.
-        values = self._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
-                                   level_blocks=5, products=products, whole_paths=True)
-        if request.instrument is not None and "brightness_temperature" in request.quantities:
-            from .instrument import brightness_temperature
-            values["brightness_temperature"] = brightness_temperature(
-                values["radiance"], request.instrument.centers)
-        return self._create_path_dataset(values, request)
+        return two_stream.thermal_radiance(self, request, remove_pedestal, range_policy)
 
     def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
                               quantities=("absorption_g_mean",), remove_pedestal=None,
@@ -1521,21 +1309,20 @@ class Spectroscopy(object):
             products.append(_Product("sorted_column", "sorted_column", True))
 
         def sweeper(call, run):
-            grid = call.grid()
+            fills = paths._FilledOnce(call)
+            grid = fills.grid
             scratch, index_scratch = call.take(run), call.take(run, columns=pairs)
             index_rows = None if want_columns else call.take(run, columns=pairs)
             weight_rows = call.take(run) if want_sums else None
             weighted_rows = call.take(run) if want_sums else None
-            weight_row = call.take(1) if request.weights is not None else None
-            filled = []
+            # scale*irradiance with scale = 1: the caller's weights, bit for bit.
+            weight_row = None if request.weights is None else fills.take(
+                1, lambda row: call.engine.solar_spectrum(
+                    grid, row, call.columns, irradiance=request.weights, scale=1.,
+                    asynchronous=True))
 
             def sweep(index, beta, a, b, outputs):
-                if weight_row is not None and not filled:
-                    # scale*irradiance with scale = 1: the caller's weights, bit for bit.
-                    call.engine.solar_spectrum(grid, weight_row, call.columns,
-                                               irradiance=request.weights, scale=1.,
-                                               asynchronous=True)
-                    filled.append(True)
+                fills.queue()
                 rows = b - a
                 call.engine.band_distribution_weighted(
                     beta, call.columns, request.starts,
@@ -1569,10 +1356,10 @@ class Spectroscopy(object):
     _flux_interfaces = paths._flux_interfaces
     _solar_request, _solar_interfaces = paths._solar_request, paths._solar_interfaces
     _create_solar_dataset = paths._create_solar_dataset
-    _solar_flux_request = paths._solar_flux_request
-    _thermal_flux_request = paths._thermal_flux_request
-    _thermal_flux_linear_request = paths._thermal_flux_linear_request
-    _thermal_radiance_request = paths._thermal_radiance_request
+    _solar_flux_request = two_stream._solar_flux_request
+    _thermal_flux_request = two_stream._thermal_flux_request
+    _thermal_flux_linear_request = two_stream._thermal_flux_linear_request
+    _thermal_radiance_request = two_stream._thermal_radiance_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
 

@@ -15,7 +15,7 @@ linear source gives the level-temperature source's bits."""
 import numpy as np
 import pytest
 
-from pylbl_amd import paths, synthetic
+from pylbl_amd import paths, synthetic, two_stream
 from tests import scatterer_cases as sc
 from tests import thermal_cases as tc
 from tests import two_stream_cases as ts
@@ -175,7 +175,7 @@ def test_a_spectral_cloud_in_the_longwave_matches_the_mirror(fine, surface, meth
                quantities=("upward_flux", "downward_flux"), **cloud)
     arguments = (EMISSIVITY, None, surface, 1.66, cloud[TAU], cloud[OMEGA], cloud[G],
                  ("upward_flux", "downward_flux"), None, "reference")
-    request = paths._thermal_flux_linear_request(
+    request = two_stream._thermal_flux_linear_request(
         spec, thickness, SURFACE_T, interfaces, *arguments, scatterer_wavenumber=KNOTS)
     inputs = sc.Longwave("call", spec.grid, beta.reshape(21, -1), request.level_table, interfaces,
                          request.surface_temperature, request.surface_emissivity,

@@ -15,7 +15,7 @@ import re
 import numpy as np
 import pytest
 
-from pylbl_amd import Spectroscopy, paths
+from pylbl_amd import Spectroscopy, paths, two_stream
 from pylbl_amd import engine as engine_module
 from tests import abi_header, scatterer_cases as sc, sweep_cases as cases
 from tests import surface_cases as surface
@@ -412,7 +412,7 @@ def test_requests_hold_the_knot_table_and_a_level_table_without_scatterer():
     long = spec._thermal_flux_request(
         thickness, 288., 1., None, "first", 1.66, optics[TAU], optics[OMEGA], optics[G],
         ("upward_flux",), None, "reference", scatterer_wavenumber=KNOTS)
-    linear = paths._thermal_flux_linear_request(
+    linear = two_stream._thermal_flux_linear_request(
         spec, thickness, 288., INTERFACES, 1., None, "first", 1.66, optics[TAU], optics[OMEGA],
         optics[G], ("upward_flux",), None, "reference", scatterer_wavenumber=KNOTS)
     expect = np.stack([optics[name].reshape(15, 3) for name in (TAU, OMEGA, G)], axis=2)

@@ -440,21 +440,10 @@ def test_requests_hold_what_the_sweep_needs():
 
 # ---------------------------------------------------------------------------------------------
 # The queue.
-class RadianceRecorder(tc.ThermalRecorder):
-    """tests/thermal_cases.py's engine with the call of compute_thermal_radiance."""
-    def path_thermal_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin,
-                              level_table, view_cosine, surface_temperature, **keywords):
-        self.record("path_thermal_radiance", beta=beta, columns=columns, grid=grid,
-                    n_paths=n_paths, levels_per_path=levels_per_path, level_begin=level_begin,
-                    level_table=np.asarray(level_table), view_cosine=np.asarray(view_cosine),
-                    surface_temperature=np.asarray(surface_temperature),
-                    **self._described(keywords))
-
-
 @contextlib.contextmanager
 def recorded(directory):
     before = surface.SurfaceRecorder
-    surface.SurfaceRecorder = RadianceRecorder
+    surface.SurfaceRecorder = rc.RadianceRecorder
     try:
         with surface.recorded(directory) as pair:
             yield pair

@@ -318,3 +318,16 @@ def shape_cases():
 def all_cases():
     return shape_cases() + [(inputs, mu, from_last) for inputs, mu in value_cases()
                             for from_last in (False, True)]
+
+
+# ---------------------------------------------------------------------------------------------
+# The queue of a call on a stand-in engine.
+class RadianceRecorder(tc.ThermalRecorder):
+    """tests/thermal_cases.py's engine with the call of compute_thermal_radiance."""
+    def path_thermal_radiance(self, beta, columns, grid, n_paths, levels_per_path, level_begin,
+                              level_table, view_cosine, surface_temperature, **keywords):
+        self.record("path_thermal_radiance", beta=beta, columns=columns, grid=grid,
+                    n_paths=n_paths, levels_per_path=levels_per_path, level_begin=level_begin,
+                    level_table=np.asarray(level_table), view_cosine=np.asarray(view_cosine),
+                    surface_temperature=np.asarray(surface_temperature),
+                    **self._described(keywords))
