@@ -374,7 +374,14 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const AccumulateArgs a)
 // the far-wing loop (fast_ranges) takes <4> to 73 (six wavefronts per SIMD).  Asked for 7 it makes
 // do with 72 without scratch, but spills SGPRs and is slower or no faster on every bench leg
 // (config 1 +2.5 %); under this hint the merge wins on all of them
-// (profiles/r07_ab_wing_batches.txt).
+// (profiles/r07_ab_wing_batches.txt).  With the merge written so that N stays in its register
+// (accumulate_lines.h) the hint 7 was built again (-DLBL_WAVES_PER_SIMD_4=7): 71 VGPRs, 94 SGPRs,
+// 51 spilled SGPRs against 34, no scratch, the same bits.  The trip blocks of fast_ranges are
+// the same under both hints and carry no lane move, nor do core_lines and inner_batch; the
+// additional v_readlane sit in the prologue, before and after the far-wing loop and, six of
+// them, in the loop of clipped_ranges (one per row, a second in row 1, one at its foot).  Measured it is worth
+// 0.04-0.23 % on the default step and 0.3-0.5 % on eight levels, inside the parent's spread of
+// 0.20 % on the first: 6 stays (profiles/wing_trip_ab.txt).
 template <>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
 void accumulate_kernel<8>(const AccumulateArgs a)
@@ -382,8 +389,11 @@ void accumulate_kernel<8>(const AccumulateArgs a)
     accumulate_tile<8>(a);
 }
 
+#ifndef LBL_WAVES_PER_SIMD_4
+#define LBL_WAVES_PER_SIMD_4 6      // the hint of <4> (7: the A/B build of profiles/wing_trip_ab.txt)
+#endif
 template <>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LBL_WAVES_PER_SIMD_4)))
 void accumulate_kernel<4>(const AccumulateArgs a)
 {
     accumulate_tile<4>(a);

@@ -16,12 +16,18 @@ namespace lbl {
 //
 // P = 4 (the form that carries the default workload; its SIMDs are full of fp64 FMA-class work
 // here, so only fewer operations per evaluation make it faster): every batch of eight lines
-// becomes one fraction n/t per row (wing_eight), merged into a running N/T -- N = N t + n T,
+// becomes one fraction n/t per row (wing_eight), merged into a running N/T -- N = n T + (N t),
 // T = T t, three operations -- and `batches` of them (wave-uniform, per level: wing_batches(),
 // which keeps the products in range) share one reciprocal and one FMA into acc.  At most 8 line
 // records are held at a time, as before; the running sums take 2 P VGPRs.  The order of the
 // operations is fixed: results are bitwise the same from run to run.  batches = 1 is the plain
 // eight-line group.
+// The product rounded on its own is N t, the one that lives in N's register: the FMA accumulates
+// into it and N never leaves its place.  Written the other way round (N t + (n T)) the compiler
+// formed n T in a fresh register, accumulated there and copied N back once per row and batch --
+// four v_mov_b64 in the loop block of a trip, 2.2e7 per launch of the default workload
+// (profiles/wing_trip_ab.txt).  A trip now compiles to its arithmetic alone: 148 fp64
+// operations in the first batch, 160 in every later one, 12 and the four reciprocals at the end.
 template <int P>
 __device__ __forceinline__ void fast_ranges(const LineWing * __restrict__ wing,
                                             int a0, int a1, int b0, int b1, int batches,
@@ -67,7 +73,7 @@ __device__ __forceinline__ void fast_ranges(const LineWing * __restrict__ wing,
                 {
                     double n, t;
                     wing_eight(v[p], l, n, t);
-                    num[p] = __builtin_fma(num[p], t, n*den[p]);
+                    num[p] = __builtin_fma(n, den[p], num[p]*t);
                     den[p] = den[p]*t;
                 }
             }
@@ -629,8 +635,12 @@ __device__ __forceinline__ void clipped_ranges(const LineWing * __restrict__ win
                         continue;
                     }
                     const int i = r0 + lane;
-                    const double sum = lorentz_eight(v[p], l, acc[p]);
-                    acc[p] = (i >= first && i <= last) ? sum : acc[p];
+                    // Lanes outside the window add 0/den (den is a finite product of eight t):
+                    // selected on the numerator, the sum stays in its own register.
+                    double num, den;
+                    wing_eight(v[p], l, num, den);
+                    acc[p] = __builtin_fma((i >= first && i <= last) ? num : 0., rcp_newton(den),
+                                           acc[p]);
                 }
                 k += 8;
                 continue;

@@ -185,6 +185,17 @@ __host__ __device__ inline void wing_line_bounds(const GridSpec & g, double nu, 
 // K in {1, 2, 4, 8} for which the running products of fast_ranges stay normal --
 // T = prod of 8K values of t and N = sum b_i prod_{j != i} t_j (at most 8K terms) within
 // 2^-1000 .. 2^1000.  K = 1 is the eight-line group that needs no bound (today's range).
+// The merge is N = fma(n, T, N t): the product N t is rounded on its own, n T inside the FMA.
+// With amplitudes of one sign every term of N has that sign, so |N t| is one part of the new |N|
+// and never above it: the upper guard on N covers it.  Downwards N t holds at least one term
+// b_i prod t_j over the lines merged so far and the new eight, i.e. it lies above
+// 2^(n t_lo + b_lo), which the lower guard keeps at or above 2^-1000: N t is a normal number and
+// its rounding a relative 2^-53, like that of n T in the other order.  The table loader refuses no
+// sign, and the bounds are those of |bl|.  With amplitudes of both signs the upper guard still
+// holds term by term (|N| <= sum |b_i| prod t_j), while N may cancel below any lower bound.  A
+// product N t that falls under 2^-1022 then is rounded as a denormal, an absolute error below
+// 2^-1074 against terms n T of at least 2^-1000 each: it changes nothing that the cancellation
+// itself has not already taken from the sum's relative accuracy.
 __host__ __device__ inline int wing_batches(const int (&bound)[kWingBounds])
 {
     const long long t_lo = bound[kWingTLow], t_hi = -(long long)bound[kWingTHighNeg];
