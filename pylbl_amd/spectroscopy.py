@@ -841,6 +841,11 @@ class Spectroscopy(object):
                 Td = Tb*Tdp_i + Tdif_i*((Td + (Tb*Rd)*Rdir_i)*m3)
                 Rd = Rdif_i + Tdif_i*((Tdif_i*Rd)*m3) ; Tb = Tb*D_i
             downward_flux = direct + diffuse_down
+        Against the two-stream equations themselves the layer is exact to rounding, except: the
+        conservative branch neglects up to its criterion (measured 4.8e-11 of F0 per layer); and
+        inside the guard |1 - k*mu0| < 1e-4 the layer is solved at the moved mu0, which puts Rdir
+        and Tdp off by up to 0.12*(1e-4 - |1 - k*mu0|) of F0 (measured, g_c <= 0.9): 1.2e-5 of F0
+        at k*mu0 = 1 under mu0 = 1, falling linearly to 0 at the guard's edges.
         Band fluxes F_b = (band mean of F)*(n_b/n_per_v) and the heating rate, paths.heating_rate
         of the returned upward and downward fluxes, as in compute_flux.
         With g > 0 the direct irradiance is the delta-scaled beam: it contains the forward peak
