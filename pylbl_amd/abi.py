@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h,
 include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h, include/lbl_amd_kdist.h,
-include/lbl_amd_scatterer.h and include/lbl_amd_thermal_radiance.h (pylbl_amd/liblbl_amd.so), and
+include/lbl_amd_scatterer.h, include/lbl_amd_thermal_radiance.h and
+include/lbl_amd_solar_radiance.h (pylbl_amd/liblbl_amd.so), and
 nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
@@ -257,6 +258,15 @@ THERMAL_RADIANCE_PROTOTYPES = {
     "lbl_path_thermal_radiance": _BLOCK + [_i32] + _RUN + [_ptr, _f64] + [_ptr]*6 + [_i32] +
                                  [_ptr]*4 + [_i32],
 }
+# Every function of include/lbl_amd_solar_radiance.h, the header of the scattered-sunlight radiance
+# entry of the same library; each returns int.  tests/test_solar_radiance_host.py compares this
+# table with that header.
+SOLAR_RADIANCE_PROTOTYPES = {
+    # the run, level_table, solar_zenith_cosine, view_cosine, scattering_cosine, solar_row,
+    # rayleigh_row, albedo_rows, albedo, up_rows, direct_rows, diffuse_rows, n_bands, band_start,
+    # radiance_rows, radiance_mean, flags
+    "lbl_path_solar_radiance": _BLOCK + _RUN + [_ptr]*11 + [_i32] + [_ptr]*3 + [_i32],
+}
 
 _library = None
 
@@ -316,7 +326,8 @@ def library():
     for name, arguments in list(PROTOTYPES.items()) + list(TWO_STREAM_PROTOTYPES.items()) + \
             list(THERMAL_PROTOTYPES.items()) + list(THERMAL_SOURCE_PROTOTYPES.items()) + \
             list(KDIST_PROTOTYPES.items()) + list(SCATTERER_PROTOTYPES.items()) + \
-            list(THERMAL_RADIANCE_PROTOTYPES.items()):
+            list(THERMAL_RADIANCE_PROTOTYPES.items()) + \
+            list(SOLAR_RADIANCE_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

@@ -34,6 +34,7 @@
 #include "../../include/lbl_amd_kdist.h"
 #include "../../include/lbl_amd_scatterer.h"
 #include "../../include/lbl_amd_thermal_radiance.h"
+#include "../../include/lbl_amd_solar_radiance.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "band_sort_pairs.h"
@@ -53,6 +54,7 @@
 #include "twostream.h"
 #include "twostream_thermal.h"
 #include "thermal_radiance.h"
+#include "solar_radiance.h"
 
 #include "engine_core.h"
 #include "lanes_plans.inc"
@@ -511,6 +513,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "twostream_entry.inc"
 #include "thermal_entry.inc"
 #include "thermal_radiance_entry.inc"
+#include "solar_radiance_entry.inc"
 #include "band_sort_entry.inc"
 #include "band_sort_pairs_entry.inc"
 #include "instrument_entry.inc"

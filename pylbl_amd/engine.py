@@ -976,6 +976,39 @@ class Engine(object):
             _address(up_rows), _address(down_rows), n_bands, _address(starts),
             _address(radiance_rows), _address(brightness_rows), _address(radiance_mean), flags))
 
+    def path_solar_radiance(self, beta, columns, n_paths, levels_per_path, level_begin,
+                            level_table, solar_zenith_cosine, view_cosine, scattering_cosine,
+                            solar_row, up_rows, direct_rows, diffuse_rows, rayleigh_row=None,
+                            albedo=None, albedo_rows=None, band_start=None, from_last=False,
+                            asynchronous=False, radiance_rows=None, radiance_mean=None):
+        """The sunlight a viewer above the atmosphere sees scattered towards it through the whole
+        paths in the DeviceSpectra `beta`, from the two-stream fluxes path_two_stream left in
+        up_rows, direct_rows and diffuse_rows [>= rows, row length] (read only) --
+        lbl_path_solar_radiance.  Rows, columns, level_table, solar_zenith_cosine, solar_row,
+        rayleigh_row, albedo / albedo_rows, band_start, from_last and asynchronous as for
+        path_two_stream; view_cosine one per path, in (0, 1]; scattering_cosine one per path, in
+        [-1, 1].  Outputs (DeviceSpectra): radiance_rows [n_paths, row length], and with
+        band_start radiance_mean [n_paths, bands]."""
+        rows, stride, table, starts, n_bands, flags = _whole_paths(
+            beta, level_table, n_paths, albedo_rows, "albedo_rows", band_start, level_begin,
+            levels_per_path, from_last, asynchronous)
+        if solar_row.shape[1] < int(columns) or \
+                (rayleigh_row is not None and rayleigh_row.shape[1] < int(columns)):
+            raise ValueError(f"solar_row and rayleigh_row need {columns} values.")
+        mu0, mu, cos_theta, albedo = _per_path(
+            n_paths, "one solar cosine, one view cosine, one scattering cosine and one albedo "
+            "per path.", solar_zenith_cosine, view_cosine, scattering_cosine, albedo)
+        _check_outputs((up_rows, direct_rows, diffuse_rows), rows, stride)
+        _check_outputs((radiance_rows,), int(n_paths), stride)
+        _check_outputs((radiance_mean,), int(n_paths), n_bands)
+        self._check(self.lib.lbl_path_solar_radiance(
+            self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
+            int(level_begin), rows, table.ctypes.data, _address(mu0), _address(mu),
+            _address(cos_theta), solar_row.pointer, _address(rayleigh_row),
+            _address(albedo_rows), _address(albedo), _address(up_rows), _address(direct_rows),
+            _address(diffuse_rows), n_bands, _address(starts), _address(radiance_rows),
+            _address(radiance_mean), flags))
+
     def continuum_compute_many(self, continua, grid, n, temperature, pressure, vmr, out,
                                accumulate=False, asynchronous=False):
         """Several continua in one pass over the grid (lbl_continuum_compute_many): summed, in

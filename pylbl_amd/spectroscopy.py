@@ -1187,6 +1187,102 @@ class Spectroscopy(object):
             instrument, range_policy)
         return two_stream.thermal_radiance(self, request, remove_pedestal, range_policy)
 
+    def compute_solar_radiance(self, layer_thickness, solar_zenith_cosine, view_zenith_cosine=1.,
+                               relative_azimuth=180., solar_irradiance=None,
+                               solar_wavenumber=None, distance_factor=1., surface="first",
+                               surface_albedo=0., albedo_wavenumber=None, rayleigh=True,
+                               rayleigh_cross_section=None, scatterer_optical_depth=None,
+                               scatterer_single_scattering_albedo=None,
+                               scatterer_asymmetry=None, quantities=("radiance",),
+                               band_edges=None, instrument=None, remove_pedestal=None,
+                               range_policy="reference"):
+        """Sunlight scattered to a sensor: the radiance a viewer above the atmosphere sees along
+        the zenith cosine mu and the relative azimuth phi of each path, in an atmosphere that
+        absorbs, scatters by Rayleigh's law and holds one grey scatterer per level, over a
+        Lambertian surface, by the two-stream source-function technique (Toon et al. 1989):
+        compute_solar_flux's two-stream fluxes are the source of multiply scattered light, the
+        singly scattered direct beam is treated with the true phase functions (the TMS
+        correction of Nakajima & Tanaka 1988), and the transfer equation is integrated exactly
+        along the viewing direction, on the GPU, in one more sweep behind the two of
+        compute_solar_flux.  The scattering counterpart of compute_solar's
+        "reflected_radiance"; thermal emission is not included: compute_thermal_radiance's
+        result superposes.
+
+        Paths, levels, `surface`, layer_thickness, the level row (s_l, c_l, tau_c, w_c, h_c),
+        sigma(nu), A, F0 = mu0*S and the layer scalars tau, tau_s, omega, g, f, sc, t, w, gp, g1,
+        g2, g3, g4, a1, a2, k2, the conservative criterion and, in the general branch, k, the
+        cosine m that the guard around k*mu0 = 1 may have moved, x = k*m, Dm = exp(-t/m) and E are
+        compute_solar_flux's, bit for bit (m = mu0 in the conservative branch).  Inside the guard
+        the level uses m for the beam, as the flux rows do.  up[i], diffuse[i] and direct[i] are
+        its fluxes at interface i: level i lies between interfaces i (space side) and i + 1,
+        interface 0 faces space, direct[0] = F0 and diffuse[0] = 0.  The host forms, in float64,
+            cosT = -mu*mu0 + (sqrt((1 - mu)*(1 + mu))*sqrt((1 - mu0)*(1 + mu0)))*cos(phi*pi/180)
+        limited to [-1, 1].  With tau' in [0, t] measured from the level's space-side face and
+        S_i = direct[i]:
+            Dv = exp(-t/mu) ; a = (3*(gp*mu))/2
+            beam       B(tau') = S_i*exp(-tau'/m)
+            diffuse    F+(tau'), F-(tau'): the two-stream solution in the level (below)
+            source     J(tau') = (w/(2 pi))*[F+(tau')(1 + a) + F-(tau')(1 - a)]
+                               + ((omega/sc)*Pmix/(4 pi))*(S_i/m)*exp(-tau'/m)
+            Pmix = (tau_R*PR + w_c*PH)/tau_s ;  PR = (3/4)(1 + cosT^2)
+            PH = (1 - gc^2)/(1 + gc^2 - 2 gc cosT)^(3/2),  gc = h_c/w_c  (0 where w_c == 0)
+            transfer   I_top = I_bot*Dv + Integral_0^t J(tau') exp(-tau'/mu) dtau'/mu
+        F+- solve the Meador-Weaver equations
+            dF+/dtau' = g1 F+ - g2 F- - w g3 (B/m) ;  dF-/dtau' = g2 F+ - g1 F- + w g4 (B/m)
+        whose particular solution Z+- exp(-tau'/m) has, with X = (1 - x)*(1 + x) (X = 1,
+        conservative), each product, sum and quotient rounded as written:
+            ws = w*S_i ; Z+ = (ws*(g3 - a2*m))/X ; Z- = -((ws*(g4 + a1*m))/X)
+            u1 = up[i+1] - Z+*Dm ; d0 = diffuse[i] - Z-
+            bm = (m/(m + mu))*(-expm1(-(t/m + t/mu)))
+            I_top = I_bot*Dv + (w/(2 pi))*C + (((omega/sc)*Pmix)/(4 pi))*((S_i/m)*bm)
+            general:
+              Gamma = g2/(g1 + k) ; n = 1 - (Gamma*E)*(Gamma*E)
+              P = (u1 - (Gamma*E)*d0)/n ; Q = (d0 - (Gamma*E)*u1)/n
+              C = P*((1 + a) + Gamma*(1 - a))*h + Q*(Gamma*(1 + a) + (1 - a))*((1 - E*Dv)/(1 + k*mu))
+                  + (Z+*(1 + a) + Z-*(1 - a))*bm
+              h = (E - Dv)/(1 - k mu), formed without its pole and without overflow:
+                y = ((1 - k*mu)*t)/mu ; phi(z) = -expm1(-z)/z for z > 0, phi(0) = 1
+                h = E*((t/mu)*phi(y)) for y >= 0 ; h = Dv*((t/mu)*phi(-y)) for y < 0
+            conservative:
+              x = g1*t ; N = (u1 - d0)/(1 + x) ; Ev = -expm1(-t/mu)
+              C = ((u1 + d0) - x*N + a*N)*Ev + (2*(g1*N))*(mu*W) + (Z+*(1 + a) + Z-*(1 - a))*bm
+              W = Ev - (t/mu)*Dv, formed without its cancellation as
+                W = (t/mu)*(Ev - linear_weight(t/mu, Ev))
+        A level with tau == 0 is the identity; one with tau_s == 0 only attenuates, I_top =
+        I_bot*exp(-tau/mu).  The surface is Lambertian: I_L = A*((direct[L] + diffuse[L])/pi); the
+        result is I at interface 0.  The diffuse field is two-stream: against a multi-stream code
+        radiances are good to several per cent; the single scattering is exact.  The scatterers
+        are grey, the view is upward from above the atmosphere with one direction per path.
+
+        Args:
+            layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
+            distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
+            rayleigh_cross_section, scatterer_optical_depth,
+            scatterer_single_scattering_albedo, scatterer_asymmetry: as in compute_solar_flux.
+            view_zenith_cosine: mu in (0, 1]: a scalar or one per path.
+            relative_azimuth: phi [degrees], finite: a scalar or one per path; the angle between
+                         the horizontal directions of propagation of the sunlight and of the
+                         viewed light: 180 is the backscatter side, with the Sun behind the
+                         sensor.
+            quantities: "radiance".
+            band_edges, instrument: as in compute_thermal_radiance: band means of the radiance,
+                         or channel radiances, formed on the GPU.
+
+        Returns:
+            Like compute_radiance: "radiance" ("W m-2 sr-1 (cm-1)-1") with the atmosphere's dims
+            without the last, then "wavenumber", "band" or "channel".
+        Raises ValueError, before the GPU is touched, like compute_solar_flux and
+        compute_thermal_radiance, and where the blocks of one path (beta, two work blocks and the
+        three flux blocks) exceed device_output_limit: a run holds whole paths.
+        """
+        request = two_stream._solar_radiance_request(
+            self, layer_thickness, solar_zenith_cosine, view_zenith_cosine, relative_azimuth,
+            solar_irradiance, solar_wavenumber, distance_factor, surface, surface_albedo,
+            albedo_wavenumber, rayleigh, rayleigh_cross_section, scatterer_optical_depth,
+            scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
+            instrument, range_policy)
+        return two_stream.solar_radiance(self, request, remove_pedestal, range_policy)
+
     def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
                               quantities=("absorption_g_mean",), remove_pedestal=None,
                               range_policy="reference", weighting=None,
@@ -1365,6 +1461,7 @@ class Spectroscopy(object):
     _thermal_flux_request = two_stream._thermal_flux_request
     _thermal_flux_linear_request = two_stream._thermal_flux_linear_request
     _thermal_radiance_request = two_stream._thermal_radiance_request
+    _solar_radiance_request = two_stream._solar_radiance_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset
 

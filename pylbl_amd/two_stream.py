@@ -1,9 +1,10 @@
 """The two-stream products of Spectroscopy -- compute_solar_flux, compute_solar_flux_spectral,
-compute_thermal_flux, compute_thermal_flux_linear, compute_thermal_flux_spectral and
-compute_thermal_radiance -- on the host: their requests (every argument checked before anything
-touches the GPU), their sweeps and their results.  The functions take the Spectroscopy first;
-the public methods with the definitions are in spectroscopy.py, the run loop, the helpers every
-path product shares and the public constants in paths.py, which does not import this module.
+compute_thermal_flux, compute_thermal_flux_linear, compute_thermal_flux_spectral,
+compute_thermal_radiance and compute_solar_radiance -- on the host: their requests (every
+argument checked before anything touches the GPU), their sweeps and their results.  The functions
+take the Spectroscopy first; the public methods with the definitions are in spectroscopy.py, the
+run loop, the helpers every path product shares and the public constants in paths.py, which does
+not import this module.
 
 One frame serves the sweeps.  A call holds whole paths per run (paths._sweep_runs with
 whole_paths), in the Sun's order from space to the surface; its rows that do not depend on the
@@ -12,7 +13,8 @@ run -- S, sigma, a spectral surface -- are blocks filled once before the first s
 outputs receive the means (paths._Rows).  _flux_sweep is that frame for the two flux products:
 what a product supplies is the blocks it takes, its fills, and which entry it calls with which
 tables (solar_flux, thermal_flux).  thermal_radiance is the same frame with one more entry
-behind the flux entry and compute_radiance's result.
+behind the flux entry and compute_radiance's result, and solar_radiance is that again on the
+shortwave flux entry.
 """
 from collections import namedtuple
 
@@ -55,6 +57,13 @@ _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
 # None) with mu, the viewing zenith cosine of every path; its quantities are RADIANCE_QUANTITIES.
 _ThermalRadianceRequest = namedtuple("_ThermalRadianceRequest",
                                      _ThermalFluxRequest._fields + ("mu",))
+
+# compute_solar_radiance's: _SolarFluxRequest's (the scatterer knots stay None) with mu, the viewing
+# zenith cosine, and cos_theta, the cosine of the scattering angle, of every path; its quantity is
+# "radiance".
+_SolarRadianceRequest = namedtuple("_SolarRadianceRequest",
+                                   _SolarFluxRequest._fields + ("mu", "cos_theta"))
+SOLAR_RADIANCE_QUANTITIES = RADIANCE_QUANTITIES[:1]
 
 # What the entries call the rows of a quantity, and of what the sweep writes at interface 0
 # beside it ("top_" + quantity: a per-path output of the pass).
@@ -304,6 +313,41 @@ def _thermal_radiance_request(spec, layer_thickness, surface_temperature, view_z
                                                   starts=starts, instrument=instrument), mu=mu)
 
 
+def _solar_radiance_request(spec, layer_thickness, solar_zenith_cosine, view_zenith_cosine,
+                            relative_azimuth, solar_irradiance, solar_wavenumber, distance_factor,
+                            surface, surface_albedo, albedo_wavenumber, rayleigh,
+                            rayleigh_cross_section, scatterer_optical_depth,
+                            scatterer_single_scattering_albedo, scatterer_asymmetry, quantities,
+                            band_edges, instrument, range_policy):
+    """Checks every argument of compute_solar_radiance: compute_solar_flux's checks of the
+    atmosphere, the Sun, the surface, the Rayleigh row and the scatterer, the view, and
+    compute_thermal_radiance's rules for the bands and the instrument.  cos_theta is formed
+    here, in float64 and as written:
+        cosT = -mu*mu0 + (sqrt((1 - mu)*(1 + mu))*sqrt((1 - mu0)*(1 + mu0)))*cos(phi*pi/180)
+    limited to [-1, 1]."""
+    flux = _solar_flux_request(
+        spec, layer_thickness, solar_zenith_cosine, solar_irradiance, solar_wavenumber,
+        distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
+        rayleigh_cross_section, scatterer_optical_depth, scatterer_single_scattering_albedo,
+        scatterer_asymmetry, SOLAR_FLUX_INTERFACE_QUANTITIES[:1], None, range_policy,
+        caller="compute_solar_radiance")
+    mu = _per_path(view_zenith_cosine, "view_zenith_cosine", flux.shape)
+    if not np.all((mu > 0.) & (mu <= 1.)):
+        raise ValueError("view_zenith_cosine must lie in (0, 1].")
+    phi = _per_path(relative_azimuth, "relative_azimuth", flux.shape)
+    if not np.all(np.isfinite(phi)):
+        raise ValueError("relative_azimuth must be finite [degrees].")
+    mu0 = flux.mu0
+    cos_theta = -mu*mu0 + (np.sqrt((1. - mu)*(1. + mu))*np.sqrt((1. - mu0)*(1. + mu0))) * \
+        np.cos(phi*np.pi/180.)
+    cos_theta = np.ascontiguousarray(np.minimum(np.maximum(cos_theta, -1.), 1.))
+    quantities = _selection(quantities, SOLAR_RADIANCE_QUANTITIES)
+    edges, starts = _path_bands(spec, band_edges, instrument)
+    return _SolarRadianceRequest(*flux._replace(quantities=quantities, edges=edges,
+                                                starts=starts, instrument=instrument),
+                                 mu=mu, cos_theta=cos_theta)
+
+
 # ---------------------------------------------------------------------------------------------
 # The sweeps.
 def _flux_sweep(spec, request, remove_pedestal, range_policy, interface_quantities, product):
@@ -434,6 +478,46 @@ def thermal_radiance(spec, request, remove_pedestal, range_policy):
     values = spec._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
                               level_blocks=5, products=products, whole_paths=True)
     return _create_path_dataset(spec, _channel_brightness(values, request), request)
+
+
+def solar_radiance(spec, request, remove_pedestal, range_policy):
+    """The sweeps of compute_solar_radiance: the flux entry into three blocks of the call, and
+    the view entry behind it on the same run."""
+    bands = request.starts is not None
+    # From space to the surface: "first" has its surface at level 0.
+    step = _Pass(request.surface == "first", (), request.quantities)
+
+    def sweeper(call, run):
+        fills = _FilledOnce(call)
+        solar = fills.solar_row(request)
+        sigma = fills.rayleigh_row(request.rayleigh_values) if request.rayleigh else None
+        albedo_rows = fills.surface_rows(request.albedo_knots, request.albedo)
+        work = call.take(2*run)
+        up, direct, diffuse = call.take(run), call.take(run), call.take(run)
+        surface = dict(rayleigh_row=sigma, albedo_rows=albedo_rows,
+                       albedo=None if albedo_rows is not None else request.albedo,
+                       from_last=step.from_last, asynchronous=True)
+        # With bands the radiance on the grid is a block of this call, the output its means.
+        rows = _Rows(call, step, run, bands)
+
+        def sweep(index, beta, a, b, outputs):
+            fills.queue()
+            fluxes = dict(up_rows=_first_rows(up, b - a), direct_rows=_first_rows(direct, b - a),
+                          diffuse_rows=_first_rows(diffuse, b - a))
+            call.engine.path_two_stream(
+                beta, call.columns, call.paths, call.per_path, a, request.level_table[a:b],
+                request.mu0, solar, _first_rows(work, 2*(b - a)), **surface, **fluxes)
+            call.engine.path_solar_radiance(
+                beta, call.columns, call.paths, call.per_path, a, request.level_table[a:b],
+                request.mu0, request.mu, request.cos_theta, solar, band_start=request.starts,
+                **surface, **fluxes, **rows.keywords(_RADIANCE_ROWS, outputs, b - a))
+        return sweep
+    products = None if request.instrument is None else \
+        [_Product(q, q, False) for q in request.quantities]
+    # Six blocks per level: beta, the two work rows and the three flux rows.
+    values = spec._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
+                              level_blocks=6, products=products, whole_paths=True)
+    return _create_path_dataset(spec, values, request)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@
 # thermal_down_kernel, vector and scalar rows, each with the source of the level temperatures
 # (Lb0E as the second template argument) and with the linear-in-tau one (Lb1E); the last template
 # argument of the two-stream kernels is Lb1E with the spectral scatterer and Lb0E with the grey one;
-# "thermal_radiance" thermal_view_kernel of lbl_path_thermal_radiance alone, vector and scalar rows).
+# "thermal_radiance" thermal_view_kernel of lbl_path_thermal_radiance alone, vector and scalar rows;
+# "solar_radiance" solar_view_kernel of lbl_path_solar_radiance likewise).
 # Also prints the md5 of the device code's .text: unchanged by edits that only move host code.
 set -e
 LIB=${LIB:-pylbl_amd/liblbl_amd.so}
@@ -21,7 +22,8 @@ $LLVM/llvm-readelf --notes $TMP/co | python3 -c "
 import re, sys
 text = sys.stdin.read()
 pattern = sys.argv[1] if len(sys.argv) > 1 else ''
-pattern = {'thermal_radiance': 'thermal_view_kernel'}.get(pattern, pattern)
+pattern = {'thermal_radiance': 'thermal_view_kernel',
+           'solar_radiance': 'solar_view_kernel'}.get(pattern, pattern)
 for block in text.split('- .agpr_count')[1:]:
     name = re.search(r'\.name:\s+(\S+)', block)
     if not name or pattern not in name.group(1):
