@@ -180,8 +180,10 @@ def _clamp(x, lo, hi):
     return min(max(x, lo), hi)
 
 
-def schedule_tile(case, tiling, farfield, nu, lv, tile, shift=True):
-    """TileSchedule of tile_schedule.h, by the same keys and clamps."""
+def schedule_keys(case, tiling, lv, tile, shift=True):
+    """(s, keys) of a tile: its bounds, centre and radius, and the eight (key, above) pairs
+    schedule_tile searches for, in the order of TileSchedule (lo a1 c1 c2 a2 hi f1 f2).  `above`:
+    the first index with nu > key, else with nu >= key."""
     i0, i1 = tile_bounds(tiling, tile, case.npv, case.n)
     smax = lv.shift_max if shift else 0.
     npv, v0, cut = case.npv, case.v0, case.cut_off
@@ -191,17 +193,17 @@ def schedule_tile(case, tiling, farfield, nu, lv, tile, shift=True):
     full_hi = float(i0//npv + v0 + cut)
     v_lo, v_hi = float(wavenumber(case, i0)), float(wavenumber(case, i1))
     u0, radius, core, half, side = far_radius(lv, v_lo, v_hi, shift)
-    below = lambda key: int(np.searchsorted(nu, key, "left"))       # first nu >= key
-    above = lambda key: int(np.searchsorted(nu, key, "right"))      # first nu > key
     s = SimpleNamespace(i0=i0, i1=i1, v_lo=v_lo, v_hi=v_hi, u0=u0, radius=radius, side=side,
                         half=half, core=core)
-    s.lo = below(any_lo - smax)
-    s.a1 = below(full_lo + smax)
-    s.c1 = below(v_lo - core)
-    s.c2 = above(v_hi + core)
-    s.a2 = below(full_hi + 1. - smax)
-    s.hi = below(any_hi + 1. + smax)
-    f1, f2 = above(u0 - radius - smax), below(u0 + radius + smax)
+    keys = ((any_lo - smax, False), (full_lo + smax, False), (v_lo - core, False),
+            (v_hi + core, True), (full_hi + 1. - smax, False), (any_hi + 1. + smax, False),
+            (u0 - radius - smax, True), (u0 + radius + smax, False))
+    return s, keys
+
+
+def clamp_schedule(s, found, farfield):
+    """The clamps of schedule_tile on the eight indices found for schedule_keys, into s."""
+    s.lo, s.a1, s.c1, s.c2, s.a2, s.hi, f1, f2 = found
     if s.hi < s.lo:
         s.hi = s.lo
     s.a1 = _clamp(s.a1, s.lo, s.hi)
@@ -213,6 +215,13 @@ def schedule_tile(case, tiling, farfield, nu, lv, tile, shift=True):
         s.f1 = _clamp(f1, s.a1, s.c1)
         s.f2 = _clamp(f2, s.c2, s.a2)
     return s
+
+
+def schedule_tile(case, tiling, farfield, nu, lv, tile, shift=True):
+    """TileSchedule of tile_schedule.h, by the same keys and clamps."""
+    s, keys = schedule_keys(case, tiling, lv, tile, shift)
+    found = [int(np.searchsorted(nu, key, "right" if above else "left")) for key, above in keys]
+    return clamp_schedule(s, found, farfield)
 
 
 def partition(case, table, temperature, pressure, mutation=None):

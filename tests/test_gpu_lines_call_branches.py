@@ -22,6 +22,9 @@ Where the other branches of compute() (csrc/compute_call.inc) are reached:
   inline / copied levels (kInlineLevels 4)  test_gpu_fuzz_delivery (1-5 levels); test_gpu_api:
                                             test_level_chunking_and_strides (7 levels, then fewer
                                             per pass)
+  the schedule's bracketed table searches   test_gpu_schedule_search (every cell scale, no cell
+                                            table, keys off either end of it, empty cells; both
+                                            prologues, inline and copied levels)
   blocking calls of several threads         test_gpu_threads
   overlap_pedestal = 0                      here
   fill_level failing in a later pass        here (in the first pass: test_gpu_api:
