@@ -203,7 +203,6 @@ int lbl_continuum_compute_many(lbl_engine * engine, int32_t n_continua,
             "lbl_continuum_compute_many: bad argument (the output is a device block: "
             "LBL_OUT_DEVICE).");
         if (status != LBL_OK || n_levels == 0) return status;
-        if (n_levels > 65535) return fail(engine, LBL_BAD_ARGUMENT, "more than 65535 levels.");
         std::vector<ContinuumSet *> sets;
         int total_bands = 0;
         for (int m = 0; m < n_continua; ++m)
@@ -259,49 +258,60 @@ int lbl_continuum_compute_many(lbl_engine * engine, int32_t n_continua,
             engine->groups.push_back(std::move(fresh));
             group = engine->groups.back().get();
         }
+        // Up to 65535 levels at a time, like the one-slot calls (SlotCall::run): the levels are a
+        // launch dimension of both kernels.  Chunk after chunk on one stream, through the same
+        // level block and coarse spectra.
         // (waits first: the previous call's copy may still read the pinned level block)
-        ContinuumLevel * staged = group->pinned.refill((size_t)n_continua*n_levels);
-        group->levels.reserve((size_t)n_continua*n_levels);
-        group->coarse.reserve((size_t)n_levels*group->level_points);
-        group->slopes.reserve((size_t)n_levels*group->level_points);
-        for (int m = 0; m < n_continua; ++m)
+        const long long chunk = std::min<long long>(n_levels, 65535);
+        ContinuumLevel * staged = group->pinned.refill((size_t)(n_continua*chunk));
+        group->levels.reserve((size_t)(n_continua*chunk));
+        group->coarse.reserve((size_t)(chunk*group->level_points));
+        group->slopes.reserve((size_t)(chunk*group->level_points));
+        for (long long base = 0; base < n_levels; base += chunk)
         {
-            for (int l = 0; l < n_levels; ++l)
+            const int count = (int)std::min<long long>(chunk, n_levels - base);
+            for (int m = 0; m < n_continua; ++m)
             {
-                // vmr: [continuum][level][LBL_VMR_COUNT] -- LBL_VMR_SELF differs between them
-                staged[(size_t)m*n_levels + l] = continuum_level(
-                    temperature[l], pressure[l]*0.01,
-                    vmr + ((size_t)m*n_levels + l)*LBL_VMR_COUNT);      // utils.py:13,172
+                for (int l = 0; l < count; ++l)
+                {
+                    // vmr: [continuum][level][LBL_VMR_COUNT] -- LBL_VMR_SELF differs between them
+                    staged[(size_t)m*count + l] = continuum_level(
+                        temperature[base + l], pressure[base + l]*0.01,
+                        vmr + ((size_t)m*n_levels + base + l)*LBL_VMR_COUNT);   // utils.py:13,172
+                }
             }
-        }
-        group->pinned.upload(group->levels.data, (size_t)n_continua*n_levels, stream);
-        engine->timed(kTimeBandSpectra, stream, [&] {
-            dim3 blocks((unsigned)((group->widest + 255)/256), (unsigned)group->n_bands,
-                        (unsigned)n_levels);
-            hipLaunchKernelGGL(group_band_spectra_kernel, blocks, dim3(256), 0, stream,
-                               group->bands.data, group->level_points, group->levels.data,
-                               n_levels, group->coarse.data, group->slopes.data);
-            HIP_TRY(hipGetLastError());
-        });
-        engine->timed(kTimeContinuum, stream, [&] {
-            // PT points x LV levels per thread.  Measured (round 5,
-            // profiles/r05_perf_continuum_group.txt): 4 x 1 for one level (23 us for three continua at
-            // 5 M points; 2 x 1: 29, 8 x 1: 28), 4 x 2 for batches; taking the bands two to four at a
-            // time (table values requested together) only cost registers.
-            const int pt = 4, lv = n_levels == 1 ? 1 : 2;
-            const long long per_block = 256*pt;
-            dim3 blocks((unsigned)((call.n + per_block - 1)/per_block),
-                        (unsigned)((n_levels + lv - 1)/lv));
+            group->pinned.upload(group->levels.data, (size_t)n_continua*count, stream);
+            engine->timed(kTimeBandSpectra, stream, [&] {
+                dim3 blocks((unsigned)((group->widest + 255)/256), (unsigned)group->n_bands,
+                            (unsigned)count);
+                hipLaunchKernelGGL(group_band_spectra_kernel, blocks, dim3(256), 0, stream,
+                                   group->bands.data, group->level_points, group->levels.data,
+                                   count, group->coarse.data, group->slopes.data);
+                HIP_TRY(hipGetLastError());
+            });
+            double * target = extinction + base*call.stride;
+            engine->timed(kTimeContinuum, stream, [&] {
+                // PT points x LV levels per thread.  Measured (round 5,
+                // profiles/r05_perf_continuum_group.txt): 4 x 1 for one level (23 us for three
+                // continua at 5 M points; 2 x 1: 29, 8 x 1: 28), 4 x 2 for batches; taking the
+                // bands two to four at a time (table values requested together) only cost
+                // registers.
+                const int pt = 4, lv = count == 1 ? 1 : 2;
+                const long long per_block = 256*pt;
+                dim3 blocks((unsigned)((call.n + per_block - 1)/per_block),
+                            (unsigned)((count + lv - 1)/lv));
 #define LBL_GROUP_INTERP(PT, LV)                                                             \
-            hipLaunchKernelGGL((group_interp_kernel<PT, LV>), blocks, dim3(256), 0,          \
-                               stream, group->bands.data, group->n_bands,                    \
-                               group->level_points, group->coarse.data, group->slopes.data,  \
-                               call.g->form(), call.n, n_levels, extinction, call.stride,    \
-                               call.add_into ? 1 : 0)
-            if (n_levels == 1) LBL_GROUP_INTERP(4, 1); else LBL_GROUP_INTERP(4, 2);
+                hipLaunchKernelGGL((group_interp_kernel<PT, LV>), blocks, dim3(256), 0,      \
+                                   stream, group->bands.data, group->n_bands,                \
+                                   group->level_points, group->coarse.data,                  \
+                                   group->slopes.data, call.g->form(), call.n, count,        \
+                                   target, call.stride, call.add_into ? 1 : 0)
+                if (count == 1) LBL_GROUP_INTERP(4, 1); else LBL_GROUP_INTERP(4, 2);
 #undef LBL_GROUP_INTERP
-            HIP_TRY(hipGetLastError());
-        });
+                HIP_TRY(hipGetLastError());
+            });
+            if (base + count < n_levels) group->pinned.wait();
+        }
         group->mark(stream);
         return call.close();
     });

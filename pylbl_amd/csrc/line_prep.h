@@ -101,6 +101,14 @@ __host__ __device__ inline void mark_empty(LineWing & w, LineCore & c)
     for (int i = 0; i < 10; ++i) c.pad[i] = 0;
 }
 
+// The index ranges of a line's core and inner regions are kept inside [kIndexFloor, kIndexCeiling]:
+// up to 2^30, one past the last point of the largest grid the entry takes (2^30 - 1 points), and
+// down to -1e9, so that `index - i0` (rows_meeting, accumulate_lines.h) fits an int for every
+// first point i0 of a tile.  (The ceiling was 1e9 once: on a grid of more than 1e9 points the
+// ranges of the lines beyond that index ended there, and their rows were summed as far wing.)
+constexpr double kIndexFloor = -1.e9;
+constexpr double kIndexCeiling = 1073741824.;
+
 // Grid indices that may fall inside |x| < xlim1, the inner regions of a line (w4 regions 2-3,
 // CPF12; voigt.c:98-186): conservative, with the margins of core_first / core_last above.
 __host__ __device__ inline void inner_index_range(double centre, double repwid, double xlim1,
@@ -109,10 +117,10 @@ __host__ __device__ inline void inner_index_range(double centre, double repwid, 
     const double near = (xlim1/repwid)*(1. + 1.e-9);
     double lo = floor((centre - near - (double)v0)*n_per_v) - 1.;
     double hi = floor((centre + near - (double)v0)*n_per_v) + 2.;
-    if (lo < -1.e9) lo = -1.e9;
-    if (hi > 1.e9) hi = 1.e9;
-    if (hi < -1.e9) hi = -1.e9;
-    if (lo > 1.e9) lo = 1.e9;
+    if (lo < kIndexFloor) lo = kIndexFloor;
+    if (hi > kIndexCeiling) hi = kIndexCeiling;
+    if (hi < kIndexFloor) hi = kIndexFloor;
+    if (lo > kIndexCeiling) lo = kIndexCeiling;
     first = (int)lo;
     last = (int)hi;
 }
@@ -311,10 +319,10 @@ __host__ __device__ inline int prepare_line(const LevelScalars & lv, const GridS
         const double reach = (xlim0/repwid)*(1. + 1.e-9);
         double lo = floor((centre - reach - (double)g.v0)*g.n_per_v) - 1.;
         double hi = floor((centre + reach - (double)g.v0)*g.n_per_v) + 2.;
-        if (lo < -1.e9) lo = -1.e9;
-        if (hi > 1.e9) hi = 1.e9;
-        if (hi < -1.e9) hi = -1.e9;
-        if (lo > 1.e9) lo = 1.e9;
+        if (lo < kIndexFloor) lo = kIndexFloor;
+        if (hi > kIndexCeiling) hi = kIndexCeiling;
+        if (hi < kIndexFloor) hi = kIndexFloor;
+        if (lo > kIndexCeiling) lo = kIndexCeiling;
         c.core_first = (int)lo;
         c.core_last = (int)hi;
         const double sure = (xlim0/repwid)*(1. - 1.e-9);

@@ -25,6 +25,12 @@ Where the other branches of compute() (csrc/compute_call.inc) are reached:
   the schedule's bracketed table searches   test_gpu_schedule_search (every cell scale, no cell
                                             table, keys off either end of it, empty cells; both
                                             prologues, inline and copied levels)
+  more than 65 535 levels                   test_gpu_many_levels (65 535, 65 536, 65 547 and 131 073
+                                            levels: gridDim.y == 65535, passes at base 65535 and
+                                            131070, every output route; the passes counted)
+  grids past 2^28 points                    test_gpu_many_levels: test_largest_grid (1 073 709 056
+                                            points, lines on the indices 0, 2^28, 2^29, 3 2^28 and
+                                            n - 1) and the refusal of 2^30
   blocking calls of several threads         test_gpu_threads
   overlap_pedestal = 0                      here
   fill_level failing in a later pass        here (in the first pass: test_gpu_api:

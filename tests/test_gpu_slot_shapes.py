@@ -346,20 +346,22 @@ def test_continuum_more_than_65535_levels(engine, continua, continuum_oracle):
     check_rows(got, expect, 7, compare)
 
 
-def test_group_of_65536_levels_is_refused(engine, continua, continuum_oracle):
+def test_group_of_65536_levels(engine, continua, continuum_oracle):
+    """The group call cuts its levels into runs of 65535 like SlotCall::run (it refused them
+    once): 65536 levels, the second run one level (group_interp_kernel<4, 1>), rows 0..6 against
+    the oracle and every row bit for bit against row r % 7; then the same group on seven levels."""
     from pylbl_amd import mt_ckd
-    from pylbl_amd.engine import DeviceSpectra, EngineError
+    from pylbl_amd.engine import DeviceSpectra
     grid = np.asarray([-15., 0., 2.5, 2200., 4500.])
     members = [continua["H2OForeign"], continua["H2OSelf"]]
     t7, p7, vmr7 = atmosphere(7)
     index = np.arange(65536) % 7
     block = DeviceSpectra(engine, 65536, grid.size)
     try:
-        with pytest.raises(EngineError) as error:
-            mt_ckd.spectra_levels_many(members, t7[index], p7[index],
-                                       {k: v[index] for k, v in vmr7.items()}, grid, block)
-        assert str(error.value) == "status 2: more than 65535 levels."
-        # the engine goes on: the same group, seven levels
+        mt_ckd.spectra_levels_many(members, t7[index], p7[index],
+                                   {k: np.ascontiguousarray(v[index]) for k, v in vmr7.items()},
+                                   grid, block)
+        many = block.to_host()
         rows = block.rows(7)
         mt_ckd.spectra_levels_many(members, t7, p7, vmr7, grid, rows)
         got = rows.to_host()
@@ -367,4 +369,7 @@ def test_group_of_65536_levels_is_refused(engine, continua, continuum_oracle):
         block.free()
     expect = sum(continuum_expect(continuum_oracle, o, t7, p7, vmr7, grid)
                  for o in ("H2OForeign", "H2OSelf"))
-    close(got, expect, "after the refused call", floor=1e-12)
+    close(got, expect, "the group on seven levels", floor=1e-12)
+    assert same_bits(many[:7], got)
+    check_rows(many, expect, 7, lambda rows, reference: close(rows, reference, "rows 0..6",
+                                                              floor=1e-12))

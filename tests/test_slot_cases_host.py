@@ -43,8 +43,10 @@ def test_mirrors_restate_the_headers():
         assert statement in continuum, statement
     assert "xsec_interp_kernel<4, 1>" in entry and "xsec_interp_kernel<2, 4>" in entry
     assert "if (count == 1) LBL_INTERP(4, 1); else LBL_INTERP(2, 4);" in entry
-    assert "if (n_levels == 1) LBL_GROUP_INTERP(4, 1); else LBL_GROUP_INTERP(4, 2);" in entry
+    # (per run of levels since the group call cuts them into runs of 65535 itself)
+    assert "if (count == 1) LBL_GROUP_INTERP(4, 1); else LBL_GROUP_INTERP(4, 2);" in entry
     assert "std::min<long long>(n_levels, 65535)" in slot
+    assert "const long long chunk = std::min<long long>(n_levels, 65535);" in entry
     assert [(i.points, i.run) for i in INSTANCES] == [(256*i.pt, 64*i.pt) for i in INSTANCES]
 
 
