@@ -35,6 +35,7 @@
 #include "../../include/lbl_amd_scatterer.h"
 #include "../../include/lbl_amd_thermal_radiance.h"
 #include "../../include/lbl_amd_solar_radiance.h"
+#include "../../include/lbl_amd_scatterer_radiance.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "band_sort_pairs.h"

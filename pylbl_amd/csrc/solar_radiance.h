@@ -71,6 +71,20 @@
 // the level and direct_rows and diffuse_rows of the next level towards space (F0 and 0 at the
 // path's last step), and it restates the layer scalars: two_stream_layer is not touched.  It
 // writes one row per path.
+//
+// kSpectral (lbl_path_solar_radiance_spectral; include/lbl_amd_scatterer_radiance.h): tau_c, w_c
+// and h_c of a level come per grid point from the scatterer's knot table (scatterer.h) in place of
+// the level row, as in twostream.h's spectral kernels and through the same scatterer_lane, so that
+// the view and the flux sweeps before it place every column among the knots identically.  Per
+// level and column the six knot values are loaded together ahead of the level's arithmetic; then
+// w_c = omega_c*tau_c, h_c = w_c*g_c, PH from gc = h_c/w_c -- from the products, as the grey kernel
+// forms it, so that a flat table gives its bits -- and the same solar_view_level.  gc: with g_c <=
+// 1 - 2^-53 and w_c a normal number, w_c*g_c lies at least half an ulp of w_c below w_c and rounds
+// below it, and the quotient of two doubles h_c < w_c rounds to at most 1 - 2^-53; a subnormal w_c
+// can give h_c == w_c, so gc is limited to 1 - 2^-53 (kSolarViewMaxAsymmetry), which changes no
+// value below it.  The wave-uniform short cut is taken where the call has no Rayleigh row and no
+// knot of the level scatters (the `scatters` word lbl_path_thermal_two_stream_spectral uses too).
+// Without kSpectral nothing of this is read or compiled.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -96,11 +110,41 @@ struct PathSolarView : PathTwoStream
     double * rad;               // [paths][stride]: I at interface 0
 };
 
+// lbl_path_solar_radiance_spectral's: PathTwoStreamSpectral's table and knots with the same view,
+// flux rows and output.
+struct PathSolarViewSpectral : PathTwoStreamSpectral
+{
+    const double * mu;
+    const double * cos_theta;
+    const double * up;
+    const double * direct;
+    const double * diffuse;
+    double * rad;
+    const double * scatters;    // [count]: 0 where every knot of flat level first + i has
+                                // omega_c*tau_c == 0, else 1
+};
+
+template <bool kSpectral>
+using SolarViewArguments = std::conditional_t<kSpectral, PathSolarViewSpectral, PathSolarView>;
+
+constexpr double kSolarViewMaxAsymmetry = 1. - 0x1p-53;     // the largest double below 1
+
 // PH of a level's scatterer at cosT (0 where the level holds none).
 __device__ __forceinline__ double solar_view_henyey(double w_c, double h_c, double cos_theta)
 {
     if (w_c == 0.) return 0.;
     const double gc = h_c/w_c;
+    const double den = (1. + gc*gc) - (2.*gc)*cos_theta;
+    return (1. - gc*gc)/(den*sqrt(den));
+}
+
+// kSpectral: the same of an element's interpolated scatterer, with gc kept below 1 (the head of
+// this file).
+__device__ __forceinline__ double solar_view_henyey_limited(double w_c, double h_c,
+                                                            double cos_theta)
+{
+    if (w_c == 0.) return 0.;
+    const double gc = fmin(h_c/w_c, kSolarViewMaxAsymmetry);
     const double den = (1. + gc*gc) - (2.*gc)*cos_theta;
     return (1. - gc*gc)/(den*sqrt(den));
 }
@@ -191,9 +235,10 @@ __device__ __forceinline__ double solar_view_level(double s, double c, double ta
 }
 
 // grid and kVector as for path_sweep_kernel; a.from_last is the order of this sweep, surface to
-// space.  Whole paths: every lane starts and finishes its path.
-template <bool kVector>
-__global__ __launch_bounds__(kPathThreads) void solar_view_kernel(PathSolarView a)
+// space.  Whole paths: every lane starts and finishes its path.  kSpectral: the scatterer comes
+// from its knot table (scatterer.h) in place of the level rows; without it nothing of that is read.
+template <bool kVector, bool kSpectral = false>
+__global__ __launch_bounds__(kPathThreads) void solar_view_kernel(SolarViewArguments<kSpectral> a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
@@ -221,9 +266,67 @@ __global__ __launch_bounds__(kPathThreads) void solar_view_kernel(PathSolarView 
         }
     }
 
+    ScattererLane knots;
+    if constexpr (kSpectral) knots = two_stream_knots<kVector>(a, l);
+
     path_levels<kSolarViewAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
                                                       long long at) {
         const double * row = level + (long long)(k*l.direction)*kTwoStreamLevelWords;
+        if constexpr (kSpectral)
+        {
+            const double s = row[0], c = row[1];
+            const int index = l.index0 + k*l.direction;
+            const int m = a.scatterer.n_knots;
+            const double * rows = scatterer_rows(a.scatterer, index);
+            if (a.sigma == nullptr && a.scatters[index] == 0.)
+            {
+#pragma unroll
+                for (int i = 0; i < kPathWidth; ++i)
+                {
+                    const double tau_c = scatterer_value(rows, knots.j[i], knots.u[i]);
+                    const double tau_a = s*b[i];
+                    const double tau = tau_a + tau_c;
+                    rad[i] = rad[i]*exp(-tau/mu);
+                }
+                return;
+            }
+            double tau_c[kPathWidth], omega_c[kPathWidth], g_c[kPathWidth];
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                tau_c[i] = scatterer_value(rows, knots.j[i], knots.u[i]);
+                omega_c[i] = scatterer_value(rows + m, knots.j[i], knots.u[i]);
+                g_c[i] = scatterer_value(rows + 2*m, knots.j[i], knots.u[i]);
+            }
+            // The grey branch's loads, restated: moved into a function that both branches
+            // call, they change the instructions of the grey instantiations.
+            double up1[kPathWidth], direct0[kPathWidth], diffuse0[kPathWidth];
+            path_load<kVector>(a.up + at, width, up1);
+            if (k + 1 < l.n)
+            {
+                path_load<kVector>(a.direct + (at + l.row_step), width, direct0);
+                path_load<kVector>(a.diffuse + (at + l.row_step), width, diffuse0);
+            }
+            else
+            {
+#pragma unroll
+                for (int i = 0; i < kPathWidth; ++i)
+                {
+                    direct0[i] = f0[i];
+                    diffuse0[i] = 0.;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                const double w_c = omega_c[i]*tau_c[i];
+                const double h_c = w_c*g_c[i];
+                const double ph = solar_view_henyey_limited(w_c, h_c, cos_theta);
+                rad[i] = solar_view_level(s, c, tau_c[i], w_c, h_c, mu0, mu, pr, ph, b[i],
+                                          sigma[i], up1[i], direct0[i], diffuse0[i], rad[i]);
+            }
+            return;
+        }
         const double s = row[0], c = row[1], tau_c = row[2], w_c = row[3], h_c = row[4];
         if (a.sigma == nullptr && w_c == 0.)
         {

@@ -2,23 +2,28 @@
 // one zenith cosine and one scattering angle per path, from the two-stream fluxes
 // lbl_path_two_stream left in HBM (kernel: solar_radiance.h; band means: path.h).  Included by
 // engine.hip after thermal_radiance_entry.inc; shares path_entry.inc's PathCall, TwoStreamCall,
-// PathTables and PathBands.
-extern "C" {
+// PathTables and PathBands.  lbl_path_solar_radiance_spectral
+// (include/lbl_amd_scatterer_radiance.h): the same from the fluxes of
+// lbl_path_two_stream_spectral on the grid `grid`, with twostream_entry.inc's ScattererTable.
+namespace {
 
-int lbl_path_solar_radiance(lbl_engine * engine, double * beta, int64_t row_stride,
-                            int64_t columns, int32_t n_paths, int32_t levels_per_path,
-                            int32_t level_begin, int32_t level_count, const double * level_table,
-                            const double * solar_zenith_cosine, const double * view_cosine,
-                            const double * scattering_cosine, const double * solar_row,
-                            const double * rayleigh_row, const double * albedo_rows,
-                            const double * albedo, const double * up_rows,
-                            const double * direct_rows, const double * diffuse_rows,
-                            int32_t n_bands, const int64_t * band_start, double * radiance_rows,
-                            double * radiance_mean, int32_t flags)
+// Both entries.  name: the entry's; spectral: the scatterer's knot table on the grid `grid`, or
+// null for the grey scatterer of the level table.
+int path_solar_radiance(lbl_engine * engine, const char * name, double * beta, int64_t row_stride,
+                        int64_t columns, int32_t n_paths, int32_t levels_per_path,
+                        int32_t level_begin, int32_t level_count, const double * level_table,
+                        int32_t grid, ScattererTable * spectral,
+                        const double * solar_zenith_cosine, const double * view_cosine,
+                        const double * scattering_cosine, const double * solar_row,
+                        const double * rayleigh_row, const double * albedo_rows,
+                        const double * albedo, const double * up_rows,
+                        const double * direct_rows, const double * diffuse_rows, int32_t n_bands,
+                        const int64_t * band_start, double * radiance_rows,
+                        double * radiance_mean, int32_t flags)
 {
     return path_entry(engine, flags, [&] {
-        PathCall call{engine, "lbl_path_solar_radiance", row_stride, columns, n_paths,
-                      levels_per_path, level_begin, level_count, flags};
+        PathCall call{engine, name, row_stride, columns, n_paths, levels_per_path, level_begin,
+                      level_count, flags};
         // One row per path.
         double * const rows[1] = {radiance_rows};
         double * const mean[1] = {radiance_mean};
@@ -57,6 +62,10 @@ int lbl_path_solar_radiance(lbl_engine * engine, double * beta, int64_t row_stri
         }
         if (radiance_rows == nullptr) return call.bad("no output requested.");
         if (radiance_mean != nullptr && n_bands == 0) return call.bad("band means need n_bands > 0.");
+        if (spectral != nullptr)
+        {
+            if (const char * problem = call.find_grid(grid)) return call.bad(problem);
+        }
         if (const char * problem = two.check_levels(level_table, kTwoStreamLevelWords))
         {
             return call.bad(problem);
@@ -95,6 +104,14 @@ int lbl_path_solar_radiance(lbl_engine * engine, double * beta, int64_t row_stri
         {
             return call.bad(problem);
         }
+        if (spectral != nullptr)
+        {
+            if (const char * problem = spectral->check(level_table, level_count,
+                                                       kTwoStreamLevelWords, 2))
+            {
+                return call.bad(problem);
+            }
+        }
 
         const PathRun & run = call.run;
         PathTables tables;
@@ -106,32 +123,44 @@ int lbl_path_solar_radiance(lbl_engine * engine, double * beta, int64_t row_stri
         const size_t mu_at = tables.add(run.paths, view_cosine + run.first_path);
         const size_t cos_at = tables.add(run.paths, scattering_cosine + run.first_path);
         tables.add(bands, band_start);
+        if (spectral != nullptr) spectral->stage(tables, level_count);
         const double * d_tables = call.begin(tables);
 
-        PathSolarView a;
-        call.fill(a, beta, nullptr);
-        a.level = d_tables + level_at;
-        a.mu0 = d_tables + mu0_at;
-        a.albedo = d_tables + albedo_at;
-        a.table_path = run.first_path;
-        a.solar = solar_row;
-        a.sigma = rayleigh_row;
-        a.albedo_rows = albedo_rows;
-        a.work = nullptr;
-        for (int q = 0; q < 4; ++q) a.level_out[q] = a.top_out[q] = nullptr;
-        a.mu = d_tables + mu_at;
-        a.cos_theta = d_tables + cos_at;
-        a.up = up_rows;
-        a.direct = direct_rows;
-        a.diffuse = diffuse_rows;
-        a.rad = radiance_rows;
+        const double * nu = spectral != nullptr ? call.grid->wavenumber.data : nullptr;
         const bool vector = path_vector(row_stride, {beta, solar_row, rayleigh_row, albedo_rows,
                                                      up_rows, direct_rows, diffuse_rows,
-                                                     radiance_rows});
-        // Surface -> space: against the order space -> surface, which is from_last() (the surface
-        // is level 0), as lbl_path_two_stream's up sweep.
-        a.from_last = call.from_last() ? 0 : 1;
-        two.sweep(a, vector, [](auto v) { return solar_view_kernel<decltype(v)::value>; });
+                                                     radiance_rows, nu});
+        dispatch([&](auto knots) {
+            constexpr bool kSpectral = decltype(knots)::value;
+            SolarViewArguments<kSpectral> a;
+            call.fill(a, beta, nullptr);
+            a.level = d_tables + level_at;
+            a.mu0 = d_tables + mu0_at;
+            a.albedo = d_tables + albedo_at;
+            a.table_path = run.first_path;
+            a.solar = solar_row;
+            a.sigma = rayleigh_row;
+            a.albedo_rows = albedo_rows;
+            a.work = nullptr;
+            for (int q = 0; q < 4; ++q) a.level_out[q] = a.top_out[q] = nullptr;
+            a.mu = d_tables + mu_at;
+            a.cos_theta = d_tables + cos_at;
+            a.up = up_rows;
+            a.direct = direct_rows;
+            a.diffuse = diffuse_rows;
+            a.rad = radiance_rows;
+            if constexpr (kSpectral)
+            {
+                a.scatterer = spectral->on_device(d_tables, nu);
+                a.scatters = d_tables + spectral->scatters_at;
+            }
+            // Surface -> space: against the order space -> surface, which is from_last() (the
+            // surface is level 0), as lbl_path_two_stream's up sweep.
+            a.from_last = call.from_last() ? 0 : 1;
+            two.sweep(a, vector, [](auto v) {
+                return solar_view_kernel<decltype(v)::value, kSpectral>;
+            });
+        }, spectral != nullptr);
         // beta and the flux rows are only read; they count as written, like beta in every path
         // entry, so that the next call that writes them waits for this sweep.
         call.note_rows(beta, level_count);
@@ -142,6 +171,47 @@ int lbl_path_solar_radiance(lbl_engine * engine, double * beta, int64_t row_stri
         call.means(bands, PathMeanRows::kStarted, radiance_rows, radiance_mean);
         return LBL_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int lbl_path_solar_radiance(lbl_engine * engine, double * beta, int64_t row_stride,
+                            int64_t columns, int32_t n_paths, int32_t levels_per_path,
+                            int32_t level_begin, int32_t level_count, const double * level_table,
+                            const double * solar_zenith_cosine, const double * view_cosine,
+                            const double * scattering_cosine, const double * solar_row,
+                            const double * rayleigh_row, const double * albedo_rows,
+                            const double * albedo, const double * up_rows,
+                            const double * direct_rows, const double * diffuse_rows,
+                            int32_t n_bands, const int64_t * band_start, double * radiance_rows,
+                            double * radiance_mean, int32_t flags)
+{
+    return path_solar_radiance(
+        engine, "lbl_path_solar_radiance", beta, row_stride, columns, n_paths, levels_per_path,
+        level_begin, level_count, level_table, 0, nullptr, solar_zenith_cosine, view_cosine,
+        scattering_cosine, solar_row, rayleigh_row, albedo_rows, albedo, up_rows, direct_rows,
+        diffuse_rows, n_bands, band_start, radiance_rows, radiance_mean, flags);
+}
+
+int lbl_path_solar_radiance_spectral(
+    lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns, int32_t n_paths,
+    int32_t levels_per_path, int32_t level_begin, int32_t level_count, const double * level_table,
+    int32_t grid, int32_t n_knots, const double * knot_wavenumber, const double * knot_optics,
+    const double * solar_zenith_cosine, const double * view_cosine,
+    const double * scattering_cosine, const double * solar_row, const double * rayleigh_row,
+    const double * albedo_rows, const double * albedo, const double * up_rows,
+    const double * direct_rows, const double * diffuse_rows, int32_t n_bands,
+    const int64_t * band_start, double * radiance_rows, double * radiance_mean, int32_t flags)
+{
+    ScattererTable spectral{n_knots, knot_wavenumber, knot_optics};
+    return path_solar_radiance(
+        engine, "lbl_path_solar_radiance_spectral", beta, row_stride, columns, n_paths,
+        levels_per_path, level_begin, level_count, level_table, grid, &spectral,
+        solar_zenith_cosine, view_cosine, scattering_cosine, solar_row, rayleigh_row, albedo_rows,
+        albedo, up_rows, direct_rows, diffuse_rows, n_bands, band_start, radiance_rows,
+        radiance_mean, flags);
 }
 
 }  // extern "C"

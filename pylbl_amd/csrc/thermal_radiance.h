@@ -49,6 +49,18 @@
 // space (0 at the path's last step), and it recomputes the layer scalars.  A clear level costs one
 // exp, one expm1 and the Planck function and reads no flux rows.  It writes one row per path, and
 // the brightness temperature beside it where asked.
+//
+// kSpectral (lbl_path_thermal_radiance_spectral; include/lbl_amd_scatterer_radiance.h): tau_c,
+// w_c and g_c of a level come per grid point from the scatterer's knot table (scatterer.h) in place
+// of the level row, as in twostream_thermal.h's spectral kernels and through the same
+// scatterer_lane, so that the view and the flux sweeps before it place every column among the
+// knots identically.  A level none of whose knots scatters (the `scatters` word of the flux entry)
+// is clear for the whole wavefront, with tau = s*beta + tau_c(nu), and reads no flux row.  In a
+// level that scatters every element takes thermal_view_cloudy with its own tau_c, w_c =
+// omega_c*tau_c, f = g_c*g_c, gp = g_c/(1 + g_c) and a = (3*(gp*mu))/2; an element whose tau is 0
+// takes the clear line (x = 0: the identity), as in the flux kernels.  The level's six knot values
+// per column are loaded together ahead of its arithmetic.  Without kSpectral nothing of this is
+// read or compiled.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -71,6 +83,20 @@ struct PathThermalView : PathThermal
     double * rad;               // [paths][stride]: I at interface 0, or null
     double * bt;                // [paths][stride]: its brightness temperature, or null
 };
+
+// lbl_path_thermal_radiance_spectral's: PathThermalSpectral's table and knots with the same view,
+// flux rows and outputs.
+struct PathThermalViewSpectral : PathThermalSpectral
+{
+    const double * mu;
+    const double * up;
+    const double * down;
+    double * rad;
+    double * bt;
+};
+
+template <bool kSpectral>
+using ThermalViewArguments = std::conditional_t<kSpectral, PathThermalViewSpectral, PathThermalView>;
 
 // phi(z) = -expm1(-z)/z for z > 0, 1 at z = 0.
 __device__ __forceinline__ double thermal_view_phi(double z)
@@ -129,9 +155,11 @@ __device__ __forceinline__ double thermal_view_cloudy(const ThermalLevel & v, do
 }
 
 // grid and kVector as for path_sweep_kernel; a.from_last is the order of this sweep, surface to
-// space.  Whole paths: every lane starts and finishes its path.
-template <bool kVector>
-__global__ __launch_bounds__(kPathThreads) void thermal_view_kernel(PathThermalView a)
+// space.  Whole paths: every lane starts and finishes its path.  kSpectral: the scatterer comes
+// from its knot table (scatterer.h) in place of the level rows; without it nothing of that is read.
+template <bool kVector, bool kSpectral = false>
+__global__ __launch_bounds__(kPathThreads) void thermal_view_kernel(
+    ThermalViewArguments<kSpectral> a)
 {
     const PathLane l = path_lane(a);
     if (l.idle) return;
@@ -167,8 +195,70 @@ __global__ __launch_bounds__(kPathThreads) void thermal_view_kernel(PathThermalV
         }
     }
 
+    ScattererLane knots;
+    if constexpr (kSpectral) knots = scatterer_lane(a.scatterer, c.nu);
+
     path_levels<kThermalViewAhead, kVector>(a, l, [&](int k, const double (&b)[kPathWidth],
                                                         long long at) {
+        if constexpr (kSpectral)
+        {
+            const int index = l.index0 + k*l.direction;
+            ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
+            const int m = a.scatterer.n_knots;
+            const double * rows = scatterer_rows(a.scatterer, index);
+            if (a.scatters[index] == 0.)
+            {
+#pragma unroll
+                for (int i = 0; i < kPathWidth; ++i)
+                {
+                    const double tau_c = scatterer_value(rows, knots.j[i], knots.u[i]);
+                    const double tau_a = v.s*b[i];
+                    const double tau = tau_a + tau_c;
+                    const double x = tau/mu;
+                    rad[i] = rad[i]*exp(-x) +
+                             planck(c.nu[i], c.c1nu3[i], c.c2nu[i], v.temperature)*(-expm1(-x));
+                }
+                return;
+            }
+            double tau_c[kPathWidth], omega_c[kPathWidth], g_c[kPathWidth];
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                tau_c[i] = scatterer_value(rows, knots.j[i], knots.u[i]);
+                omega_c[i] = scatterer_value(rows + m, knots.j[i], knots.u[i]);
+                g_c[i] = scatterer_value(rows + 2*m, knots.j[i], knots.u[i]);
+            }
+            // The grey branch's loads, restated: moved into a function that both branches
+            // call, they change the instructions of the grey instantiations.
+            double up1[kPathWidth], down0[kPathWidth];
+            path_load<kVector>(a.up + at, width, up1);
+            if (k + 1 < l.n)
+            {
+                path_load<kVector>(a.down + (at + l.row_step), width, down0);
+            }
+            else
+            {
+#pragma unroll
+                for (int i = 0; i < kPathWidth; ++i) down0[i] = 0.;
+            }
+#pragma unroll
+            for (int i = 0; i < kPathWidth; ++i)
+            {
+                v.tau_c = tau_c[i];
+                // tau == 0, where the cloudy line would form 0/0: the clear line at x = 0, which
+                // is rad*1 + B*0, the identity.
+                if (v.s*b[i] + v.tau_c == 0.) continue;
+                const double planck_b = planck(c.nu[i], c.c1nu3[i], c.c2nu[i], v.temperature);
+                v.w_c = omega_c[i]*tau_c[i];
+                v.f = g_c[i]*g_c[i];
+                v.gp = g_c[i]/(1. + g_c[i]);
+                const double view_a = (3.*(v.gp*mu))/2.;
+                rad[i] = thermal_view_cloudy(v, d, mu, view_a, b[i], planck_b,
+                                             thermal_pi_planck(c, i, v.temperature), up1[i],
+                                             down0[i], rad[i]);
+            }
+            return;
+        }
         const ThermalLevel v = thermal_level(level + (long long)(k*l.direction)*kThermalLevelWords);
         if (v.clear)
         {

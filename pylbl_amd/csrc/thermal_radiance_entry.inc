@@ -2,21 +2,26 @@
 // zenith cosine per path, from the two-stream fluxes lbl_path_thermal_two_stream left in HBM
 // (kernel: thermal_radiance.h; band means: path.h).  Included by engine.hip after
 // thermal_entry.inc; shares path_entry.inc's PathCall, TwoStreamCall, PathTables and PathBands.
-extern "C" {
+// lbl_path_thermal_radiance_spectral (include/lbl_amd_scatterer_radiance.h): the same from the
+// fluxes of lbl_path_thermal_two_stream_spectral, with twostream_entry.inc's ScattererTable.
+namespace {
 
-int lbl_path_thermal_radiance(lbl_engine * engine, double * beta, int64_t row_stride,
-                              int64_t columns, int32_t grid, int32_t n_paths,
-                              int32_t levels_per_path, int32_t level_begin, int32_t level_count,
-                              const double * level_table, double diffusivity,
-                              const double * view_cosine, const double * surface_temperature,
-                              const double * emissivity_rows, const double * emissivity,
-                              const double * up_rows, const double * down_rows, int32_t n_bands,
-                              const int64_t * band_start, double * radiance_rows,
-                              double * brightness_rows, double * radiance_mean, int32_t flags)
+// Both entries.  name: the entry's; spectral: the scatterer's knot table, or null for the grey
+// scatterer of the level table.
+int path_thermal_radiance(lbl_engine * engine, const char * name, double * beta,
+                          int64_t row_stride, int64_t columns, int32_t grid, int32_t n_paths,
+                          int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+                          const double * level_table, ScattererTable * spectral,
+                          double diffusivity, const double * view_cosine,
+                          const double * surface_temperature, const double * emissivity_rows,
+                          const double * emissivity, const double * up_rows,
+                          const double * down_rows, int32_t n_bands, const int64_t * band_start,
+                          double * radiance_rows, double * brightness_rows,
+                          double * radiance_mean, int32_t flags)
 {
     return path_entry(engine, flags, [&] {
-        PathCall call{engine, "lbl_path_thermal_radiance", row_stride, columns, n_paths,
-                      levels_per_path, level_begin, level_count, flags};
+        PathCall call{engine, name, row_stride, columns, n_paths, levels_per_path, level_begin,
+                      level_count, flags};
         // One row per path of each output; only the radiance has a band mean.
         double * const rows[2] = {radiance_rows, brightness_rows};
         double * const mean[2] = {radiance_mean, nullptr};
@@ -91,6 +96,14 @@ int lbl_path_thermal_radiance(lbl_engine * engine, double * beta, int64_t row_st
         {
             return call.bad(problem);
         }
+        if (spectral != nullptr)
+        {
+            if (const char * problem = spectral->check(level_table, level_count,
+                                                       kThermalLevelWords, 1))
+            {
+                return call.bad(problem);
+            }
+        }
 
         const PathRun & run = call.run;
         PathTables tables;
@@ -100,31 +113,43 @@ int lbl_path_thermal_radiance(lbl_engine * engine, double * beta, int64_t row_st
             tables.add(run.paths, emissivity != nullptr ? emissivity + run.first_path : nullptr);
         const size_t mu_at = tables.add(run.paths, view_cosine + run.first_path);
         tables.add(bands, band_start);
+        if (spectral != nullptr) spectral->stage(tables, level_count);
         const double * d_tables = call.begin(tables);
 
-        PathThermalView a;
-        call.fill(a, beta, nullptr);
-        a.nu = call.grid->wavenumber.data;
-        a.level = d_tables + level_at;
-        a.diffusivity = diffusivity;
-        a.surface_t = d_tables + ts_at;
-        a.surface_e = d_tables + eps_at;
-        a.table_path = run.first_path;
-        a.emissivity_rows = emissivity_rows;
-        a.work = nullptr;
-        a.edge = nullptr;
-        for (int q = 0; q < 2; ++q) a.level_out[q] = a.top_out[q] = nullptr;
-        a.mu = d_tables + mu_at;
-        a.up = up_rows;
-        a.down = down_rows;
-        a.rad = radiance_rows;
-        a.bt = brightness_rows;
-        const bool vector = path_vector(row_stride, {beta, a.nu, emissivity_rows, up_rows,
+        const double * nu = call.grid->wavenumber.data;
+        const bool vector = path_vector(row_stride, {beta, nu, emissivity_rows, up_rows,
                                                      down_rows, radiance_rows, brightness_rows});
-        // Surface -> space: against the order space -> surface, which is from_last() (the surface
-        // is level 0), as lbl_path_thermal_two_stream's up sweep.
-        a.from_last = call.from_last() ? 0 : 1;
-        two.sweep(a, vector, [](auto v) { return thermal_view_kernel<decltype(v)::value>; });
+        dispatch([&](auto knots) {
+            constexpr bool kSpectral = decltype(knots)::value;
+            ThermalViewArguments<kSpectral> a;
+            call.fill(a, beta, nullptr);
+            a.nu = nu;
+            a.level = d_tables + level_at;
+            a.diffusivity = diffusivity;
+            a.surface_t = d_tables + ts_at;
+            a.surface_e = d_tables + eps_at;
+            a.table_path = run.first_path;
+            a.emissivity_rows = emissivity_rows;
+            a.work = nullptr;
+            a.edge = nullptr;
+            for (int q = 0; q < 2; ++q) a.level_out[q] = a.top_out[q] = nullptr;
+            a.mu = d_tables + mu_at;
+            a.up = up_rows;
+            a.down = down_rows;
+            a.rad = radiance_rows;
+            a.bt = brightness_rows;
+            if constexpr (kSpectral)
+            {
+                a.scatterer = spectral->on_device(d_tables, nu);
+                a.scatters = d_tables + spectral->scatters_at;
+            }
+            // Surface -> space: against the order space -> surface, which is from_last() (the
+            // surface is level 0), as lbl_path_thermal_two_stream's up sweep.
+            a.from_last = call.from_last() ? 0 : 1;
+            two.sweep(a, vector, [](auto v) {
+                return thermal_view_kernel<decltype(v)::value, kSpectral>;
+            });
+        }, spectral != nullptr);
         // beta and the flux rows are only read; they count as written, like beta in every path
         // entry, so that the next call that writes them waits for this sweep.
         call.note_rows(beta, level_count);
@@ -135,6 +160,45 @@ int lbl_path_thermal_radiance(lbl_engine * engine, double * beta, int64_t row_st
         call.means(bands, PathMeanRows::kStarted, radiance_rows, radiance_mean);
         return LBL_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int lbl_path_thermal_radiance(lbl_engine * engine, double * beta, int64_t row_stride,
+                              int64_t columns, int32_t grid, int32_t n_paths,
+                              int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+                              const double * level_table, double diffusivity,
+                              const double * view_cosine, const double * surface_temperature,
+                              const double * emissivity_rows, const double * emissivity,
+                              const double * up_rows, const double * down_rows, int32_t n_bands,
+                              const int64_t * band_start, double * radiance_rows,
+                              double * brightness_rows, double * radiance_mean, int32_t flags)
+{
+    return path_thermal_radiance(
+        engine, "lbl_path_thermal_radiance", beta, row_stride, columns, grid, n_paths,
+        levels_per_path, level_begin, level_count, level_table, nullptr, diffusivity, view_cosine,
+        surface_temperature, emissivity_rows, emissivity, up_rows, down_rows, n_bands, band_start,
+        radiance_rows, brightness_rows, radiance_mean, flags);
+}
+
+int lbl_path_thermal_radiance_spectral(
+    lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns, int32_t grid,
+    int32_t n_paths, int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+    const double * level_table, int32_t n_knots, const double * knot_wavenumber,
+    const double * knot_optics, double diffusivity, const double * view_cosine,
+    const double * surface_temperature, const double * emissivity_rows, const double * emissivity,
+    const double * up_rows, const double * down_rows, int32_t n_bands,
+    const int64_t * band_start, double * radiance_rows, double * brightness_rows,
+    double * radiance_mean, int32_t flags)
+{
+    ScattererTable spectral{n_knots, knot_wavenumber, knot_optics};
+    return path_thermal_radiance(
+        engine, "lbl_path_thermal_radiance_spectral", beta, row_stride, columns, grid, n_paths,
+        levels_per_path, level_begin, level_count, level_table, &spectral, diffusivity,
+        view_cosine, surface_temperature, emissivity_rows, emissivity, up_rows, down_rows,
+        n_bands, band_start, radiance_rows, brightness_rows, radiance_mean, flags);
 }
 
 }  // extern "C"

@@ -960,6 +960,39 @@ class Engine(object):
         view_cosine one per path, in (0, 1].  Outputs (DeviceSpectra, None: not wanted):
         radiance_rows and brightness_rows [n_paths, row length], and with band_start
         radiance_mean [n_paths, bands]."""
+        self._path_thermal_radiance(
+            "path_thermal_radiance", beta, columns, grid, n_paths, levels_per_path, level_begin,
+            level_table, None, view_cosine, surface_temperature, up_rows, down_rows, diffusivity,
+            emissivity, emissivity_rows, band_start, from_last, asynchronous, radiance_rows,
+            brightness_rows, radiance_mean)
+
+    def path_thermal_radiance_spectral(self, beta, columns, grid, n_paths, levels_per_path,
+                                       level_begin, level_table, knot_wavenumber, knot_optics,
+                                       view_cosine, surface_temperature, up_rows, down_rows,
+                                       diffusivity=1.66, emissivity=None, emissivity_rows=None,
+                                       band_start=None, from_last=False, asynchronous=False,
+                                       radiance_rows=None, brightness_rows=None,
+                                       radiance_mean=None):
+        """path_thermal_radiance with the scatterer of every level as a table over wavenumber,
+        from the fluxes path_thermal_two_stream_spectral left in up_rows and down_rows --
+        lbl_path_thermal_radiance_spectral.  knot_wavenumber [M] and knot_optics [rows, M, 3] as
+        for path_thermal_two_stream_spectral; tau_c, w_c and g_c of level_table are 0;
+        everything else as for path_thermal_radiance."""
+        self._path_thermal_radiance(
+            "path_thermal_radiance_spectral", beta, columns, grid, n_paths, levels_per_path,
+            level_begin, level_table, _knot_table(knot_wavenumber, knot_optics,
+                                                  int(beta.shape[0])),
+            view_cosine, surface_temperature, up_rows, down_rows, diffusivity, emissivity,
+            emissivity_rows, band_start, from_last, asynchronous, radiance_rows, brightness_rows,
+            radiance_mean)
+
+    def _path_thermal_radiance(self, name, beta, columns, grid, n_paths, levels_per_path,
+                               level_begin, level_table, spectral, view_cosine,
+                               surface_temperature, up_rows, down_rows, diffusivity, emissivity,
+                               emissivity_rows, band_start, from_last, asynchronous,
+                               radiance_rows, brightness_rows, radiance_mean):
+        """The call of path_thermal_radiance (spectral None) and of
+        path_thermal_radiance_spectral (spectral: knots, optics, M): lbl_<name>."""
         rows, stride, table, starts, n_bands, flags = _whole_paths(
             beta, level_table, n_paths, emissivity_rows, "emissivity_rows", band_start,
             level_begin, levels_per_path, from_last, asynchronous)
@@ -969,9 +1002,14 @@ class Engine(object):
         _check_outputs((up_rows, down_rows), rows, stride)
         _check_outputs((radiance_rows, brightness_rows), int(n_paths), stride)
         _check_outputs((radiance_mean,), int(n_paths), n_bands)
-        self._check(self.lib.lbl_path_thermal_radiance(
+        knots = []
+        if spectral is not None:
+            knot, optics, n_knots = spectral
+            knots = [n_knots, knot.ctypes.data, optics.ctypes.data]
+        self._check(getattr(self.lib, "lbl_" + name)(
             self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
-            int(levels_per_path), int(level_begin), rows, table.ctypes.data, float(diffusivity),
+            int(levels_per_path), int(level_begin), rows, table.ctypes.data, *knots,
+            float(diffusivity),
             _address(mu), _address(ts), _address(emissivity_rows), _address(emissivity),
             _address(up_rows), _address(down_rows), n_bands, _address(starts),
             _address(radiance_rows), _address(brightness_rows), _address(radiance_mean), flags))
@@ -989,6 +1027,39 @@ class Engine(object):
         path_two_stream; view_cosine one per path, in (0, 1]; scattering_cosine one per path, in
         [-1, 1].  Outputs (DeviceSpectra): radiance_rows [n_paths, row length], and with
         band_start radiance_mean [n_paths, bands]."""
+        self._path_solar_radiance(
+            "path_solar_radiance", beta, columns, n_paths, levels_per_path, level_begin,
+            level_table, None, solar_zenith_cosine, view_cosine, scattering_cosine, solar_row,
+            up_rows, direct_rows, diffuse_rows, rayleigh_row, albedo, albedo_rows, band_start,
+            from_last, asynchronous, radiance_rows, radiance_mean)
+
+    def path_solar_radiance_spectral(self, beta, columns, grid, n_paths, levels_per_path,
+                                     level_begin, level_table, knot_wavenumber, knot_optics,
+                                     solar_zenith_cosine, view_cosine, scattering_cosine,
+                                     solar_row, up_rows, direct_rows, diffuse_rows,
+                                     rayleigh_row=None, albedo=None, albedo_rows=None,
+                                     band_start=None, from_last=False, asynchronous=False,
+                                     radiance_rows=None, radiance_mean=None):
+        """path_solar_radiance with the scatterer of every level as a table over wavenumber, from
+        the fluxes path_two_stream_spectral left in up_rows, direct_rows and diffuse_rows --
+        lbl_path_solar_radiance_spectral.  grid, knot_wavenumber [M] and knot_optics [rows, M, 3]
+        as for path_two_stream_spectral; tau_c, w_c and h_c of level_table are 0; everything
+        else as for path_solar_radiance."""
+        self._path_solar_radiance(
+            "path_solar_radiance_spectral", beta, columns, n_paths, levels_per_path, level_begin,
+            level_table,
+            (int(grid),) + _knot_table(knot_wavenumber, knot_optics, int(beta.shape[0])),
+            solar_zenith_cosine, view_cosine, scattering_cosine, solar_row, up_rows, direct_rows,
+            diffuse_rows, rayleigh_row, albedo, albedo_rows, band_start, from_last, asynchronous,
+            radiance_rows, radiance_mean)
+
+    def _path_solar_radiance(self, name, beta, columns, n_paths, levels_per_path, level_begin,
+                             level_table, spectral, solar_zenith_cosine, view_cosine,
+                             scattering_cosine, solar_row, up_rows, direct_rows, diffuse_rows,
+                             rayleigh_row, albedo, albedo_rows, band_start, from_last,
+                             asynchronous, radiance_rows, radiance_mean):
+        """The call of path_solar_radiance (spectral None) and of path_solar_radiance_spectral
+        (spectral: grid, knots, optics, M): lbl_<name>."""
         rows, stride, table, starts, n_bands, flags = _whole_paths(
             beta, level_table, n_paths, albedo_rows, "albedo_rows", band_start, level_begin,
             levels_per_path, from_last, asynchronous)
@@ -1001,9 +1072,13 @@ class Engine(object):
         _check_outputs((up_rows, direct_rows, diffuse_rows), rows, stride)
         _check_outputs((radiance_rows,), int(n_paths), stride)
         _check_outputs((radiance_mean,), int(n_paths), n_bands)
-        self._check(self.lib.lbl_path_solar_radiance(
+        knots = []
+        if spectral is not None:
+            grid, knot, optics, n_knots = spectral
+            knots = [grid, n_knots, knot.ctypes.data, optics.ctypes.data]
+        self._check(getattr(self.lib, "lbl_" + name)(
             self.handle, beta.pointer, stride, int(columns), int(n_paths), int(levels_per_path),
-            int(level_begin), rows, table.ctypes.data, _address(mu0), _address(mu),
+            int(level_begin), rows, table.ctypes.data, *knots, _address(mu0), _address(mu),
             _address(cos_theta), solar_row.pointer, _address(rayleigh_row),
             _address(albedo_rows), _address(albedo), _address(up_rows), _address(direct_rows),
             _address(diffuse_rows), n_bands, _address(starts), _address(radiance_rows),

@@ -1283,6 +1283,94 @@ class Spectroscopy(object):
             instrument, range_policy)
         return two_stream.solar_radiance(self, request, remove_pedestal, range_policy)
 
+    def compute_thermal_radiance_spectral(self, layer_thickness, surface_temperature,
+                                          scatterer_wavenumber, scatterer_optical_depth,
+                                          scatterer_single_scattering_albedo,
+                                          scatterer_asymmetry, view_zenith_cosine=1.,
+                                          surface_emissivity=1., emissivity_wavenumber=None,
+                                          surface="first", diffusivity=1.66,
+                                          quantities=("radiance",), band_edges=None,
+                                          instrument=None, remove_pedestal=None,
+                                          range_policy="reference"):
+        """compute_thermal_radiance with cloud and aerosol optics that vary with wavenumber: the
+        cloudy spectrum a sounder measures.  The scatterer of every level is a table over the
+        knots scatterer_wavenumber, interpolated and limited per grid point as in
+        compute_solar_flux_spectral (include/lbl_amd_scatterer.h):
+            j = the largest index with k_j <= nu, limited to 0 .. M-2
+            u = (nu - k_j)/(k_{j+1} - k_j), limited to [0, 1]
+            v = e_j + u*(e_{j+1} - e_j), limited to [min(e_j, e_{j+1}), max(e_j, e_{j+1})]
+            w_c = omega_c*tau_c
+        The fluxes are compute_thermal_flux_spectral's (isothermal levels), and the view sweep
+        behind them places every grid point among the knots by the same lines.  A level whose
+        knots all have omega_c*tau_c == 0 is a clear level, with tau = tau_a + tau_c(nu):
+            x = tau/mu ; I_top = I_bot*exp(-x) + B*(-expm1(-x))
+        In any other level every grid point takes compute_thermal_radiance's cloudy lines with
+        its own tau_c, w_c, f = g_c*g_c, gp = g_c/(1 + g_c) and a = (3*(gp*mu))/2; where tau == 0
+        the clear line (x = 0, the identity).  A table that is flat in nu gives
+        compute_thermal_radiance's result bit for bit; with no scatterer anywhere, eps = 1 and
+        mu = 1 the result is compute_radiance's bit for bit.  Levels are isothermal: there is no
+        interface_temperature.
+
+        Args:
+            scatterer_wavenumber, scatterer_optical_depth, scatterer_single_scattering_albedo,
+            scatterer_asymmetry: as in compute_solar_flux_spectral.
+            Everything else as in compute_thermal_radiance.
+
+        Returns:
+            Like compute_thermal_radiance, with the attribute (the key) "scatterer": "spectral".
+        Raises ValueError like it, all of them before the GPU is touched.
+        """
+        request = two_stream._thermal_radiance_request(
+            self, layer_thickness, surface_temperature, view_zenith_cosine, surface_emissivity,
+            emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
+            scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
+            instrument, range_policy,
+            scatterer_wavenumber=two_stream._given_knots(scatterer_wavenumber),
+            caller="compute_thermal_radiance_spectral")
+        return two_stream.thermal_radiance(self, request, remove_pedestal, range_policy)
+
+    def compute_solar_radiance_spectral(self, layer_thickness, solar_zenith_cosine,
+                                        scatterer_wavenumber, scatterer_optical_depth,
+                                        scatterer_single_scattering_albedo, scatterer_asymmetry,
+                                        view_zenith_cosine=1., relative_azimuth=180.,
+                                        solar_irradiance=None, solar_wavenumber=None,
+                                        distance_factor=1., surface="first", surface_albedo=0.,
+                                        albedo_wavenumber=None, rayleigh=True,
+                                        rayleigh_cross_section=None, quantities=("radiance",),
+                                        band_edges=None, instrument=None, remove_pedestal=None,
+                                        range_policy="reference"):
+        """compute_solar_radiance with cloud and aerosol optics that vary with wavenumber: the
+        cloudy or hazy spectrum a shortwave spectrometer measures.  The scatterer of every level
+        is a table over the knots scatterer_wavenumber, interpolated and limited per grid point
+        as in compute_solar_flux_spectral (j, u and v as in compute_thermal_radiance_spectral),
+        with w_c = omega_c*tau_c and h_c = w_c*g_c formed per grid point on the GPU.  The fluxes
+        are compute_solar_flux_spectral's, and the view sweep behind them places every grid
+        point among the knots by the same lines.  Per grid point tau_c, w_c and h_c go into
+        compute_solar_radiance's level, and the Henyey-Greenstein factor PH is per grid point
+        too, from gc = h_c/w_c (0 where w_c == 0; limited to 1 - 2^-53, which it can only reach
+        where w_c is a subnormal number).  Without Rayleigh scattering a level none of whose
+        knots scatters only attenuates: I_top = I_bot*exp(-(tau_a + tau_c(nu))/mu).  A table
+        that is flat in nu gives compute_solar_radiance's result bit for bit.
+
+        Args:
+            scatterer_wavenumber, scatterer_optical_depth, scatterer_single_scattering_albedo,
+            scatterer_asymmetry: as in compute_solar_flux_spectral.
+            Everything else as in compute_solar_radiance.
+
+        Returns:
+            Like compute_solar_radiance, with the attribute (the key) "scatterer": "spectral".
+        Raises ValueError like it, all of them before the GPU is touched.
+        """
+        request = two_stream._solar_radiance_request(
+            self, layer_thickness, solar_zenith_cosine, view_zenith_cosine, relative_azimuth,
+            solar_irradiance, solar_wavenumber, distance_factor, surface, surface_albedo,
+            albedo_wavenumber, rayleigh, rayleigh_cross_section, scatterer_optical_depth,
+            scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
+            instrument, range_policy,
+            scatterer_wavenumber=two_stream._given_knots(scatterer_wavenumber),
+            caller="compute_solar_radiance_spectral")
+        return two_stream.solar_radiance(self, request, remove_pedestal, range_policy)
+
     def compute_kdistribution(self, band_edges, g_edges=16, g_points=None,
                               quantities=("absorption_g_mean",), remove_pedestal=None,
                               range_policy="reference", weighting=None,

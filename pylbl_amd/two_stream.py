@@ -1,6 +1,7 @@
 """The two-stream products of Spectroscopy -- compute_solar_flux, compute_solar_flux_spectral,
 compute_thermal_flux, compute_thermal_flux_linear, compute_thermal_flux_spectral,
-compute_thermal_radiance and compute_solar_radiance -- on the host: their requests (every
+compute_thermal_radiance, compute_solar_radiance, compute_thermal_radiance_spectral and
+compute_solar_radiance_spectral -- on the host: their requests (every
 argument checked before anything touches the GPU), their sweeps and their results.  The functions
 take the Spectroscopy first; the public methods with the definitions are in spectroscopy.py, the
 run loop, the helpers every path product shares and the public constants in paths.py, which does
@@ -53,12 +54,14 @@ _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
     "emissivity_knots", "edge_temperature", "scatterer_knots", "scatterer_optics"),
     defaults=(None, None, None))
 
-# compute_thermal_radiance's: _ThermalFluxRequest's (edge_temperature and the scatterer knots stay
-# None) with mu, the viewing zenith cosine of every path; its quantities are RADIANCE_QUANTITIES.
+# compute_thermal_radiance's: _ThermalFluxRequest's (edge_temperature stays None; the scatterer
+# knots too, unless the call is compute_thermal_radiance_spectral) with mu, the viewing zenith
+# cosine of every path; its quantities are RADIANCE_QUANTITIES.
 _ThermalRadianceRequest = namedtuple("_ThermalRadianceRequest",
                                      _ThermalFluxRequest._fields + ("mu",))
 
-# compute_solar_radiance's: _SolarFluxRequest's (the scatterer knots stay None) with mu, the viewing
+# compute_solar_radiance's: _SolarFluxRequest's (the scatterer knots stay None unless the call is
+# compute_solar_radiance_spectral) with mu, the viewing
 # zenith cosine, and cos_theta, the cosine of the scattering angle, of every path; its quantity is
 # "radiance".
 _SolarRadianceRequest = namedtuple("_SolarRadianceRequest",
@@ -292,15 +295,16 @@ def _thermal_radiance_request(spec, layer_thickness, surface_temperature, view_z
                               surface_emissivity, emissivity_wavenumber, surface, diffusivity,
                               scatterer_optical_depth, scatterer_single_scattering_albedo,
                               scatterer_asymmetry, quantities, band_edges, instrument,
-                              range_policy):
-    """Checks every argument of compute_thermal_radiance: compute_thermal_flux's checks of the
-    atmosphere, the surface, D and the scatterer, the view, and compute_radiance's rules for the
-    quantities, the bands and the instrument."""
+                              range_policy, scatterer_wavenumber=None,
+                              caller="compute_thermal_radiance"):
+    """Checks every argument of compute_thermal_radiance (of `caller`, which shares them):
+    compute_thermal_flux's checks of the atmosphere, the surface, D and the scatterer, the view,
+    and compute_radiance's rules for the quantities, the bands and the instrument."""
     flux = _thermal_flux_request(
         spec, layer_thickness, surface_temperature, surface_emissivity, emissivity_wavenumber,
         surface, diffusivity, scatterer_optical_depth, scatterer_single_scattering_albedo,
         scatterer_asymmetry, THERMAL_FLUX_QUANTITIES[:2], None, range_policy,
-        caller="compute_thermal_radiance")
+        scatterer_wavenumber=scatterer_wavenumber, caller=caller)
     mu = _per_path(view_zenith_cosine, "view_zenith_cosine", flux.shape)
     if not np.all((mu > 0.) & (mu <= 1.)):
         raise ValueError("view_zenith_cosine must lie in (0, 1].")
@@ -318,8 +322,10 @@ def _solar_radiance_request(spec, layer_thickness, solar_zenith_cosine, view_zen
                             surface, surface_albedo, albedo_wavenumber, rayleigh,
                             rayleigh_cross_section, scatterer_optical_depth,
                             scatterer_single_scattering_albedo, scatterer_asymmetry, quantities,
-                            band_edges, instrument, range_policy):
-    """Checks every argument of compute_solar_radiance: compute_solar_flux's checks of the
+                            band_edges, instrument, range_policy, scatterer_wavenumber=None,
+                            caller="compute_solar_radiance"):
+    """Checks every argument of compute_solar_radiance (of `caller`, which shares them):
+    compute_solar_flux's checks of the
     atmosphere, the Sun, the surface, the Rayleigh row and the scatterer, the view, and
     compute_thermal_radiance's rules for the bands and the instrument.  cos_theta is formed
     here, in float64 and as written:
@@ -330,7 +336,7 @@ def _solar_radiance_request(spec, layer_thickness, solar_zenith_cosine, view_zen
         distance_factor, surface, surface_albedo, albedo_wavenumber, rayleigh,
         rayleigh_cross_section, scatterer_optical_depth, scatterer_single_scattering_albedo,
         scatterer_asymmetry, SOLAR_FLUX_INTERFACE_QUANTITIES[:1], None, range_policy,
-        caller="compute_solar_radiance")
+        scatterer_wavenumber=scatterer_wavenumber, caller=caller)
     mu = _per_path(view_zenith_cosine, "view_zenith_cosine", flux.shape)
     if not np.all((mu > 0.) & (mu <= 1.)):
         raise ValueError("view_zenith_cosine must lie in (0, 1].")
@@ -442,8 +448,9 @@ def thermal_flux(spec, request, remove_pedestal, range_policy):
 
 
 def thermal_radiance(spec, request, remove_pedestal, range_policy):
-    """The sweeps of compute_thermal_radiance: the flux entry into two blocks of the call, and
-    the view entry behind it on the same run."""
+    """The sweeps of compute_thermal_radiance and, where the request holds a knot table, of
+    compute_thermal_radiance_spectral: the flux entry into two blocks of the call, and the view
+    entry behind it on the same run."""
     bands = request.starts is not None
     swept = _swept_radiance(request, request.quantities)
     # From space to the surface: "first" has its surface at level 0.
@@ -457,9 +464,25 @@ def thermal_radiance(spec, request, remove_pedestal, range_policy):
         # With bands the radiance on the grid is a block of this call, the output its means.
         rows = _Rows(call, step, run, bands)
 
+        def spectral_sweep(beta, a, b, outputs, fluxes):
+            # The same two entries with the knot table, whose rows are the run's.
+            run = (beta, call.columns, fills.grid, call.paths, call.per_path, a,
+                   request.level_table[a:b], request.scatterer_knots,
+                   request.scatterer_optics[a:b])
+            call.engine.path_thermal_two_stream_spectral(
+                *run, request.surface_temperature, _first_rows(work, 2*(b - a)), **surface,
+                **fluxes)
+            blocks = dict.fromkeys(() if bands else ("radiance_rows", "brightness_rows"))
+            blocks.update(rows.keywords(_RADIANCE_ROWS, outputs, b - a))
+            call.engine.path_thermal_radiance_spectral(
+                *run, request.mu, request.surface_temperature, band_start=request.starts,
+                **surface, **fluxes, **blocks)
+
         def sweep(index, beta, a, b, outputs):
             fills.queue()
             fluxes = dict(up_rows=_first_rows(up, b - a), down_rows=_first_rows(down, b - a))
+            if request.scatterer_knots is not None:
+                return spectral_sweep(beta, a, b, outputs, fluxes)
             call.engine.path_thermal_two_stream(
                 beta, call.columns, fills.grid, call.paths, call.per_path, a,
                 request.level_table[a:b], request.surface_temperature,
@@ -481,8 +504,9 @@ def thermal_radiance(spec, request, remove_pedestal, range_policy):
 
 
 def solar_radiance(spec, request, remove_pedestal, range_policy):
-    """The sweeps of compute_solar_radiance: the flux entry into three blocks of the call, and
-    the view entry behind it on the same run."""
+    """The sweeps of compute_solar_radiance and, where the request holds a knot table, of
+    compute_solar_radiance_spectral: the flux entry into three blocks of the call, and the view
+    entry behind it on the same run."""
     bands = request.starts is not None
     # From space to the surface: "first" has its surface at level 0.
     step = _Pass(request.surface == "first", (), request.quantities)
@@ -500,10 +524,23 @@ def solar_radiance(spec, request, remove_pedestal, range_policy):
         # With bands the radiance on the grid is a block of this call, the output its means.
         rows = _Rows(call, step, run, bands)
 
+        def spectral_sweep(beta, a, b, outputs, fluxes):
+            # The same two entries with the knot table, whose rows are the run's.
+            run = (beta, call.columns, fills.grid, call.paths, call.per_path, a,
+                   request.level_table[a:b], request.scatterer_knots,
+                   request.scatterer_optics[a:b], request.mu0)
+            call.engine.path_two_stream_spectral(
+                *run, solar, _first_rows(work, 2*(b - a)), **surface, **fluxes)
+            call.engine.path_solar_radiance_spectral(
+                *run, request.mu, request.cos_theta, solar, band_start=request.starts,
+                **surface, **fluxes, **rows.keywords(_RADIANCE_ROWS, outputs, b - a))
+
         def sweep(index, beta, a, b, outputs):
             fills.queue()
             fluxes = dict(up_rows=_first_rows(up, b - a), direct_rows=_first_rows(direct, b - a),
                           diffuse_rows=_first_rows(diffuse, b - a))
+            if request.scatterer_knots is not None:
+                return spectral_sweep(beta, a, b, outputs, fluxes)
             call.engine.path_two_stream(
                 beta, call.columns, call.paths, call.per_path, a, request.level_table[a:b],
                 request.mu0, solar, _first_rows(work, 2*(b - a)), **surface, **fluxes)

@@ -8,7 +8,10 @@
 # (Lb0E as the second template argument) and with the linear-in-tau one (Lb1E); the last template
 # argument of the two-stream kernels is Lb1E with the spectral scatterer and Lb0E with the grey one;
 # "thermal_radiance" thermal_view_kernel of lbl_path_thermal_radiance alone, vector and scalar rows;
-# "solar_radiance" solar_view_kernel of lbl_path_solar_radiance likewise).
+# "solar_radiance" solar_view_kernel of lbl_path_solar_radiance likewise; each lists the grey
+# instantiations (Lb0E as the second template argument) and the spectral ones of
+# lbl_path_thermal_radiance_spectral and lbl_path_solar_radiance_spectral (Lb1E); "view_kernel" all
+# eight: DESIGN.md section 30 has their table, and none may show scratch).
 # Also prints the md5 of the device code's .text: unchanged by edits that only move host code.
 set -e
 LIB=${LIB:-pylbl_amd/liblbl_amd.so}
