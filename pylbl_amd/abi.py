@@ -1,8 +1,8 @@
 """ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h,
 include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h, include/lbl_amd_kdist.h,
 include/lbl_amd_scatterer.h, include/lbl_amd_thermal_radiance.h,
-include/lbl_amd_solar_radiance.h and include/lbl_amd_scatterer_radiance.h
-(pylbl_amd/liblbl_amd.so), and nothing else:
+include/lbl_amd_solar_radiance.h, include/lbl_amd_scatterer_radiance.h and
+include/lbl_amd_thermal_radiance_source.h (pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -279,6 +279,14 @@ SCATTERER_RADIANCE_PROTOTYPES = {
     "lbl_path_solar_radiance_spectral": _BLOCK + _RUN + [_ptr, _i32, _i32, _ptr, _ptr] +
                                         [_ptr]*10 + [_i32] + [_ptr]*3 + [_i32],
 }
+# Every function of include/lbl_amd_thermal_radiance_source.h, the header of the all-sky radiance
+# entry with the linear-in-tau source; each returns int.
+# tests/test_thermal_radiance_source_host.py compares this table with that header.
+THERMAL_RADIANCE_SOURCE_PROTOTYPES = {
+    # lbl_path_thermal_radiance's with edge_temperature after level_table
+    "lbl_path_thermal_radiance_source": _BLOCK + [_i32] + _RUN + [_ptr, _ptr, _f64] + [_ptr]*6 +
+                                        [_i32] + [_ptr]*4 + [_i32],
+}
 
 _library = None
 
@@ -340,7 +348,8 @@ def library():
             list(KDIST_PROTOTYPES.items()) + list(SCATTERER_PROTOTYPES.items()) + \
             list(THERMAL_RADIANCE_PROTOTYPES.items()) + \
             list(SOLAR_RADIANCE_PROTOTYPES.items()) + \
-            list(SCATTERER_RADIANCE_PROTOTYPES.items()):
+            list(SCATTERER_RADIANCE_PROTOTYPES.items()) + \
+            list(THERMAL_RADIANCE_SOURCE_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

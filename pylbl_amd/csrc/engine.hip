@@ -36,6 +36,7 @@
 #include "../../include/lbl_amd_thermal_radiance.h"
 #include "../../include/lbl_amd_solar_radiance.h"
 #include "../../include/lbl_amd_scatterer_radiance.h"
+#include "../../include/lbl_amd_thermal_radiance_source.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "band_sort_pairs.h"
@@ -55,6 +56,7 @@
 #include "twostream.h"
 #include "twostream_thermal.h"
 #include "thermal_radiance.h"
+#include "thermal_radiance_source.h"
 #include "solar_radiance.h"
 
 #include "engine_core.h"

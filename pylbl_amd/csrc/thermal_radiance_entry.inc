@@ -4,15 +4,20 @@
 // thermal_entry.inc; shares path_entry.inc's PathCall, TwoStreamCall, PathTables and PathBands.
 // lbl_path_thermal_radiance_spectral (include/lbl_amd_scatterer_radiance.h): the same from the
 // fluxes of lbl_path_thermal_two_stream_spectral, with twostream_entry.inc's ScattererTable.
+// lbl_path_thermal_radiance_source (include/lbl_amd_thermal_radiance_source.h): the same with the
+// linear-in-tau source, from the fluxes of lbl_path_thermal_two_stream_source and its edge table
+// (kernel: thermal_radiance_source.h; path_entry.inc's check_edge_temperatures).
 namespace {
 
-// Both entries.  name: the entry's; spectral: the scatterer's knot table, or null for the grey
-// scatterer of the level table.
+// All three entries.  name: the entry's; edge_temperature: [level_count][2] where `linear`, else
+// null: the source of the level temperatures; spectral: the scatterer's knot table, or null for
+// the grey scatterer of the level table (never with `linear`).
 int path_thermal_radiance(lbl_engine * engine, const char * name, double * beta,
                           int64_t row_stride, int64_t columns, int32_t grid, int32_t n_paths,
                           int32_t levels_per_path, int32_t level_begin, int32_t level_count,
-                          const double * level_table, ScattererTable * spectral,
-                          double diffusivity, const double * view_cosine,
+                          const double * level_table, const double * edge_temperature,
+                          bool linear, ScattererTable * spectral, double diffusivity,
+                          const double * view_cosine,
                           const double * surface_temperature, const double * emissivity_rows,
                           const double * emissivity, const double * up_rows,
                           const double * down_rows, int32_t n_bands, const int64_t * band_start,
@@ -26,11 +31,13 @@ int path_thermal_radiance(lbl_engine * engine, const char * name, double * beta,
         double * const rows[2] = {radiance_rows, brightness_rows};
         double * const mean[2] = {radiance_mean, nullptr};
         const TwoStreamCall two{call, 2, 0, rows, mean};
-        if (beta == nullptr || level_table == nullptr || view_cosine == nullptr ||
-            surface_temperature == nullptr)
+        if (beta == nullptr || level_table == nullptr || (linear && edge_temperature == nullptr) ||
+            view_cosine == nullptr || surface_temperature == nullptr)
         {
-            return call.bad("beta, level_table, view_cosine and surface_temperature must not be "
-                            "NULL.");
+            return call.bad(linear ? "beta, level_table, edge_temperature, view_cosine and "
+                                     "surface_temperature must not be NULL."
+                                   : "beta, level_table, view_cosine and surface_temperature must "
+                                     "not be NULL.");
         }
         if ((emissivity_rows == nullptr) == (emissivity == nullptr))
         {
@@ -70,6 +77,11 @@ int path_thermal_radiance(lbl_engine * engine, const char * name, double * beta,
             if (!(row[2] <= row[1])) return call.bad("the level table needs w_c <= tau_c.");
             if (!(row[3] < 1.)) return call.bad("the level table needs g_c in [0, 1).");
             if (!(row[4] > 0.)) return call.bad("the level table needs T_l > 0.");
+        }
+        if (const char * problem = check_edge_temperatures(edge_temperature, level_begin,
+                                                           level_count, levels_per_path))
+        {
+            return call.bad(problem);
         }
         if (!(diffusivity >= 1. && diffusivity <= 2.))
         {
@@ -113,6 +125,7 @@ int path_thermal_radiance(lbl_engine * engine, const char * name, double * beta,
             tables.add(run.paths, emissivity != nullptr ? emissivity + run.first_path : nullptr);
         const size_t mu_at = tables.add(run.paths, view_cosine + run.first_path);
         tables.add(bands, band_start);
+        const size_t edge_at = tables.add(linear ? 2*(size_t)level_count : 0, edge_temperature);
         if (spectral != nullptr) spectral->stage(tables, level_count);
         const double * d_tables = call.begin(tables);
 
@@ -131,7 +144,7 @@ int path_thermal_radiance(lbl_engine * engine, const char * name, double * beta,
             a.table_path = run.first_path;
             a.emissivity_rows = emissivity_rows;
             a.work = nullptr;
-            a.edge = nullptr;
+            a.edge = linear ? d_tables + edge_at : nullptr;
             for (int q = 0; q < 2; ++q) a.level_out[q] = a.top_out[q] = nullptr;
             a.mu = d_tables + mu_at;
             a.up = up_rows;
@@ -146,6 +159,16 @@ int path_thermal_radiance(lbl_engine * engine, const char * name, double * beta,
             // Surface -> space: against the order space -> surface, which is from_last() (the
             // surface is level 0), as lbl_path_thermal_two_stream's up sweep.
             a.from_last = call.from_last() ? 0 : 1;
+            if constexpr (!kSpectral)
+            {
+                if (linear)
+                {
+                    two.sweep(a, vector, [](auto v) {
+                        return thermal_view_source_kernel<decltype(v)::value>;
+                    });
+                    return;
+                }
+            }
             two.sweep(a, vector, [](auto v) {
                 return thermal_view_kernel<decltype(v)::value, kSpectral>;
             });
@@ -178,9 +201,25 @@ int lbl_path_thermal_radiance(lbl_engine * engine, double * beta, int64_t row_st
 {
     return path_thermal_radiance(
         engine, "lbl_path_thermal_radiance", beta, row_stride, columns, grid, n_paths,
-        levels_per_path, level_begin, level_count, level_table, nullptr, diffusivity, view_cosine,
-        surface_temperature, emissivity_rows, emissivity, up_rows, down_rows, n_bands, band_start,
-        radiance_rows, brightness_rows, radiance_mean, flags);
+        levels_per_path, level_begin, level_count, level_table, nullptr, false, nullptr,
+        diffusivity, view_cosine, surface_temperature, emissivity_rows, emissivity, up_rows,
+        down_rows, n_bands, band_start, radiance_rows, brightness_rows, radiance_mean, flags);
+}
+
+int lbl_path_thermal_radiance_source(
+    lbl_engine * engine, double * beta, int64_t row_stride, int64_t columns, int32_t grid,
+    int32_t n_paths, int32_t levels_per_path, int32_t level_begin, int32_t level_count,
+    const double * level_table, const double * edge_temperature, double diffusivity,
+    const double * view_cosine, const double * surface_temperature,
+    const double * emissivity_rows, const double * emissivity, const double * up_rows,
+    const double * down_rows, int32_t n_bands, const int64_t * band_start,
+    double * radiance_rows, double * brightness_rows, double * radiance_mean, int32_t flags)
+{
+    return path_thermal_radiance(
+        engine, "lbl_path_thermal_radiance_source", beta, row_stride, columns, grid, n_paths,
+        levels_per_path, level_begin, level_count, level_table, edge_temperature, true, nullptr,
+        diffusivity, view_cosine, surface_temperature, emissivity_rows, emissivity, up_rows,
+        down_rows, n_bands, band_start, radiance_rows, brightness_rows, radiance_mean, flags);
 }
 
 int lbl_path_thermal_radiance_spectral(
@@ -196,9 +235,9 @@ int lbl_path_thermal_radiance_spectral(
     ScattererTable spectral{n_knots, knot_wavenumber, knot_optics};
     return path_thermal_radiance(
         engine, "lbl_path_thermal_radiance_spectral", beta, row_stride, columns, grid, n_paths,
-        levels_per_path, level_begin, level_count, level_table, &spectral, diffusivity,
-        view_cosine, surface_temperature, emissivity_rows, emissivity, up_rows, down_rows,
-        n_bands, band_start, radiance_rows, brightness_rows, radiance_mean, flags);
+        levels_per_path, level_begin, level_count, level_table, nullptr, false, &spectral,
+        diffusivity, view_cosine, surface_temperature, emissivity_rows, emissivity, up_rows,
+        down_rows, n_bands, band_start, radiance_rows, brightness_rows, radiance_mean, flags);
 }
 
 }  // extern "C"

@@ -966,6 +966,24 @@ class Engine(object):
             emissivity, emissivity_rows, band_start, from_last, asynchronous, radiance_rows,
             brightness_rows, radiance_mean)
 
+    def path_thermal_radiance_source(self, beta, columns, grid, n_paths, levels_per_path,
+                                     level_begin, level_table, edge_temperature, view_cosine,
+                                     surface_temperature, up_rows, down_rows, diffusivity=1.66,
+                                     emissivity=None, emissivity_rows=None, band_start=None,
+                                     from_last=False, asynchronous=False, radiance_rows=None,
+                                     brightness_rows=None, radiance_mean=None):
+        """path_thermal_radiance with the linear-in-tau source, from the fluxes
+        path_thermal_two_stream_source left in up_rows and down_rows for the same edge table --
+        lbl_path_thermal_radiance_source.  edge_temperature [rows, 2] as for
+        path_thermal_two_stream_source; everything else as for path_thermal_radiance."""
+        if edge_temperature is None:
+            raise ValueError("path_thermal_radiance_source needs edge_temperature.")
+        self._path_thermal_radiance(
+            "path_thermal_radiance_source", beta, columns, grid, n_paths, levels_per_path,
+            level_begin, level_table, None, view_cosine, surface_temperature, up_rows, down_rows,
+            diffusivity, emissivity, emissivity_rows, band_start, from_last, asynchronous,
+            radiance_rows, brightness_rows, radiance_mean, edge_temperature=edge_temperature)
+
     def path_thermal_radiance_spectral(self, beta, columns, grid, n_paths, levels_per_path,
                                        level_begin, level_table, knot_wavenumber, knot_optics,
                                        view_cosine, surface_temperature, up_rows, down_rows,
@@ -990,9 +1008,11 @@ class Engine(object):
                                level_begin, level_table, spectral, view_cosine,
                                surface_temperature, up_rows, down_rows, diffusivity, emissivity,
                                emissivity_rows, band_start, from_last, asynchronous,
-                               radiance_rows, brightness_rows, radiance_mean):
-        """The call of path_thermal_radiance (spectral None) and of
-        path_thermal_radiance_spectral (spectral: knots, optics, M): lbl_<name>."""
+                               radiance_rows, brightness_rows, radiance_mean,
+                               edge_temperature=None):
+        """The call of path_thermal_radiance (spectral None), of path_thermal_radiance_spectral
+        (spectral: knots, optics, M) and of path_thermal_radiance_source (edge_temperature):
+        lbl_<name>."""
         rows, stride, table, starts, n_bands, flags = _whole_paths(
             beta, level_table, n_paths, emissivity_rows, "emissivity_rows", band_start,
             level_begin, levels_per_path, from_last, asynchronous)
@@ -1002,7 +1022,8 @@ class Engine(object):
         _check_outputs((up_rows, down_rows), rows, stride)
         _check_outputs((radiance_rows, brightness_rows), int(n_paths), stride)
         _check_outputs((radiance_mean,), int(n_paths), n_bands)
-        knots = []
+        edges = _edge_rows(edge_temperature, rows)
+        knots = [] if edges is None else [edges.ctypes.data]
         if spectral is not None:
             knot, optics, n_knots = spectral
             knots = [n_knots, knot.ctypes.data, optics.ctypes.data]

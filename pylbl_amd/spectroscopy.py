@@ -1187,6 +1187,70 @@ class Spectroscopy(object):
             instrument, range_policy)
         return two_stream.thermal_radiance(self, request, remove_pedestal, range_policy)
 
+    def compute_thermal_radiance_linear(self, layer_thickness, surface_temperature,
+                                        interface_temperature, view_zenith_cosine=1.,
+                                        surface_emissivity=1., emissivity_wavenumber=None,
+                                        surface="first", diffusivity=1.66,
+                                        scatterer_optical_depth=None,
+                                        scatterer_single_scattering_albedo=None,
+                                        scatterer_asymmetry=None, quantities=("radiance",),
+                                        band_edges=None, instrument=None, remove_pedestal=None,
+                                        range_policy="reference"):
+        """compute_thermal_radiance with a source that is linear in optical depth: within every
+        level the Planck function runs linearly in the level's delta-scaled optical depth
+        between its values at the level's two interfaces, as
+        compute_radiance(source="linear_in_tau") has it for the clear sky and
+        compute_thermal_flux_linear for the fluxes through clouds, so that a cloudy and a clear
+        sounder spectrum share one source treatment.  An isothermal optically thick level
+        radiates at its mean temperature instead of the temperature of the face the radiation
+        leaves through: tenths of a kelvin of brightness temperature in line cores.
+
+        The fluxes are compute_thermal_flux_linear's.  Every level scalar (tau, omega, sc, t, w,
+        g1, g2, dif, su, k2, k, E, Gamma, gp, a), the clear / conservative / general decisions,
+        Dm, Em, h, W, the surface line and the result at interface 0 are
+        compute_thermal_radiance's, bit for bit; the level temperature enters beta only.  With B
+        as in compute_radiance, per level and grid point, each product, sum and quotient rounded
+        as written:
+            Bt = B(T at the level's space-side interface) ; Bb = B(T at its surface-side one)
+            dB = Bb - Bt ; B(tau) = Bt + dB*tau/t for tau in [0, t] from the space-side face
+        The two-stream system with this source has the particular solution
+        F+-p = pi*(B(tau) +- B'/su), so with
+            c = (pi*dB)/(su*t)
+        f+ = [compute_thermal_radiance's homogeneous part] + c, f- = [the same] - c and
+            u1 = (up[i+1] - pi*Bb) - c ; d0 = (down[i] - pi*Bt) + c      (P, Q, N from these)
+            C = [compute_thermal_radiance's C of its branch] + (2*(a*c))*Em
+            cloudy level:
+              I_top = I_bot*Dm + (Bt*Em + dB*(Em - linear_weight(t/mu, Em))) + (w/(2 pi))*C
+            clear level (w_c == 0):
+              x = tau/mu ; A = -expm1(-x) ; lw = linear_weight(x, A)
+              I_top = I_bot*exp(-x) + (Bb*(A - lw) + Bt*lw)
+        The clear line is compute_radiance's own: without scatterers, with eps = 1 and mu = 1 the
+        call returns compute_radiance(layer_thickness, boundary_temperature=surface_temperature,
+        source="linear_in_tau", interface_temperature=...) bit for bit.  The cloudy line is exact
+        at dB = 0: a path whose levels are all cloudy and whose interface and level temperatures
+        are all equal has compute_thermal_radiance's bits; a clear level under equal
+        temperatures agrees with it to roundings.
+
+        Args:
+            interface_temperature: the atmosphere's shape with L + 1 along the last axis, finite
+                         and > 0 [K]; interface i lies between levels i-1 and i, as in
+                         compute_thermal_flux_linear.  surface_temperature stays apart from the
+                         interface temperature at the surface: a skin-temperature jump is allowed.
+            Everything else as in compute_thermal_radiance.
+
+        Returns:
+            Like compute_thermal_radiance, with the attribute (the key) "source":
+            "linear_in_tau".
+        Raises ValueError like compute_thermal_radiance and compute_thermal_flux_linear, all of
+        them before the GPU is touched.
+        """
+        request = two_stream._thermal_radiance_linear_request(
+            self, layer_thickness, surface_temperature, interface_temperature,
+            view_zenith_cosine, surface_emissivity, emissivity_wavenumber, surface, diffusivity,
+            scatterer_optical_depth, scatterer_single_scattering_albedo, scatterer_asymmetry,
+            quantities, band_edges, instrument, range_policy)
+        return two_stream.thermal_radiance(self, request, remove_pedestal, range_policy)
+
     def compute_solar_radiance(self, layer_thickness, solar_zenith_cosine, view_zenith_cosine=1.,
                                relative_azimuth=180., solar_irradiance=None,
                                solar_wavenumber=None, distance_factor=1., surface="first",
@@ -1549,6 +1613,7 @@ class Spectroscopy(object):
     _thermal_flux_request = two_stream._thermal_flux_request
     _thermal_flux_linear_request = two_stream._thermal_flux_linear_request
     _thermal_radiance_request = two_stream._thermal_radiance_request
+    _thermal_radiance_linear_request = two_stream._thermal_radiance_linear_request
     _solar_radiance_request = two_stream._solar_radiance_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset

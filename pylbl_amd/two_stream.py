@@ -1,7 +1,7 @@
 """The two-stream products of Spectroscopy -- compute_solar_flux, compute_solar_flux_spectral,
 compute_thermal_flux, compute_thermal_flux_linear, compute_thermal_flux_spectral,
-compute_thermal_radiance, compute_solar_radiance, compute_thermal_radiance_spectral and
-compute_solar_radiance_spectral -- on the host: their requests (every
+compute_thermal_radiance, compute_thermal_radiance_linear, compute_solar_radiance,
+compute_thermal_radiance_spectral and compute_solar_radiance_spectral -- on the host: their requests (every
 argument checked before anything touches the GPU), their sweeps and their results.  The functions
 take the Spectroscopy first; the public methods with the definitions are in spectroscopy.py, the
 run loop, the helpers every path product shares and the public constants in paths.py, which does
@@ -54,9 +54,10 @@ _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
     "emissivity_knots", "edge_temperature", "scatterer_knots", "scatterer_optics"),
     defaults=(None, None, None))
 
-# compute_thermal_radiance's: _ThermalFluxRequest's (edge_temperature stays None; the scatterer
-# knots too, unless the call is compute_thermal_radiance_spectral) with mu, the viewing zenith
-# cosine of every path; its quantities are RADIANCE_QUANTITIES.
+# compute_thermal_radiance's: _ThermalFluxRequest's (edge_temperature stays None unless the call
+# is compute_thermal_radiance_linear; the scatterer knots too, unless it is
+# compute_thermal_radiance_spectral) with mu, the viewing zenith cosine of every path; its
+# quantities are RADIANCE_QUANTITIES.
 _ThermalRadianceRequest = namedtuple("_ThermalRadianceRequest",
                                      _ThermalFluxRequest._fields + ("mu",))
 
@@ -317,6 +318,17 @@ def _thermal_radiance_request(spec, layer_thickness, surface_temperature, view_z
                                                   starts=starts, instrument=instrument), mu=mu)
 
 
+def _thermal_radiance_linear_request(spec, layer_thickness, surface_temperature,
+                                     interface_temperature, view_zenith_cosine, *arguments):
+    """Checks every argument of compute_thermal_radiance_linear: compute_thermal_radiance's
+    request with the interface temperatures of the linear-in-tau source."""
+    request = _thermal_radiance_request(spec, layer_thickness, surface_temperature,
+                                        view_zenith_cosine, *arguments,
+                                        caller="compute_thermal_radiance_linear")
+    return request._replace(edge_temperature=_edge_temperatures(
+        "linear_in_tau", interface_temperature, request.shape))
+
+
 def _solar_radiance_request(spec, layer_thickness, solar_zenith_cosine, view_zenith_cosine,
                             relative_azimuth, solar_irradiance, solar_wavenumber, distance_factor,
                             surface, surface_albedo, albedo_wavenumber, rayleigh,
@@ -448,8 +460,9 @@ def thermal_flux(spec, request, remove_pedestal, range_policy):
 
 
 def thermal_radiance(spec, request, remove_pedestal, range_policy):
-    """The sweeps of compute_thermal_radiance and, where the request holds a knot table, of
-    compute_thermal_radiance_spectral: the flux entry into two blocks of the call, and the view
+    """The sweeps of compute_thermal_radiance and, where the request holds a knot table or
+    interface temperatures, of compute_thermal_radiance_spectral and
+    compute_thermal_radiance_linear: the flux entry into two blocks of the call, and the view
     entry behind it on the same run."""
     bands = request.starts is not None
     swept = _swept_radiance(request, request.quantities)
@@ -478,11 +491,26 @@ def thermal_radiance(spec, request, remove_pedestal, range_policy):
                 *run, request.mu, request.surface_temperature, band_start=request.starts,
                 **surface, **fluxes, **blocks)
 
+        def linear_sweep(beta, a, b, outputs, fluxes):
+            # The same two entries with the linear-in-tau source, whose edge rows are the run's.
+            run = (beta, call.columns, fills.grid, call.paths, call.per_path, a,
+                   request.level_table[a:b], request.edge_temperature[a:b])
+            call.engine.path_thermal_two_stream_source(
+                *run, request.surface_temperature, _first_rows(work, 2*(b - a)), **surface,
+                **fluxes)
+            blocks = dict.fromkeys(() if bands else ("radiance_rows", "brightness_rows"))
+            blocks.update(rows.keywords(_RADIANCE_ROWS, outputs, b - a))
+            call.engine.path_thermal_radiance_source(
+                *run, request.mu, request.surface_temperature, band_start=request.starts,
+                **surface, **fluxes, **blocks)
+
         def sweep(index, beta, a, b, outputs):
             fills.queue()
             fluxes = dict(up_rows=_first_rows(up, b - a), down_rows=_first_rows(down, b - a))
             if request.scatterer_knots is not None:
                 return spectral_sweep(beta, a, b, outputs, fluxes)
+            if request.edge_temperature is not None:
+                return linear_sweep(beta, a, b, outputs, fluxes)
             call.engine.path_thermal_two_stream(
                 beta, call.columns, fills.grid, call.paths, call.per_path, a,
                 request.level_table[a:b], request.surface_temperature,

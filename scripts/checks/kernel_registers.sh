@@ -11,7 +11,9 @@
 # "solar_radiance" solar_view_kernel of lbl_path_solar_radiance likewise; each lists the grey
 # instantiations (Lb0E as the second template argument) and the spectral ones of
 # lbl_path_thermal_radiance_spectral and lbl_path_solar_radiance_spectral (Lb1E); "view_kernel" all
-# eight: DESIGN.md section 30 has their table, and none may show scratch).
+# eight: DESIGN.md section 30 has their table, and none may show scratch; "thermal_view" the four
+# of thermal_view_kernel and the two of thermal_view_source_kernel, the view sweep of
+# lbl_path_thermal_radiance_source: DESIGN.md section 31).
 # Also prints the md5 of the device code's .text: unchanged by edits that only move host code.
 set -e
 LIB=${LIB:-pylbl_amd/liblbl_amd.so}
