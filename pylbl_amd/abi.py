@@ -1,8 +1,9 @@
 """ctypes binding of the C ABI in include/lbl_amd.h, include/lbl_amd_twostream.h,
 include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h, include/lbl_amd_kdist.h,
 include/lbl_amd_scatterer.h, include/lbl_amd_thermal_radiance.h,
-include/lbl_amd_solar_radiance.h, include/lbl_amd_scatterer_radiance.h and
-include/lbl_amd_thermal_radiance_source.h (pylbl_amd/liblbl_amd.so), and nothing else:
+include/lbl_amd_solar_radiance.h, include/lbl_amd_scatterer_radiance.h,
+include/lbl_amd_thermal_radiance_source.h and include/lbl_amd_wing.h
+(pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
 reader).
@@ -287,6 +288,12 @@ THERMAL_RADIANCE_SOURCE_PROTOTYPES = {
     "lbl_path_thermal_radiance_source": _BLOCK + [_i32] + _RUN + [_ptr, _ptr, _f64] + [_ptr]*6 +
                                         [_i32] + [_ptr]*4 + [_i32],
 }
+# Every function of include/lbl_amd_wing.h, the header of the far-wing group records of the same
+# library; each returns int.  tests/test_wing_scaled_host.py compares this table with that header.
+WING_PROTOTYPES = {
+    # centre, g2, bl, lines, record
+    "lbl_wing_group": [_ptr, _ptr, _ptr, _i32, _ptr],
+}
 
 _library = None
 
@@ -349,7 +356,7 @@ def library():
             list(THERMAL_RADIANCE_PROTOTYPES.items()) + \
             list(SOLAR_RADIANCE_PROTOTYPES.items()) + \
             list(SCATTERER_RADIANCE_PROTOTYPES.items()) + \
-            list(THERMAL_RADIANCE_SOURCE_PROTOTYPES.items()):
+            list(THERMAL_RADIANCE_SOURCE_PROTOTYPES.items()) + list(WING_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

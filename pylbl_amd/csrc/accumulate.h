@@ -17,7 +17,9 @@
 // gives cut points lo <= a1 <= f1 <= c1 <= c2 <= f2 <= a2 <= hi into that order:
 //   [f1,c1) and [c2,f2): windows certainly cover the whole tile and the tile is certainly
 //                        in the Lorentz far wing of the line  -> branch-free fast loop,
-//                        eight lines per reciprocal (up to 64 in accumulate_kernel<4>);
+//                        eight lines per reciprocal (up to 64 in accumulate_kernel<4>, which
+//                        on tiles from max(64, 2 (cut_off + 2)) cm-1 upwards sums the
+//                        table-aligned eights from their scaled records: scaled_ranges);
 //   [a1,f1) and [f2,a2): the same, and far enough away for the optional power series of
 //                        farfield.h (empty, f1 = a1 and f2 = a2, when that is off);
 //   [c1,c2):             the tile may hold points of the line's core -> core_lines(): per line
@@ -122,6 +124,10 @@ struct AccumulateArgs
     const double * far_series;      // [levels][n_tiles][kFarTerms] or nullptr (farfield.h)
     const int * wing_bounds;        // [levels][kWingBounds] (line_prep.h): range of the far-wing terms
     int wing_batches;               // cap on wing_batches() (engine option "wing_batches")
+    const WingGroup * groups;       // [levels][ceil(n_lines/8)] (line_prep.h): the aligned eights, scaled
+    int group_base;                 // the line the groups are counted from
+    int scaled_from;                // tiles whose first point is at or beyond this index take them:
+                                    // v >= max(64, 2 (cut_off + 2)) there (accumulate_kernel<4>)
     double * partial;               // [levels][partial_slots][64*P] sums of split tiles
     long long partial_slots;
     double * k;                     // [levels][level_stride]
@@ -174,6 +180,29 @@ __device__ __forceinline__ void share_of(int j0, int j1, int part, int parts, fl
     const int cut1 = min((int)(scale*((float)(part + 1)*inverse)), units);
     begin = j0 + (cut0 << unit_shift);
     end = (part + 1 == parts) ? j1 : j0 + (cut1 << unit_shift);
+}
+
+// Share `part` of `parts` of the range [j0, j1) for the scaled eights: [s0, s1) is its share of the
+// range's whole table-aligned eights (multiples of 8, cut by share_of eight lines at a time), and
+// [r0, r1) the ragged lines it takes as well -- part 0 those in front of the first aligned eight
+// (the whole range when it holds no aligned eight), the last part those behind the last one.
+__device__ __forceinline__ void aligned_share_of(int j0, int j1, int part, int parts,
+                                                 float inverse, int base, int & s0,
+                                                 int & s1, int & r0, int & r1)
+{
+    // (eights are counted from line `base`, at or below which no line is real)
+    const int first = base + ((max(j0, base) - base + 7) & ~7);
+    const int last = j1 > base ? base + ((j1 - base) & ~7) : first;
+    if (first >= last)
+    {
+        s0 = s1 = first;
+        r0 = j0;
+        r1 = part == 0 ? j1 : j0;
+        return;
+    }
+    share_of(first, last, part, parts, inverse, 3, s0, s1);
+    r0 = part + 1 == parts ? last : j0;
+    r1 = part + 1 == parts ? j1 : (part == 0 ? first : j0);
 }
 
 // One 256-thread workgroup per work item.  Its four wavefronts own the SAME 64*P grid points
@@ -230,8 +259,21 @@ __device__ __forceinline__ void accumulate_tile(const AccumulateArgs & a)
     share_of(sc.a2, sc.hi, piece, pieces, inverse, clipped_in_groups ? 3 : 0, g.begin[2], e);
     g.count[2] = e - g.begin[2];
     // [a1,f1) and [f2,a2) are summed by the far-field series (empty when that is off).
-    share_of(sc.f1, sc.c1, piece, pieces, inverse, 2, fa0, fa1);
-    share_of(sc.c2, sc.f2, piece, pieces, inverse, 2, fb0, fb1);
+    // accumulate_kernel<4> on a tile at or above the gate of the scaled eights: the whole
+    // table-aligned eights of each range are shared out eight lines at a time ([sa0,sa1),
+    // [sb0,sb1): scaled_ranges), the up to seven lines in front of them go to the first share and
+    // the up to seven behind them to the last, down the quads and left-overs below.
+    int sa0 = 0, sa1 = 0, sb0 = 0, sb1 = 0;
+    if (P == 4 && i0 >= a.scaled_from)
+    {
+        aligned_share_of(sc.f1, sc.c1, piece, pieces, inverse, a.group_base, sa0, sa1, fa0, fa1);
+        aligned_share_of(sc.c2, sc.f2, piece, pieces, inverse, a.group_base, sb0, sb1, fb0, fb1);
+    }
+    else
+    {
+        share_of(sc.f1, sc.c1, piece, pieces, inverse, 2, fa0, fa1);
+        share_of(sc.c2, sc.f2, piece, pieces, inverse, 2, fb0, fb1);
+    }
     // Left-over lines of the far-wing ranges (fewer than four each) take the general path.
     g.begin[3] = fa0 + ((fa1 - fa0) & ~3);
     g.count[3] = (fa1 - fa0) & 3;
@@ -249,6 +291,12 @@ __device__ __forceinline__ void accumulate_tile(const AccumulateArgs & a)
             const int * __restrict__ wb = a.wing_bounds + level*kWingBounds;
             const int bound[kWingBounds] = {wb[0], wb[1], wb[2], wb[3]};
             batches = __builtin_amdgcn_readfirstlane(min(wing_batches(bound), a.wing_batches));
+        }
+        if constexpr (P == 4)
+        {
+            const WingGroup * __restrict__ groups =
+                a.groups + (long long)level*((a.n_lines + 7) >> 3);
+            scaled_ranges(wing, groups, a.group_base, sa0, sa1, sb0, sb1, batches, lane, v, acc);
         }
         fast_ranges<P>(wing, fa0, fa1, fb0, fb1, batches, v, acc);
     }

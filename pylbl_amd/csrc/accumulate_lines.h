@@ -1,5 +1,6 @@
 // The hot kernel's line loops: what a wavefront does with each of the cut-point ranges of its
 // tile (accumulate.h states the ranges) -- fast_ranges (far wing, eight lines per reciprocal),
+// scaled_ranges (the table-aligned eights of the far wing as chains of unit numerators, <4>),
 // clipped_ranges / general_line (windows that end inside the tile), core_lines / core_pair (tiles
 // that may hold a line's core: voigt.c:74-189 row by row, two lines per reciprocal) and inner_ranges / inner_batch (the
 // points nearer than xlim1, packed by class through LDS).  Included by accumulate.h after its
@@ -106,6 +107,113 @@ __device__ __forceinline__ void fast_ranges(const LineWing * __restrict__ wing,
         {
             acc[p] = lorentz_four(v[p], l1.centre, l1.g2, l1.bl, l2.centre, l2.g2, l2.bl,
                                   l3.centre, l3.g2, l3.bl, l4.centre, l4.g2, l4.bl, acc[p]);
+        }
+    }
+}
+
+// The far-wing loop of accumulate_kernel<4> over a wavefront's table-aligned eights, [a0,a1) and
+// [b0,b1) (line indices, `group_base` plus multiples of 8), on tiles that begin at or above max(64, 2 (cut_off + 2))
+// cm-1.  A group is summed from its scaled record (line_prep.h, WingGroup) as a chain of unit
+// numerators on pre-scaled offsets (scaled_eight): per row u = v - m, which is exact, the chain,
+// n = beta N -- 32 operations where wing_eight has 37 -- and the fraction n/t joins the running
+// N/T as in fast_ranges: N = fma(n, T, N t), T = T t, `batches` groups per reciprocal.  t is the
+// product of the eight t_i up to rounding (beta is the geometric mean of the amplitudes), so the
+// running products have the magnitudes wing_batches() bounds.  The record arrives by scalar
+// loads, 26 doubles per group where the eight LineWing records are 32.  A vector instruction of
+// gfx950 reads one scalar operand, so d' = fma(u, s, nas) takes nas from a vector register: one
+// v_mov_b64 per line and batch, shared by the four rows -- 148 vector instructions per batch
+// where fast_ranges has 160.  (Fetched by vector loads of one address instead, the same value on
+// every lane, the copies go and the step is slower: profiles/wing_scaled_ab.txt.)
+// A plain group (beta = 0: an amplitude that is not positive, a centre beyond 1.5 cm-1 of m, ...)
+// passes through that loop without a branch and without a trace: its record gives t' = 1 on every
+// line, so n = 0 N = 0 and t = 1 -- N = fma(0, T, N 1), T = T 1.  (With a branch the loop had two
+// bodies that left the running sums in different registers, and eight v_mov_b64 at their join.)
+// Its lines are added afterwards from their LineWing records, eight per reciprocal
+// (lorentz_eight).  An eight never spans the two ranges; a trip may.  The order of the operations
+// is fixed.
+template <bool First>
+__device__ __forceinline__ void scaled_batch(const WingGroup * __restrict__ g,
+                                             const double (&v)[4], double (&num)[4],
+                                             double (&den)[4])
+{
+    const double beta = g->beta, m = g->m;
+    double s[8], gs[8], nas[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+    {
+        nas[i] = g->nas[i];
+        s[i] = g->s[i];
+        gs[i] = g->gs[i];
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+    {
+        double n, t;
+        scaled_eight(v[p] - m, s, nas, gs, n, t);
+        n = beta*n;
+        if (First)
+        {
+            num[p] = n;
+            den[p] = t;
+        }
+        else
+        {
+            num[p] = __builtin_fma(n, den[p], num[p]*t);
+            den[p] = den[p]*t;
+        }
+    }
+}
+
+__device__ __forceinline__ void scaled_ranges(const LineWing * __restrict__ wing,
+                                              const WingGroup * __restrict__ groups, int group_base,
+                                              int a0, int a1, int b0, int b1, int batches,
+                                              int lane, const double (&v)[4], double (&acc)[4])
+{
+    // (the cuts come out of share_of's float arithmetic: said to be wave-uniform here, the loop
+    // counts and the record addresses stay in scalar registers)
+    a0 = __builtin_amdgcn_readfirstlane(a0);
+    b0 = __builtin_amdgcn_readfirstlane(b0);
+    const int ea = __builtin_amdgcn_readfirstlane((a1 - a0) >> 3);
+    const int eights = ea + __builtin_amdgcn_readfirstlane((b1 - b0) >> 3);
+    auto line_of = [&](int at) { return at < ea ? a0 + 8*at : b0 + 8*(at - ea); };
+    auto group_of = [&](int at) { return groups + ((line_of(at) - group_base) >> 3); };
+    for (int o = 0; o < eights; )
+    {
+        const int stop = min(o + batches, eights);
+        double num[4], den[4];
+        scaled_batch<true>(group_of(o), v, num, den);
+        for (++o; o < stop; ++o)
+        {
+            scaled_batch<false>(group_of(o), v, num, den);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+        {
+            acc[p] = __builtin_fma(num[p], rcp_newton(den[p]), acc[p]);
+        }
+    }
+    // The plain groups, 64 at a time: lane = group looks at beta, the wavefront walks the bits.
+    for (int base = 0; base < eights; base += 64)
+    {
+        const int at = min(base + lane, eights - 1);
+        const bool plain = base + lane < eights && !(group_of(at)->beta != 0.);
+        unsigned long long left = __ballot(plain);
+        while (left != 0)
+        {
+            const int j = line_of(base + __builtin_ctzll(left));
+            WingTerm l[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+            {
+                const LineWing w = wing[j + i];
+                l[i] = WingTerm{w.centre, w.g2, w.bl};
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+            {
+                acc[p] = lorentz_eight(v[p], l, acc[p]);
+            }
+            left &= left - 1;
         }
     }
 }

@@ -260,6 +260,7 @@ void reserve_for_call(const LinesCall & c)
     lane.levels.reserve((size_t)chunk);
     lane.wing.reserve((size_t)(chunk*std::max(n_lines, 1ll)));
     lane.core.reserve((size_t)(chunk*std::max(n_lines, 1ll)));
+    lane.groups.reserve((size_t)(chunk*std::max((n_lines + 7) >> 3, 1ll)));
     lane.schedule.reserve((size_t)(chunk*n_tiles));
     if (t.want_k && !t.out_device) lane.staging.reserve((size_t)(chunk*s.n_long));
     if (c.with_pedestal && t.out_device && t.add_into_block)
@@ -380,6 +381,16 @@ int inner_points_everywhere(const LevelScalars * levels, int count, const Comput
     return (rq.cut_off - 1. <= reach + tile_width + 1.) ? 1 : 0;
 }
 
+// The line from which the eights of the scaled far-wing records are counted (line_prep.h,
+// WingGroup): the first line of the sorted table that the range rule can accept, nu >= v0 -
+// (cut_off + 1) under either policy.  What lies below it in the table moves no group.
+long long wing_group_base(const CallShape & s)
+{
+    const std::vector<double> & nu = s.m->column[0];
+    return (long long)(std::lower_bound(nu.begin(), nu.begin() + s.m->n_lines, s.rule.nu_min) -
+                       nu.begin());
+}
+
 // LBL_PREP_HOST: the per-line scalars of `count` levels made by the host's own prepare_line
 // (line_prep.h, the code the prologue kernel runs) and copied over; the tile cut points by
 // schedule_kernel.  Adds the closed-form eval count to *rq.evals.
@@ -387,6 +398,7 @@ struct HostPrep
 {
     std::vector<LineWing> wing;
     std::vector<LineCore> core;
+    std::vector<WingGroup> groups;
     std::vector<double> derived;
     std::vector<int> wing_bounds;
 };
@@ -427,12 +439,40 @@ void prepare_on_host(lbl_engine * engine, Lane & lane, const ComputeRequest & rq
                 }
             }
         }
+        // The scaled records of the eights counted from the first line the range rule can accept
+        // (line_prep.h): what prepare_block makes.  Only accumulate_kernel<4> reads them.
+        const long long base = wing_group_base(s);
+        const long long n_groups = s.points == 4 ? (n_lines - base + 7) >> 3 : 0;
+        const long long group_stride = (n_lines + 7) >> 3;
+        hp.groups.assign((size_t)(count*group_stride), WingGroup());
+        for (int l = 0; l < count; ++l)
+        {
+            for (long long group = 0; group < n_groups; ++group)
+            {
+                double centre[8], g2[8], bl[8];
+                const long long first = base + 8*group;
+                const int lines = (int)std::min(8ll, n_lines - first);
+                for (int i = 0; i < 8; ++i)
+                {
+                    const bool real = i < lines;
+                    const LineWing * w = real ? &hp.wing[(size_t)(l*n_lines + first + i)]
+                                              : nullptr;
+                    centre[i] = real ? w->centre : 0.;
+                    g2[i] = real ? w->g2 : 1.;
+                    bl[i] = real ? w->bl : 0.;
+                }
+                wing_group_of(centre, g2, bl, lines, hp.groups[(size_t)(l*group_stride + group)]);
+            }
+        }
         engine->timed(kTimePrepare, stream, [&] {
             HIP_TRY(hipMemcpyAsync(lane.wing.data, hp.wing.data(),
                                    hp.wing.size()*sizeof(LineWing), hipMemcpyHostToDevice,
                                    stream));
             HIP_TRY(hipMemcpyAsync(lane.core.data, hp.core.data(),
                                    hp.core.size()*sizeof(LineCore), hipMemcpyHostToDevice,
+                                   stream));
+            HIP_TRY(hipMemcpyAsync(lane.groups.data, hp.groups.data(),
+                                   hp.groups.size()*sizeof(WingGroup), hipMemcpyHostToDevice,
                                    stream));
             HIP_TRY(hipMemcpyAsync(lane.wing_bounds.data, hp.wing_bounds.data(),
                                    hp.wing_bounds.size()*sizeof(int), hipMemcpyHostToDevice,
@@ -471,7 +511,8 @@ void launch_prologue(const LinesCall & c, int count, HostPrep & hp)
     {
         std::memcpy(packed.level, lane.level_feed.block, count*sizeof(LevelScalars));
     }
-    const int prepare_blocks = (int)((s.m->n_lines + 255)/256);
+    // (the threads begin up to eight lines in front of the table: prepare_block)
+    const int prepare_blocks = (int)((s.m->n_lines + 8 + 255)/256);
     const int schedule_blocks = c.traits.want_k ? (int)((8ll*s.tiling.n_tiles + 255)/256) : 0;
     // (every bound starts at kWingBoundsFill: byte 0x7f)
     HIP_TRY(hipMemsetAsync(lane.wing_bounds.data, 0x7f, (size_t)count*kWingBounds*sizeof(int),
@@ -484,7 +525,8 @@ void launch_prologue(const LinesCall & c, int count, HostPrep & hp)
                            lane.schedule.data,
                            rq.derived != nullptr ? lane.derived.data : nullptr,
                            rq.evals != nullptr ? lane.evals.data : nullptr,
-                           lane.wing_bounds.data);
+                           lane.wing_bounds.data,
+                           s.points == 4 ? lane.groups.data : nullptr, (int)wing_group_base(s));
         HIP_TRY(hipGetLastError());
     });
 }
@@ -553,6 +595,15 @@ AccumulateArgs accumulate_args(const LinesCall & c, const Lane::Pass & p)
     args.far_series = s.farfield ? lane.far_series.data : nullptr;
     args.wing_bounds = lane.wing_bounds.data;
     args.wing_batches = c.engine->wing_batches;
+    args.groups = lane.groups.data;
+    args.group_base = (int)wing_group_base(s);
+    {
+        // Tiles that begin at or above max(64, 2 (cut_off + 2)) cm-1 take the scaled eights: as a
+        // grid index, v = v0 + i/n_per_v (accumulate_lines.h, scaled_ranges).
+        const long long gate = std::max(64ll, 2ll*((long long)g.cut_off + 2));
+        const long long from = std::max(0ll, gate - (long long)g.v0)*(long long)g.n_per_v;
+        args.scaled_from = (int)std::min(from, 0x7fffffffll);
+    }
     args.partial = lane.partial.data;
     args.partial_slots = c.plan.partial_slots;
     args.level_stride = p.sums_stride;

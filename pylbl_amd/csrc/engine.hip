@@ -37,6 +37,7 @@
 #include "../../include/lbl_amd_solar_radiance.h"
 #include "../../include/lbl_amd_scatterer_radiance.h"
 #include "../../include/lbl_amd_thermal_radiance_source.h"
+#include "../../include/lbl_amd_wing.h"
 #include "accumulate.h"
 #include "band_sort.h"
 #include "band_sort_pairs.h"
@@ -81,6 +82,31 @@ int lbl_wing_batches(const int32_t * bounds)
     if (bounds == nullptr) return 1;
     const int bound[kWingBounds] = {bounds[0], bounds[1], bounds[2], bounds[3]};
     return wing_batches(bound);
+}
+
+int lbl_wing_group(const double * centre, const double * g2, const double * bl, int32_t lines,
+                   double * record)
+{
+    if (centre == nullptr || g2 == nullptr || bl == nullptr || record == nullptr) return -1;
+    double c[8], g[8], b[8];
+    for (int i = 0; i < 8; ++i)
+    {
+        const bool real = i < lines;
+        c[i] = real ? centre[i] : 0.;
+        g[i] = real ? g2[i] : 1.;
+        b[i] = real ? bl[i] : 0.;
+    }
+    WingGroup group;
+    wing_group_of(c, g, b, std::min(std::max((int)lines, 0), 8), group);
+    for (int i = 0; i < 8; ++i)
+    {
+        record[3*i] = group.s[i];
+        record[3*i + 1] = group.nas[i];
+        record[3*i + 2] = group.gs[i];
+    }
+    record[24] = group.beta;
+    record[25] = group.m;
+    return group.beta != 0. ? 1 : 0;
 }
 
 int lbl_engine_create(int device, lbl_engine ** engine)

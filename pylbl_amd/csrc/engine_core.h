@@ -153,6 +153,7 @@ struct Lane
     bool used = false;              // something was queued here since lane 0 last joined it
     DeviceBuffer<LineWing> wing;
     DeviceBuffer<LineCore> core;
+    DeviceBuffer<WingGroup> groups; // [levels][ceil(n_lines/8)]: the table-aligned eights, scaled
     DeviceBuffer<TileSchedule> schedule;
     DeviceBuffer<LevelScalars> levels;
     DeviceBuffer<double> staging;   // spectra on their way to host memory

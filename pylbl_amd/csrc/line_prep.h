@@ -235,6 +235,142 @@ __host__ __device__ inline int wing_batches(const int (&bound)[kWingBounds])
     return 1;
 }
 
+// The eights of a level (lines base + 8 g .. base + 8 g + 7 of the sorted table, base the first line
+// the call's range rule can accept: what lies below a call's windows moves no group) as the far-wing
+// loop of accumulate_kernel<4> takes them where a tile is eligible (accumulate_lines.h,
+// scaled_ranges): the eight amplitudes folded into the denominators, so that the eight fractions
+// sum as a chain of unit numerators.
+//   m     = rint(centre of the first line): v - m and centre - m are exact (Sterbenz) for tiles
+//           at or above max(64, 2 (cut_off + 2)) cm-1 and lines within kWingGroupReach of m;
+//   beta  = geometric mean of the eight bl (wing_group_beta);
+//   s     = sqrt(beta/bl), nas = -((centre - m) s), gs = g2 (s s) per line, so that
+//           t' = fma(d', d', gs), d' = fma(v - m, s, nas), is t beta/bl up to rounding and
+//           sum bl/t = beta sum 1/t'.
+// A group is PLAIN (beta = 0, m = 0 and s = nas = 0, gs = 1 on every line, so that the chain
+// gives t' = 1 and the group adds 0/1 to the loop's running sums; the loop then sums it from its
+// LineWing records, as before) when it has fewer than eight lines of the table, when any bl is not a
+// positive normal number (mark_empty's records, amplitudes of the other sign), when any centre is
+// farther than kWingGroupReach from m, when the binary exponents of its amplitudes span more than
+// kWingGroupSpread (the partial products of the chain then leave the range its whole product
+// keeps: they differ from the products of t by at most 2^(2 spread)), or when any field comes out
+// not finite (s and gs: not normal).  The rule reads the line scalars alone: host and device make
+// the same records, bit for bit (divisions, square roots, frexp and ldexp are exact or correctly
+// rounded on both).
+struct WingScaled
+{
+    double s, nas, gs;
+};
+
+struct alignas(16) WingGroup
+{
+    double s[8];
+    double gs[8];
+    double nas[8];
+    double beta;            // 0: a plain group
+    double m;
+};
+static_assert(sizeof(WingGroup) == 208, "WingGroup is read by wide loads: 26 doubles");
+
+__host__ __device__ inline void wing_group_set(WingGroup & g, int i, const WingScaled & l)
+{
+    g.s[i] = l.s;
+    g.nas[i] = l.nas;
+    g.gs[i] = l.gs;
+}
+
+// A line of a plain group: d' = 0 v + 0 and t' = 0 + 1 at every point.
+constexpr WingScaled kWingPlainLine = {0., 0., 1.};
+constexpr double kWingGroupReach = 1.5;
+constexpr int kWingGroupSpread = 128;
+
+__host__ __device__ inline bool wing_is_normal(double x)
+{
+    const double a = fabs(x);
+    return a >= 2.2250738585072014e-308 && a <= 1.7976931348623157e308;
+}
+
+// The geometric mean of eight positive normal numbers: mantissas multiplied in index order (a
+// product in [2^-8, 1)), exponents added, the sum split into 8 q + r, three square roots of the
+// mantissa product times 2^r and a last ldexp by q.  Within a few 2^-53 of the exact root.
+__host__ __device__ inline double wing_group_beta(const double (&bl)[8])
+{
+    double mantissa = 1.;
+    int exponent = 0;
+    for (int i = 0; i < 8; ++i)
+    {
+        int e;
+        mantissa *= frexp(bl[i], &e);
+        exponent += e;
+    }
+    const int q = exponent >> 3, r = exponent & 7;      // floor and remainder, also below zero
+    return ldexp(sqrt(sqrt(sqrt(ldexp(mantissa, r)))), q);
+}
+
+// What the eight amplitudes and the first centre decide: false = plain.
+__host__ __device__ inline bool wing_group_header(double first_centre, const double (&bl)[8],
+                                                  int lines, double & beta, double & m)
+{
+    beta = 0.;
+    m = 0.;
+    if (lines < 8 || !(fabs(first_centre) < 4.e15))
+    {
+        return false;
+    }
+    int low = 4096, high = -4096;
+    for (int i = 0; i < 8; ++i)
+    {
+        if (!(bl[i] > 0.) || !wing_is_normal(bl[i]))
+        {
+            return false;
+        }
+        const int e = ilogb(bl[i]);
+        low = e < low ? e : low;
+        high = e > high ? e : high;
+    }
+    if (high - low > kWingGroupSpread)
+    {
+        return false;
+    }
+    beta = wing_group_beta(bl);
+    m = rint(first_centre);
+    return wing_is_normal(beta);
+}
+
+// One line of a group whose header passed: false = the group is plain after all.
+__host__ __device__ inline bool wing_group_line(double centre, double g2, double bl, double beta,
+                                                double m, WingScaled & out)
+{
+    const double a = centre - m;
+    const double s = sqrt(beta/bl);
+    out.s = s;
+    out.nas = -(a*s);
+    out.gs = g2*(s*s);
+    return fabs(a) <= kWingGroupReach && wing_is_normal(s) && wing_is_normal(out.gs) &&
+           fabs(out.nas) <= 1.7976931348623157e308;
+}
+
+// The record of one group from its eight line records (`lines` of them belong to the table).
+__host__ __device__ inline void wing_group_of(const double (&centre)[8], const double (&g2)[8],
+                                              const double (&bl)[8], int lines, WingGroup & out)
+{
+    double beta, m;
+    bool scaled = wing_group_header(centre[0], bl, lines, beta, m);
+    for (int i = 0; i < 8; ++i)
+    {
+        WingScaled l;
+        scaled = wing_group_line(centre[i], g2[i], bl[i], beta, m, l) && scaled;
+        wing_group_set(out, i, l);
+    }
+    out.beta = beta;
+    out.m = m;
+    if (!scaled)
+    {
+        for (int i = 0; i < 8; ++i) wing_group_set(out, i, kWingPlainLine);
+        out.beta = 0.;
+        out.m = 0.;
+    }
+}
+
 // status: 1 evaluated, 0 window right of the grid / empty, -1 not accepted by the range rule.
 // derived (optional, 8 doubles): centre, alpha, gamma, strength, first, last, status, 0.
 __host__ __device__ inline int prepare_line(const LevelScalars & lv, const GridSpec & g,

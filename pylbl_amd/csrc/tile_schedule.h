@@ -204,14 +204,19 @@ __device__ __forceinline__ void prepare_block(const LineTableView & t, const Lev
                                               LineCore * __restrict__ core,
                                               double * __restrict__ derived,
                                               unsigned long long * __restrict__ evals,
-                                              int * __restrict__ wing_bounds)
+                                              int * __restrict__ wing_bounds,
+                                              WingGroup * __restrict__ groups, int group_base)
 {
-    const long long j = (long long)block*blockDim.x + threadIdx.x;
+    // Thread -> line, shifted so that eight neighbouring lanes hold one group of the scaled
+    // records: groups are counted from line group_base (the first line the call's range rule can
+    // accept), and the first block begins up to eight lines in front of the table.
+    const long long j = (long long)block*blockDim.x + threadIdx.x + ((group_base & 7) - 8);
     unsigned long long count = 0;
     int bound[kWingBounds] = {kWingBoundsFill, kWingBoundsFill, kWingBoundsFill, kWingBoundsFill};
-    if (j < t.n_lines)
+    LineWing w;
+    w.centre = 0.; w.g2 = 1.; w.bl = 0.;
+    if (j >= 0 && j < t.n_lines)
     {
-        LineWing w;
         LineCore c;
         const double nu = t.nu[j];
         const int slot = t.iso_slot[j];     // -1: no mass / partition function (never accepted)
@@ -227,6 +232,38 @@ __device__ __forceinline__ void prepare_block(const LineTableView & t, const Lev
             count = (unsigned long long)(w.last - w.first + 1);
         }
         wing_line_bounds(g, nu, status, w, c, bound);
+    }
+    if (groups != nullptr)
+    {
+        // The scaled records of the eights counted from group_base (line_prep.h, WingGroup): eight
+        // neighbouring lanes hold a group.  Every lane forms the group's header from the eight
+        // amplitudes and its own line's fields; the group is scaled when all eight lanes agree.
+        // (wave-uniform: every lane of the block is here)
+        const int lane = threadIdx.x & 63, leader = lane & ~7;
+        double bl[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) bl[i] = __shfl(w.bl, leader + i, 64);
+        const double first_centre = __shfl(w.centre, leader, 64);
+        const long long first_line = j - (lane - leader);
+        const int lines = first_line < group_base ? 0
+                        : (int)min(8ll, max(0ll, t.n_lines - first_line));
+        double beta, m;
+        WingScaled mine;
+        bool scaled = wing_group_header(first_centre, bl, lines, beta, m);
+        scaled = wing_group_line(w.centre, w.g2, w.bl, beta, m, mine) && scaled;
+        const unsigned long long agree = __ballot(scaled);
+        scaled = ((agree >> leader) & 0xffull) == 0xffull;
+        if (j >= group_base && j < t.n_lines)
+        {
+            WingGroup * __restrict__ out = groups + (long long)level*((t.n_lines + 7) >> 3) +
+                                           ((j - group_base) >> 3);
+            wing_group_set(*out, lane - leader, scaled ? mine : kWingPlainLine);
+            if (lane == leader)
+            {
+                out->beta = scaled ? beta : 0.;
+                out->m = scaled ? m : 0.;
+            }
+        }
     }
     {
         // The level's far-wing bounds (wing_batches()): minimum over the block, then one atomic
@@ -284,7 +321,9 @@ __global__ __launch_bounds__(256) void prologue_kernel(const LineTableView t,
                                                        TileSchedule * __restrict__ schedule,
                                                        double * __restrict__ derived,
                                                        unsigned long long * __restrict__ evals,
-                                                       int * __restrict__ wing_bounds)
+                                                       int * __restrict__ wing_bounds,
+                                                       WingGroup * __restrict__ groups,
+                                                       const int group_base)
 {
     const int level = blockIdx.y;
     const LevelScalars & lv = use_inline ? inline_levels.level[level] : levels[level];
@@ -298,7 +337,7 @@ __global__ __launch_bounds__(256) void prologue_kernel(const LineTableView t,
     if ((int)blockIdx.x < prepare_blocks)
     {
         prepare_block(t, lv, g, rule, blockIdx.x, level, wing, core, derived, evals,
-                      wing_bounds);
+                      wing_bounds, groups, group_base);
         return;
     }
     const int thread = (blockIdx.x - prepare_blocks)*blockDim.x + threadIdx.x;

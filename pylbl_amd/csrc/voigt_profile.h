@@ -18,6 +18,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "line_prep.h"
+
 namespace lbl {
 
 // 1/t for t well inside the normal range: v_rcp_f64 (about 25 good bits on gfx950) plus
@@ -91,6 +93,33 @@ __device__ __forceinline__ void wing_eight(double v, const WingTerm (&l)[8],
     const double nb = __builtin_fma(n56, t78, n78*t56), tb = t56*t78;
     num = __builtin_fma(na, tb, nb*ta);
     den = ta*tb;
+}
+
+// A table-aligned eight in its scaled form (line_prep.h, WingGroup) at one point, u = v - m:
+// sum 1/t'_i = num/den with t'_i = d'^2 + gs_i, d' = u s_i - a_i s_i.  The numerators are 1, so
+// a fraction joins the chain with two operations (N = N t' + T, T = T t') where wing_eight's
+// pairing takes three: 8 FMAs for d', 8 for t', an addition and a product for the second line,
+// two operations each for the six others -- 30 where wing_eight has 37.  The caller multiplies
+// num by the group's beta (sum bl_i/t_i = beta sum 1/t'_i) and forms u once per row and group.
+__device__ __forceinline__ void scaled_eight(double u, const double (&s)[8],
+                                             const double (&nas)[8], const double (&gs)[8],
+                                             double & num, double & den)
+{
+    const double d0 = __builtin_fma(u, s[0], nas[0]);
+    const double d1 = __builtin_fma(u, s[1], nas[1]);
+    const double t0 = __builtin_fma(d0, d0, gs[0]);
+    const double t1 = __builtin_fma(d1, d1, gs[1]);
+    double N = t0 + t1, T = t0*t1;
+#pragma unroll
+    for (int i = 2; i < 8; ++i)
+    {
+        const double d = __builtin_fma(u, s[i], nas[i]);
+        const double t = __builtin_fma(d, d, gs[i]);
+        N = __builtin_fma(N, t, T);
+        T = T*t;
+    }
+    num = N;
+    den = T;
 }
 
 // Eight far-wing lines at one point with a single reciprocal, added to `sum`: 40 FMA-class
