@@ -2,7 +2,8 @@
 include/lbl_amd_thermal.h, include/lbl_amd_thermal_source.h, include/lbl_amd_kdist.h,
 include/lbl_amd_scatterer.h, include/lbl_amd_thermal_radiance.h,
 include/lbl_amd_solar_radiance.h, include/lbl_amd_scatterer_radiance.h,
-include/lbl_amd_thermal_radiance_source.h and include/lbl_amd_wing.h
+include/lbl_amd_thermal_radiance_source.h, include/lbl_amd_thermal_radiance_observer.h and
+include/lbl_amd_wing.h
 (pylbl_amd/liblbl_amd.so), and nothing else:
 the mirrors of the header's #defines, struct lbl_band, one table of every function's prototype,
 the loader that applies it, and the one call sequence that needs no engine (the SQLite table
@@ -288,6 +289,15 @@ THERMAL_RADIANCE_SOURCE_PROTOTYPES = {
     "lbl_path_thermal_radiance_source": _BLOCK + [_i32] + _RUN + [_ptr, _ptr, _f64] + [_ptr]*6 +
                                         [_i32] + [_ptr]*4 + [_i32],
 }
+# Every function of include/lbl_amd_thermal_radiance_observer.h, the header of the all-sky radiance
+# entry for an observer at any interface, looking down or up; each returns int.
+# tests/test_thermal_radiance_observer_host.py compares this table with that header.
+THERMAL_RADIANCE_OBSERVER_PROTOTYPES = {
+    # lbl_path_thermal_radiance_source's with observer_levels and view_up after view_cosine
+    "lbl_path_thermal_radiance_observer": _BLOCK + [_i32] + _RUN + [_ptr, _ptr, _f64, _ptr, _ptr,
+                                                                    _i32] + [_ptr]*5 + [_i32] +
+                                          [_ptr]*4 + [_i32],
+}
 # Every function of include/lbl_amd_wing.h, the header of the far-wing group records of the same
 # library; each returns int.  tests/test_wing_scaled_host.py compares this table with that header.
 WING_PROTOTYPES = {
@@ -356,7 +366,8 @@ def library():
             list(THERMAL_RADIANCE_PROTOTYPES.items()) + \
             list(SOLAR_RADIANCE_PROTOTYPES.items()) + \
             list(SCATTERER_RADIANCE_PROTOTYPES.items()) + \
-            list(THERMAL_RADIANCE_SOURCE_PROTOTYPES.items()) + list(WING_PROTOTYPES.items()):
+            list(THERMAL_RADIANCE_SOURCE_PROTOTYPES.items()) + \
+            list(THERMAL_RADIANCE_OBSERVER_PROTOTYPES.items()) + list(WING_PROTOTYPES.items()):
         function = getattr(lib, name)
         function.argtypes = arguments
         function.restype = RESULT_TYPES.get(name, c_int32)

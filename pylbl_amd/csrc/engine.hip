@@ -37,6 +37,7 @@
 #include "../../include/lbl_amd_solar_radiance.h"
 #include "../../include/lbl_amd_scatterer_radiance.h"
 #include "../../include/lbl_amd_thermal_radiance_source.h"
+#include "../../include/lbl_amd_thermal_radiance_observer.h"
 #include "../../include/lbl_amd_wing.h"
 #include "accumulate.h"
 #include "band_sort.h"
@@ -58,6 +59,7 @@
 #include "twostream_thermal.h"
 #include "thermal_radiance.h"
 #include "thermal_radiance_source.h"
+#include "thermal_radiance_observer.h"
 #include "solar_radiance.h"
 
 #include "engine_core.h"
@@ -542,6 +544,7 @@ int lbl_timing_busy(lbl_engine * engine, double busy_ms[8])
 #include "twostream_entry.inc"
 #include "thermal_entry.inc"
 #include "thermal_radiance_entry.inc"
+#include "thermal_radiance_observer_entry.inc"
 #include "solar_radiance_entry.inc"
 #include "band_sort_entry.inc"
 #include "band_sort_pairs_entry.inc"

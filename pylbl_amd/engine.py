@@ -984,6 +984,41 @@ class Engine(object):
             diffusivity, emissivity, emissivity_rows, band_start, from_last, asynchronous,
             radiance_rows, brightness_rows, radiance_mean, edge_temperature=edge_temperature)
 
+    def path_thermal_radiance_observer(self, beta, columns, grid, n_paths, levels_per_path,
+                                       level_begin, level_table, view_cosine, observer_levels,
+                                       surface_temperature, up_rows, down_rows,
+                                       edge_temperature=None, view_up=False, diffusivity=1.66,
+                                       emissivity=None, emissivity_rows=None, band_start=None,
+                                       from_last=False, asynchronous=False, radiance_rows=None,
+                                       brightness_rows=None, radiance_mean=None):
+        """path_thermal_radiance (edge_temperature None) or path_thermal_radiance_source for an
+        observer after observer_levels[p] levels of path p, a whole number in [0,
+        levels_per_path], looking down (from the surface towards space) or, with view_up, up
+        (from space towards the surface) -- lbl_path_thermal_radiance_observer.  up_rows and
+        down_rows are the fluxes of path_thermal_two_stream or, with edge_temperature, of
+        path_thermal_two_stream_source; everything else as for path_thermal_radiance."""
+        rows, stride, table, starts, n_bands, flags = _whole_paths(
+            beta, level_table, n_paths, emissivity_rows, "emissivity_rows", band_start,
+            level_begin, levels_per_path, from_last, asynchronous)
+        mu, ts, emissivity = _per_path(n_paths, "one view cosine, one surface temperature and one "
+                                       "emissivity per path.", view_cosine, surface_temperature,
+                                       emissivity)
+        passed = np.asarray(observer_levels)
+        if passed.shape != (int(n_paths),) or passed.dtype.kind not in "iu":
+            raise ValueError("observer_levels needs one whole number per path.")
+        passed = np.ascontiguousarray(passed, dtype=np.int32)
+        _check_outputs((up_rows, down_rows), rows, stride)
+        _check_outputs((radiance_rows, brightness_rows), int(n_paths), stride)
+        _check_outputs((radiance_mean,), int(n_paths), n_bands)
+        edges = _edge_rows(edge_temperature, rows)
+        self._check(self.lib.lbl_path_thermal_radiance_observer(
+            self.handle, beta.pointer, stride, int(columns), int(grid), int(n_paths),
+            int(levels_per_path), int(level_begin), rows, table.ctypes.data, _address(edges),
+            float(diffusivity), _address(mu), passed.ctypes.data, int(bool(view_up)),
+            _address(ts), _address(emissivity_rows), _address(emissivity), _address(up_rows),
+            _address(down_rows), n_bands, _address(starts), _address(radiance_rows),
+            _address(brightness_rows), _address(radiance_mean), flags))
+
     def path_thermal_radiance_spectral(self, beta, columns, grid, n_paths, levels_per_path,
                                        level_begin, level_table, knot_wavenumber, knot_optics,
                                        view_cosine, surface_temperature, up_rows, down_rows,

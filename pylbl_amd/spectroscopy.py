@@ -1251,6 +1251,76 @@ class Spectroscopy(object):
             quantities, band_edges, instrument, range_policy)
         return two_stream.thermal_radiance(self, request, remove_pedestal, range_policy)
 
+    def compute_thermal_radiance_at(self, layer_thickness, surface_temperature,
+                                    observer_interface=None, looking="down",
+                                    interface_temperature=None, view_zenith_cosine=1.,
+                                    surface_emissivity=1., emissivity_wavenumber=None,
+                                    surface="first", diffusivity=1.66,
+                                    scatterer_optical_depth=None,
+                                    scatterer_single_scattering_albedo=None,
+                                    scatterer_asymmetry=None, quantities=("radiance",),
+                                    band_edges=None, instrument=None, remove_pedestal=None,
+                                    range_policy="reference"):
+        """compute_thermal_radiance (with interface_temperature:
+        compute_thermal_radiance_linear) for an observer at any interface of the atmosphere,
+        looking down or up: what a zenith-viewing spectrometer on the ground sees of a cloud
+        base, and what a sounder on an aircraft or a balloon sees above, between or below cloud
+        decks.
+
+        A ray that travels downward through a level is the ray that travels upward through the
+        mirrored level, and the layer's two-stream solution is symmetric under that mirror.  So
+        with E the face by which the ray enters a level and X the face by which it leaves,
+        F_with the flux travelling with the ray at E, F_against the flux travelling against it
+        at X and B_E, B_X the Planck values at the two faces, the level maps I_E to I_X by
+        compute_thermal_radiance's lines (compute_thermal_radiance_linear's with
+        interface_temperature), each product, sum and quotient rounded as written, with
+            up[i+1] := F_with ; down[i] := F_against ; Bb := B_E ; Bt := B_X
+        and every level scalar, a = (3*(gp*mu))/2 among them, unchanged.
+            looking="down": the radiance travelling away from the surface at the observer.  It
+              starts from compute_thermal_radiance's Lambertian surface line and passes the
+              levels between the surface and the observer (E is a level's surface-side face).
+            looking="up": the radiance travelling toward the surface at the observer.  It starts
+              from 0 at the interface facing space and passes the levels between space and the
+              observer (E is a level's space-side face); with interface_temperature
+                c = (pi*(B_space - B_surface))/(su*t)
+                u1 = (down[i] - pi*B_space) - c ; d0 = (up[i+1] - pi*B_surface) + c
+        down = 0 at the interface facing space is used only where the outermost level itself is
+        passed; an observer inside the atmosphere has a downward flux at its interface, which
+        is read.  Looking down from the interface facing space the call returns
+        compute_thermal_radiance's (compute_thermal_radiance_linear's) bits; without
+        scatterers, with eps = 1 and mu = 1 every interface gives the matching level of
+        compute_radiance(..., cumulative=True) bit for bit, in both directions.
+
+        Args:
+            observer_interface: an integer, or one per path (the atmosphere's shape without its
+                         last axis), in 0 ... L: the index on the "interface" dim of
+                         compute_thermal_flux's result.  Interface i lies on the level-0 side of
+                         level i, interface L beyond the last level.  None: the far end of the
+                         view -- looking down the interface facing space, looking up the
+                         surface.  An observer at the near end passes no level and sees the
+                         surface line (down) or 0 (up).
+            looking: "down" or "up".
+            interface_temperature: None for isothermal levels, or
+                         compute_thermal_radiance_linear's interface temperatures (L + 1 along
+                         the last axis), which make the source linear in tau.
+            Everything else as in compute_thermal_radiance.
+
+        Returns:
+            Like compute_thermal_radiance, with the per-path coordinate "observer_interface" and
+            the attribute "looking" (both keys without xarray), and with interface_temperature
+            the attribute "source": "linear_in_tau".
+        Raises ValueError like compute_thermal_radiance and compute_thermal_radiance_linear, and
+        for an observer_interface that is no integer, out of range or of a wrong shape and a
+        `looking` other than "down" or "up", all of them before the GPU is touched.
+        """
+        request = two_stream._thermal_radiance_at_request(
+            self, layer_thickness, surface_temperature, observer_interface, looking,
+            interface_temperature, view_zenith_cosine, surface_emissivity,
+            emissivity_wavenumber, surface, diffusivity, scatterer_optical_depth,
+            scatterer_single_scattering_albedo, scatterer_asymmetry, quantities, band_edges,
+            instrument, range_policy)
+        return two_stream.thermal_radiance_at(self, request, remove_pedestal, range_policy)
+
     def compute_solar_radiance(self, layer_thickness, solar_zenith_cosine, view_zenith_cosine=1.,
                                relative_azimuth=180., solar_irradiance=None,
                                solar_wavenumber=None, distance_factor=1., surface="first",
@@ -1614,6 +1684,7 @@ class Spectroscopy(object):
     _thermal_flux_linear_request = two_stream._thermal_flux_linear_request
     _thermal_radiance_request = two_stream._thermal_radiance_request
     _thermal_radiance_linear_request = two_stream._thermal_radiance_linear_request
+    _thermal_radiance_at_request = two_stream._thermal_radiance_at_request
     _solar_radiance_request = two_stream._solar_radiance_request
     _create_path_dataset = paths._create_path_dataset
     _create_flux_dataset = paths._create_flux_dataset

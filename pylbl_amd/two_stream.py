@@ -1,7 +1,8 @@
 """The two-stream products of Spectroscopy -- compute_solar_flux, compute_solar_flux_spectral,
 compute_thermal_flux, compute_thermal_flux_linear, compute_thermal_flux_spectral,
-compute_thermal_radiance, compute_thermal_radiance_linear, compute_solar_radiance,
-compute_thermal_radiance_spectral and compute_solar_radiance_spectral -- on the host: their requests (every
+compute_thermal_radiance, compute_thermal_radiance_linear, compute_thermal_radiance_at,
+compute_solar_radiance, compute_thermal_radiance_spectral and compute_solar_radiance_spectral -- on
+the host: their requests (every
 argument checked before anything touches the GPU), their sweeps and their results.  The functions
 take the Spectroscopy first; the public methods with the definitions are in spectroscopy.py, the
 run loop, the helpers every path product shares and the public constants in paths.py, which does
@@ -60,6 +61,15 @@ _ThermalFluxRequest = namedtuple("_ThermalFluxRequest", _COMMON + (
 # quantities are RADIANCE_QUANTITIES.
 _ThermalRadianceRequest = namedtuple("_ThermalRadianceRequest",
                                      _ThermalFluxRequest._fields + ("mu",))
+
+# compute_thermal_radiance_at's: _ThermalRadianceRequest's (edge_temperature: its
+# interface_temperature, or None) with the observer: observer_interface [paths], the interface of
+# compute_thermal_flux's "interface" dim at which every path's observer stands, `looking` ("down" or
+# "up") and observer_levels [paths], int32: n_p, the levels the ray passes on its way there.
+_ThermalObserverRequest = namedtuple(
+    "_ThermalObserverRequest",
+    _ThermalRadianceRequest._fields + ("observer_interface", "looking", "observer_levels"))
+LOOKING = ("down", "up")
 
 # compute_solar_radiance's: _SolarFluxRequest's (the scatterer knots stay None unless the call is
 # compute_solar_radiance_spectral) with mu, the viewing
@@ -329,6 +339,51 @@ def _thermal_radiance_linear_request(spec, layer_thickness, surface_temperature,
         "linear_in_tau", interface_temperature, request.shape))
 
 
+def _observer_levels(observer_interface, looking, surface, shape):
+    """(observer_interface, n_p), one of each per path: the interface (0 ... L, on the level-0
+    side of level i, L beyond the last level; None: the far end of the view) and the levels the
+    ray passes -- looking down those between the surface and the observer, looking up those
+    between space and the observer."""
+    if looking not in LOOKING:
+        raise ValueError(f'looking must be "down" or "up", not {looking!r}.')
+    levels, per_path_shape = int(shape[-1]), tuple(shape[:-1])
+    # The surface is at interface 0 ("first") or L; the far end of a view down is space.
+    surface_at_zero = surface == "first"
+    if observer_interface is None:
+        observer_interface = levels if surface_at_zero == (looking == "down") else 0
+    given = np.asarray(observer_interface)
+    if given.dtype.kind not in "iu":
+        raise ValueError("observer_interface must be an integer, or integers, one per path.")
+    if given.shape not in ((), per_path_shape):
+        raise ValueError(f"observer_interface has shape {given.shape}: give one integer or one "
+                         f"per path, shaped {per_path_shape}.")
+    if np.any(given < 0) or np.any(given > levels):
+        raise ValueError(f"observer_interface must lie in 0 ... {levels}, the interfaces of the "
+                         "atmosphere.")
+    interface = np.ascontiguousarray(np.broadcast_to(given, per_path_shape).ravel(),
+                                     dtype=np.int64)
+    from_zero = surface_at_zero == (looking == "down")
+    passed = interface if from_zero else levels - interface
+    return interface, np.ascontiguousarray(passed, dtype=np.int32)
+
+
+def _thermal_radiance_at_request(spec, layer_thickness, surface_temperature, observer_interface,
+                                 looking, interface_temperature, view_zenith_cosine,
+                                 surface_emissivity, emissivity_wavenumber, surface, *arguments):
+    """Checks every argument of compute_thermal_radiance_at: compute_thermal_radiance's request,
+    with interface temperatures compute_thermal_radiance_linear's, and the observer."""
+    request = _thermal_radiance_request(spec, layer_thickness, surface_temperature,
+                                        view_zenith_cosine, surface_emissivity,
+                                        emissivity_wavenumber, surface, *arguments,
+                                        caller="compute_thermal_radiance_at")
+    if interface_temperature is not None:
+        request = request._replace(edge_temperature=_edge_temperatures(
+            "linear_in_tau", interface_temperature, request.shape))
+    interface, passed = _observer_levels(observer_interface, looking, surface, request.shape)
+    return _ThermalObserverRequest(*request, observer_interface=interface, looking=looking,
+                                   observer_levels=passed)
+
+
 def _solar_radiance_request(spec, layer_thickness, solar_zenith_cosine, view_zenith_cosine,
                             relative_azimuth, solar_irradiance, solar_wavenumber, distance_factor,
                             surface, surface_albedo, albedo_wavenumber, rayleigh,
@@ -463,7 +518,8 @@ def thermal_radiance(spec, request, remove_pedestal, range_policy):
     """The sweeps of compute_thermal_radiance and, where the request holds a knot table or
     interface temperatures, of compute_thermal_radiance_spectral and
     compute_thermal_radiance_linear: the flux entry into two blocks of the call, and the view
-    entry behind it on the same run."""
+    entry behind it on the same run.  A request with an observer (compute_thermal_radiance_at)
+    queues the same flux entry and the observer's view entry behind it."""
     bands = request.starts is not None
     swept = _swept_radiance(request, request.quantities)
     # From space to the surface: "first" has its surface at level 0.
@@ -504,9 +560,31 @@ def thermal_radiance(spec, request, remove_pedestal, range_policy):
                 *run, request.mu, request.surface_temperature, band_start=request.starts,
                 **surface, **fluxes, **blocks)
 
+        def observer_sweep(beta, a, b, outputs, fluxes):
+            # The flux entry of the source, then the one view entry for both sources; the run's
+            # paths are a//per_path ... b//per_path.
+            run = (beta, call.columns, fills.grid, call.paths, call.per_path, a,
+                   request.level_table[a:b])
+            edges = None if request.edge_temperature is None else request.edge_temperature[a:b]
+            work_rows = _first_rows(work, 2*(b - a))
+            if edges is None:
+                call.engine.path_thermal_two_stream(
+                    *run, request.surface_temperature, work_rows, **surface, **fluxes)
+            else:
+                call.engine.path_thermal_two_stream_source(
+                    *run, edges, request.surface_temperature, work_rows, **surface, **fluxes)
+            blocks = dict.fromkeys(() if bands else ("radiance_rows", "brightness_rows"))
+            blocks.update(rows.keywords(_RADIANCE_ROWS, outputs, b - a))
+            call.engine.path_thermal_radiance_observer(
+                *run, request.mu, request.observer_levels, request.surface_temperature,
+                edge_temperature=edges, view_up=request.looking == "up",
+                band_start=request.starts, **surface, **fluxes, **blocks)
+
         def sweep(index, beta, a, b, outputs):
             fills.queue()
             fluxes = dict(up_rows=_first_rows(up, b - a), down_rows=_first_rows(down, b - a))
+            if isinstance(request, _ThermalObserverRequest):
+                return observer_sweep(beta, a, b, outputs, fluxes)
             if request.scatterer_knots is not None:
                 return spectral_sweep(beta, a, b, outputs, fluxes)
             if request.edge_temperature is not None:
@@ -529,6 +607,20 @@ def thermal_radiance(spec, request, remove_pedestal, range_policy):
     values = spec._sweep_runs(request, [step], remove_pedestal, range_policy, sweeper,
                               level_blocks=5, products=products, whole_paths=True)
     return _create_path_dataset(spec, _channel_brightness(values, request), request)
+
+
+def thermal_radiance_at(spec, request, remove_pedestal, range_policy):
+    """compute_thermal_radiance_at: thermal_radiance's sweeps with the observer's view entry, and
+    its result with the per-path coordinate observer_interface and the attribute looking."""
+    result = thermal_radiance(spec, request, remove_pedestal, range_policy)
+    per_path = request.observer_interface.reshape(request.shape[:-1])
+    if isinstance(result, dict):
+        result.update(observer_interface=per_path, looking=request.looking)
+        return result
+    result = result.assign_coords(
+        observer_interface=(list(spec.atmosphere.dims)[:-1], per_path))
+    result.attrs["looking"] = request.looking
+    return result
 
 
 def solar_radiance(spec, request, remove_pedestal, range_policy):

@@ -13,7 +13,10 @@
 # lbl_path_thermal_radiance_spectral and lbl_path_solar_radiance_spectral (Lb1E); "view_kernel" all
 # eight: DESIGN.md section 30 has their table, and none may show scratch; "thermal_view" the four
 # of thermal_view_kernel and the two of thermal_view_source_kernel, the view sweep of
-# lbl_path_thermal_radiance_source: DESIGN.md section 31).
+# lbl_path_thermal_radiance_source: DESIGN.md section 31; "thermal_observer" the eight of
+# thermal_observer_kernel, the sweep of lbl_path_thermal_radiance_observer -- vector or scalar
+# rows, isothermal or linear-in-tau source, looking down or up as the three template arguments:
+# DESIGN.md section 32 has their table, and none may show scratch).
 # Also prints the md5 of the device code's .text: unchanged by edits that only move host code.
 set -e
 LIB=${LIB:-pylbl_amd/liblbl_amd.so}
