@@ -67,10 +67,12 @@ def shapes():
     return table
 
 
-def run(engine, inputs, mu, layout, runs, from_last, passed, up, bands=None, wanted=NAMES):
-    """Every output of the entry over `runs` of whole paths (first level, count)."""
+def run(engine, inputs, mu, layout, runs, from_last, passed, up, bands=None, wanted=NAMES,
+        fluxes=None):
+    """Every output of the entry over `runs` of whole paths (first level, count); fluxes: the
+    flux rows it reads (None: the float64 mirror's)."""
     n, columns, levels = inputs.levels_per_path, inputs.columns, inputs.levels
-    fluxes = flux_rows(inputs, from_last)
+    fluxes = flux_rows(inputs, from_last) if fluxes is None else fluxes
     beta = block(inputs.beta, levels, columns, layout, np.nan)
     rows_up = block(fluxes["up"], levels, columns, layout, np.nan)
     rows_down = block(fluxes["down"], levels, columns, layout, np.nan)
